@@ -9,6 +9,11 @@ device-resident synthetic batch of EuroSAT-shaped 64x64 RGB images (BASELINE.jso
 AE + classification head, 64-d latent, bf16 storage / fp32 accumulation).  With N > 1 every rank holds a replica and a
 512-image shard of the global batch; gradients are averaged with one RCCL all-reduce per step (weak scaling).
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds what takes runs of its own: the live
+per-kernel roofline, the other BASELINE configurations (configs[1], configs[4]'s shape, the B=64 grid) and the CPU baseline.
+`--dump-outputs DIR` writes what the last timed step left for its caller (loss scalars, parameters, BatchNorm buffers) as
+DIR/<name>.npy; the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -41,6 +46,35 @@ def make_batch(b, device, seed):
     x = torch.rand((b, 3, 64, 64), generator=g, dtype=torch.float32)
     y = torch.randint(0, 10, (b,), generator=g, dtype=torch.int64)
     return x.to(device), y.to(device)
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 20           # an array of more elements is written as a fixed, seeded sample of this many
+
+
+def dump_outputs(outdir, pairs):
+    """--dump-outputs: what the last timed step left for its caller, one DIR/<name>.npy per array (float32; integer counters as
+    float64).  pairs: (prefix, model, engine) per trained configuration -- the loss scalars of the last step (loss_last), the
+    accumulated loss sums (loss_accum) and the module's state_dict (parameters + BatchNorm buffers) after it."""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {}
+    for prefix, model, eng in pairs:
+        arrays[prefix + "loss_last"] = eng.loss_last
+        arrays[prefix + "loss_accum"] = eng.loss_accum
+        for k, v in model.state_dict().items():
+            arrays[prefix + "state." + k] = v
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float32) if a.dtype.kind == "f" and a.dtype.itemsize <= 4 else a.astype(np.float64)
+        if a.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))
+            a = a.reshape(-1)[idx]
+        arrays[name] = a
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs, more than {DUMP_BUDGET_BYTES >> 20} MB")
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def host_cores():
@@ -271,6 +305,8 @@ def side_workload(args, device):
         sec = time_steps(lambda: AEEngine.group_train_step(es, xs, ys, al, lr), args.steps, args.warmup)
         if any(e.gate_timeouts() for e in es):
             raise SystemExit("a gate time-out in the timed region")
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, [(f"cfg{i}.", m, e) for i, (m, e) in enumerate(engs)])
         print(json.dumps({"metric": "EuroSAT 64x64 RGB images/sec (AE+MLP train step)", "value": round(8 * 64 / sec, 1), "unit": "images/s", "n_gpus": 1,
                           "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * sec, 4), "higher_is_better": True, "scaling": "weak",
                           "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
@@ -296,6 +332,8 @@ def side_workload(args, device):
     loss = float(eng.loss_last[0].item())
     if not np.isfinite(loss) or eng.gate_timeouts():
         raise SystemExit("non-finite loss or a gate time-out in the timed region")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [("", model, eng)])
     out = {"metric": "EuroSAT 64x64 RGB images/sec (AE+MLP train step)", "value": round(batch / sec, 1), "unit": "images/s", "n_gpus": 1,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * sec, 4), "higher_is_better": True, "scaling": "weak",
            "vs_baseline": None, "dtype": dtype, "data": "synthetic",
@@ -318,6 +356,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-configs", action="store_true", help="skip the extra BASELINE configs[1] measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs that take runs of their own: live kernel roofline, the other BASELINE configs, the CPU baseline "
+                         "(--no-roofline / --no-configs / --no-cpu-baseline drop single legs of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss scalars, parameters, BatchNorm buffers) as DIR/<name>.npy")
     ap.add_argument("--workload", choices=("c3", "c2", "c5fp8", "c5bf16", "grid8"), default="c3",
                     help="c3 = BASELINE configs[2], the headline (default); the others run the same loop over configs[1] / configs[4]'s shape")
     args = ap.parse_args()
@@ -391,6 +434,8 @@ def main():
         raise SystemExit("a side-stream gate timed out in the timed region (results invalid)")
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, [("", model, eng)])
         total_images = args.batch * world * args.steps
         value = total_images / el
         ms = 1e3 * el / args.steps
@@ -416,13 +461,13 @@ def main():
         out["step_roofline"] = {"hbm_floor_us": round(step_bytes / (HBM_PEAK_GBS * 1e3), 1),
                                 "mfma_floor_us": round(args.batch * FLOP_PER_IMG_TRAIN / (MFMA_BF16_PEAK_TFLOPS * 1e6), 1),
                                 "frac_of_hbm_floor": round(step_bytes / (HBM_PEAK_GBS * 1e3) / (ms * 1e3), 4)}
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             try:
                 # local steps only: the other ranks have left the loop, so no collective may be issued from here
                 out["roofline"] = kernel_roofline(eng, lambda: eng.train_step(x, y, ALPHA, LR), args.batch)
             except Exception as e:  # the headline number must still be printed
                 out["roofline"] = {"error": str(e)[:200]}
-        if world == 1 and not args.no_configs:
+        if args.full and world == 1 and not args.no_configs:
             # the other single-GPU BASELINE config, measured the same way (not the headline: parity-tested in tests/):
             # configs[1] = batch 256, encoder + decoder reconstruction (MSE) only
             try:
@@ -448,7 +493,7 @@ def main():
                 out["configs"]["grid_b64"]["vs_b512_single_model"] = round(out["configs"]["grid_b64"]["images_per_s"] / value, 3)
             except Exception as e:
                 out.setdefault("configs", {})["grid_b64"] = {"error": str(e)[:200]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline()
             except Exception as e:

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -77,8 +78,8 @@ def test_site_of_and_site_model_on_every_kernel_name_of_the_committed_summaries(
 
 @pytest.mark.gpu
 def test_bench_line_contract_and_roofline_arithmetic():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-configs"],
-                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline",
+                        "--no-configs"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines                     # ONE JSON line on stdout
@@ -121,3 +122,68 @@ def test_bench_side_workload_line_carries_its_own_roofline():
     prof = rf["from_committed_profile"]
     assert prof["summary"].startswith(("profiles/r03_bench_c2_", "profiles/r04_bench_c2_")) and prof["summary_commit"]
     assert rf["traffic"] == prof["pmc_traffic_bytes_per_launch"]
+
+
+def test_dump_outputs_writes_float_arrays_samples_large_ones_and_keeps_the_budget(tmp_path, monkeypatch):
+    """bench.dump_outputs on host tensors: one <name>.npy per array (float32, integer counters as float64), an array above
+    DUMP_SAMPLE elements as the same seeded sample every time, and nothing written when the whole would exceed the budget."""
+    import torch
+    import bench
+
+    class Eng:
+        loss_last = torch.tensor([1.5, 0.25, 2.0, 0.0])
+        loss_accum = torch.arange(8, dtype=torch.float32)
+
+    torch.manual_seed(0)
+    m = torch.nn.Sequential(torch.nn.Linear(4096, 300), torch.nn.BatchNorm1d(300))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), [("", m, Eng())])
+    names = {f[:-4] for f in os.listdir(tmp_path / "a")}
+    assert names == {"loss_last", "loss_accum"} | {"state." + k for k in m.state_dict()}
+    for n in names:
+        a, b = np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "loss_last.npy"), Eng.loss_last.numpy())
+    assert np.load(tmp_path / "a" / "state.1.num_batches_tracked.npy").dtype == np.float64
+    w = m[0].weight.detach().numpy().reshape(-1)
+    got = np.load(tmp_path / "a" / "state.0.weight.npy")
+    assert w.size > bench.DUMP_SAMPLE and got.shape == (bench.DUMP_SAMPLE,) and np.isin(got, w).all()
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "state.0.bias.npy"), m[0].bias.detach().numpy())
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 1 << 20)
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "c"), [("", m, Eng())])
+    assert not os.listdir(tmp_path / "c")
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """A plain run times exactly --steps steps and prints the headline line without the --full legs; --dump-outputs holds the
+    state the timed steps left: every state_dict entry, BatchNorm counters at warmup + steps, the loss of the last step."""
+    import torch
+    import eae_amd
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["steps"] == 7 and d["warmup"] == 3 and d["unit"] == "images/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert abs(d["value"] - 512 / (d["ms_per_step"] * 1e-3)) <= 1e-3 * d["value"]
+    assert not {"roofline", "configs", "cpu_baseline"} & set(d), sorted(d)
+    torch.manual_seed(0)
+    init = eae_amd.SupervisedAutoencoder(latent_dim=64, num_classes=10).state_dict()
+    files = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert set(files) == {"loss_last", "loss_accum"} | {"state." + k for k in init}
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    for n, a in files.items():
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), n
+    for k, v in init.items():
+        a = files["state." + k]
+        if k.endswith("num_batches_tracked"):
+            assert a == 10, (k, a)
+        else:
+            assert a.shape == tuple(v.shape), k
+    assert np.abs(files["state.enc.encoder.0.weight"] - init["enc.encoder.0.weight"].numpy()).max() > 0
+    assert abs(float(files["loss_last"][0]) - d["config"]["final_loss"]) <= 1e-4
+    assert files["loss_accum"][3] == 512 * 10          # images accumulated over warmup + timed steps

@@ -1,6 +1,6 @@
 """Parameter hash after each of 7 train steps, eager or (EAE_GRAPH=1) graph path, for the product library or a variant (EAE_LIB_PATH).  Diagnostic tool (GPU box)."""
 import os, sys, hashlib
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np, torch
 import golden_util as gu
 from helpers import ae_state_np, load_state_np

@@ -2,7 +2,7 @@
 single-stream contexts from four threads, c = one group of 8 on the default stream, d = two groups of 8 from two threads, e = the same for 10 steps only; e.g.
 `python tools/grid_order_probe.py cd`.  Diagnostic tool (GPU box)."""
 import os, sys, time, gc, torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 import eae_amd
 from eae_amd.engine import AEEngine, engine_for
