@@ -6,12 +6,12 @@ that restate its inline loops.  All arithmetic runs in hand-written gfx950 HIP k
 C ABI declared in ``include/eae.h``.
 """
 from .modules import Encoder, Decoder, SupervisedAutoencoder, MLP  # noqa: F401
-from .augment import augment_batch  # noqa: F401
+from .augment import augment_batch, stage_bands  # noqa: F401
 from .train import (fit_autoencoder, grid_search_autoencoder, extract_features, fit_mlp, grid_search_mlp,  # noqa: F401
                     evaluate)
 from .report import confusion_matrix, classification_report, loss_heatmap  # noqa: F401
 from .probe import ce_mse_ratio_probe  # noqa: F401
 
 __all__ = ["Encoder", "Decoder", "SupervisedAutoencoder", "MLP", "fit_autoencoder", "grid_search_autoencoder",
-           "extract_features", "fit_mlp", "grid_search_mlp", "evaluate", "augment_batch",
+           "extract_features", "fit_mlp", "grid_search_mlp", "evaluate", "augment_batch", "stage_bands",
            "confusion_matrix", "classification_report", "loss_heatmap", "ce_mse_ratio_probe"]

@@ -14,7 +14,7 @@ vp = C.c_void_p
 
 class EaeConfig(C.Structure):
     _fields_ = [("latent_dim", C.c_int), ("num_classes", C.c_int), ("image_h", C.c_int), ("image_w", C.c_int),
-                ("max_batch", C.c_int), ("quant", C.c_int), ("side_streams", C.c_int)]
+                ("max_batch", C.c_int), ("quant", C.c_int), ("side_streams", C.c_int), ("in_channels", C.c_int)]
 
 
 class EaeStepIO(C.Structure):
@@ -99,6 +99,13 @@ _PROTOS = {
     "eae_op_head_scratch_floats": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
     "eae_op_head_ce": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_longlong]),
     "eae_op_sigmoid_bwd": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "eae_op_pack_edge": (C.c_int, [vp, vp, C.c_int, vp, vp]),
+    "eae_op_edge_conv_c": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp]),
+    "eae_op_edge_wgrad_c": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, EaeSrc, vp, C.c_longlong, vp]),
+    "eae_op_deconv4_loss_c": (C.c_int, [vp, EaeSrc, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_float, vp, vp, vp]),
+    "eae_op_sigmoid_bwd_c": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "eae_stage_bands": (C.c_int, [vp, vp, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_float,
+                                  C.c_ulonglong, C.c_ulonglong, vp, vp]),
     "eae_augment": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_ulonglong, C.c_ulonglong, vp, vp]),
     "eae_op_adam": (C.c_int, [vp, vp, vp, vp, vp, C.c_longlong, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_longlong]),
     "eae_mlp_layout": (C.c_int, [C.c_int, C.c_int, c_ll_p, c_ll_p]),

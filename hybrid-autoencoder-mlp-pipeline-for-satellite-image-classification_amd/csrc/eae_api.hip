@@ -46,12 +46,14 @@ const int W3_B[6] = {32, 64, 128, 128, 64, 32};
 const int PREBN_BIAS[7] = {1, 5, 9, 13, 21, 25, 29};  // biases in front of a BatchNorm: gradient is identically zero
 
 long long r4(long long n) { return (n + 3) & ~3LL; }
+int bands_of(const eae_config& c) { return c.in_channels == 0 ? 3 : c.in_channels; }     // in_channels 0 = RGB
 
 void param_sizes(const eae_config& c, long long* sz) {
   const long long P = (long long)(c.image_h / 16) * (c.image_w / 16), K = 256 * P, L = c.latent_dim, C = c.num_classes;
-  const long long s[38] = {32 * 27, 32, 32, 32, 64 * 32 * 9, 64, 64, 64, 128 * 64 * 9, 128, 128, 128, 256 * 128 * 9, 256, 256, 256,
+  const long long N = bands_of(c);      // conv1 weight [32,N,3,3], deconv4 weight [32,N,3,3] ([Cin,Cout,kh,kw]) and bias [N]
+  const long long s[38] = {32 * 9 * N, 32, 32, 32, 64 * 32 * 9, 64, 64, 64, 128 * 64 * 9, 128, 128, 128, 256 * 128 * 9, 256, 256, 256,
                            L * K, L, K * L, K, 256 * 128 * 9, 128, 128, 128, 128 * 64 * 9, 64, 64, 64, 64 * 32 * 9, 32, 32, 32,
-                           32 * 27, 3, 128 * L, 128, C * 128, C};
+                           32 * 9 * N, N, 128 * L, 128, C * 128, C};
   for (int i = 0; i < 38; ++i) sz[i] = s[i];
 }
 
@@ -62,6 +64,8 @@ int check_cfg(const eae_config* c) {
   if (c->num_classes <= 0 || c->num_classes > 64) return eae_set_error(EAE_ERR_ARG, "num_classes must be in 1..64");
   if (c->max_batch <= 0) return eae_set_error(EAE_ERR_ARG, "max_batch must be positive");
   if (c->quant != 0 && c->quant != 1) return eae_set_error(EAE_ERR_ARG, "quant must be 0 (bf16) or 1 (fp8 conv GEMMs)");
+  if (c->in_channels < 0 || c->in_channels > 16) return eae_set_error(EAE_ERR_ARG, "in_channels must be in 1..16 (0 = 3)");
+  if (c->quant == 1 && bands_of(*c) != 3) return eae_set_error(EAE_ERR_ARG, "quant=1 (fp8) supports in_channels = 3 only");
   if (c->quant == 1 && (c->image_h % 128 || c->image_w % 256))
     return eae_set_error(EAE_ERR_ARG, "quant=1: the fp8 kernels are built for 16 x 8 tiles on every map (image height % 128 == 0, width % 256 == 0)");
   return 0;
@@ -72,6 +76,7 @@ int check_cfg(const eae_config* c) {
 struct eae_ctx {
   eae_config cfg;
   int H, W, L, C, Bm;
+  int Cin = 3, CP = 4;             // image bands (eae_config::in_channels) and their padded width in the edge kernels (edge_cp)
   // The latent-projection kernels work on a latent width padded to a multiple of 64 (Lp): the padded weight rows / columns are
   // zero in the packs, so the padded latent columns are exactly zero.  When Lp != L (`lpad`) the kernels that produce gradients in
   // parameter layout write padded shadows (gs_*), which compact_* copies into the gradient arena; with Lp == L they write the arena.
@@ -244,6 +249,7 @@ extern "C" int eae_create(const eae_config* cfg, eae_ctx** out) {
   if (int rc = check_cfg(cfg)) return rc;
   eae_ctx* c = new eae_ctx();
   c->cfg = *cfg; c->H = cfg->image_h; c->W = cfg->image_w; c->L = cfg->latent_dim; c->C = cfg->num_classes; c->Bm = cfg->max_batch;
+  c->Cin = bands_of(*cfg); c->CP = edge_cp(c->Cin);
   c->Lp = (c->L + 63) / 64 * 64; c->lpad = c->Lp != c->L;
   c->Pn = (long long)(c->H / 16) * (c->W / 16); c->K = 256 * c->Pn;
   eae_ae_layout(cfg, c->poff, c->bnoff);
@@ -257,7 +263,7 @@ extern "C" int eae_create(const eae_config* cfg, eae_ctx** out) {
   const unsigned dy_mask_env = (getenv("EAE_DY_MASK") ? (unsigned)strtoul(getenv("EAE_DY_MASK"), nullptr, 0) : 0u) & 0x3cu;
   for (int i = 1; i < 4; ++i) o_dyy[i] = ((dy_mask_env >> i) & 1u) ? carve(Bm * c->act_elems(i + 1) * 2) : 0;
   for (int i = 0; i < 3; ++i) o_dyu[i] = ((dy_mask_env >> (4 + i)) & 1u) ? carve(Bm * c->act_elems(3 - i) * 2) : 0;
-  size_t o_d0 = carve(Bm * c->K * 2), o_gd0 = carve(Bm * c->K * 2), o_g4 = carve(Bm * (size_t)c->H * c->W * 4 * 2);
+  size_t o_d0 = carve(Bm * c->K * 2), o_gd0 = carve(Bm * c->K * 2), o_g4 = carve(Bm * (size_t)c->H * c->W * c->CP * 2);
   size_t o_z = carve(Bm * c->Lp * 4), o_dz = carve(Bm * c->Lp * 4), o_dzc = carve(Bm * c->Lp * 4);
   size_t o_cf[7], o_cb[7];
   for (int l = 0; l < 7; ++l) { o_cf[l] = carve(4 * BN_C[l] * 4); o_cb[l] = carve(3 * BN_C[l] * 4); }
@@ -286,7 +292,7 @@ extern "C" int eae_create(const eae_config* cfg, eae_ctx** out) {
     if (getenv("EAE_ONE_SIDE_STREAM")) c->nx = 0;
   }
   for (int i = 0; i < c->nx; ++i) o_wscrx[i] = carve(c->wscratch_floats * 4);
-  size_t o_wscrm = carve((size_t)2048 * 864 * 4);
+  size_t o_wscrm = carve((size_t)2048 * 288 * c->Cin * 4);
   size_t o_acc[7], acc_total = 0;
   {
     const int Bi = (int)Bm;
@@ -306,7 +312,7 @@ extern "C" int eae_create(const eae_config* cfg, eae_ctx** out) {
   size_t o_accb = carve(2 * acc_total + 32);  // forward accumulators, then the backward ones (cleared together)   // conv1 weight gradient (last kernel of the backward, runs on the main stream)
   const int ksplit = (int)(c->K / 128);
   size_t o_fcp = carve((size_t)ksplit * Bm * c->Lp * 4);
-  size_t o_mse = carve(std::max((size_t)eae_edge_tiles((int)Bm, c->H, c->W), (size_t)((Bm * c->H * c->W + 255) / 256)) * 4 * 4);
+  size_t o_mse = carve(std::max((size_t)eae_edge_tiles((int)Bm, c->H, c->W), (size_t)((Bm * c->H * c->W + 255) / 256)) * edge_lp_stride(c->Cin) * 4);
   const long long hb = eae_head_blocks((int)Bm, 256);     // (the narrow-row variant of wide latents has the most blocks)
   c->head_stride = r4(128LL * c->Lp) + 128 + r4(128LL * c->C) + r4(c->C);
   size_t o_gsew = 0, o_gseb = 0, o_gsdw = 0, o_gsh = 0, o_zst = 0;
@@ -324,7 +330,8 @@ extern "C" int eae_create(const eae_config* cfg, eae_ctx** out) {
     d.lv = d0; d.q_layer = -1;
     descs.push_back(d);
   };
-  c->pk_c1 = pcarve(32 * 64 * 2); add(c->poff[0], c->pk_c1, 32 * 64, PACK_K36, 32, 3, 0, 0);
+  const int KP = (9 * c->CP + 31) / 32 * 32;      // conv1 / deconv4-backward pack [32][KP] (edge_conv_kernel)
+  c->pk_c1 = pcarve(32 * KP * 2); add(c->poff[0], c->pk_c1, 32 * KP, PACK_KCP, 32, c->Cin, c->CP, 0);
   for (int i = 0; i < 6; ++i) {
     long long n = (long long)W3_A[i] * W3_B[i] * 9;
     c->pk_p1[i] = pcarve(n * 2); add(c->poff[W3_PARAM[i]], c->pk_p1[i], n, PACK_3x3_P1, W3_A[i], W3_B[i], 0, 0);
@@ -335,8 +342,8 @@ extern "C" int eae_create(const eae_config* cfg, eae_ctx** out) {
     }
   }
   c->fp8 = cfg->quant == 1;
-  c->pk_d4j = pcarve(16 * 128 * 2); add(c->poff[32], c->pk_d4j, 16 * 128, PACK_DECONV4_JOINT, 0, 0, 0, 0);
-  c->pk_d4k = pcarve(32 * 64 * 2); add(c->poff[32], c->pk_d4k, 32 * 64, PACK_K36, 32, 3, 0, 0);
+  c->pk_d4j = pcarve(4 * c->CP * 128 * 2); add(c->poff[32], c->pk_d4j, 4 * c->CP * 128, PACK_DECONV4_JOINT, 0, c->Cin, 0, 0);
+  c->pk_d4k = pcarve(32 * KP * 2); add(c->poff[32], c->pk_d4k, 32 * KP, PACK_KCP, 32, c->Cin, c->CP, 0);
   const long long LK = c->Lp * c->K;      // d0 = padded latent width, lv = the real one (rows / columns beyond it are zero)
   c->pk_we1 = pcarve(LK * 2); add(c->poff[16], c->pk_we1, LK, PACK_FC_ROWMAJOR_KPERM, c->Lp, 256, (int)c->Pn, 0);
   c->pk_we2 = pcarve(LK * 2); add(c->poff[16], c->pk_we2, LK, PACK_FC_TRANS_KPERM, c->Lp, 256, (int)c->Pn, 0);
@@ -401,7 +408,7 @@ extern "C" int eae_create(const eae_config* cfg, eae_ctx** out) {
   c->use_graph = getenv("EAE_GRAPH") != nullptr && getenv("EAE_NO_GRAPH") == nullptr;
   e = hipMemcpy(c->descs_dev, descs.data(), descs.size() * sizeof(PackDesc), hipMemcpyHostToDevice);
   if (e == hipSuccess && c->blk_tot > 0) e = hipMemcpy(c->blkmap, blkmap.data(), (size_t)c->blk_tot * sizeof(unsigned short), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(c->g4, 0, Bm * (size_t)c->H * c->W * 4 * 2);
+  if (e == hipSuccess) e = hipMemset(c->g4, 0, Bm * (size_t)c->H * c->W * c->CP * 2);
   if (e == hipSuccess && c->lpad) e = hipMemset(c->zstage, 0, Bm * (size_t)c->Lp * 4);
   if (e == hipSuccess) e = hipMemset(c->z, 0, Bm * (size_t)c->Lp * 4);
   if (e == hipSuccess) e = hipMemset(c->dz, 0, Bm * (size_t)c->Lp * 4);
@@ -980,7 +987,7 @@ int run_encoder(eae_ctx* c, hipStream_t st, const float* x, int B, bool train) {
   const int H = c->H, W = c->W;
   {
     EdgeArgs a;
-    a.src3 = x; a.B = B; a.H = H; a.W = W;
+    a.src3 = x; a.B = B; a.H = H; a.W = W; a.C = c->Cin;
     a.c = ConvArgs();
     a.c.wpack = (const bf16_t*)(c->pack + c->pk_c1); a.c.bias = c->P + c->poff[1]; a.c.out = c->y[0];
     a.c.stat_part = train ? c->stat : nullptr; a.c.B = B;
@@ -1058,7 +1065,7 @@ int run_decoder(eae_ctx* c, hipStream_t st, const float* z, int B, bool train, c
   d.src = src_bnrelu(c->u[2], c->coef_f[6]);
   d.wjoint = (const bf16_t*)(c->pack + c->pk_d4j); d.bias = c->P + c->poff[33];
   d.x = target; d.x_hat = x_hat; d.g4 = want_grad ? c->g4 : nullptr; d.loss_part = (want_loss || want_grad) ? c->msepart : nullptr;
-  d.gscale = gscale; d.B = B; d.Hin = H / 2; d.Win = W / 2;
+  d.gscale = gscale; d.B = B; d.Hin = H / 2; d.Win = W / 2; d.C = c->Cin;
   fold_consumer(c, d.fold, 6, (long long)B * (H / 2) * (W / 2), train);
   {
     ProfBracket pb(c, EAE_PROF_DECONV4_LOSS, st);
@@ -1098,7 +1105,7 @@ int forward_impl(eae_ctx* c, hipStream_t st, const eae_step_io* io, bool want_gr
   RC(ensure_packed(c, st));
   RC(prep_accumulators(c, st, train));
   RC(run_encoder(c, st, io->x, B, train));
-  const double numel = (double)B * 3.0 * c->H * c->W;
+  const double numel = (double)B * c->Cin * c->H * c->W;
   const float gscale = (float)(2.0 * io->alpha / numel);
   const bool want_loss = io->loss_accum || io->loss_last;
   const bool head = io->head != 0;
@@ -1130,12 +1137,13 @@ int forward_impl(eae_ctx* c, hipStream_t st, const eae_step_io* io, bool want_gr
       float *accum = io->loss_accum, *last = io->loss_last;
       const int ntile = eae_edge_tiles(B, c->H, c->W);
       sq_push(c, [=](hipStream_t ls, float*) {
-        return eae_launch_loss_finalize(ls, c->msepart, ntile, c->cepart, n_ce, alpha, numel, B, c->G + c->poff[33], accum, last, poison_word(c));
+        return eae_launch_loss_finalize(ls, c->msepart, ntile, c->cepart, n_ce, alpha, numel, B, c->G + c->poff[33], accum, last, poison_word(c),
+                                        c->Cin);
       }, 0);
       sq_fork(c);                  // released by the first kernel of the backward-data chain (backward_impl commits behind it)
     } else {
       RC(eae_launch_loss_finalize(st, c->msepart, eae_edge_tiles(B, c->H, c->W), c->cepart, n_ce, io->alpha, numel, B,
-                                  want_grad ? c->G + c->poff[33] : nullptr, io->loss_accum, io->loss_last, poison_word(c)));
+                                  want_grad ? c->G + c->poff[33] : nullptr, io->loss_accum, io->loss_last, poison_word(c), c->Cin));
     }
   }
   return 0;
@@ -1188,14 +1196,15 @@ int backward_impl(eae_ctx* c, hipStream_t st, const eae_step_io* io, const float
       }, 0);
     }
     sq_push(c, [=](hipStream_t ss, float* scr) {
-      return eae_launch_edge_wgrad(ss, SRC3_NHWC4_BF16, c->g4, B, H, W, src_bnrelu(c->u[2], c->coef_f[6]), SRC_BNRELU, scr,
-                                   c->wscratch_floats, c->G + c->poff[32], prof_hook_for(c, EAE_PROF_SITE(7, 2)));
+      return eae_launch_edge_wgrad(ss, SRC3_NHWCP_BF16, c->g4, B, H, W, src_bnrelu(c->u[2], c->coef_f[6]), SRC_BNRELU, scr,
+                                   c->wscratch_floats, c->G + c->poff[32], prof_hook_for(c, EAE_PROF_SITE(7, 2)), nullptr, nullptr, 0,
+                                   nullptr, nullptr, c->Cin);
     }, 0);
     sq_fork(c);
     // ---- deconv4: backward-data into u[2]'s BN+ReLU
     {
       EdgeArgs a;
-      a.src3 = c->g4; a.B = B; a.H = H; a.W = W;
+      a.src3 = c->g4; a.B = B; a.H = H; a.W = W; a.C = c->Cin;
       a.c = ConvArgs();
       a.c.wpack = (const bf16_t*)(c->pack + c->pk_d4k); a.c.out = c->gu[2]; a.c.stat_part = c->stat;
       a.c.yprev = c->u[2]; a.c.prev_coef = c->coef_f[6]; a.c.B = B;
@@ -1203,7 +1212,7 @@ int backward_impl(eae_ctx* c, hipStream_t st, const eae_step_io* io, const float
       take_sig(c, a.c);
       {
         ProfBracket pb(c, EAE_PROF_DECONV4_BWD, st);
-        RC(eae_launch_edge_conv(st, SRC3_NHWC4_BF16, EPI_MASK, a));
+        RC(eae_launch_edge_conv(st, SRC3_NHWCP_BF16, EPI_MASK, a));
       }
       RC(sq_commit(c, st));
       RC(bn_bwd_fin(c, st, 6, eae_edge_tiles(B, H, W), (long long)B * (H / 2) * (W / 2)));
@@ -1406,8 +1415,8 @@ int backward_impl(eae_ctx* c, hipStream_t st, const eae_step_io* io, const float
     struct Mid { eae_ctx* c; hipStream_t st; } mid = {c, st};
     auto mid_fn = [](void* u, GateArgs* g) { Mid* m = static_cast<Mid*>(u); return join_side_begin(m->c, m->st, g); };
     RC(eae_launch_edge_wgrad(st, SRC3_NCHW_F32, io->x, B, H, W, src_bnbwd(c->gy[0], c->y[0], c->coef_b[0]), SRC_BNBWD, c->wscratch_main,
-                             2048LL * 864, c->G + c->poff[0], prof_hook_for(c, EAE_PROF_CONV1_WGRAD), &bf0, sg.sig, sg.sig_val,
-                             tail_gate ? +mid_fn : nullptr, &mid));
+                             2048LL * 288 * c->Cin, c->G + c->poff[0], prof_hook_for(c, EAE_PROF_CONV1_WGRAD), &bf0, sg.sig, sg.sig_val,
+                             tail_gate ? +mid_fn : nullptr, &mid, c->Cin));
   }
   RC(join_side(c, st));                                 // (nothing left to wait for when the gate went with the reduction)
   if (c->fp8) RC(eae_launch_fp8_scales(st, c->q));      // every reader of this step's scales has finished: derive the next step's
@@ -1440,9 +1449,9 @@ extern "C" int eae_ae_backward(eae_ctx* c, void* stream, long long generation, c
   const int B = c->fwd_B;
   eae_step_io io = eae_step_io();
   io.x = x; io.B = B; io.train = 1; io.head = (dlogits != nullptr) ? 1 : 0;
-  RC(eae_launch_sigmoid_bwd(st, x_hat, dx_hat, c->g4, c->msepart, B, c->H, c->W));
+  RC(eae_launch_sigmoid_bwd(st, x_hat, dx_hat, c->g4, c->msepart, B, c->H, c->W, c->Cin));
   const int nblk = (int)(((long long)B * c->H * c->W + 255) / 256);
-  RC(eae_launch_loss_finalize(st, c->msepart, nblk, nullptr, 0, 0.f, 1.0, B, c->G + c->poff[33], nullptr, nullptr));
+  RC(eae_launch_loss_finalize(st, c->msepart, nblk, nullptr, 0, 0.f, 1.0, B, c->G + c->poff[33], nullptr, nullptr, nullptr, c->Cin));
   if (dlogits) RC(run_head(c, st, B, nullptr, nullptr, true, dlogits));
   // An eval-mode forward normalises with the running statistics: y -> gamma*(y - rm)*invstd_r + beta is affine per channel, so its
   // backward is dy = gamma*invstd_r * g with dgamma = sum g*xhat_r, dbeta = sum g -- the same kernels with the batch-size terms
@@ -1706,6 +1715,7 @@ int group_run(int what, eae_ctx* const* ctxs, int n, int mult, void* stream, con
     if (what == 0 && (!c->M || !c->V)) return eae_set_error(EAE_ERR_STATE, "adam: moment arenas must be bound");
     if (c->prof_on || c->fp8 || c->dp_comm || c->use_gates != c0->use_gates || c->use_side != c0->use_side || c->nx != c0->nx)
       return eae_set_error(EAE_ERR_STATE, "group call: members must share the stream layout, with profiling, fp8 and data parallel off");
+    if (c->Cin != c0->Cin) return eae_set_error(EAE_ERR_ARG, "group call: members must share in_channels");
     for (int j = 0; j < k; ++j) if (ctxs[j] == c) return eae_set_error(EAE_ERR_ARG, "group call: a context appears twice");
   }
   RC(streams_distinct(c0, user));
@@ -1834,9 +1844,9 @@ extern "C" int eae_decoder_backward(eae_ctx* c, void* stream, long long generati
   const int B = c->fwd_B;
   eae_step_io io = eae_step_io();
   io.B = B; io.train = 1; io.head = 0;
-  RC(eae_launch_sigmoid_bwd(st, x_hat, dx_hat, c->g4, c->msepart, B, c->H, c->W));
+  RC(eae_launch_sigmoid_bwd(st, x_hat, dx_hat, c->g4, c->msepart, B, c->H, c->W, c->Cin));
   const int nblk = (int)(((long long)B * c->H * c->W + 255) / 256);
-  RC(eae_launch_loss_finalize(st, c->msepart, nblk, nullptr, 0, 0.f, 1.0, B, c->G + c->poff[33], nullptr, nullptr));
+  RC(eae_launch_loss_finalize(st, c->msepart, nblk, nullptr, 0, 0.f, 1.0, B, c->G + c->poff[33], nullptr, nullptr, nullptr, c->Cin));
   c->bwd_eval = c->dec_ready == 2;
   if (c->bwd_eval) c->prebn_dirty = true;
   int rc = backward_impl(c, st, &io, nullptr, 1);
@@ -2120,6 +2130,54 @@ extern "C" int eae_op_deconv4_loss(void* stream, eae_src a3, int B, int Hin, int
   d.loss_part = loss_part; d.gscale = gscale; d.B = B; d.Hin = Hin; d.Win = Win;
   return eae_launch_deconv4_loss((hipStream_t)stream, a3.mode, d);
 }
+// C-band forms of the four edge ops (in_channels 1..16; the ops above are these at C = 3)
+extern "C" int eae_op_edge_conv_c(void* stream, int src_kind, const void* src, int C, int B, int H, int W, const void* wpack,
+                                  const float* bias, void* out, float* stat_part, int epilogue, const void* yprev, const float* prev_coef) {
+  EdgeArgs a;
+  a.src3 = src; a.B = B; a.H = H; a.W = W; a.C = C;
+  a.c = ConvArgs();
+  a.c.wpack = (const bf16_t*)wpack; a.c.bias = bias; a.c.out = (bf16_t*)out; a.c.stat_part = stat_part;
+  a.c.yprev = (const bf16_t*)yprev; a.c.prev_coef = prev_coef; a.c.B = B;
+  return eae_launch_edge_conv((hipStream_t)stream, src_kind, epilogue, a);
+}
+extern "C" int eae_op_edge_wgrad_c(void* stream, int src_kind, const void* src, int C, int B, int H, int W, eae_src side, float* scratch,
+                                   long long scratch_floats, float* dw) {
+  return eae_launch_edge_wgrad((hipStream_t)stream, src_kind, src, B, H, W, to_src(side), side.mode, scratch, scratch_floats, dw,
+                               nullptr, nullptr, nullptr, 0, nullptr, nullptr, C);
+}
+extern "C" int eae_op_deconv4_loss_c(void* stream, eae_src a3, int C, int B, int Hin, int Win, const void* wjoint, const float* bias,
+                                     const float* x, float gscale, float* x_hat, void* g, float* loss_part) {
+  Deconv4Args d = Deconv4Args();
+  d.src = to_src(a3); d.wjoint = (const bf16_t*)wjoint; d.bias = bias; d.x = x; d.x_hat = x_hat; d.g4 = (bf16_t*)g;
+  d.loss_part = loss_part; d.gscale = gscale; d.B = B; d.Hin = Hin; d.Win = Win; d.C = C;
+  return eae_launch_deconv4_loss((hipStream_t)stream, a3.mode, d);
+}
+extern "C" int eae_op_sigmoid_bwd_c(void* stream, const float* x_hat, const float* dx_hat, int C, int B, int H, int W, void* g, float* db,
+                                    float* scratch) {
+  hipStream_t st = (hipStream_t)stream;
+  RC(eae_launch_sigmoid_bwd(st, x_hat, dx_hat, g, scratch, B, H, W, C));
+  const int nblk = (int)(((long long)B * H * W + 255) / 256);
+  return eae_launch_loss_finalize(st, scratch, nblk, nullptr, 0, 0.f, 1.0, B, db, nullptr, nullptr, nullptr, C);
+}
+extern "C" int eae_op_pack_edge(void* stream, const float* w, int C, void* wpack, void* wjoint) {
+  // the engine's own conv1 / deconv4 pack descriptors (eae_create) in a two-entry table allocated for the call; synchronises its stream
+  if (C < 1 || C > 16) return eae_set_error(EAE_ERR_ARG, "pack_edge: in_channels must be in 1..16");
+  if (!w || !wpack) return eae_set_error(EAE_ERR_ARG, "pack_edge: w and wpack are required");
+  const int CP = edge_cp(C), KP = (9 * CP + 31) / 32 * 32;
+  PackDesc d[2];
+  d[0] = PackDesc{0, 0, 32LL * KP, PACK_KCP, 32, C, CP, 0, 0, -1};
+  d[1] = PackDesc{0, wjoint ? (long long)((char*)wjoint - (char*)wpack) : 0, 4LL * CP * 128, PACK_DECONV4_JOINT, 0, C, 0, 0, 0, -1};
+  PackDesc* dev = nullptr;
+  EAE_HIP(hipMalloc(&dev, sizeof(d)));
+  hipError_t e = hipMemcpyAsync(dev, d, sizeof(d), hipMemcpyHostToDevice, (hipStream_t)stream);
+  int rc = e == hipSuccess ? eae_launch_pack_all((hipStream_t)stream, dev, wjoint ? 2 : 1, w, wpack) : 0;
+  const hipError_t es = hipStreamSynchronize((hipStream_t)stream);     // the table is freed below: the launch must have finished
+  hipFree(dev);
+  if (e != hipSuccess) return eae_set_error(EAE_ERR_HIP, hipGetErrorString(e));
+  if (rc) return rc;
+  if (es != hipSuccess) return eae_set_error(EAE_ERR_HIP, hipGetErrorString(es));
+  return 0;
+}
 extern "C" int eae_op_wgrad_s2(void* stream, eae_src small_src, eae_src big_src, int cs, int cb, int B, int Hs, int Ws, float* scratch,
                                long long scratch_floats, float* dw) {
   WgradArgs w = WgradArgs();
@@ -2213,6 +2271,12 @@ extern "C" int eae_op_pack3x3(void* stream, const float* w, int A, int B, void* 
   hipStreamSynchronize((hipStream_t)stream);
   hipFree(dev);
   return rc;
+}
+extern "C" int eae_stage_bands(void* stream, const void* src, int elem_bytes, long long N, int C, int H, int W, const long long* index,
+                               int B, const float* divisor, float* out, int train, float noise_std, unsigned long long seed,
+                               unsigned long long step, const int* params, const float* noise) {
+  return eae_launch_stage_bands((hipStream_t)stream, src, elem_bytes, N, C, H, W, index, B, divisor, out, train, noise_std, seed, step, params,
+                                noise);
 }
 extern "C" int eae_augment(void* stream, const void* in_u8, float* out, int B, int H, int W, int train, float noise_std,
                            unsigned long long seed, unsigned long long step, const int* params, const float* noise) {

@@ -1,8 +1,10 @@
-// Kernels for the two 3-channel "edge" layers, which carry the most bytes and the least math (hard parts):
-//   enc.conv1  (R.md:292)  x fp32 NCHW [B,3,H,W]            -> y1 [B,H/2,W/2,32]
-//   dec.deconv4 (R.md:382) a3 [B,H/2,W/2,32] -> sigmoid -> x_hat [B,3,H,W], fused with MSE loss and its gradient
-// K = 27 is padded to 32 in LDS only (one v_mfma_f32_16x16x32_bf16 K-step), N = 3 is handled by computing the four
-// sub-pixel phases jointly (N = 4 phases x 3 channels = 12 of 16 MFMA columns), never by padding in HBM.
+// Kernels for the two C-band "edge" layers (C = 1..16 image bands, 3 for RGB), which carry the most bytes and the least math
+// (hard parts):
+//   enc.conv1  (R.md:292)  x fp32 NCHW [B,C,H,W]            -> y1 [B,H/2,W/2,32]
+//   dec.deconv4 (R.md:382) a3 [B,H/2,W/2,32] -> sigmoid -> x_hat [B,C,H,W], fused with MSE loss and its gradient
+// The bands are padded to CP = 4 / 8 / 16 in LDS and in deconv4's bf16 output gradient only: K = 9*CP is padded to 64 / 96 / 160
+// (2 / 3 / 5 v_mfma_f32_16x16x32_bf16 K-steps), and N = C is handled by computing the four sub-pixel phases jointly (N = 4 phases x C
+// bands in 1, 2 or 4 MFMA column tiles: 12 of 16 columns for RGB), never by padding the fp32 image in HBM.
 #pragma once
 #include "eae_common.hip.h"
 #include "eae_igemm.hip.h"
@@ -17,119 +19,199 @@ __device__ int g_edge_dbg_block = 0;
 #endif
 
 enum { SRC3_NCHW_F32 = 0,     // fp32 planar image (the loader contract)
-       SRC3_NHWC4_BF16 = 1 }; // bf16 pixels padded to 4 channels (gradient of the pre-sigmoid output)
+       SRC3_NHWCP_BF16 = 1 }; // bf16 pixels padded to CP channels (gradient of the pre-sigmoid output)
+
+// Band counts: C (1..16, a run-time argument) image bands are staged as CP = 4, 8 or 16 (the trailing template argument of every
+// edge kernel).  CP = 4 is the RGB form: C = 3 is a compile-time constant there (edge_bands), so it compiles to the registers,
+// arithmetic and summation order of the 3-band kernels.  Generic forms with a run-time C measured 3-5 % slower on the RGB step
+// (DESIGN.md section 10).  C = 1, 2 and 4..8 -> CP = 8, C = 9..16 -> CP = 16.
+constexpr int edge_cp(int C) { return C == 3 ? 4 : C <= 8 ? 8 : 16; }
+template <int CP> __device__ __forceinline__ int edge_bands(int C) { return CP == 4 ? 3 : C; }
+template <int CP> struct EdgeK {
+  static constexpr int CMAX = CP == 4 ? 3 : CP;       // most bands a CP form takes
+  static constexpr int KP = (9 * CP + 31) / 32 * 32;  // packed conv K (k = tap*CP + c): 64, 96, 160
+  static constexpr int KS = KP / 32;                  // v_mfma_f32_16x16x32_bf16 k-steps: 2, 3, 5
+  static constexpr int KC = (9 * CMAX + 31) / 32;     // 32-wide im2col chunks of the weight gradient (k = tap*C + c): at most 1, 3, 5
+  static constexpr int NT = CP / 4;                   // deconv4: 16-column MFMA tiles of the 4 phases x C outputs
+};
+// loss partial row of deconv4 / sigmoid backward: {sum diff^2, sum g(c) for c < C}, padded to whole float4s (4 floats for C = 3)
+__host__ __device__ constexpr int edge_lp_stride(int C) { return (C + 4) / 4 * 4; }
 
 constexpr int E_TH = 4, E_TW = 32;                 // 128 output pixels (conv view) / 128 input positions (deconv view)
-constexpr int E_PH = 2 * E_TH + 1, E_PW = 2 * E_TW + 1;   // 9 x 65 patch of the 3-channel tensor
-constexpr int E_PATCH = E_PH * E_PW * 4;           // bf16 elements ([row][col][4])
+constexpr int E_PH = 2 * E_TH + 1, E_PW = 2 * E_TW + 1;   // 9 x 65 patch of the C-band tensor
+template <int CP> constexpr int e_patch() { return E_PH * E_PW * CP; }     // bf16 elements ([row][col][CP])
 constexpr int E_AT = 128 * PIX_STRIDE;             // im2col tile [128][32 + pad]
 
-// Stage the 3-channel patch (rows iy0.., cols ix0..) as bf16 [E_PH][E_PW][4] with zero padding outside the image.
-// Every pixel of the patch is written exactly once, as a whole 8-byte [c0, c1, c2, 0] pixel: a thread takes 4 consecutive pixels of
-// a row -- for the planar fp32 source one float4 per colour plane -- and writes them with four 8-byte stores (the patch starts one
-// pixel left of a 16-byte boundary: the halo column).  Round 2 cleared the patch, synchronised, and scattered 2-byte elements plane
-// by plane (12 ds_write_b16 per float4 triple): by the stamps 4.8-8.5 K of conv1's 9.5-14.6 K workgroup cycles.  One barrier, at the end.
+// Stage the C-band patch (rows iy0.., cols ix0..) as bf16 [E_PH][E_PW][CP] with zero padding outside the image and in bands >= C.
+// Every pixel of the patch is written exactly once, as whole CP-band pixels: a thread takes 4 consecutive pixels of a row -- for the
+// planar fp32 source one float4 per band -- and writes them with 8-byte (CP = 4) or 16-byte stores (the patch starts one pixel
+// left of a 16-byte boundary: the halo column).  Round 2 cleared the patch, synchronised, and scattered 2-byte elements plane by
+// plane (12 ds_write_b16 per float4 triple): by the stamps 4.8-8.5 K of conv1's 9.5-14.6 K workgroup cycles.  One barrier, at the end.
 // (split into a load and a write half so that a loop over tiles can keep the NEXT tile's raw values in flight: edge_wgrad_kernel)
-template <int SRC3> struct Patch3Regs { float4 v[3]; };                 // planar fp32: one float4 per colour plane (halo threads: .x only)
-template <> struct Patch3Regs<1> { uint4 v[2]; };                      // bf16 NHWC4: up to two 16-byte pieces per thread
-template <int SRC3>
-__device__ __forceinline__ void patch3_load(const void* src, int n, int H, int W, int iy0, int ix0, Patch3Regs<SRC3>& r) {
+template <int CP> constexpr int e_pieces_row() { return 8 * CP; }                 // 16-byte pieces of a row's 64 interior pixels
+template <int CP> constexpr int e_halo_row() { return CP == 4 ? 1 : CP / 8; }     // pieces of the halo pixel (CP = 4: half a piece)
+template <int CP> constexpr int e_nld() { return (E_PH * (e_pieces_row<CP>() + e_halo_row<CP>()) + 255) / 256; }
+template <int SRC3, int CP> struct Patch3Regs { float4 v[EdgeK<CP>::CMAX]; };     // planar fp32: one float4 per band (halo threads: .x only)
+template <int CP> struct Patch3Regs<SRC3_NHWCP_BF16, CP> { uint4 v[e_nld<CP>()]; };   // bf16 NHWC-CP: 16-byte pieces
+template <int SRC3, int CP>
+__device__ __forceinline__ void patch3_load(const void* src, int C, int n, int H, int W, int iy0, int ix0, Patch3Regs<SRC3, CP>& r) {
   const int tid = threadIdx.x;
   if constexpr (SRC3 == SRC3_NCHW_F32) {
     const float* x = static_cast<const float*>(src);
+    constexpr int CMAX = EdgeK<CP>::CMAX;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) r.v[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int c = 0; c < CMAX; ++c) r.v[c] = make_float4(0.f, 0.f, 0.f, 0.f);
     // interior columns ix0+1 .. ix0+64 are image columns (ix0 = 2*tx0-1, tx0 multiple of 32 -> 16-byte aligned rows)
     if (tid < E_PH * 16) {
       const int c4 = tid & 15, rr = tid >> 4;
       const int iy = iy0 + rr, ix = ix0 + 1 + c4 * 4;
       if (iy >= 0 && iy < H) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) r.v[c] = *reinterpret_cast<const float4*>(x + (((size_t)n * 3 + c) * H + iy) * W + ix);
+        for (int c = 0; c < CMAX; ++c)
+          if (c < C) r.v[c] = *reinterpret_cast<const float4*>(x + (((size_t)n * C + c) * H + iy) * W + ix);
       }
     } else if (tid < E_PH * 16 + E_PH) {          // left halo column: a real pixel for tiles not at the image edge, else zero padding
       const int iy = iy0 + tid - E_PH * 16;
       if (ix0 >= 0 && iy >= 0 && iy < H) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) r.v[c].x = x[(((size_t)n * 3 + c) * H + iy) * W + ix0];
+        for (int c = 0; c < CMAX; ++c)
+          if (c < C) r.v[c].x = x[(((size_t)n * C + c) * H + iy) * W + ix0];
       }
     }
   } else {
     const bf16_t* g = static_cast<const bf16_t*>(src);
+    constexpr int IPR = e_pieces_row<CP>(), HPR = e_halo_row<CP>();
 #pragma unroll
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; k < e_nld<CP>(); ++k) {
       const int i = tid + k * 256;
       r.v[k] = make_uint4(0, 0, 0, 0);
-      if (i < E_PH * 32) {                        // 2 pixels (16 B) per piece
-        const int c2 = i & 31, rr = i >> 5;
-        const int iy = iy0 + rr, ix = ix0 + 1 + c2 * 2;
-        if (iy >= 0 && iy < H) r.v[k] = *reinterpret_cast<const uint4*>(g + (((size_t)n * H + iy) * W + ix) * 4);
-      } else if (i < E_PH * 32 + E_PH) {          // the halo column
-        const int iy = iy0 + i - E_PH * 32;
+      if (i < E_PH * IPR) {                       // 16-byte pieces of the interior pixels
+        const int pc = i % IPR, rr = i / IPR;
+        const int iy = iy0 + rr;
+        if (iy >= 0 && iy < H) r.v[k] = *reinterpret_cast<const uint4*>(g + (((size_t)n * H + iy) * W + ix0 + 1) * CP + pc * 8);
+      } else if (i < E_PH * (IPR + HPR)) {        // the halo column
+        const int j = i - E_PH * IPR, rr = j / HPR, hp = j % HPR;
+        const int iy = iy0 + rr;
         if (ix0 >= 0 && iy >= 0 && iy < H) {
-          const uint2 h = *reinterpret_cast<const uint2*>(g + (((size_t)n * H + iy) * W + ix0) * 4);
-          r.v[k].x = h.x; r.v[k].y = h.y;
+          if constexpr (CP == 4) {
+            const uint2 h = *reinterpret_cast<const uint2*>(g + (((size_t)n * H + iy) * W + ix0) * CP);
+            r.v[k].x = h.x; r.v[k].y = h.y;
+          } else {
+            r.v[k] = *reinterpret_cast<const uint4*>(g + (((size_t)n * H + iy) * W + ix0) * CP + hp * 8);
+          }
         }
       }
     }
   }
 }
-template <int SRC3>
-__device__ __forceinline__ void patch3_write(bf16_t* p3, const Patch3Regs<SRC3>& r) {
+template <int SRC3, int CP>
+__device__ __forceinline__ void patch3_write(bf16_t* p3, const Patch3Regs<SRC3, CP>& r) {
   const int tid = threadIdx.x;
   if constexpr (SRC3 == SRC3_NCHW_F32) {
+    constexpr int CMAX = EdgeK<CP>::CMAX;
+    auto put = [&](bf16_t* d, int e) __attribute__((always_inline)) {
+      uint32_t w[CP / 2];
+#pragma unroll
+      for (int c = 0; c < CP; c += 2) {
+        const float lo = c >= CMAX ? 0.f : e == 0 ? r.v[c].x : e == 1 ? r.v[c].y : e == 2 ? r.v[c].z : r.v[c].w;
+        const float hi = c + 1 >= CMAX ? 0.f : e == 0 ? r.v[c + 1].x : e == 1 ? r.v[c + 1].y : e == 2 ? r.v[c + 1].z : r.v[c + 1].w;
+        w[c / 2] = c >= CMAX ? 0u : c + 1 >= CMAX ? f2bf(lo) : pack2(lo, hi);
+      }
+      if constexpr (CP == 4) {
+        *reinterpret_cast<uint2*>(d) = make_uint2(w[0], w[1]);
+      } else {
+#pragma unroll
+        for (int q = 0; q < CP / 8; ++q) reinterpret_cast<uint4*>(d)[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+      }
+    };
     if (tid < E_PH * 16) {
       const int c4 = tid & 15, rr = tid >> 4;
-      uint2* d = reinterpret_cast<uint2*>(p3 + (rr * E_PW + 1 + c4 * 4) * 4);
-      d[0] = make_uint2(pack2(r.v[0].x, r.v[1].x), f2bf(r.v[2].x));
-      d[1] = make_uint2(pack2(r.v[0].y, r.v[1].y), f2bf(r.v[2].y));
-      d[2] = make_uint2(pack2(r.v[0].z, r.v[1].z), f2bf(r.v[2].z));
-      d[3] = make_uint2(pack2(r.v[0].w, r.v[1].w), f2bf(r.v[2].w));
+      bf16_t* d = p3 + (rr * E_PW + 1 + c4 * 4) * CP;
+      put(d, 0); put(d + CP, 1); put(d + 2 * CP, 2); put(d + 3 * CP, 3);
     } else if (tid < E_PH * 16 + E_PH) {
-      *reinterpret_cast<uint2*>(p3 + ((tid - E_PH * 16) * E_PW) * 4) = make_uint2(pack2(r.v[0].x, r.v[1].x), f2bf(r.v[2].x));
+      put(p3 + ((tid - E_PH * 16) * E_PW) * CP, 0);
     }
   } else {
+    constexpr int IPR = e_pieces_row<CP>(), HPR = e_halo_row<CP>();
 #pragma unroll
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; k < e_nld<CP>(); ++k) {
       const int i = tid + k * 256;
-      if (i < E_PH * 32) {
-        const int c2 = i & 31, rr = i >> 5;
-        uint2* d = reinterpret_cast<uint2*>(p3 + (rr * E_PW + 1 + c2 * 2) * 4);
-        d[0] = make_uint2(r.v[k].x, r.v[k].y);
-        d[1] = make_uint2(r.v[k].z, r.v[k].w);
-      } else if (i < E_PH * 32 + E_PH) {
-        *reinterpret_cast<uint2*>(p3 + ((i - E_PH * 32) * E_PW) * 4) = make_uint2(r.v[k].x, r.v[k].y);
+      if (i < E_PH * IPR) {
+        const int pc = i % IPR, rr = i / IPR;
+        bf16_t* d = p3 + (rr * E_PW + 1) * CP + pc * 8;
+        if constexpr (CP == 4) {         // 8-byte aligned only (the interior starts one 8-byte pixel into the row)
+          reinterpret_cast<uint2*>(d)[0] = make_uint2(r.v[k].x, r.v[k].y);
+          reinterpret_cast<uint2*>(d)[1] = make_uint2(r.v[k].z, r.v[k].w);
+        } else {
+          *reinterpret_cast<uint4*>(d) = r.v[k];
+        }
+      } else if (i < E_PH * (IPR + HPR)) {
+        const int j = i - E_PH * IPR, rr = j / HPR, hp = j % HPR;
+        if constexpr (CP == 4) *reinterpret_cast<uint2*>(p3 + (rr * E_PW) * CP) = make_uint2(r.v[k].x, r.v[k].y);
+        else *reinterpret_cast<uint4*>(p3 + (rr * E_PW) * CP + hp * 8) = r.v[k];
       }
     }
   }
 }
-template <int SRC3>
-__device__ __forceinline__ void stage_patch3(const void* src, bf16_t* p3, int n, int H, int W, int iy0, int ix0) {
-  Patch3Regs<SRC3> r;
-  patch3_load<SRC3>(src, n, H, W, iy0, ix0, r);
-  patch3_write<SRC3>(p3, r);
+template <int SRC3, int CP>
+__device__ __forceinline__ void stage_patch3(const void* src, int C, bf16_t* p3, int n, int H, int W, int iy0, int ix0) {
+  Patch3Regs<SRC3, CP> r;
+  patch3_load<SRC3, CP>(src, C, n, H, W, iy0, ix0, r);
+  patch3_write<SRC3, CP>(p3, r);
   __syncthreads();
 }
 
-// Build the im2col tile [128 pixels][32 k] (k = tap*3 + c, zero for k >= 27) from the staged patch.
-__device__ __forceinline__ void build_im2col27(const bf16_t* p3, bf16_t* at) {
+// im2col of the weight gradient: k = tap*C + c (K = 9C, zero for k >= 9C), in 32-wide chunks.  A thread fills the same 8 k of
+// every tile (kg = tid & 3): their patch offsets (or -1) are computed once, before the tile loop.
+template <int CP>
+__device__ __forceinline__ void im2col_offsets(int C, int kc, int (&off)[8]) {
+  const int kg = threadIdx.x & 3;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int k = kc * 32 + kg * 8 + j;
+    const int tap = k / C, c = k % C;
+    off[j] = (k < 9 * C) ? ((tap / 3) * E_PW + tap % 3) * CP + c : -1;
+  }
+}
+// Build the im2col tile [128 pixels][32 k] of one chunk from the staged patch.
+template <int CP>
+__device__ __forceinline__ void build_im2col(const bf16_t* p3, bf16_t* at, const int (&off)[8]) {
   const int tid = threadIdx.x;
+  if constexpr (CP == 4) {          // RGB: k = tap*3 + c (zero for k >= 27), as the 3-band kernel had it
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      int q = tid + i * 256;
+      int m = q >> 2, kg = q & 3;
+      int ty = m / E_TW, tx = m % E_TW;
+      uint32_t w[4];
+#pragma unroll
+      for (int j = 0; j < 8; j += 2) {
+        uint32_t e[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          int k = kg * 8 + j + u;
+          int tap = k / 3, c = k % 3;
+          int ky = tap / 3, kx = tap % 3;
+          e[u] = (k < 27) ? (uint32_t)p3[((2 * ty + ky) * E_PW + 2 * tx + kx) * 4 + c] : 0u;
+        }
+        w[j >> 1] = e[0] | (e[1] << 16);
+      }
+      *reinterpret_cast<uint4*>(at + m * PIX_STRIDE + kg * 8) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+    return;
+  }
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     int q = tid + i * 256;
     int m = q >> 2, kg = q & 3;
     int ty = m / E_TW, tx = m % E_TW;
+    const bf16_t* pb = p3 + ((2 * ty) * E_PW + 2 * tx) * CP;
     uint32_t w[4];
 #pragma unroll
     for (int j = 0; j < 8; j += 2) {
       uint32_t e[2];
 #pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        int k = kg * 8 + j + u;
-        int tap = k / 3, c = k % 3;
-        int ky = tap / 3, kx = tap % 3;
-        e[u] = (k < 27) ? (uint32_t)p3[((2 * ty + ky) * E_PW + 2 * tx + kx) * 4 + c] : 0u;
-      }
+      for (int u = 0; u < 2; ++u) e[u] = off[j + u] >= 0 ? (uint32_t)pb[off[j + u]] : 0u;
       w[j >> 1] = e[0] | (e[1] << 16);
     }
     *reinterpret_cast<uint4*>(at + m * PIX_STRIDE + kg * 8) = make_uint4(w[0], w[1], w[2], w[3]);
@@ -137,21 +219,23 @@ __device__ __forceinline__ void build_im2col27(const bf16_t* p3, bf16_t* at) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// out[m][32] = im2col27(src3)[m][32] . Wp[32][32]^T      (conv1 forward; backward-data of deconv4)
+// out[m][32] = im2col(src)[m][9C] . Wp[32][9C]^T      (conv1 forward; backward-data of deconv4)
 // ---------------------------------------------------------------------------------------------------------------
 struct EdgeArgs {
-  const void* src3;        // fp32 NCHW [B,3,H,W] or bf16 NHWC4 [B,H,W,4]
-  int B, H, W;             // spatial size of the 3-channel tensor
-  ConvArgs c;              // wpack [32][64] (k = tap*4 + c, zero where c == 3 or k >= 36), bias, out [B,H/2,W/2,32], stat_part, yprev, prev_coef
+  const void* src3;        // fp32 NCHW [B,C,H,W] or bf16 NHWC-CP [B,H,W,CP]
+  int B, H, W;             // spatial size of the C-band tensor
+  ConvArgs c;              // wpack [32][KP] (k = tap*CP + c, zero where c >= C or k >= 9*CP), bias, out [B,H/2,W/2,32], stat_part, yprev, prev_coef
+  int C = 3;               // bands (1..16; edge_cp(C) == CP)
 };
 
-// No im2col tile: with k = tap*4 + c (c = 0..3, the 4th channel and k >= 36 are zero in the weights: K = 64, two MFMA k-steps)
-// a lane's 8 consecutive k are TWO whole pixels of the staged [row][col][4] patch, so the pixel operand is two ds_read_b64
-// straight from the patch.  The weights are the MFMA A operand: an accumulator lane holds 4 consecutive output channels of
-// one pixel (8-byte tile writes instead of 16 two-byte ones).
-template <int SRC3, int EPI>
+// No im2col tile: with k = tap*CP + c (bands >= C and k >= 9*CP are zero in the weights: K = KP, 2 / 3 / 5 MFMA k-steps) a lane's 8
+// consecutive k are whole pixel pieces of the staged [row][col][CP] patch (two pixels for CP = 4, one for 8, half a pixel for 16), so
+// the pixel operand is read straight from the patch.  The weights are the MFMA A operand: an accumulator lane holds 4 consecutive
+// output channels of one pixel (8-byte tile writes instead of 16 two-byte ones).
+template <int SRC3, int EPI, int CP>
 __device__ __forceinline__ void edge_conv_body(const EdgeArgs& a) {
-  __shared__ __attribute__((aligned(16))) bf16_t p3[E_PATCH];
+  constexpr int KP = EdgeK<CP>::KP, KS = EdgeK<CP>::KS;
+  __shared__ __attribute__((aligned(16))) bf16_t p3[e_patch<CP>()];
   // output tile [128][40] (10 KB); the statistics reduction scratch [2][64][32] floats (16 KB) reuses the same memory: TileEpilogue::end()
   // starts with a barrier behind the last read of the tile (31.3 -> 20.7 KB of LDS per block: 7 instead of 5 blocks per CU)
   __shared__ __attribute__((aligned(16))) float red[2 * 64 * 32];
@@ -166,33 +250,47 @@ __device__ __forceinline__ void edge_conv_body(const EdgeArgs& a) {
   const int n = t;
   const int kgl = lane >> 4;
   eae_signal(a.c.sig, a.c.sig_val);
-  // weight fragments first (independent of the patch): A[channel][k], 2 m-tiles x 2 k-steps
-  bf16x8 wf[2][2];
+  // weight fragments first (independent of the patch): A[channel][k], 2 m-tiles x KS k-steps
+  bf16x8 wf[2][KS];
 #pragma unroll
   for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-      wf[mt][ks] = *reinterpret_cast<const bf16x8*>(a.c.wpack + (mt * 16 + (lane & 15)) * 64 + ks * 32 + kgl * 8);
+    for (int ks = 0; ks < KS; ++ks)
+      wf[mt][ks] = *reinterpret_cast<const bf16x8*>(a.c.wpack + (mt * 16 + (lane & 15)) * KP + ks * 32 + kgl * 8);
   EDGE_STAMP(16);
-  stage_patch3<SRC3>(a.src3, p3, n, a.H, a.W, 2 * tyb * E_TH - 1, 2 * txb * E_TW - 1);      // ends with a barrier
+  stage_patch3<SRC3, CP>(a.src3, edge_bands<CP>(a.C), p3, n, a.H, a.W, 2 * tyb * E_TH - 1, 2 * txb * E_TW - 1);      // ends with a barrier
   EDGE_STAMP(17);
   f32x4 acc[2][2];
 #pragma unroll
   for (int nt = 0; nt < 2; ++nt) {
     const int m = (wave * 2 + nt) * 16 + (lane & 15);                // this lane's pixel of the n-tile
     const int ty = m / E_TW, tx = m % E_TW;
-    const bf16_t* pb = p3 + ((2 * ty) * E_PW + 2 * tx) * 4;
-    // k-step 0: taps 2*kgl and 2*kgl+1; k-step 1: tap 8 (lane group 0 only), everything else multiplies zero weights
-    const int t0 = 2 * kgl, t1 = 2 * kgl + 1;
-    union { bf16x8 v; uint2 h[2]; } f0, f1;
-    f0.h[0] = *reinterpret_cast<const uint2*>(pb + ((t0 / 3) * E_PW + (t0 % 3)) * 4);
-    f0.h[1] = *reinterpret_cast<const uint2*>(pb + ((t1 / 3) * E_PW + (t1 % 3)) * 4);
-    f1.h[0] = (kgl == 0) ? *reinterpret_cast<const uint2*>(pb + (2 * E_PW + 2) * 4) : make_uint2(0, 0);
-    f1.h[1] = make_uint2(0, 0);
+    const bf16_t* pb = p3 + ((2 * ty) * E_PW + 2 * tx) * CP;
+    if constexpr (CP == 4) {
+      // RGB, as the 3-band kernel: k-step 0 = taps 2*kgl and 2*kgl+1; k-step 1 = tap 8 (lane group 0 only), everything else
+      // multiplies zero weights
+      const int t0 = 2 * kgl, t1 = 2 * kgl + 1;
+      union { bf16x8 v; uint2 h[2]; } f0, f1;
+      f0.h[0] = *reinterpret_cast<const uint2*>(pb + ((t0 / 3) * E_PW + (t0 % 3)) * 4);
+      f0.h[1] = *reinterpret_cast<const uint2*>(pb + ((t1 / 3) * E_PW + (t1 % 3)) * 4);
+      f1.h[0] = (kgl == 0) ? *reinterpret_cast<const uint2*>(pb + (2 * E_PW + 2) * 4) : make_uint2(0, 0);
+      f1.h[1] = make_uint2(0, 0);
 #pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-      acc[mt][nt] = mfma16(wf[mt][0], f0.v, (f32x4){0.f, 0.f, 0.f, 0.f});
-      acc[mt][nt] = mfma16(wf[mt][1], f1.v, acc[mt][nt]);
+      for (int mt = 0; mt < 2; ++mt) {
+        acc[mt][nt] = mfma16(wf[mt][0], f0.v, (f32x4){0.f, 0.f, 0.f, 0.f});
+        acc[mt][nt] = mfma16(wf[mt][1], f1.v, acc[mt][nt]);
+      }
+    } else {
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        // this lane's k = ks*32 + kgl*8 .. +7 = half (CP = 16) or all (CP = 8) of one tap's pixel; taps >= 9 multiply zero weights
+        const int k0 = ks * 32 + kgl * 8;
+        const int tap = k0 / CP, c0 = k0 % CP;
+        union { bf16x8 v; uint4 q; } f;
+        f.q = tap < 9 ? *reinterpret_cast<const uint4*>(pb + ((tap / 3) * E_PW + (tap % 3)) * CP + c0) : make_uint4(0, 0, 0, 0);
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) acc[mt][nt] = mfma16(wf[mt][ks], f.v, ks == 0 ? (f32x4){0.f, 0.f, 0.f, 0.f} : acc[mt][nt]);
+      }
     }
   }
   // D[channel][pixel]: col = lane & 15 = pixel, rows (lane >> 4) * 4 + r = 4 consecutive channels
@@ -219,39 +317,42 @@ __device__ __forceinline__ void edge_conv_body(const EdgeArgs& a) {
   tile_epilogue<32, 32, EPI>(a.c, at, red, 0, blockIdx.x, 128, rowmap);
   EDGE_STAMP(19);
 }
-template <int SRC3, int EPI>
-__global__ __launch_bounds__(256) void edge_conv_kernel(EdgeArgs a) { edge_conv_body<SRC3, EPI>(a); }
-template <int SRC3, int EPI>
-__global__ __launch_bounds__(256) void edge_conv_kernel_g(GroupPack<EdgeArgs> p, int gz) { edge_conv_body<SRC3, EPI>(group_args<EdgeArgs>(gz)); }
+template <int SRC3, int EPI, int CP>
+__global__ __launch_bounds__(256) void edge_conv_kernel(EdgeArgs a) { edge_conv_body<SRC3, EPI, CP>(a); }
+template <int SRC3, int EPI, int CP>
+__global__ __launch_bounds__(256) void edge_conv_kernel_g(GroupPack<EdgeArgs> p, int gz) { edge_conv_body<SRC3, EPI, CP>(group_args<EdgeArgs>(gz)); }
 
 // ---------------------------------------------------------------------------------------------------------------
-// R[k][c] = sum_m im2col27(src3)[m][k] * T(side)[m][c]     (weight gradient of conv1 and of deconv4)
+// R[k][c] = sum_m im2col(src)[m][k] * T(side)[m][c]     (weight gradient of conv1 and of deconv4)
 // Each block sweeps `tiles_per_block` 128-pixel tiles and writes one fp32 partial in the REFERENCE layout
-// [c][3][3][3] (index c*27 + cx*9 + tap with k = tap*3 + cx), summed later by reduce_slices (deterministic).
+// [c][C][3][3] (index c*9C + cx*9 + tap with k = tap*C + cx), summed later by reduce_slices (deterministic).
 // ---------------------------------------------------------------------------------------------------------------
 struct EdgeWgradArgs {
   const void* src3;
   int B, H, W;
   SrcDesc side;           // [B,H/2,W/2,32] tensor with its load transform
-  float* part;            // [nblocks][32*27]
+  float* part;            // [nblocks][32*9C]
   int tiles_per_block, ntiles;
   BnBwdFold bfold;        // SRC_BNBWD side: coefficient table from the layer's backward accumulators (eae_common.hip.h)
   unsigned* sig;          // progress word of the caller's stream, published when the kernel starts (ConvArgs::sig); nullptr: none
   unsigned sig_val;
+  int C;                  // bands (1..16; edge_cp(C) == CP)
 };
 
-template <int SRC3, int SMODE>
+template <int SRC3, int SMODE, int CP>
 __device__ __forceinline__ void edge_wgrad_body(const EdgeWgradArgs& a) {
+  constexpr int KC = EdgeK<CP>::KC;
   eae_signal(a.sig, a.sig_val);
-  __shared__ __attribute__((aligned(16))) bf16_t p3[E_PATCH];
-  // the two operand tiles; the cross-wave reduction image of the epilogue (16 KB) reuses them (41.9 -> 26 KB of LDS per block:
-  // 6 instead of 3 blocks per CU)
+  __shared__ __attribute__((aligned(16))) bf16_t p3[e_patch<CP>()];
+  // the two operand tiles (im2col chunk, side); the cross-wave reduction image of the epilogue (16 KB) reuses them (41.9 -> 26 KB of
+  // LDS per block: 6 instead of 3 blocks per CU).  More than one 32-wide k chunk (C > 3) goes through the im2col tile in turn.
   static_assert(2 * E_AT * sizeof(bf16_t) >= 4 * 2 * 2 * 64 * 4 * sizeof(float), "reduction image must fit the operand tiles");
   __shared__ __attribute__((aligned(16))) bf16_t tiles[2 * E_AT];
   bf16_t* const at = tiles;
   bf16_t* const st = tiles + E_AT;
   float (*racc)[2][2][64 * 4] = reinterpret_cast<float (*)[2][2][64 * 4]>(tiles);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int C = edge_bands<CP>(a.C), nkc = (9 * C + 31) / 32;
   const int Hout = a.H >> 1, Wout = a.W >> 1;
   const int tiles_x = Wout / E_TW, tiles_y = Hout / E_TH;
   const int kgs = tid & 3;
@@ -267,20 +368,27 @@ __device__ __forceinline__ void edge_wgrad_body(const EdgeWgradArgs& a) {
     }
     cc.load(coefp, 32, kgs * 8);
   }
-  f32x4 acc[2][2];
+  int off[KC][8];
+  if constexpr (CP != 4) {
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
+    for (int kc = 0; kc < KC; ++kc) im2col_offsets<CP>(C, kc, off[kc]);
+  }
+  f32x4 acc[KC][2][2];
 #pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int kc = 0; kc < KC; ++kc)
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) acc[kc][i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
   const int g = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
-  // Tile loop with the NEXT tile's raw values (side pieces + 3-channel patch) requested before this tile is multiplied: round 2
+  // Tile loop with the NEXT tile's raw values (side pieces + C-band patch) requested before this tile is multiplied: round 2
   // loaded, staged and multiplied one tile after the other, every tile exposing a memory round trip (conv1's weight gradient is the
   // last kernel of the backward: 32 us on the critical path).
   const int t_begin = blockIdx.x * a.tiles_per_block;
   int t_end = t_begin + a.tiles_per_block;
   if (t_end > a.ntiles) t_end = a.ntiles;
   RawPiece<SMODE> raw[2];
-  Patch3Regs<SRC3> pr;
+  Patch3Regs<SRC3, CP> pr;
   auto request = [&](int t) __attribute__((always_inline)) {
     const int txb = t % tiles_x; t /= tiles_x;
     const int tyb = t % tiles_y; t /= tiles_y;
@@ -292,18 +400,18 @@ __device__ __forceinline__ void edge_wgrad_body(const EdgeWgradArgs& a) {
       size_t off = ((((size_t)n * Hout + tyb * E_TH + ty) * Wout) + txb * E_TW + tx) * 32 + kgs * 8;
       load_piece<SMODE>(a.side, off, true, raw[i]);
     }
-    patch3_load<SRC3>(a.src3, n, a.H, a.W, 2 * tyb * E_TH - 1, 2 * txb * E_TW - 1, pr);
+    patch3_load<SRC3, CP>(a.src3, C, n, a.H, a.W, 2 * tyb * E_TH - 1, 2 * txb * E_TW - 1, pr);
   };
   if (t_begin < t_end) request(t_begin);
   for (int t = t_begin; t < t_end; ++t) {
     __syncthreads();                 // the previous tile's fragment reads (at, st) and im2col reads (p3) are done
-    patch3_write<SRC3>(p3, pr);
+    patch3_write<SRC3, CP>(p3, pr);
     uint4 sv[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) sv[i] = transform_piece<SMODE>(raw[i], true, cc);
     if (t + 1 < t_end) request(t + 1);
-    __syncthreads();                 // the 3-channel patch is complete
-    build_im2col27(p3, at);
+    __syncthreads();                 // the C-band patch is complete
+    build_im2col<CP>(p3, at, off[0]);
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       int m = (tid + i * 256) >> 2;
@@ -321,65 +429,86 @@ __device__ __forceinline__ void edge_wgrad_body(const EdgeWgradArgs& a) {
 #pragma unroll
     for (int it = 0; it < 2; ++it)
 #pragma unroll
-      for (int jt = 0; jt < 2; ++jt) acc[it][jt] = mfma16(ka[it], sb[jt], acc[it][jt]);
+      for (int jt = 0; jt < 2; ++jt) acc[0][it][jt] = mfma16(ka[it], sb[jt], acc[0][it][jt]);
+#pragma unroll
+    for (int kc = 1; kc < KC; ++kc) {          // further k chunks (C > 3): rebuild the im2col tile
+      if (kc < nkc) {
+        __syncthreads();
+        build_im2col<CP>(p3, at, off[kc]);
+        __syncthreads();
+#pragma unroll
+        for (int it = 0; it < 2; ++it) ka[it] = tr_frag(at + r_lo * PIX_STRIDE + it * 16 + 4 * p, at + r_hi * PIX_STRIDE + it * 16 + 4 * p);
+#pragma unroll
+        for (int it = 0; it < 2; ++it)
+#pragma unroll
+          for (int jt = 0; jt < 2; ++jt) acc[kc][it][jt] = mfma16(ka[it], sb[jt], acc[kc][it][jt]);
+      }
+    }
   }
-  // cross-wave reduction (fixed order) and store in reference layout
-  __syncthreads();            // every wave has read its fragments of the last tile: the image may overwrite the tiles
+  // cross-wave reduction (fixed order) and store in reference layout, one 32-wide k chunk at a time
 #pragma unroll
-  for (int it = 0; it < 2; ++it)
+  for (int kc = 0; kc < KC; ++kc) {
+    if (kc >= nkc) break;
+    __syncthreads();            // every wave has read its fragments of the last tile / the previous chunk's image: the image may overwrite the tiles
 #pragma unroll
-    for (int jt = 0; jt < 2; ++jt)
+    for (int it = 0; it < 2; ++it)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) racc[wave][it][jt][lane * 4 + r] = acc[it][jt][r];
-  __syncthreads();
-  // 4 (it,jt) tiles x 256 values = 1024 outputs; thread handles 4
+      for (int jt = 0; jt < 2; ++jt)
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    int e = tid + i * 256;
-    int tile = e >> 8, idx = e & 255;
-    int it = tile >> 1, jt = tile & 1;
-    float v = racc[0][it][jt][idx] + racc[1][it][jt][idx] + racc[2][it][jt][idx] + racc[3][it][jt][idx];
-    int l = idx >> 2, r = idx & 3;
-    int k = it * 16 + (l >> 4) * 4 + r;     // D row  = k index (im2col side)
-    int c = jt * 16 + (l & 15);             // D col  = side channel
-    if (k < 27) {
-      int tap = k / 3, cx = k % 3;
-      a.part[(size_t)blockIdx.x * (32 * 27) + c * 27 + cx * 9 + tap] = v;
+        for (int r = 0; r < 4; ++r) racc[wave][it][jt][lane * 4 + r] = acc[kc][it][jt][r];
+    __syncthreads();
+    // 4 (it,jt) tiles x 256 values = 1024 outputs; thread handles 4
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      int e = tid + i * 256;
+      int tile = e >> 8, idx = e & 255;
+      int it = tile >> 1, jt = tile & 1;
+      float v = racc[0][it][jt][idx] + racc[1][it][jt][idx] + racc[2][it][jt][idx] + racc[3][it][jt][idx];
+      int l = idx >> 2, r = idx & 3;
+      int k = kc * 32 + it * 16 + (l >> 4) * 4 + r;     // D row  = k index (im2col side)
+      int c = jt * 16 + (l & 15);                        // D col  = side channel
+      if (k < 9 * C) {
+        int tap = k / C, cx = k % C;
+        a.part[(size_t)blockIdx.x * (32 * 9 * C) + c * 9 * C + cx * 9 + tap] = v;
+      }
     }
   }
 }
-template <int SRC3, int SMODE>
-__global__ __launch_bounds__(256) void edge_wgrad_kernel(EdgeWgradArgs a) { edge_wgrad_body<SRC3, SMODE>(a); }
-template <int SRC3, int SMODE>
-__global__ __launch_bounds__(256) void edge_wgrad_kernel_g(GroupPack<EdgeWgradArgs> p, int gz) { edge_wgrad_body<SRC3, SMODE>(group_args<EdgeWgradArgs>(gz)); }
+template <int SRC3, int SMODE, int CP>
+__global__ __launch_bounds__(256) void edge_wgrad_kernel(EdgeWgradArgs a) { edge_wgrad_body<SRC3, SMODE, CP>(a); }
+template <int SRC3, int SMODE, int CP>
+__global__ __launch_bounds__(256) void edge_wgrad_kernel_g(GroupPack<EdgeWgradArgs> p, int gz) { edge_wgrad_body<SRC3, SMODE, CP>(group_args<EdgeWgradArgs>(gz)); }
 
 // ---------------------------------------------------------------------------------------------------------------
 // deconv4 forward (all four phases jointly) + sigmoid + MSE loss + its gradient      (R.md:382-383, 622, 649)
 //   s[n,oy,ox,co] = b[co] + sum over the 2x2 input neighbourhood ;  x_hat = sigmoid(s)
-//   loss partial  = sum (x_hat - x)^2 ;  g4 = gscale * (x_hat - x) * x_hat * (1 - x_hat)   (gscale = alpha*2/numel)
+//   loss partial  = sum (x_hat - x)^2 ;  g = gscale * (x_hat - x) * x_hat * (1 - x_hat)   (gscale = alpha*2/numel)
 // ---------------------------------------------------------------------------------------------------------------
 struct Deconv4Args {
   SrcDesc src;             // a3 = BNRELU(u3)  [B,Hin,Win,32]
-  const bf16_t* wjoint;    // [16][128]  n = phase*3+co, k = nb*32+ci
-  const float* bias;       // [3]
-  const float* x;          // target fp32 NCHW [B,3,2Hin,2Win] or nullptr (forward only)
+  const bf16_t* wjoint;    // [16*NT][128]  n = phase*C+co, k = nb*32+ci
+  const float* bias;       // [C]
+  const float* x;          // target fp32 NCHW [B,C,2Hin,2Win] or nullptr (forward only)
   float* x_hat;            // fp32 NCHW or nullptr
-  bf16_t* g4;              // bf16 NHWC4 [B,2Hin,2Win,4] or nullptr
-  float* loss_part;        // [ntiles][4]: sum diff^2, sum g (co = 0,1,2)   or nullptr
+  bf16_t* g4;              // bf16 NHWC-CP [B,2Hin,2Win,CP] or nullptr
+  float* loss_part;        // [ntiles][edge_lp_stride(C)]: sum diff^2, sum g (co = 0..C-1), zero padding   or nullptr
   float gscale;
   int B, Hin, Win;
   BnFold fold;             // BNRELU source: coefficient table of deconv3's BatchNorm from its accumulators
+  int C = 3;               // bands (1..16; edge_cp(C) == CP)
 };
 
-template <int SRC>
+template <int SRC, int CP>
 __device__ __forceinline__ void deconv4_loss_body(const Deconv4Args& a) {
   constexpr int PH = E_TH + 1, PW = E_TW + 1, NPIX = PH * PW;       // 5 x 33 input pixels
   constexpr int NPA = (NPIX * 4 + 255) / 256;
-  // the pre-sigmoid tile `sl` (8.7 KB) reuses the patch (13.2 KB) once every wave has read its fragments: 8 blocks per CU
-  __shared__ __attribute__((aligned(16))) bf16_t patch[NPIX * PIX_STRIDE];
-  static_assert(sizeof(bf16_t) * NPIX * PIX_STRIDE >= sizeof(float) * 128 * 17, "the tile must fit the patch");
+  constexpr int NT = EdgeK<CP>::NT, SLW = 16 * NT + 1;              // pre-sigmoid tile [128][16*NT + 1] floats
+  constexpr int PATCH_B = (int)sizeof(bf16_t) * NPIX * PIX_STRIDE, SL_B = (int)sizeof(float) * 128 * SLW;
+  // the pre-sigmoid tile `sl` (8.7 KB for CP = 4) reuses the patch (13.2 KB) once every wave has read its fragments: 8 blocks per CU
+  __shared__ __attribute__((aligned(16))) bf16_t patch[(PATCH_B > SL_B ? PATCH_B : SL_B) / 2];
   float* const sl = reinterpret_cast<float*>(patch);
-  __shared__ float redl[4][4];
+  __shared__ float redl[4][1 + EdgeK<CP>::CMAX];
+  const int C = edge_bands<CP>(a.C), LPS = edge_lp_stride(C);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int Hout = a.Hin * 2, Wout = a.Win * 2;
   const int tiles_x = a.Win / E_TW, tiles_y = a.Hin / E_TH;
@@ -425,81 +554,110 @@ __device__ __forceinline__ void deconv4_loss_body(const Deconv4Args& a) {
   EDGE_STAMP(2);
   __syncthreads();
   EDGE_STAMP(3);
-  f32x4 acc[2];
-  acc[0] = acc[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  f32x4 acc[NT][2];
+#pragma unroll
+  for (int j = 0; j < NT; ++j) acc[j][0] = acc[j][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int nb = 0; nb < 4; ++nb) {
-    bf16x8 bfr = *reinterpret_cast<const bf16x8*>(a.wjoint + (lane & 15) * 128 + nb * 32 + kgl * 8);
 #pragma unroll
-    for (int mi = 0; mi < 2; ++mi) {
-      int pos = (wave * 2 + mi) * 16 + (lane & 15);
-      int ty = pos / E_TW, tx = pos % E_TW;
-      bf16x8 af = *reinterpret_cast<const bf16x8*>(patch + ((ty + (nb >> 1)) * PW + tx + (nb & 1)) * PIX_STRIDE + kgl * 8);
-      acc[mi] = mfma16(af, bfr, acc[mi]);
+    for (int j = 0; j < NT; ++j) {
+      bf16x8 bfr = *reinterpret_cast<const bf16x8*>(a.wjoint + (j * 16 + (lane & 15)) * 128 + nb * 32 + kgl * 8);
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi) {
+        int pos = (wave * 2 + mi) * 16 + (lane & 15);
+        int ty = pos / E_TW, tx = pos % E_TW;
+        bf16x8 af = *reinterpret_cast<const bf16x8*>(patch + ((ty + (nb >> 1)) * PW + tx + (nb & 1)) * PIX_STRIDE + kgl * 8);
+        acc[j][mi] = mfma16(af, bfr, acc[j][mi]);
+      }
     }
   }
   EDGE_STAMP(4);
   __syncthreads();                 // every wave has read its patch fragments: the tiles below overwrite the patch
 #pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
+  for (int j = 0; j < NT; ++j)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) sl[((wave * 2 + mi) * 16 + (lane >> 4) * 4 + r) * 17 + (lane & 15)] = acc[mi][r];
+    for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sl[((wave * 2 + mi) * 16 + (lane >> 4) * 4 + r) * SLW + j * 16 + (lane & 15)] = acc[j][mi][r];
   __syncthreads();
   EDGE_STAMP(5);
-  // Elementwise pass, one thread per OUTPUT PIXEL (2 pixels per thread: oy = tid / 64 + 4 i, ox = tid % 64), all three channels: the
+  // Elementwise pass, one thread per OUTPUT PIXEL (2 pixels per thread: oy = tid / 64 + 4 i, ox = tid % 64), all C bands: the
   // target / x_hat accesses stay coalesced per plane (a wave = one 64-pixel row segment of a plane), and the gradient pixel
-  // [g0, g1, g2, 0] leaves as ONE 8-byte NHWC4 store.  (Round 2 went element by element in NCHW order -- 6 elements per thread, each
-  // with its own 64-bit address arithmetic -- and staged the gradient tile through LDS with 2-byte scatter writes, a clear and two
-  // more barriers: by the stamps this phase was 7.7-12 K of a workgroup's 23-38 K cycles, all of it VALU issue at 8 workgroups per CU.)
-  float lsum = 0.f, gsum[3] = {0.f, 0.f, 0.f};
-  const float b0 = a.bias[0], b1 = a.bias[1], b2 = a.bias[2];
+  // [g0 .. g(C-1), 0 ..] leaves as whole CP-band stores (8 bytes for CP = 4).  (Round 2 went element by element in NCHW order -- 6
+  // elements per thread, each with its own 64-bit address arithmetic -- and staged the gradient tile through LDS with 2-byte scatter
+  // writes, a clear and two more barriers: by the stamps this phase was 7.7-12 K of a workgroup's 23-38 K cycles, all of it VALU
+  // issue at 8 workgroups per CU.)
+  constexpr int CMAX = EdgeK<CP>::CMAX;
+  float lsum = 0.f, gsum[CMAX];
+  float bb[CMAX];
+#pragma unroll
+  for (int co = 0; co < CMAX; ++co) { gsum[co] = 0.f; bb[co] = co < C ? a.bias[co] : 0.f; }
   const size_t plane = (size_t)Hout * Wout;
   const int ox = tid & 63;
-  float xt[2][3];                    // the six target values of this thread, requested together (the stores below may not be reordered against loads)
+  float xt[2][CMAX];                 // the target values of this thread, requested together (the stores below may not be reordered against loads)
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
-    for (int co = 0; co < 3; ++co)
-      xt[i][co] = a.x ? a.x[((size_t)n * 3 + co) * plane + (size_t)(2 * iy0 + (tid >> 6) + 4 * i) * Wout + 2 * ix0 + ox] : 0.f;
+    for (int co = 0; co < CMAX; ++co)
+      xt[i][co] = (a.x && co < C) ? a.x[((size_t)n * C + co) * plane + (size_t)(2 * iy0 + (tid >> 6) + 4 * i) * Wout + 2 * ix0 + ox] : 0.f;
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int oy = (tid >> 6) + 4 * i;
     const int pos = (oy >> 1) * E_TW + (ox >> 1), ph = (oy & 1) * 2 + (ox & 1);
-    const float* sp = sl + pos * 17 + ph * 3;
-    const float s3[3] = {sp[0] + b0, sp[1] + b1, sp[2] + b2};
+    const float* sp = sl + pos * SLW + ph * C;
     const size_t pix = (size_t)(2 * iy0 + oy) * Wout + 2 * ix0 + ox;
-    const size_t gi = (size_t)n * 3 * plane + pix;
-    uint32_t gb[3] = {0u, 0u, 0u};
+    const size_t gi = (size_t)n * C * plane + pix;
+    uint32_t gb[CP];
 #pragma unroll
-    for (int co = 0; co < 3; ++co) {
-      const float xh = 1.0f / (1.0f + __expf(-s3[co]));
-      if (a.x_hat) a.x_hat[gi + co * plane] = xh;
-      if (a.x) {
-        const float d = xh - xt[i][co];
-        lsum = fmaf(d, d, lsum);
-        if (a.g4) {
-          gb[co] = f2bf(a.gscale * d * xh * (1.0f - xh));
-          gsum[co] += bf2f(gb[co]);
+    for (int co = 0; co < CP; ++co) gb[co] = 0u;
+#pragma unroll
+    for (int co = 0; co < CMAX; ++co) {
+      if (co < C) {
+        const float s = sp[co] + bb[co];
+        const float xh = 1.0f / (1.0f + __expf(-s));
+        if (a.x_hat) a.x_hat[gi + co * plane] = xh;
+        if (a.x) {
+          const float d = xh - xt[i][co];
+          lsum = fmaf(d, d, lsum);
+          if (a.g4) {
+            gb[co] = f2bf(a.gscale * d * xh * (1.0f - xh));
+            gsum[co] += bf2f(gb[co]);
+          }
         }
       }
     }
-    if (a.g4) *reinterpret_cast<uint2*>(a.g4 + ((size_t)n * plane + pix) * 4) = make_uint2(gb[0] | (gb[1] << 16), gb[2]);
+    if (a.g4) {
+      bf16_t* gp = a.g4 + ((size_t)n * plane + pix) * CP;
+      if constexpr (CP == 4) {
+        *reinterpret_cast<uint2*>(gp) = make_uint2(gb[0] | (gb[1] << 16), gb[2] | (gb[3] << 16));
+      } else {
+#pragma unroll
+        for (int q = 0; q < CP / 8; ++q)
+          reinterpret_cast<uint4*>(gp)[q] = make_uint4(gb[8 * q] | (gb[8 * q + 1] << 16), gb[8 * q + 2] | (gb[8 * q + 3] << 16),
+                                                       gb[8 * q + 4] | (gb[8 * q + 5] << 16), gb[8 * q + 6] | (gb[8 * q + 7] << 16));
+      }
+    }
   }
   EDGE_STAMP(6);
   if (a.loss_part) {
-    float v[4] = {lsum, gsum[0], gsum[1], gsum[2]};
+    float v[1 + CMAX];
+    v[0] = lsum;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
+    for (int k = 0; k < CMAX; ++k) v[1 + k] = gsum[k];
 #pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) v[k] += __shfl_xor(v[k], o);
-      if (lane == 0) redl[wave][k] = v[k];
+    for (int k = 0; k < 1 + CMAX; ++k) {
+      if (k <= C) {
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) v[k] += __shfl_xor(v[k], o);
+        if (lane == 0) redl[wave][k] = v[k];
+      }
     }
     __syncthreads();
-    if (tid < 4) a.loss_part[(size_t)blockIdx.x * 4 + tid] = redl[0][tid] + redl[1][tid] + redl[2][tid] + redl[3][tid];
+    if (tid < LPS) a.loss_part[(size_t)blockIdx.x * LPS + tid] = tid <= C ? redl[0][tid] + redl[1][tid] + redl[2][tid] + redl[3][tid] : 0.f;
   }
   EDGE_STAMP(7);
 }
-template <int SRC>
-__global__ __launch_bounds__(256) void deconv4_loss_kernel(Deconv4Args a) { deconv4_loss_body<SRC>(a); }
-template <int SRC>
-__global__ __launch_bounds__(256) void deconv4_loss_kernel_g(GroupPack<Deconv4Args> p, int gz) { deconv4_loss_body<SRC>(group_args<Deconv4Args>(gz)); }
+template <int SRC, int CP>
+__global__ __launch_bounds__(256) void deconv4_loss_kernel(Deconv4Args a) { deconv4_loss_body<SRC, CP>(a); }
+template <int SRC, int CP>
+__global__ __launch_bounds__(256) void deconv4_loss_kernel_g(GroupPack<Deconv4Args> p, int gz) { deconv4_loss_body<SRC, CP>(group_args<Deconv4Args>(gz)); }

@@ -1,4 +1,5 @@
-// Host-side dispatch of the 3-channel edge-layer kernels (enc.conv1, dec.deconv4).
+// Host-side dispatch of the C-band edge-layer kernels (enc.conv1, dec.deconv4): the band count C (1..16) picks the padded width
+// CP = edge_cp(C), the last template argument of every edge kernel.
 #include "eae_internal.h"
 #include <cstdlib>
 #include "eae_edge.hip.h"
@@ -8,34 +9,44 @@ static int check_edge_shape(int B, int H, int W) {
   if (B <= 0 || H % 8 || W % 64) return eae_set_error(-2, "edge layer: image height must be a multiple of 8 and width of 64");
   return 0;
 }
+static int check_bands(int C) {
+  if (C < 1 || C > 16) return eae_set_error(-2, "edge layer: in_channels must be in 1..16");
+  return 0;
+}
 
 int eae_launch_edge_conv(hipStream_t st, int src3_kind, int epi, const EdgeArgs& a0) {
   if (int rc = check_edge_shape(a0.B, a0.H, a0.W)) return rc;
+  if (int rc = check_bands(a0.C)) return rc;
   EdgeArgs a = a0;
+  const int cp = edge_cp(a.C);
   dim3 grid(a.B * (a.H / 2 / E_TH) * (a.W / 2 / E_TW));
   a.c.ntiles = (int)grid.x;
-#define CASE(S, E) if (src3_kind == S && epi == E) { eae_launch(edge_conv_kernel<S, E>, edge_conv_kernel_g<S, E>, grid, dim3(256), 0, st, a); EAE_LAUNCH_CHECK(); return 0; }
+#define CASE1(S, E, P) if (src3_kind == S && epi == E && cp == P) { eae_launch(edge_conv_kernel<S, E, P>, edge_conv_kernel_g<S, E, P>, grid, dim3(256), 0, st, a); EAE_LAUNCH_CHECK(); return 0; }
+#define CASE(S, E) CASE1(S, E, 4) CASE1(S, E, 8) CASE1(S, E, 16)
   CASE(SRC3_NCHW_F32, EPI_FWD)
-  CASE(SRC3_NHWC4_BF16, EPI_MASK)
-  CASE(SRC3_NHWC4_BF16, EPI_PLAIN)
+  CASE(SRC3_NHWCP_BF16, EPI_MASK)
+  CASE(SRC3_NHWCP_BF16, EPI_PLAIN)
   CASE(SRC3_NCHW_F32, EPI_PLAIN)
 #undef CASE
+#undef CASE1
   return eae_set_error(-2, "edge_conv: combination not instantiated");
 }
 
 int eae_edge_tiles(int B, int H, int W) { return B * (H / 2 / E_TH) * (W / 2 / E_TW); }
 
-// dw [32][3][3][3] = reduce over blocks of the per-block partials. scratch must hold nblocks*864 floats.
+// dw [32][C][3][3] = reduce over blocks of the per-block partials. scratch must hold nblocks*288*C floats.
 int eae_launch_edge_wgrad(hipStream_t st, int src3_kind, const void* src3, int B, int H, int W, const SrcDesc& side, int smode,
                           float* scratch, long long scratch_floats, float* dw, const EaeProfHook* hook, const BnBwdFold* bfold,
-                          unsigned* sig, unsigned sig_val, int (*mid)(void*, GateArgs*), void* mid_user) {
+                          unsigned* sig, unsigned sig_val, int (*mid)(void*, GateArgs*), void* mid_user, int C) {
   if (int rc = check_edge_shape(B, H, W)) return rc;
+  if (int rc = check_bands(C)) return rc;
+  const int cp = edge_cp(C), slice = 32 * 9 * C;
   // the kernel addresses both operands through buffer descriptors with 32-bit byte offsets below OOB_OFF
   if ((long long)B * H * W * 16 >= 0x7fffff00LL) return eae_set_error(-2, "edge_wgrad: batch too large for one launch (2 GB per operand)");
   EdgeWgradArgs a;
   a.bfold = bfold ? *bfold : BnBwdFold();
   a.sig = sig; a.sig_val = sig_val;
-  a.src3 = src3; a.B = B; a.H = H; a.W = W; a.side = side; a.part = scratch;
+  a.src3 = src3; a.B = B; a.H = H; a.W = W; a.side = side; a.part = scratch; a.C = C;
   a.ntiles = eae_edge_tiles(B, H, W);
   // Workgroups: each writes a partial, so their number also sets the reduction behind the kernel.  Round 4 re-sweep at B=512 (ms per
   // step, main / side cap): 1024 / 1024 0.4875-0.4891, 512 / 1024 0.4832, 512 / 512 0.4821, 512 / 256 0.4794-0.4795, 768 / 256 0.4788,
@@ -43,25 +54,27 @@ int eae_launch_edge_wgrad(hipStream_t st, int src3_kind, const void* src3, int B
   static const int cap = getenv("EAE_EDGE_WGRAD_BLOCKS") ? atoi(getenv("EAE_EDGE_WGRAD_BLOCKS")) : 512;
   // a launch beside the backward-data chain (deconv4's weight gradient, side stream) takes fewer CUs from it with fewer blocks
   static const int cap_side = getenv("EAE_EDGE_WGRAD_SIDE_BLOCKS") ? atoi(getenv("EAE_EDGE_WGRAD_SIDE_BLOCKS")) : 256;
-  int lim = (src3_kind == SRC3_NHWC4_BF16) ? cap_side : cap;
+  int lim = (src3_kind == SRC3_NHWCP_BF16) ? cap_side : cap;
   if (eae_geo_mult > 1) lim = lim / eae_geo_mult > 32 ? lim / eae_geo_mult : 32;      // member of a grouped step: the caps are per launch
   int nblocks = a.ntiles < lim ? a.ntiles : lim;
-  while ((long long)nblocks * 864 > scratch_floats && nblocks > 1) nblocks /= 2;
+  while ((long long)nblocks * slice > scratch_floats && nblocks > 1) nblocks /= 2;
   a.tiles_per_block = (a.ntiles + nblocks - 1) / nblocks;
   nblocks = (a.ntiles + a.tiles_per_block - 1) / a.tiles_per_block;
-  if ((long long)nblocks * 864 > scratch_floats) return eae_set_error(-2, "edge_wgrad: scratch too small");
-#define CASE(S, M) if (src3_kind == S && smode == M) { if (hook) hook->begin(hook->user, st); eae_launch(edge_wgrad_kernel<S, M>, edge_wgrad_kernel_g<S, M>, dim3(nblocks), dim3(256), 0, st, a); if (hook) hook->end(hook->user, st); EAE_LAUNCH_CHECK(); goto reduce; }
+  if ((long long)nblocks * slice > scratch_floats) return eae_set_error(-2, "edge_wgrad: scratch too small");
+#define CASE1(S, M, P) if (src3_kind == S && smode == M && cp == P) { if (hook) hook->begin(hook->user, st); eae_launch(edge_wgrad_kernel<S, M, P>, edge_wgrad_kernel_g<S, M, P>, dim3(nblocks), dim3(256), 0, st, a); if (hook) hook->end(hook->user, st); EAE_LAUNCH_CHECK(); goto reduce; }
+#define CASE(S, M) CASE1(S, M, 4) CASE1(S, M, 8) CASE1(S, M, 16)
   CASE(SRC3_NCHW_F32, SRC_BNBWD)
-  CASE(SRC3_NHWC4_BF16, SRC_BNRELU)
+  CASE(SRC3_NHWCP_BF16, SRC_BNRELU)
   CASE(SRC3_NCHW_F32, SRC_RAW)
 #undef CASE
+#undef CASE1
   return eae_set_error(-2, "edge_wgrad: combination not instantiated");
 reduce:
   GateArgs tail = GateArgs();      // mid(): the caller's work between the two launches; a gate it returns is waited for in the reduction's tail
   if (mid) { if (int rc = mid(mid_user, &tail)) return rc; }
   {
-    const ReduceTallArgs ra = {scratch, nblocks, (long)(864 / 4), dw, tail};
-    eae_launch(reduce_slices_tall_kernel, reduce_slices_tall_kernel_g, dim3((864 / 4 + 3) / 4), dim3(256), 0, st, ra);
+    const ReduceTallArgs ra = {scratch, nblocks, (long)(slice / 4), dw, tail};
+    eae_launch(reduce_slices_tall_kernel, reduce_slices_tall_kernel_g, dim3((slice / 4 + 3) / 4), dim3(256), 0, st, ra);
   }
   EAE_LAUNCH_CHECK();
   return 0;
@@ -69,48 +82,76 @@ reduce:
 
 int eae_launch_deconv4_loss(hipStream_t st, int smode, const Deconv4Args& a) {
   if (a.B <= 0 || a.Hin % E_TH || a.Win % E_TW) return eae_set_error(-2, "deconv4: input must be a multiple of 4 x 32");
+  if (int rc = check_bands(a.C)) return rc;
   dim3 grid(a.B * (a.Hin / E_TH) * (a.Win / E_TW));
-  if (smode == SRC_BNRELU) eae_launch(deconv4_loss_kernel<SRC_BNRELU>, deconv4_loss_kernel_g<SRC_BNRELU>, grid, dim3(256), 0, st, a);
-  else if (smode == SRC_RAW) eae_launch(deconv4_loss_kernel<SRC_RAW>, deconv4_loss_kernel_g<SRC_RAW>, grid, dim3(256), 0, st, a);
-  else return eae_set_error(-2, "deconv4: source mode not instantiated");
-  EAE_LAUNCH_CHECK();
-  return 0;
+  const int cp = edge_cp(a.C);
+#define CASE(M, P) if (smode == M && cp == P) { eae_launch(deconv4_loss_kernel<M, P>, deconv4_loss_kernel_g<M, P>, grid, dim3(256), 0, st, a); EAE_LAUNCH_CHECK(); return 0; }
+  CASE(SRC_BNRELU, 4) CASE(SRC_BNRELU, 8) CASE(SRC_BNRELU, 16)
+  CASE(SRC_RAW, 4) CASE(SRC_RAW, 8) CASE(SRC_RAW, 16)
+#undef CASE
+  return eae_set_error(-2, "deconv4: source mode not instantiated");
 }
 
 // g4[n,oy,ox,c] = bf16(dx_hat * x_hat * (1 - x_hat))   (backward of nn.Sigmoid, R.md:383, for an externally supplied dL/dx_hat)
-// fp32 NCHW in, bf16 NHWC4 out; part[block][4] = {0, sum g(c=0), sum g(c=1), sum g(c=2)} (bias gradient of deconv4)
+// fp32 NCHW [B,C,H,W] in, bf16 NHWC-CP out; part[block][edge_lp_stride(C)] = {0, sum g(c) for c < C, zero padding} (bias gradient of
+// deconv4)
+template <int CP>
 __global__ EAE_NO_PK __launch_bounds__(256) void sigmoid_bwd_kernel(const float* __restrict__ xh, const float* __restrict__ dxh, bf16_t* __restrict__ g4,
-                                                           float* __restrict__ part, long npix_total, long plane) {
-  __shared__ float red[4][4];
+                                                           float* __restrict__ part, long npix_total, long plane, int C_) {
+  const int C = edge_bands<CP>(C_);
+  constexpr int CMAX = EdgeK<CP>::CMAX;
+  __shared__ float red[4][1 + CMAX];
+  const int LPS = edge_lp_stride(C);
   const long p = (long)blockIdx.x * 256 + threadIdx.x;      // pixel index n*H*W + oy*W + ox
-  float g[3] = {0.f, 0.f, 0.f};
+  float g[CMAX];
+#pragma unroll
+  for (int c = 0; c < CMAX; ++c) g[c] = 0.f;
   if (p < npix_total) {
     const long n = p / plane, r = p % plane;
-    uint32_t w[3];
+    uint32_t w[CP];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      float x = xh[(n * 3 + c) * plane + r];
-      w[c] = f2bf(dxh[(n * 3 + c) * plane + r] * x * (1.0f - x));
-      g[c] = bf2f(w[c]);
+    for (int c = 0; c < CP; ++c) w[c] = 0u;
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c) {
+      if (c < C) {
+        float x = xh[(n * C + c) * plane + r];
+        w[c] = f2bf(dxh[(n * C + c) * plane + r] * x * (1.0f - x));
+        g[c] = bf2f(w[c]);
+      }
     }
-    *reinterpret_cast<uint2*>(g4 + p * 4) = make_uint2(w[0] | (w[1] << 16), w[2]);
+    if constexpr (CP == 4) {
+      *reinterpret_cast<uint2*>(g4 + p * 4) = make_uint2(w[0] | (w[1] << 16), w[2] | (w[3] << 16));
+    } else {
+#pragma unroll
+      for (int q = 0; q < CP / 8; ++q)
+        reinterpret_cast<uint4*>(g4 + p * CP)[q] = make_uint4(w[8 * q] | (w[8 * q + 1] << 16), w[8 * q + 2] | (w[8 * q + 3] << 16),
+                                                              w[8 * q + 4] | (w[8 * q + 5] << 16), w[8 * q + 6] | (w[8 * q + 7] << 16));
+    }
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-  for (int c = 0; c < 3; ++c) {
+  for (int c = 0; c < CMAX; ++c) {
+    if (c < C) {
 #pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) g[c] += __shfl_xor(g[c], o);
-    if (lane == 0) red[wave][c + 1] = g[c];
+      for (int o = 32; o >= 1; o >>= 1) g[c] += __shfl_xor(g[c], o);
+      if (lane == 0) red[wave][c + 1] = g[c];
+    }
   }
   __syncthreads();
-  if (threadIdx.x < 4)
-    part[(size_t)blockIdx.x * 4 + threadIdx.x] = threadIdx.x == 0 ? 0.f : red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+  if ((int)threadIdx.x < LPS)
+    part[(size_t)blockIdx.x * LPS + threadIdx.x] = (threadIdx.x == 0 || (int)threadIdx.x > C) ? 0.f
+        : red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
-int eae_launch_sigmoid_bwd(hipStream_t st, const float* x_hat, const float* dx_hat, void* g4, float* part, int B, int H, int W) {
+int eae_launch_sigmoid_bwd(hipStream_t st, const float* x_hat, const float* dx_hat, void* g4, float* part, int B, int H, int W, int C) {
+  if (int rc = check_bands(C)) return rc;
   const long plane = (long)H * W, tot = plane * B;
   EAE_NO_GROUP("sigmoid_bwd");
-  hipLaunchKernelGGL(sigmoid_bwd_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, x_hat, dx_hat, (bf16_t*)g4, part, tot, plane);
+  const dim3 grid((unsigned)((tot + 255) / 256));
+  const int cp = edge_cp(C);
+  if (cp == 4) hipLaunchKernelGGL(sigmoid_bwd_kernel<4>, grid, dim3(256), 0, st, x_hat, dx_hat, (bf16_t*)g4, part, tot, plane, C);
+  else if (cp == 8) hipLaunchKernelGGL(sigmoid_bwd_kernel<8>, grid, dim3(256), 0, st, x_hat, dx_hat, (bf16_t*)g4, part, tot, plane, C);
+  else hipLaunchKernelGGL(sigmoid_bwd_kernel<16>, grid, dim3(256), 0, st, x_hat, dx_hat, (bf16_t*)g4, part, tot, plane, C);
   EAE_LAUNCH_CHECK();
   return 0;
 }

@@ -230,56 +230,73 @@ __device__ __forceinline__ double lf_wave_sum(double v) {
   for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
-struct LossFinArgs { const float* mse_part; int n_mse; const float* ce_part; int n_ce; float alpha, inv_numel, B; float* db4; float* accum; float* last; const unsigned* poison; };
+// mse_part rows are NQ float4s: {sum diff^2, sum g(c) for the nch bands, zero padding} (NQ = 1 for RGB)
+struct LossFinArgs { const float* mse_part; int n_mse; const float* ce_part; int n_ce; float alpha, inv_numel, B; float* db4; float* accum; float* last; const unsigned* poison; int nch; };
+template <int NQ>
 __device__ __forceinline__ EAE_NO_PK void loss_finalize_body(const LossFinArgs& a) {
   const float* mse_part = a.mse_part; const int n_mse = a.n_mse; const float* ce_part = a.ce_part; const int n_ce = a.n_ce;
   const float alpha = a.alpha, inv_numel = a.inv_numel, B = a.B;
   float* db4 = a.db4; float* accum = a.accum; float* last = a.last; const unsigned* poison = a.poison;
-  __shared__ double red[4][6];
+  constexpr int NS = 4 * NQ + 2;      // the mse row's 4*NQ sums, then CE and the number correct
+  __shared__ double red[4][NS];
   const int tid = threadIdx.x;
-  double s[6] = {0, 0, 0, 0, 0, 0};
+  double s[NS];
+#pragma unroll
+  for (int k = 0; k < NS; ++k) s[k] = 0;
   // 8 loads in flight per thread: with one load per loop iteration every iteration exposed a full memory round trip (16 of them at
   // B=512: that, not the reduction, was this kernel's 16 us)
   // (ONE 1024-thread block with every row requested in the first round was measured too: 29 us in situ instead of 11 -- a 16-wave
   //  workgroup waits for a CU with that many free wave slots beside the register-filling weight-gradient workgroups)
   for (int i0 = tid; i0 < n_mse; i0 += 256 * 8) {
-    float4 v[8];
+    float4 v[8][NQ];
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const int i = i0 + q * 256;
-      v[q] = i < n_mse ? reinterpret_cast<const float4*>(mse_part)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int j = 0; j < NQ; ++j) v[q][j] = i < n_mse ? reinterpret_cast<const float4*>(mse_part)[(size_t)i * NQ + j] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
 #pragma unroll
-    for (int q = 0; q < 8; ++q) { s[0] += v[q].x; s[1] += v[q].y; s[2] += v[q].z; s[3] += v[q].w; }
-  }
-  for (int i = tid; i < n_ce; i += 256) { s[4] += ce_part[i * 2]; s[5] += ce_part[i * 2 + 1]; }
+    for (int q = 0; q < 8; ++q)
 #pragma unroll
-  for (int k = 0; k < 6; ++k) {       // (round 2: a 9-step LDS tree with 8 barriers over fp64[256][6], 16-18 us inside the step)
+      for (int j = 0; j < NQ; ++j) { s[4 * j] += v[q][j].x; s[4 * j + 1] += v[q][j].y; s[4 * j + 2] += v[q][j].z; s[4 * j + 3] += v[q][j].w; }
+  }
+  for (int i = tid; i < n_ce; i += 256) { s[NS - 2] += ce_part[i * 2]; s[NS - 1] += ce_part[i * 2 + 1]; }
+#pragma unroll
+  for (int k = 0; k < NS; ++k) {       // (round 2: a 9-step LDS tree with 8 barriers over fp64[256][6], 16-18 us inside the step)
     const double w = lf_wave_sum(s[k]);
     if ((tid & 63) == 0) red[tid >> 6][k] = w;
   }
   __syncthreads();
   if (tid == 0) {
-    double r[6];
+    double r[NS];
 #pragma unroll
-    for (int k = 0; k < 6; ++k) r[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+    for (int k = 0; k < NS; ++k) r[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
     float mse = (float)(r[0] * inv_numel);
-    float cem = n_ce ? (float)(r[4] / B) : 0.f;
+    float cem = n_ce ? (float)(r[NS - 2] / B) : 0.f;
     float loss = alpha * mse + cem;
     // a BatchNorm layer of this step saw non-finite statistics (bn_fold_fwd_finish): the losses read NaN like the reference's
     if (poison != nullptr && __hip_atomic_load(poison, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) loss = mse = cem = __builtin_nanf("");
-    if (db4) { db4[0] = (float)r[1]; db4[1] = (float)r[2]; db4[2] = (float)r[3]; }
-    if (accum) { accum[0] += loss * B; accum[1] += mse * B; accum[2] += cem * B; accum[3] += B; accum[4] += (float)r[5]; }
+    if (db4) for (int k = 0; k < a.nch; ++k) db4[k] = (float)r[1 + k];
+    if (accum) { accum[0] += loss * B; accum[1] += mse * B; accum[2] += cem * B; accum[3] += B; accum[4] += (float)r[NS - 1]; }
     if (last) { last[0] = loss; last[1] = mse; last[2] = cem; }
   }
 }
-__global__ EAE_NO_PK __launch_bounds__(256) void loss_finalize_kernel(LossFinArgs a) { loss_finalize_body(a); }
-__global__ EAE_NO_PK __launch_bounds__(256) void loss_finalize_kernel_g(GroupPack<LossFinArgs> p, int gz) { loss_finalize_body(group_args<LossFinArgs>(gz)); }
+template <int NQ>
+__global__ EAE_NO_PK __launch_bounds__(256) void loss_finalize_kernel(LossFinArgs a) { loss_finalize_body<NQ>(a); }
+template <int NQ>
+__global__ EAE_NO_PK __launch_bounds__(256) void loss_finalize_kernel_g(GroupPack<LossFinArgs> p, int gz) { loss_finalize_body<NQ>(group_args<LossFinArgs>(gz)); }
 
 int eae_launch_loss_finalize(hipStream_t st, const float* mse_part, int n_mse, const float* ce_part, int n_ce, float alpha,
-                             double numel, int B, float* db4, float* accum, float* last, const unsigned* poison) {
-  const LossFinArgs la = {mse_part, n_mse, ce_part, n_ce, alpha, (float)(1.0 / numel), (float)B, db4, accum, last, poison};
-  eae_launch(loss_finalize_kernel, loss_finalize_kernel_g, dim3(1), dim3(256), 0, st, la);
+                             double numel, int B, float* db4, float* accum, float* last, const unsigned* poison, int nch) {
+  const LossFinArgs la = {mse_part, n_mse, ce_part, n_ce, alpha, (float)(1.0 / numel), (float)B, db4, accum, last, poison, nch};
+  switch ((nch + 4) / 4) {      // float4s per mse row (edge_lp_stride)
+    case 1: eae_launch(loss_finalize_kernel<1>, loss_finalize_kernel_g<1>, dim3(1), dim3(256), 0, st, la); break;
+    case 2: eae_launch(loss_finalize_kernel<2>, loss_finalize_kernel_g<2>, dim3(1), dim3(256), 0, st, la); break;
+    case 3: eae_launch(loss_finalize_kernel<3>, loss_finalize_kernel_g<3>, dim3(1), dim3(256), 0, st, la); break;
+    case 4: eae_launch(loss_finalize_kernel<4>, loss_finalize_kernel_g<4>, dim3(1), dim3(256), 0, st, la); break;
+    case 5: eae_launch(loss_finalize_kernel<5>, loss_finalize_kernel_g<5>, dim3(1), dim3(256), 0, st, la); break;
+    default: return eae_set_error(-2, "loss_finalize: in_channels must be in 1..16");
+  }
   EAE_LAUNCH_CHECK();
   return 0;
 }

@@ -40,12 +40,12 @@ int eae_edge_tiles(int B, int H, int W);
 int eae_launch_edge_wgrad(hipStream_t st, int src3_kind, const void* src3, int B, int H, int W, const SrcDesc& side, int smode,
                           float* scratch, long long scratch_floats, float* dw, const EaeProfHook* hook = nullptr,
                           const struct BnBwdFold* bfold = nullptr, unsigned* sig = nullptr, unsigned sig_val = 0,
-                          int (*mid)(void*, GateArgs*) = nullptr, void* mid_user = nullptr);
+                          int (*mid)(void*, GateArgs*) = nullptr, void* mid_user = nullptr, int C = 3);
 int eae_launch_deconv4_loss(hipStream_t st, int smode, const Deconv4Args& a);
 int eae_launch_wgrad_s2(hipStream_t st, const WgradArgs& a, int cs, int cb, int smode, int bmode, float* scratch,
                         long long scratch_floats, float* dw, const EaeProfHook* hook = nullptr);
 int eae_launch_fc_nt(hipStream_t st, const FcNtArgs& a, int amode, int epi, int ksplit);
 int eae_launch_fc_reduce(hipStream_t st, const float* part, int nsl, int M, int N, const float* bias, const float* addend,
                          const float* addend2, float* out);
-int eae_launch_sigmoid_bwd(hipStream_t st, const float* x_hat, const float* dx_hat, void* g4, float* part, int B, int H, int W);
+int eae_launch_sigmoid_bwd(hipStream_t st, const float* x_hat, const float* dx_hat, void* g4, float* part, int B, int H, int W, int C = 3);
 int eae_launch_fc_tn(hipStream_t st, const FcTnArgs& a, int pmode, int qmode);

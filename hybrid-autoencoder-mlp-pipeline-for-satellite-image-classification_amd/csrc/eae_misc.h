@@ -3,7 +3,7 @@
 #include <stdint.h>
 
 enum { PACK_COPY = 0, PACK_3x3_P1, PACK_3x3_P2, PACK_K27, PACK_DECONV4_JOINT, PACK_FC_ROWMAJOR_KPERM, PACK_FC_TRANS_KPERM,
-       PACK_FC_ROWPERM, PACK_FC_ROWPERM_TRANS, PACK_K36, PACK_PAD_COLS };
+       PACK_FC_ROWPERM, PACK_FC_ROWPERM_TRANS, PACK_KCP, PACK_PAD_COLS };
 
 struct PackDesc {
   long long src_off;   // element offset into the fp32 parameter arena
@@ -81,5 +81,8 @@ int eae_launch_adam_scaled(hipStream_t st, float* p, const float* g, float* m, f
                            double eps, double wd, long long step, float gscale, void* zero_buf = nullptr, long long zero_bytes = 0,
                            const unsigned* bad = nullptr, const unsigned* bad2 = nullptr, float* nan_out = nullptr, int nan_fill = 0,
                            int max_blocks = 0 /* 0: 2048; the grid-stride loop covers the rest */);
+int eae_launch_stage_bands(hipStream_t st, const void* src, int elem_bytes, long long N, int C, int H, int W, const long long* index, int B,
+                           const float* divisor, float* out, int train, float std, unsigned long long seed, unsigned long long step,
+                           const int* params, const float* noise);
 int eae_launch_augment(hipStream_t st, const void* in_u8, float* out, int B, int H, int W, int train, float std, unsigned long long seed,
                        unsigned long long step, const int* params, const float* noise);

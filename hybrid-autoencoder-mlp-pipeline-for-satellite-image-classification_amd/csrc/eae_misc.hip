@@ -226,20 +226,22 @@ __device__ __forceinline__ float pack_fetch(const PackDesc& d, const float* __re
       unsigned tap = k / 3u, c = k % 3u;
       return src[(a * 3u + c) * 9u + tap];
     }
-    case PACK_K36: {      // dst [A][64] with k = tap*4 + c (zero for c == 3 and k >= 36)  <- src [A][3][3][3]   (edge_conv_kernel)
-      unsigned k = i & 63u, a = i >> 6;
-      if (k >= 36u || (k & 3u) == 3u) return 0.f;
-      return src[(a * 3u + (k & 3u)) * 9u + (k >> 2)];
+    case PACK_KCP: {      // dst [A][KP] with k = tap*CP + c, KP = 9*CP padded to 32 (zero for c >= C and k >= 9*CP)  <- src [A][C][3][3]
+      // (d1 = C, d2 = CP; edge_conv_kernel.  CP = 4: dst [A][64])
+      const unsigned KP = (9u * d2 + 31u) & ~31u, k = i % KP, a = i / KP, tap = k / d2, c = k % d2;
+      if (tap >= 9u || c >= d1) return 0.f;
+      return src[(a * d1 + c) * 9u + tap];
     }
-    case PACK_DECONV4_JOINT: {   // dst [16][128]: n = phase*3+co, k = nb*32+ci  <- src [32 ci][3 co][3][3]
+    case PACK_DECONV4_JOINT: {   // dst [16*NT][128]: n = phase*C+co, k = nb*32+ci  <- src [32 ci][C co][3][3]   (d1 = C)
       int k = i & 127; int n = i >> 7;
-      if (n >= 12) return 0.f;
-      int ph = n / 3, co = n % 3, nb = k >> 5, ci = k & 31;
+      const int C = (int)d1;
+      if (n >= 4 * C) return 0.f;
+      int ph = n / C, co = n % C, nb = k >> 5, ci = k & 31;
       int py = ph >> 1, px = ph & 1, dy = nb >> 1, dx = nb & 1;
       int ky = py == 0 ? (dy == 0 ? 1 : -1) : (dy == 0 ? 2 : 0);
       int kx = px == 0 ? (dx == 0 ? 1 : -1) : (dx == 0 ? 2 : 0);
       if (ky < 0 || kx < 0) return 0.f;
-      return src[(ci * 3 + co) * 9 + ky * 3 + kx];
+      return src[(ci * C + co) * 9 + ky * 3 + kx];
     }
     // FC modes: d0 = latent width PADDED to a multiple of 64, d.lv = the real width (rows / columns >= lv are zero; the source
     // tensor has lv of them)
@@ -749,6 +751,82 @@ __global__ EAE_NO_PK __launch_bounds__(256) void augment_kernel(const uint8_t* _
   }
 #pragma unroll
   for (int c = 0; c < 3; ++c) out[((long)n * 3 + c) * plane + r] = v[c];
+}
+
+// Multispectral staging: the same transform for C bands of a dataset kept in device memory, gathered by index.
+//   out[b,c,y,x] = src[n, c, y+top-4, flip ? W-1-(x+left-4) : x+left-4] / divisor[c] (0 outside) + std * N(0,1),  n = index[b] (or b)
+// src uint8 or uint16 planar [N,C,H,W] (e.g. reflectance x 10000); the division is a true one, as ToTensor's.  (flip, top, left)
+// come from the Philox stream of augment_kernel (keyed by (seed, step) and the batch position b) unless `params` is given; the
+// noise from one Philox call per pixel and group of four bands (Box-Muller pairs) unless `noise` [B,C,H,W] is given.  An index
+// outside 0..N-1 yields NaN for that image instead of a read outside the dataset.
+template <typename T>
+__global__ EAE_NO_PK __launch_bounds__(256) void stage_bands_kernel(const T* __restrict__ src, long long N, int C, int H, int W,
+                                                           const long long* __restrict__ index, int B, const float* __restrict__ divisor,
+                                                           float* __restrict__ out, int train, float std, unsigned long long seed,
+                                                           unsigned long long step, const int* __restrict__ params,
+                                                           const float* __restrict__ noise) {
+  const long plane = (long)H * W;
+  const long p = (long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= plane * B) return;
+  const int b = (int)(p / plane), r = (int)(p % plane), y = r / W, x = r % W;
+  const long long n = index ? index[b] : (long long)b;
+  const bool valid = n >= 0 && n < N;
+  int flip = 0, top = 4, left = 4;
+  if (train) {
+    if (params) { flip = params[b * 3]; top = params[b * 3 + 1]; left = params[b * 3 + 2]; }
+    else {
+      uint32_t o[4];
+      philox4((uint32_t)b, 0x5eedu, (uint32_t)step, (uint32_t)(step >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), o);
+      flip = o[0] >> 31; top = (int)(((unsigned long long)o[1] * 9) >> 32); left = (int)(((unsigned long long)o[2] * 9) >> 32);
+    }
+  }
+  const int sy = y + top - 4;
+  int sx = x + left - 4;
+  const bool inside = valid && sy >= 0 && sy < H && sx >= 0 && sx < W;
+  if (flip) sx = W - 1 - sx;
+  const T* q = src + (inside ? (((size_t)n * C * H + sy) * W + sx) : (size_t)0);
+  for (int c0 = 0; c0 < C; c0 += 4) {
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+    if (train && std != 0.f && !noise) {
+      uint32_t o[4];
+      philox4((uint32_t)p, ((uint32_t)(p >> 32) ^ 0xA5A5u) + ((uint32_t)c0 << 16), (uint32_t)step, (uint32_t)(step >> 32), (uint32_t)seed,
+              ~(uint32_t)(seed >> 32), o);
+      const float u1 = ((o[0] >> 8) + 1) * (1.0f / 16777216.0f), u2 = (o[1] >> 8) * (1.0f / 16777216.0f);
+      const float u3 = ((o[2] >> 8) + 1) * (1.0f / 16777216.0f), u4 = (o[3] >> 8) * (1.0f / 16777216.0f);
+      const float r1 = sqrtf(-2.0f * __logf(u1)), r2 = sqrtf(-2.0f * __logf(u3));
+      z[0] = r1 * __cosf(6.28318530718f * u2); z[1] = r1 * __sinf(6.28318530718f * u2);
+      z[2] = r2 * __cosf(6.28318530718f * u4); z[3] = r2 * __sinf(6.28318530718f * u4);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int c = c0 + j;
+      if (c >= C) break;
+      float v = inside ? (float)q[(size_t)c * plane] / divisor[c] : 0.f;
+      if (!valid) v = __builtin_nanf("");
+      if (train && std != 0.f) v = fmaf(std, noise ? noise[((long)b * C + c) * plane + r] : z[j], v);
+      out[((long)b * C + c) * plane + r] = v;
+    }
+  }
+}
+
+int eae_launch_stage_bands(hipStream_t st, const void* src, int elem_bytes, long long N, int C, int H, int W, const long long* index, int B,
+                           const float* divisor, float* out, int train, float std, unsigned long long seed, unsigned long long step,
+                           const int* params, const float* noise) {
+  if (!src || !divisor || !out || N <= 0 || B <= 0 || H <= 0 || W <= 0) return eae_set_error(-2, "stage_bands: bad argument");
+  if (C < 1 || C > 16) return eae_set_error(-2, "stage_bands: in_channels must be in 1..16");
+  if (elem_bytes != 1 && elem_bytes != 2) return eae_set_error(-2, "stage_bands: source must be uint8 or uint16 (elem_bytes 1 or 2)");
+  if (!index && B > N) return eae_set_error(-2, "stage_bands: without an index the batch is the first B images (B <= N)");
+  const long tot = (long)B * H * W;
+  EAE_NO_GROUP("stage_bands_kernel");
+  const dim3 grid((unsigned)((tot + 255) / 256));
+  if (elem_bytes == 1)
+    hipLaunchKernelGGL(stage_bands_kernel<uint8_t>, grid, dim3(256), 0, st, (const uint8_t*)src, N, C, H, W, index, B, divisor, out, train, std,
+                       seed, step, params, noise);
+  else
+    hipLaunchKernelGGL(stage_bands_kernel<uint16_t>, grid, dim3(256), 0, st, (const uint16_t*)src, N, C, H, W, index, B, divisor, out, train,
+                       std, seed, step, params, noise);
+  EAE_LAUNCH_CHECK();
+  return 0;
 }
 
 int eae_launch_augment(hipStream_t st, const void* in_u8, float* out, int B, int H, int W, int train, float std, unsigned long long seed,

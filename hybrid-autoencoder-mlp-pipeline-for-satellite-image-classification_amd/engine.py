@@ -57,21 +57,21 @@ class AEEngine:
         self.root_ref = weakref.ref(root)
         if isinstance(root, SupervisedAutoencoder):
             enc, dec, cls = root.enc, root.dec, root.classifier
-            latent, classes, size = root.latent_dim, root.num_classes, root.enc.image_size
+            latent, classes, size, bands = root.latent_dim, root.num_classes, root.enc.image_size, root.enc.in_channels
         elif isinstance(root, Encoder):
-            enc, dec, cls, latent, classes, size = root, None, None, root.latent_dim, 10, root.image_size
+            enc, dec, cls, latent, classes, size, bands = root, None, None, root.latent_dim, 10, root.image_size, root.in_channels
         elif isinstance(root, Decoder):
-            enc, dec, cls, latent, classes, size = None, root, None, root.latent_dim, 10, root.image_size
+            enc, dec, cls, latent, classes, size, bands = None, root, None, root.latent_dim, 10, root.image_size, root.out_channels
         else:
             raise TypeError(type(root))
-        self.latent, self.classes, self.size = latent, classes, size
+        self.latent, self.classes, self.size, self.bands = latent, classes, size, int(bands)
         p0 = next(root.parameters())
         self.device = p0.device
         _require_gpu(self.device)
         # side_streams: None / 0 = the engine's default (two side streams), 1 / 2 = that many, -1 = none (one stream per context: what
         # several contexts stepped concurrently want, include/eae.h eae_config.side_streams)
         self.side_streams = int(side_streams or 0)
-        self.cfg = EaeConfig(latent, classes, size, size, int(max_batch), self.quant, self.side_streams)
+        self.cfg = EaeConfig(latent, classes, size, size, int(max_batch), self.quant, self.side_streams, self.bands)
         self.max_batch = int(max_batch)
         poff = (C.c_longlong * 39)()
         boff = (C.c_longlong * 15)()
@@ -210,9 +210,9 @@ class AEEngine:
 
     # ------------------------------------------------------------------ steps
     def _io(self, x, labels, train, head, alpha, x_hat=None, logits=None, z=None, accum=True):
-        if x.device != self.device or x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or \
+        if x.device != self.device or x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != self.bands or \
                 x.shape[2] != self.size or x.shape[3] != self.size:
-            raise RuntimeError(f"expected float32 input [B,3,{self.size},{self.size}] on {self.device}, got "
+            raise RuntimeError(f"expected float32 input [B,{self.bands},{self.size},{self.size}] on {self.device}, got "
                                f"{tuple(x.shape)} {x.dtype} on {x.device}")
         if not x.is_contiguous():
             x = x.contiguous()
@@ -230,7 +230,7 @@ class AEEngine:
     @_on_device
     def forward(self, x, labels=None, train=False, head=True, alpha=1.0, want=("x_hat", "logits", "z"), accum=False):
         b = x.shape[0]
-        x_hat = torch.empty((b, 3, self.size, self.size), dtype=torch.float32, device=self.device) if "x_hat" in want else None
+        x_hat = torch.empty((b, self.bands, self.size, self.size), dtype=torch.float32, device=self.device) if "x_hat" in want else None
         logits = torch.empty((b, self.classes), dtype=torch.float32, device=self.device) if ("logits" in want and head) else None
         z = torch.empty((b, self.latent), dtype=torch.float32, device=self.device) if "z" in want else None
         io, keep = self._io(x, labels, train, head, alpha, x_hat, logits, z, accum)
@@ -326,7 +326,7 @@ class AEEngine:
         b = z.shape[0]
         if b > self.max_batch:
             raise RuntimeError(f"batch {b} exceeds the engine's max_batch {self.max_batch}")
-        x_hat = torch.empty((b, 3, self.size, self.size), dtype=torch.float32, device=self.device)
+        x_hat = torch.empty((b, self.bands, self.size, self.size), dtype=torch.float32, device=self.device)
         check(self.lib.eae_decoder_forward(self.ctx, _stream(), _ptr(z), b, int(train), _ptr(x_hat)))
         return x_hat
 

@@ -59,21 +59,30 @@ class _Marker(nn.Module):
     forward = _no_forward
 
 
+def _bands(n, what):
+    """Image band count of the engine's edge layers: 1..16 (3 = RGB, the reference's value)."""
+    if isinstance(n, bool) or int(n) != n or not 1 <= int(n) <= 16:
+        raise ValueError(f"{what} must be an integer in 1..16 (image bands), got {n!r}")
+    return int(n)
+
+
 def _engine():
     from . import engine
     return engine
 
 
 class Encoder(nn.Module):
-    """R.md:287-313. forward(x [B,3,H,W] fp32) -> z [B,latent_dim]."""
+    """R.md:287-313. forward(x [B,in_channels,H,W] fp32) -> z [B,latent_dim].  in_channels: image bands, 1..16 (the reference's
+    RGB is 3); only conv1's weight [32,in_channels,3,3] depends on it."""
 
-    def __init__(self, latent_dim, image_size=64):
+    def __init__(self, latent_dim, image_size=64, in_channels=3):
         super().__init__()
         self.latent_dim = int(latent_dim)
         self.image_size = int(image_size)
+        self.in_channels = _bands(in_channels, "in_channels")
         fmap = self.image_size // 16
         self.encoder = nn.Sequential(
-            ConvS2Params(3, 32, 3, stride=2, padding=1), BatchNorm2dParams(32), _Marker("ReLU"),
+            ConvS2Params(self.in_channels, 32, 3, stride=2, padding=1), BatchNorm2dParams(32), _Marker("ReLU"),
             ConvS2Params(32, 64, 3, stride=2, padding=1), BatchNorm2dParams(64), _Marker("ReLU"),
             ConvS2Params(64, 128, 3, stride=2, padding=1), BatchNorm2dParams(128), _Marker("ReLU"),
             ConvS2Params(128, 256, 3, stride=2, padding=1), BatchNorm2dParams(256), _Marker("ReLU"),
@@ -86,12 +95,14 @@ class Encoder(nn.Module):
 
 
 class Decoder(nn.Module):
-    """R.md:361-389. forward(z [B,latent_dim]) -> x_hat [B,3,H,W] in (0,1)."""
+    """R.md:361-389. forward(z [B,latent_dim]) -> x_hat [B,out_channels,H,W] in (0,1).  out_channels: image bands, 1..16 (3 = RGB);
+    only deconv4's weight [32,out_channels,3,3] and bias [out_channels] depend on it."""
 
-    def __init__(self, latent_dim, image_size=64):
+    def __init__(self, latent_dim, image_size=64, out_channels=3):
         super().__init__()
         self.latent_dim = int(latent_dim)
         self.image_size = int(image_size)
+        self.out_channels = _bands(out_channels, "out_channels")
         fmap = self.image_size // 16
         self.decoder_input = LinearParams(self.latent_dim, 256 * fmap * fmap)
         self.decoder = nn.Sequential(
@@ -99,7 +110,7 @@ class Decoder(nn.Module):
             DeconvS2Params(256, 128, 3, stride=2, padding=1, output_padding=1), BatchNorm2dParams(128), _Marker("ReLU"),
             DeconvS2Params(128, 64, 3, stride=2, padding=1, output_padding=1), BatchNorm2dParams(64), _Marker("ReLU"),
             DeconvS2Params(64, 32, 3, stride=2, padding=1, output_padding=1), BatchNorm2dParams(32), _Marker("ReLU"),
-            DeconvS2Params(32, 3, 3, stride=2, padding=1, output_padding=1),
+            DeconvS2Params(32, self.out_channels, 3, stride=2, padding=1, output_padding=1),
             _Marker("Sigmoid"),
         )
 
@@ -108,14 +119,15 @@ class Decoder(nn.Module):
 
 
 class SupervisedAutoencoder(nn.Module):
-    """R.md:416-433. forward(x) -> (x_hat, logits, z)."""
+    """R.md:416-433. forward(x) -> (x_hat, logits, z); x and x_hat are [B,in_channels,H,W]."""
 
-    def __init__(self, latent_dim, num_classes=10, image_size=64):
+    def __init__(self, latent_dim, num_classes=10, image_size=64, in_channels=3):
         super().__init__()
         self.latent_dim = int(latent_dim)
         self.num_classes = int(num_classes)
-        self.enc = Encoder(latent_dim, image_size)
-        self.dec = Decoder(latent_dim, image_size)
+        self.in_channels = _bands(in_channels, "in_channels")
+        self.enc = Encoder(latent_dim, image_size, in_channels=self.in_channels)
+        self.dec = Decoder(latent_dim, image_size, out_channels=self.in_channels)
         self.classifier = nn.Sequential(
             LinearParams(self.latent_dim, 128),
             _Marker("ReLU"),

@@ -126,13 +126,15 @@ def _first_batch_size(loader, default=64):
 
 # ------------------------------------------------------------------------------------------------ autoencoder
 def fit_autoencoder(train_loader, val_loader, alpha, lr, latent_dim=64, num_classes=10, num_epochs=80, patience=15,
-                    device="cuda", model=None, stepper=None, head=True, verbose=True, log=print, graph=None, side_streams=None):
+                    device="cuda", model=None, stepper=None, head=True, verbose=True, log=print, graph=None, side_streams=None,
+                    in_channels=3):
     """One (alpha, lr) configuration of the reference's AE loop (R.md:619-697).
 
     Returns dict(model, train_curve, val_curve, best_val_loss, epochs).  As in the reference, `model` holds the weights of
-    the LAST epoch run (R.md:705 keeps a live reference, not the best epoch's weights)."""
+    the LAST epoch run (R.md:705 keeps a live reference, not the best epoch's weights).  in_channels: image bands of the model built
+    here (1..16; the loaders yield [B,in_channels,H,W])."""
     if model is None and stepper is None:
-        model = SupervisedAutoencoder(latent_dim=latent_dim, num_classes=num_classes).to(device)
+        model = SupervisedAutoencoder(latent_dim=latent_dim, num_classes=num_classes, in_channels=in_channels).to(device)
         if side_streams is not None:
             model._eae_side_streams = side_streams      # read when the model's engine is first built (engine.engine_for)
     if stepper is None:
@@ -177,15 +179,17 @@ def fit_autoencoder(train_loader, val_loader, alpha, lr, latent_dim=64, num_clas
 
 
 def fit_autoencoder_group(train_loader, val_loader, configs, latent_dim=64, num_classes=10, num_epochs=80, patience=15,
-                          device="cuda", models=None, stepper=None, head=True, verbose=True, logs=None):
+                          device="cuda", models=None, stepper=None, head=True, verbose=True, logs=None, in_channels=3):
     """fit_autoencoder for SEVERAL (alpha, lr) configurations at once: the members share every batch of the two loaders (one pass of
     the loader per epoch for the whole group) and each keeps its own curves, best loss and early-stopping counter exactly as the
     reference's loop does for it alone (R.md:619-697); a member that stops early drops out, the others go on.
 
-    Returns one fit_autoencoder-style dict per configuration.  logs: optional list of per-configuration line lists."""
+    Returns one fit_autoencoder-style dict per configuration.  logs: optional list of per-configuration line lists.  in_channels: image
+    bands of the models built here (1..16)."""
     n = len(configs)
     if models is None and stepper is None:
-        models = [SupervisedAutoencoder(latent_dim=latent_dim, num_classes=num_classes).to(device) for _ in range(n)]
+        models = [SupervisedAutoencoder(latent_dim=latent_dim, num_classes=num_classes, in_channels=in_channels).to(device)
+                  for _ in range(n)]
         for m in models:
             m._eae_side_streams = 2              # a grouped step is fastest with two side streams (the engine's default is three)
     if stepper is None:
@@ -338,7 +342,7 @@ def run_concurrent(jobs, concurrent, device="cuda", static=False):
 def grid_search_autoencoder(train_loader, val_loader, alpha_values=(20, 25, 30, 35, 40),
                             lr_values=(1e-4, 2e-4, 5e-4, 1e-3, 2e-3, 5e-3, 1e-2, 5e-2, 1e-1), latent_dim=64, num_epochs=80,
                             patience=15, out_dir="models_best", device="cuda", verbose=True, log=print, fit_fn=None, concurrent=1,
-                            grouped=0, group_fit_fn=None, concurrent_groups=1):
+                            grouped=0, group_fit_fn=None, concurrent_groups=1, in_channels=3):
     """The reference's alpha x lr grid (R.md:599-729): trains every configuration, keeps the global best, writes
     `out_dir/AE_GLOBAL_BEST.pt` (plain state_dict) and `out_dir/validation_losses.json` (keys "alpha={a}, lr={lr}").
 
@@ -358,6 +362,9 @@ def grid_search_autoencoder(train_loader, val_loader, alpha_values=(20, 25, 30, 
     (tests/test_gpu_grid.py); what differs from the sequential grid is the data order when the loader shuffles: the members of a
     group see the same permutation per epoch instead of consecutive draws from the generator.
 
+    in_channels=C (1..16) trains multispectral models: the loaders yield [B,C,H,W]; it is passed on to the fit functions (to a custom
+    fit_fn / group_fit_fn only when it is not 3).
+
     concurrent_groups=2 (with grouped=K) runs two groups at a time from two host threads (run_concurrent), every context with ONE side
     stream: 2 x 2 streams are the GPU's four hardware queues, and one group's forward pass -- a chain of latency-bound kernels that
     leaves most CUs idle -- runs beside the other group's backward pass (bench.py `configs.grid_b64`: 16 configurations at 0.89-0.92 M
@@ -368,6 +375,8 @@ def grid_search_autoencoder(train_loader, val_loader, alpha_values=(20, 25, 30, 
     results, best = {}, {"loss": float("inf"), "info": None, "state": None, "train": None, "val": None}
     grid = [(alpha, lr) for alpha in alpha_values for lr in lr_values]
     fitted = None
+    # in_channels (image bands, 1..16) goes to the fit functions; a custom fit_fn / group_fit_fn sees it only when it is not 3
+    bands = {} if int(in_channels) == 3 else {"in_channels": int(in_channels)}
     if grouped and int(grouped) > 1:
         gfit = group_fit_fn or fit_autoencoder_group
         pairs = max(1, int(concurrent_groups or 1))
@@ -377,7 +386,7 @@ def grid_search_autoencoder(train_loader, val_loader, alpha_values=(20, 25, 30, 
             # parameter initialisation draws from torch's global generator: in grid order, on this thread (as for `concurrent`)
             prebuilt = []
             for cfgs in chunks:
-                ms = [SupervisedAutoencoder(latent_dim=latent_dim, num_classes=10).to(device) for _ in cfgs]
+                ms = [SupervisedAutoencoder(latent_dim=latent_dim, num_classes=10, in_channels=in_channels).to(device) for _ in cfgs]
                 for m in ms:
                     m._eae_side_streams = 1          # two groups x (caller's stream + one side stream) = the four hardware queues
                 prebuilt.append(ms)
@@ -388,7 +397,7 @@ def grid_search_autoencoder(train_loader, val_loader, alpha_values=(20, 25, 30, 
                 lines = [[] for _ in cfgs]
                 extra = {"models": prebuilt[gi]} if prebuilt is not None else {}
                 rs = gfit(train_loader, val_loader, cfgs, latent_dim=latent_dim, num_epochs=num_epochs, patience=patience, device=device,
-                          verbose=verbose, logs=lines, **extra)
+                          verbose=verbose, logs=lines, **bands, **extra)
                 out = []
                 for r, ln in zip(rs, lines):
                     r = dict(r)
@@ -406,7 +415,7 @@ def grid_search_autoencoder(train_loader, val_loader, alpha_values=(20, 25, 30, 
         prebuilt = {}
         if fit_fn is fit_autoencoder:
             for (alpha, lr) in grid:
-                m = SupervisedAutoencoder(latent_dim=latent_dim, num_classes=10).to(device)
+                m = SupervisedAutoencoder(latent_dim=latent_dim, num_classes=10, in_channels=in_channels).to(device)
                 if int(concurrent) >= 3:
                     m._eae_side_streams = -1
                 prebuilt[(alpha, lr)] = m
@@ -420,7 +429,7 @@ def grid_search_autoencoder(train_loader, val_loader, alpha_values=(20, 25, 30, 
                 # at K = 4.  hipGraph replay of each step is slower than eager (0.7-0.8x), more hardware queues or several processes far slower.
                 extra = {"model": prebuilt.pop((alpha, lr))} if fit_fn is fit_autoencoder else {}
                 r = fit_fn(train_loader, val_loader, alpha, lr, latent_dim=latent_dim, num_epochs=num_epochs, patience=patience,
-                           device=device, verbose=verbose, log=lines.append, **extra)
+                           device=device, verbose=verbose, log=lines.append, **bands, **extra)
                 r = dict(r)
                 # only the state_dict of a finished configuration is needed below: release its engine (workspace, streams) now
                 r["state"] = None if r.get("model") is None else {k: v.detach().cpu().clone() for k, v in r["model"].state_dict().items()}
@@ -440,7 +449,7 @@ def grid_search_autoencoder(train_loader, val_loader, alpha_values=(20, 25, 30, 
                         log(ln)
             else:
                 r = fit_fn(train_loader, val_loader, alpha, lr, latent_dim=latent_dim, num_epochs=num_epochs, patience=patience,
-                           device=device, verbose=verbose, log=log)
+                           device=device, verbose=verbose, log=log, **bands)
             results[(alpha, lr)] = r["best_val_loss"]
             if r["best_val_loss"] < best["loss"]:
                 state = r.get("state")

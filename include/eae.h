@@ -47,6 +47,9 @@ typedef struct eae_config {
                         A process reaches the GPU through 4 hardware queues: when SEVERAL contexts are stepped concurrently (a grid of
                         small configurations, train.run_concurrent) one stream per context lets four of them run side by side, three
                         streams per context share the four queues (measured at batch 64: 4 contexts 487 K vs 352 K images/s). */
+  int in_channels;   /* image bands C, 1..16 (Encoder(in_channels=C)); 0 means 3 (RGB).  Sizes conv1's weight [32,C,3,3], deconv4's
+                        weight [32,C,3,3] ([Cin,Cout,kh,kw]) and bias [C], and every image-shaped tensor [B,C,H,W] of eae_step_io and
+                        the calls below.  quant = 1 needs C = 3.  All members of an eae_group_* call must share it. */
 } eae_config;
 
 /* fp8 variant only.  eae_fp8_calibrate: `iters` (<= 0: 7) gradient steps WITHOUT optimizer on the given batch to settle the delayed
@@ -99,13 +102,13 @@ int eae_set_adam_step(eae_ctx* ctx, long long step);
 long long eae_get_adam_step(eae_ctx* ctx);
 
 typedef struct eae_step_io {
-  const float* x;            /* [B,3,H,W] fp32 NCHW, the loader contract (R.md:643) */
+  const float* x;            /* [B,C,H,W] fp32 NCHW (C = eae_config::in_channels), the loader contract (R.md:643) */
   const long long* labels;   /* [B] int64 (R.md:644) or NULL */
   int B;
   int train;                 /* 1: model.train() semantics (batch statistics, running-stat update); 0: model.eval() */
   int head;                  /* 1: classifier head + CrossEntropy; 0: encoder+decoder only (MSE) */
   float alpha;               /* loss = alpha * MSE(x_hat, x) + CE(logits, labels)   R.md:649-651 */
-  float* x_hat;              /* optional [B,3,H,W] fp32 NCHW */
+  float* x_hat;              /* optional [B,C,H,W] fp32 NCHW */
   float* logits;             /* optional [B,num_classes] fp32 */
   float* z;                  /* optional [B,latent_dim] fp32 */
   float* loss_accum;         /* optional float[8]: += loss*B, mse*B, ce*B, B, #correct  (R.md:656-657, 679-681) */
@@ -119,7 +122,7 @@ typedef struct eae_step_io {
 int eae_ae_forward(eae_ctx* ctx, void* stream, const eae_step_io* io);
 /* loss.backward() for a torch-side loss (R.md:649-653): backward of the most recent eae_ae_forward -- train mode, or eval mode
  * (io->train = 0: BatchNorm with the running statistics is differentiated as the per-channel affine map it then is; the biases in
- * front of the BatchNorms then get their gradient A[c] * sum g instead of zero) -- given the gradients of its outputs (fp32; dx_hat [B,3,H,W], dlogits [B,C] or NULL, dz [B,L] or NULL).  x = that forward's input batch
+ * front of the BatchNorms then get their gradient A[c] * sum g instead of zero) -- given the gradients of its outputs (fp32; dx_hat [B,in_channels,H,W], dlogits [B,C] or NULL, dz [B,L] or NULL).  x = that forward's input batch
  * (conv1's weight gradient reads it again: the engine keeps no pointer to caller memory across calls), x_hat = its output,
  * generation = eae_forward_generation() read right after that forward: EAE_ERR_STATE if any forward ran since.
  * Gradients of all 38 tensors land in the grad arena (train mode: biases in front of a BatchNorm are exact zeros). */
@@ -215,7 +218,7 @@ int eae_decoder_forward(eae_ctx* ctx, void* stream, const float* z, int B, int t
 /* loss.backward() through a stand-alone Encoder / Decoder (the notebook defines them as separate modules, R.md:287, 361; e.g.
  * x_hat = dec(enc(x)) with an MSE loss): backward of the most recent eae_encoder_forward / eae_decoder_forward (train or eval mode)
  * for an externally supplied gradient of its output.  generation = eae_forward_generation() right after that forward.
- * encoder: dz [B][L], x = the forward's input;  decoder: dx_hat [B,3,H,W], x_hat = the forward's output, dz_out [B][L] (may be NULL). */
+ * encoder: dz [B][L], x = the forward's input;  decoder: dx_hat [B,in_channels,H,W], x_hat = the forward's output, dz_out [B][L] (may be NULL). */
 int eae_encoder_backward(eae_ctx* ctx, void* stream, long long generation, const float* x, const float* dz);
 int eae_decoder_backward(eae_ctx* ctx, void* stream, long long generation, const float* x_hat, const float* dx_hat, float* dz_out);
 
@@ -278,6 +281,26 @@ int eae_op_edge_wgrad(void* stream, int src3_kind, const void* src3, int B, int 
                       long long scratch_floats, float* dw /*[32][3][3][3]*/);
 int eae_op_deconv4_loss(void* stream, eae_src a3, int B, int Hin, int Win, const void* wjoint, const float* bias,
                         const float* x, float gscale, float* x_hat, void* g4, float* loss_part /*[ntiles][4]*/);
+/* The same four edge ops for C image bands (1..16), padded to CP = 4 (C = 3), 8 (C <= 8) or 16 in the kernels:
+ *   eae_op_pack_edge      : the engine's packs of a [32][C][3][3] fp32 weight (conv1's, or deconv4's [Cin][Cout] one): wpack bf16
+ *                           [32][KP] with k = tap*CP + c, KP = 9*CP rounded up to 32 (64 / 96 / 160; the form eae_op_edge_conv_c takes,
+ *                           deconv4's for its backward-data) and, unless wjoint is NULL, the joint deconv4 pack bf16 [4*CP][128]
+ *                           (n = phase*C + co, k = nb*32 + ci; the form eae_op_deconv4_loss_c takes).  Synchronous: it allocates a
+ *                           small descriptor table per call and waits for the stream (a helper for tests and tools, not a hot loop).
+ *   eae_op_edge_conv_c    : src_kind 0 = fp32 NCHW [B,C,H,W], 1 = bf16 NHWC-CP [B,H,W,CP]; out [B,H/2,W/2,32]
+ *   eae_op_edge_wgrad_c   : dw [32][C][3][3]; scratch >= 288*C floats per workgroup (the launch uses fewer when it is short)
+ *   eae_op_deconv4_loss_c : x / x_hat fp32 NCHW [B,C,2Hin,2Win], g bf16 NHWC-CP [B,2Hin,2Win,CP] (bands >= C zero),
+ *                           loss_part [ntiles][4*ceil((C+1)/4)] = {sum diff^2, sum g(c) for c < C, zeros}
+ *   eae_op_sigmoid_bwd_c  : as eae_op_sigmoid_bwd, x_hat / dx_hat [B,C,H,W], g NHWC-CP, db[C]; scratch >= ceil(B*H*W/256)*4*ceil((C+1)/4) */
+int eae_op_pack_edge(void* stream, const float* w, int C, void* wpack, void* wjoint);
+int eae_op_edge_conv_c(void* stream, int src_kind, const void* src, int C, int B, int H, int W, const void* wpack,
+                       const float* bias, void* out, float* stat_part, int epilogue, const void* yprev, const float* prev_coef);
+int eae_op_edge_wgrad_c(void* stream, int src_kind, const void* src, int C, int B, int H, int W, eae_src side, float* scratch,
+                        long long scratch_floats, float* dw);
+int eae_op_deconv4_loss_c(void* stream, eae_src a3, int C, int B, int Hin, int Win, const void* wjoint, const float* bias,
+                          const float* x, float gscale, float* x_hat, void* g, float* loss_part);
+int eae_op_sigmoid_bwd_c(void* stream, const float* x_hat, const float* dx_hat, int C, int B, int H, int W, void* g, float* db,
+                         float* scratch);
 /* weight gradient of a 3x3 s2 layer: dw [cs][cb][3][3] fp32 (reference layout) */
 int eae_op_wgrad_s2(void* stream, eae_src small_src, eae_src big_src, int cs, int cb, int B, int Hs, int Ws, float* scratch,
                     long long scratch_floats, float* dw);
@@ -325,6 +348,16 @@ int eae_op_adam(void* stream, float* p, const float* g, float* m, float* v, long
  * (flip, top, left) with top,left in 0..8 and/or standard-normal noise [B,3,H,W] are supplied. */
 int eae_augment(void* stream, const void* in_u8, float* out, int B, int H, int W, int train, float noise_std,
                 unsigned long long seed, unsigned long long step, const int* params, const float* noise);
+
+/* Multispectral staging (in_channels 1..16): the same transform for a dataset kept in DEVICE memory, gathered by index.
+ * src: uint8 (elem_bytes 1) or uint16 (elem_bytes 2) planar [N,C,H,W]; index: int64 [B] of images in 0..N-1, or NULL for images
+ * 0..B-1 (an index outside 0..N-1 gives NaN for that image); divisor: fp32 [C] on the device; out: fp32 NCHW [B,C,H,W].
+ * Per image: flip -> pad-4 crop (padding reads 0) -> v / divisor[c] (a true division, as ToTensor's) -> + noise_std * N(0,1)
+ * (train = 0: the division only).  Randomness as eae_augment: Philox keyed by (seed, step), or explicit params int32 [B][3] /
+ * noise [B,C,H,W].  With C = 3, uint8 data, divisor 255 and the same explicit draws, out is eae_augment's (on CHW data). */
+int eae_stage_bands(void* stream, const void* src, int elem_bytes, long long N, int C, int H, int W, const long long* index, int B,
+                    const float* divisor, float* out, int train, float noise_std, unsigned long long seed, unsigned long long step,
+                    const int* params, const float* noise);
 
 /* ------------------------------------------------------------------ external MLP (R.md:2549-2566) ---------- */
 typedef struct eae_mlp eae_mlp;
