@@ -29,6 +29,11 @@ class EaeSrc(C.Structure):
     _fields_ = [("p0", vp), ("p1", vp), ("coef", vp), ("mode", C.c_int)]
 
 
+class EaeScene(C.Structure):
+    _fields_ = [("data", vp), ("divisor", vp), ("dtype", C.c_int), ("C", C.c_int), ("H", C.c_int), ("W", C.c_int),
+                ("patch", C.c_int), ("stride", C.c_int)]
+
+
 _PROTOS = {
     "eae_last_error": (C.c_char_p, []),
     "eae_version": (C.c_int, []),
@@ -117,6 +122,10 @@ _PROTOS = {
     "eae_mlp_backward": (C.c_int, [vp, vp, vp, C.c_int, C.c_ulonglong, vp, vp]),
     "eae_mlp_train_step": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_float, C.c_float, C.c_ulonglong, vp, vp, vp]),
     "eae_mlp_eval_step": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, vp]),
+    "eae_scene_windows": (C.c_int, [vp, C.POINTER(EaeScene), C.c_longlong, C.c_int, vp]),
+    "eae_scene_encode": (C.c_int, [vp, vp, C.POINTER(EaeScene), C.c_longlong, C.c_int, vp]),
+    "eae_scene_classify": (C.c_int, [vp, vp, vp, C.POINTER(EaeScene), C.c_longlong, C.c_longlong, vp, vp]),
+    "eae_scene_blend": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
 }
 
 EXPORTS = tuple(_PROTOS.keys())

@@ -983,7 +983,9 @@ const float* stage_latent_in(eae_ctx* c, hipStream_t st, const float* src, int B
 }
 
 // ---- encoder: x -> y[0..3] (raw, bf16) + BN coefficients -> z (fp32)
-int run_encoder(eae_ctx* c, hipStream_t st, const float* x, int B, bool train) {
+// scene (eval mode only): conv1 reads windows of a device-resident scene instead of the fp32 batch x; every later layer is unchanged
+int run_encoder(eae_ctx* c, hipStream_t st, const float* x, int B, bool train, const eae_scene* scene = nullptr,
+                const SceneSrc* ssrc = nullptr) {
   const int H = c->H, W = c->W;
   {
     EdgeArgs a;
@@ -994,7 +996,8 @@ int run_encoder(eae_ctx* c, hipStream_t st, const float* x, int B, bool train) {
     fold_producer(c, a.c, 0, train);
     {
       ProfBracket pb(c, EAE_PROF_SITE(0, 0), st);
-      RC(eae_launch_edge_conv(st, SRC3_NCHW_F32, EPI_FWD, a));
+      if (scene) RC(eae_launch_edge_conv_scene(st, eae_scene_src3_kind(scene), a, *ssrc));
+      else RC(eae_launch_edge_conv(st, SRC3_NCHW_F32, EPI_FWD, a));
     }
     RC(sync_fwd(c, st, 0, train));
     RC(bn_fwd_finalize(c, st, 0, eae_edge_tiles(B, H, W), (long long)B * (H / 2) * (W / 2), train));
@@ -1804,6 +1807,63 @@ extern "C" int eae_encoder_forward(eae_ctx* c, void* stream, const float* x, int
   RC(run_encoder(c, st, x, B, train != 0));
   c->enc_ready = train ? 1 : 2; c->fwd_B = B; c->fwd_gen += 1;
   return copy_latent_out(c, st, z, c->z, B);
+}
+
+namespace {
+int scene_ctx_checks(eae_ctx* c, const eae_scene* s, long long first, long long count, long long* nH, long long* nW) {
+  if (!c) return eae_set_error(EAE_ERR_ARG, "scene: NULL context");
+  if (!c->P || !c->bnrun) return eae_set_error(EAE_ERR_STATE, "eae_bind has not been called");
+  if (c->fp8) return eae_set_error(EAE_ERR_ARG, "scene: quant=1 (fp8) contexts are not supported");
+  RC(eae_scene_check(s, nH, nW));
+  if (s->C != c->Cin) return eae_set_error(EAE_ERR_ARG, "scene: band count does not match the encoder's in_channels");
+  if (c->H != c->W || s->patch != c->H) return eae_set_error(EAE_ERR_ARG, "scene: the patch must be the (square) image size of the model");
+  if (count <= 0 || first < 0 || first + count > *nH * *nW) return eae_set_error(EAE_ERR_ARG, "scene: windows outside the grid");
+  return 0;
+}
+// one encoder batch of windows first .. first + B - 1 (B <= max_batch) into c->z (rows of Lp floats)
+int scene_encode_batch(eae_ctx* c, hipStream_t st, const eae_scene* s, long long nW, long long first, int B) {
+  SceneSrc src;
+  eae_scene_fill_src(s, nW, first, &src);
+  return run_encoder(c, st, nullptr, B, false, s, &src);
+}
+int scene_begin(eae_ctx* c, hipStream_t st) {
+  c->fwd_ready = false; c->fwd_eval_ready = false; c->enc_ready = 0; c->dec_ready = 0;
+  c->fwd_gen += 1;          // scene activations are never differentiated: a backward of an earlier forward is refused
+  RC(ensure_packed(c, st));
+  return prep_accumulators(c, st, false);
+}
+}  // namespace
+
+extern "C" int eae_scene_encode(eae_ctx* c, void* stream, const eae_scene* s, long long first, int B, float* z) {
+  long long nH = 0, nW = 0;
+  RC(scene_ctx_checks(c, s, first, B, &nH, &nW));
+  if (!z) return eae_set_error(EAE_ERR_ARG, "scene_encode: NULL z");
+  hipStream_t st = (hipStream_t)stream;
+  RC(scene_begin(c, st));
+  for (int b0 = 0; b0 < B; b0 += c->Bm) {
+    const int nb = B - b0 < c->Bm ? B - b0 : c->Bm;
+    RC(scene_encode_batch(c, st, s, nW, first + b0, nb));
+    RC(copy_latent_out(c, st, z + (size_t)b0 * c->L, c->z, nb));
+  }
+  return 0;
+}
+
+extern "C" int eae_scene_classify(eae_ctx* c, eae_mlp* m, void* stream, const eae_scene* s, long long first, long long count, float* probs,
+                                  long long* labels) {
+  long long nH = 0, nW = 0;
+  RC(scene_ctx_checks(c, s, first, count, &nH, &nW));
+  if (!m || !probs || !labels) return eae_set_error(EAE_ERR_ARG, "scene_classify: NULL mlp, probs or labels");
+  int in_dim = 0, classes = 0, mb = 0;
+  RC(eae_mlp_dims(m, &in_dim, &classes, &mb));
+  if (in_dim != c->L) return eae_set_error(EAE_ERR_ARG, "scene_classify: the MLP's input_dim is not the encoder's latent_dim");
+  hipStream_t st = (hipStream_t)stream;
+  RC(scene_begin(c, st));
+  for (long long b0 = 0; b0 < count; b0 += c->Bm) {
+    const int nb = (int)(count - b0 < c->Bm ? count - b0 : c->Bm);
+    RC(scene_encode_batch(c, st, s, nW, first + b0, nb));
+    RC(eae_mlp_predict(m, st, c->z, c->Lp, nb, first + b0, nH * nW, probs, labels));
+  }
+  return 0;
 }
 
 namespace {

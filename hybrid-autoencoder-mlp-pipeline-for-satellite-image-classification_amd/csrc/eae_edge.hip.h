@@ -19,7 +19,38 @@ __device__ int g_edge_dbg_block = 0;
 #endif
 
 enum { SRC3_NCHW_F32 = 0,     // fp32 planar image (the loader contract)
-       SRC3_NHWCP_BF16 = 1 }; // bf16 pixels padded to CP channels (gradient of the pre-sigmoid output)
+       SRC3_NHWCP_BF16 = 1,   // bf16 pixels padded to CP channels (gradient of the pre-sigmoid output)
+       SRC3_SCENE_U8 = 2,     // P x P windows of a planar uint8 / uint16 / fp32 scene [C][Hs][Ws], value / divisor[c] (eae_scene)
+       SRC3_SCENE_U16 = 3,
+       SRC3_SCENE_F32 = 4 };
+template <int SRC3> constexpr bool src3_planar() { return SRC3 != SRC3_NHWCP_BF16; }
+
+// Scene source of conv1 (eval-mode forward only): image n of the launch is window w = first + n of the grid of P x P windows at
+// stride S (nW per row), whose origin is scene pixel (w / nW * S, w % nW * S).  Offsets are 64-bit: scenes exceed 2^31 elements.
+struct SceneSrc {
+  const void* data = nullptr;        // [C][Hs][Ws]
+  const float* div = nullptr;        // [C]
+  long long first = 0, plane = 0;    // first window of the launch; Hs * Ws
+  int Ws = 0, S = 0, nW = 0;
+};
+template <typename T> __device__ __forceinline__ float scene_val(T v, float d) { return (float)v / d; }
+// 4 consecutive scene pixels of one band: one vector load where the address allows it (window origins x are not aligned for most
+// strides and scene widths), else 4 element loads
+template <typename T> __device__ __forceinline__ float4 scene_load4(const T* p, float d) {
+  T e[4];
+  if ((reinterpret_cast<uintptr_t>(p) & (4 * sizeof(T) - 1)) == 0) {
+    if constexpr (sizeof(T) == 1) { const uchar4 v = *reinterpret_cast<const uchar4*>(p); e[0] = v.x; e[1] = v.y; e[2] = v.z; e[3] = v.w; }
+    else if constexpr (sizeof(T) == 2) { const ushort4 v = *reinterpret_cast<const ushort4*>(p); e[0] = v.x; e[1] = v.y; e[2] = v.z; e[3] = v.w; }
+    else { const float4 v = *reinterpret_cast<const float4*>(p); e[0] = v.x; e[1] = v.y; e[2] = v.z; e[3] = v.w; }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) e[i] = p[i];
+  }
+  return make_float4(scene_val(e[0], d), scene_val(e[1], d), scene_val(e[2], d), scene_val(e[3], d));
+}
+template <int SRC3> struct SceneElem { using T = float; };
+template <> struct SceneElem<SRC3_SCENE_U8> { using T = uint8_t; };
+template <> struct SceneElem<SRC3_SCENE_U16> { using T = uint16_t; };
 
 // Band counts: C (1..16, a run-time argument) image bands are staged as CP = 4, 8 or 16 (the trailing template argument of every
 // edge kernel).  CP = 4 is the RGB form: C = 3 is a compile-time constant there (edge_bands), so it compiles to the registers,
@@ -54,9 +85,37 @@ template <int CP> constexpr int e_nld() { return (E_PH * (e_pieces_row<CP>() + e
 template <int SRC3, int CP> struct Patch3Regs { float4 v[EdgeK<CP>::CMAX]; };     // planar fp32: one float4 per band (halo threads: .x only)
 template <int CP> struct Patch3Regs<SRC3_NHWCP_BF16, CP> { uint4 v[e_nld<CP>()]; };   // bf16 NHWC-CP: 16-byte pieces
 template <int SRC3, int CP>
-__device__ __forceinline__ void patch3_load(const void* src, int C, int n, int H, int W, int iy0, int ix0, Patch3Regs<SRC3, CP>& r) {
+__device__ __forceinline__ void patch3_load(const void* src, int C, int n, int H, int W, int iy0, int ix0, Patch3Regs<SRC3, CP>& r,
+                                            const SceneSrc* sc = nullptr) {
   const int tid = threadIdx.x;
-  if constexpr (SRC3 == SRC3_NCHW_F32) {
+  if constexpr (SRC3 >= SRC3_SCENE_U8) {
+    // window-local coordinates: the conv padding outside the window stays zero, even where the scene has pixels there
+    using T = typename SceneElem<SRC3>::T;
+    const T* x = static_cast<const T*>(sc->data);
+    constexpr int CMAX = EdgeK<CP>::CMAX;
+    const long long w = sc->first + n, wi = w / sc->nW, wj = w - wi * sc->nW;
+    const long long org = wi * sc->S * (long long)sc->Ws + wj * sc->S;
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c) r.v[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (tid < E_PH * 16) {
+      const int c4 = tid & 15, rr = tid >> 4;
+      const int iy = iy0 + rr, ix = ix0 + 1 + c4 * 4;
+      if (iy >= 0 && iy < H) {
+        const T* p = x + org + (long long)iy * sc->Ws + ix;
+#pragma unroll
+        for (int c = 0; c < CMAX; ++c)
+          if (c < C) r.v[c] = scene_load4<T>(p + c * sc->plane, sc->div[c]);
+      }
+    } else if (tid < E_PH * 16 + E_PH) {
+      const int iy = iy0 + tid - E_PH * 16;
+      if (ix0 >= 0 && iy >= 0 && iy < H) {
+        const T* p = x + org + (long long)iy * sc->Ws + ix0;
+#pragma unroll
+        for (int c = 0; c < CMAX; ++c)
+          if (c < C) r.v[c].x = scene_val(p[c * sc->plane], sc->div[c]);
+      }
+    }
+  } else if constexpr (SRC3 == SRC3_NCHW_F32) {
     const float* x = static_cast<const float*>(src);
     constexpr int CMAX = EdgeK<CP>::CMAX;
 #pragma unroll
@@ -107,7 +166,7 @@ __device__ __forceinline__ void patch3_load(const void* src, int C, int n, int H
 template <int SRC3, int CP>
 __device__ __forceinline__ void patch3_write(bf16_t* p3, const Patch3Regs<SRC3, CP>& r) {
   const int tid = threadIdx.x;
-  if constexpr (SRC3 == SRC3_NCHW_F32) {
+  if constexpr (src3_planar<SRC3>()) {
     constexpr int CMAX = EdgeK<CP>::CMAX;
     auto put = [&](bf16_t* d, int e) __attribute__((always_inline)) {
       uint32_t w[CP / 2];
@@ -154,9 +213,10 @@ __device__ __forceinline__ void patch3_write(bf16_t* p3, const Patch3Regs<SRC3, 
   }
 }
 template <int SRC3, int CP>
-__device__ __forceinline__ void stage_patch3(const void* src, int C, bf16_t* p3, int n, int H, int W, int iy0, int ix0) {
+__device__ __forceinline__ void stage_patch3(const void* src, int C, bf16_t* p3, int n, int H, int W, int iy0, int ix0,
+                                             const SceneSrc* sc = nullptr) {
   Patch3Regs<SRC3, CP> r;
-  patch3_load<SRC3, CP>(src, C, n, H, W, iy0, ix0, r);
+  patch3_load<SRC3, CP>(src, C, n, H, W, iy0, ix0, r, sc);
   patch3_write<SRC3, CP>(p3, r);
   __syncthreads();
 }
@@ -233,7 +293,7 @@ struct EdgeArgs {
 // the pixel operand is read straight from the patch.  The weights are the MFMA A operand: an accumulator lane holds 4 consecutive
 // output channels of one pixel (8-byte tile writes instead of 16 two-byte ones).
 template <int SRC3, int EPI, int CP>
-__device__ __forceinline__ void edge_conv_body(const EdgeArgs& a) {
+__device__ __forceinline__ void edge_conv_body(const EdgeArgs& a, const SceneSrc* sc = nullptr) {
   constexpr int KP = EdgeK<CP>::KP, KS = EdgeK<CP>::KS;
   __shared__ __attribute__((aligned(16))) bf16_t p3[e_patch<CP>()];
   // output tile [128][40] (10 KB); the statistics reduction scratch [2][64][32] floats (16 KB) reuses the same memory: TileEpilogue::end()
@@ -258,7 +318,7 @@ __device__ __forceinline__ void edge_conv_body(const EdgeArgs& a) {
     for (int ks = 0; ks < KS; ++ks)
       wf[mt][ks] = *reinterpret_cast<const bf16x8*>(a.c.wpack + (mt * 16 + (lane & 15)) * KP + ks * 32 + kgl * 8);
   EDGE_STAMP(16);
-  stage_patch3<SRC3, CP>(a.src3, edge_bands<CP>(a.C), p3, n, a.H, a.W, 2 * tyb * E_TH - 1, 2 * txb * E_TW - 1);      // ends with a barrier
+  stage_patch3<SRC3, CP>(a.src3, edge_bands<CP>(a.C), p3, n, a.H, a.W, 2 * tyb * E_TH - 1, 2 * txb * E_TW - 1, sc);  // ends with a barrier
   EDGE_STAMP(17);
   f32x4 acc[2][2];
 #pragma unroll
@@ -321,6 +381,9 @@ template <int SRC3, int EPI, int CP>
 __global__ __launch_bounds__(256) void edge_conv_kernel(EdgeArgs a) { edge_conv_body<SRC3, EPI, CP>(a); }
 template <int SRC3, int EPI, int CP>
 __global__ __launch_bounds__(256) void edge_conv_kernel_g(GroupPack<EdgeArgs> p, int gz) { edge_conv_body<SRC3, EPI, CP>(group_args<EdgeArgs>(gz)); }
+// conv1 reading P x P windows of a device-resident scene (eae_scene_encode / eae_scene_classify; eval-mode forward)
+template <int SRC3, int CP>
+__global__ __launch_bounds__(256) void edge_conv_scene_kernel(EdgeArgs a, SceneSrc s) { edge_conv_body<SRC3, EPI_FWD, CP>(a, &s); }
 
 // ---------------------------------------------------------------------------------------------------------------
 // R[k][c] = sum_m im2col(src)[m][k] * T(side)[m][c]     (weight gradient of conv1 and of deconv4)

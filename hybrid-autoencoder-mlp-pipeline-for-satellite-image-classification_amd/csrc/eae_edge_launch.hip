@@ -32,6 +32,25 @@ int eae_launch_edge_conv(hipStream_t st, int src3_kind, int epi, const EdgeArgs&
   return eae_set_error(-2, "edge_conv: combination not instantiated");
 }
 
+// conv1 over windows of a scene (eval-mode forward): the window gather is the kernel's patch load, no staged [B,C,P,P] batch
+int eae_launch_edge_conv_scene(hipStream_t st, int src3_kind, const EdgeArgs& a0, const SceneSrc& s) {
+  if (int rc = check_edge_shape(a0.B, a0.H, a0.W)) return rc;
+  if (int rc = check_bands(a0.C)) return rc;
+  EdgeArgs a = a0;
+  const int cp = edge_cp(a.C);
+  dim3 grid(a.B * (a.H / 2 / E_TH) * (a.W / 2 / E_TW));
+  a.c.ntiles = (int)grid.x;
+  EAE_NO_GROUP("edge_conv_scene_kernel");
+#define CASE1(S, P) if (src3_kind == S && cp == P) { hipLaunchKernelGGL((edge_conv_scene_kernel<S, P>), grid, dim3(256), 0, st, a, s); EAE_LAUNCH_CHECK(); return 0; }
+#define CASE(S) CASE1(S, 4) CASE1(S, 8) CASE1(S, 16)
+  CASE(SRC3_SCENE_U8)
+  CASE(SRC3_SCENE_U16)
+  CASE(SRC3_SCENE_F32)
+#undef CASE
+#undef CASE1
+  return eae_set_error(-2, "edge_conv_scene: source kind not instantiated");
+}
+
 int eae_edge_tiles(int B, int H, int W) { return B * (H / 2 / E_TH) * (W / 2 / E_TW); }
 
 // dw [32][C][3][3] = reduce over blocks of the per-block partials. scratch must hold nblocks*288*C floats.

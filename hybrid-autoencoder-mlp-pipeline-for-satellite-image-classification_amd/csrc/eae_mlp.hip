@@ -29,6 +29,10 @@ struct MlpArgs {
   int update_running;      // 0: do not touch running statistics / num_batches_tracked (recompute pass of the autograd path)
   float p_drop;
   float* logits; float* stats;    // stats: += loss*B, += B, += correct
+  int ldx;                 // row stride of x (IN, or the AE engine's padded latent width)
+  float* probs;            // eval-mode predict epilogue (scene classification): softmax -> probs[c * plane + win0 + row], or nullptr
+  long long* plabels;      // argmax (first maximum) -> plabels[win0 + row]
+  long long win0, plane;
 };
 
 // Philox4x32-10 (counter-based): keep-mask of nn.Dropout, keyed by (seed, optimisation step), counter = element index
@@ -93,7 +97,8 @@ __global__ EAE_NO_PK __launch_bounds__(T) void mlp_kernel(MlpArgs a) {
   // rows handled by this block (training: the whole batch in block 0; eval: 64 rows per block)
   const int r0 = a.train ? 0 : blockIdx.x * 64;
   const int nb = a.train ? a.B : min(64, a.B - r0);
-  const float* x = a.x + (size_t)r0 * IN;
+  const int ldx = a.ldx;
+  const float* x = a.x + (size_t)r0 * ldx;
   const float *W1 = a.P + a.off[0], *b1 = a.P + a.off[1], *g1w = a.P + a.off[2], *be1 = a.P + a.off[3];
   const float *W2 = a.P + a.off[4], *b2 = a.P + a.off[5], *g2w = a.P + a.off[6], *be2 = a.P + a.off[7];
   const float *W3 = a.P + a.off[8], *b3 = a.P + a.off[9];
@@ -103,7 +108,7 @@ __global__ EAE_NO_PK __launch_bounds__(T) void mlp_kernel(MlpArgs a) {
   for (int i = tid; i < nb * H1; i += T) {
     int b = i / H1, j = i % H1;
     float s = b1[j];
-    for (int k = 0; k < IN; ++k) s = fmaf(x[b * IN + k], W1[j * IN + k], s);
+    for (int k = 0; k < IN; ++k) s = fmaf(x[(size_t)b * ldx + k], W1[j * IN + k], s);
     h1[i] = s;
   }
   __syncthreads();
@@ -177,6 +182,18 @@ __global__ EAE_NO_PK __launch_bounds__(T) void mlp_kernel(MlpArgs a) {
   if (a.dlog_in) {
     for (int i = tid; i < nb * C; i += T) dlog[(i / C) * 16 + (i % C)] = a.dlog_in[(size_t)r0 * C + i];
     __syncthreads();
+  }
+  if (a.probs) {             // predict epilogue (eval mode): class probabilities and label of each row at its window's grid position
+    for (int b = tid; b < nb; b += T) {
+      const float* l = dlog + b * 16;
+      float mx = l[0]; int am = 0;
+      for (int c = 1; c < C; ++c) if (l[c] > mx) { mx = l[c]; am = c; }
+      float se = 0.f;
+      for (int c = 0; c < C; ++c) se += expf(l[c] - mx);
+      const long long w = a.win0 + r0 + b;
+      for (int c = 0; c < C; ++c) a.probs[c * a.plane + w] = expf(l[c] - mx) / se;
+      a.plabels[w] = am;
+    }
   }
   if (!a.labels && !a.dlog_in) return;
   float loss = 0.f, corr = 0.f;
@@ -258,7 +275,7 @@ __global__ EAE_NO_PK __launch_bounds__(T) void mlp_kernel(MlpArgs a) {
   for (int i = tid; i < H1 * IN; i += T) {
     int j = i / IN, k = i % IN;
     float s = 0.f;
-    for (int b = 0; b < nb; ++b) s = fmaf(g1[b * H1 + j], x[b * IN + k], s);
+    for (int b = 0; b < nb; ++b) s = fmaf(g1[b * H1 + j], x[(size_t)b * ldx + k], s);
     G[a.off[0] + i] = s;
   }
   if (tid < H1) { float s = 0.f; for (int b = 0; b < nb; ++b) s += g1[b * H1 + tid]; G[a.off[1] + tid] = s; }
@@ -352,6 +369,7 @@ static int mlp_launch(eae_mlp* m, hipStream_t st, const float* x, const long lon
   }
   a.seed = seed; a.step = (unsigned long long)m->adam_step; a.drop_mask = drop_mask; a.p_drop = 0.3f;
   a.logits = logits; a.stats = stats; a.dlog_in = dlog_in; a.update_running = dlog_in ? 0 : 1;
+  a.ldx = m->IN; a.probs = nullptr; a.plabels = nullptr; a.win0 = 0; a.plane = 0;
   const int grid = train ? 1 : (B + 63) / 64;
   hipLaunchKernelGGL(mlp_kernel, dim3(grid), dim3(T), 0, st, a);
   EAE_LAUNCH_CHECK();
@@ -377,4 +395,36 @@ extern "C" int eae_mlp_backward(eae_mlp* m, void* stream, const float* x, int B,
                                 const float* dlogits) {
   if (!dlogits) return eae_set_error(EAE_ERR_ARG, "mlp_backward: dlogits is NULL");
   return mlp_launch(m, (hipStream_t)stream, x, nullptr, B, 1, 1, 0, 0.f, 0.f, seed, drop_mask, nullptr, nullptr, dlogits);
+}
+
+int eae_mlp_dims(const eae_mlp* m, int* input_dim, int* classes, int* max_batch) {
+  if (!m) return eae_set_error(EAE_ERR_ARG, "mlp is NULL");
+  *input_dim = m->IN; *classes = m->C; *max_batch = m->Bm;
+  return 0;
+}
+
+// Eval-mode pass over B rows of a strided latent (the AE engine's workspace rows, stride Lp): the logits are those of
+// eae_mlp_eval_step; the epilogue writes softmax and argmax at windows win0.. of the scene grid.  B is split at max_batch.
+int eae_mlp_predict(eae_mlp* m, hipStream_t st, const float* x, int ldx, int B, long long win0, long long plane, float* probs,
+                    long long* labels) {
+  if (!m || !x || !probs || !labels) return eae_set_error(EAE_ERR_ARG, "mlp_predict: NULL argument");
+  if (!m->P) return eae_set_error(EAE_ERR_STATE, "eae_mlp_bind has not been called");
+  if (ldx < m->IN || B <= 0 || win0 < 0 || win0 + B > plane) return eae_set_error(EAE_ERR_ARG, "mlp_predict: bad shape");
+  for (int b0 = 0; b0 < B; b0 += m->Bm) {
+    const int nb = B - b0 < m->Bm ? B - b0 : m->Bm;
+    MlpArgs a;
+    a.x = x + (size_t)b0 * ldx; a.labels = nullptr; a.B = nb; a.IN = m->IN; a.C = m->C;
+    a.P = m->P; a.G = nullptr; a.M = nullptr; a.V = nullptr;
+    for (int i = 0; i < 11; ++i) a.off[i] = m->off[i];
+    a.bnrun = m->bnrun; a.nbt = nullptr;
+    a.h1 = m->h1; a.a1 = m->a1; a.h2 = m->h2; a.a2 = m->a2; a.dlog = m->dlog; a.g2 = m->g2; a.g1 = m->g1;
+    a.train = 0; a.backward = 0; a.adam = 0;
+    a.b1 = 0.9f; a.b2 = 0.999f; a.eps = 1e-8f; a.wd = 0.f; a.step_size = 0.f; a.bc2_sqrt = 1.f;
+    a.seed = 0; a.step = 0; a.drop_mask = nullptr; a.p_drop = 0.3f;
+    a.logits = nullptr; a.stats = nullptr; a.dlog_in = nullptr; a.update_running = 0;
+    a.ldx = ldx; a.probs = probs; a.plabels = labels; a.win0 = win0 + b0; a.plane = plane;
+    hipLaunchKernelGGL(mlp_kernel, dim3((nb + 63) / 64), dim3(T), 0, st, a);
+    EAE_LAUNCH_CHECK();
+  }
+  return 0;
 }

@@ -384,6 +384,36 @@ int eae_mlp_train_step(eae_mlp* m, void* stream, const float* x, const long long
 int eae_mlp_eval_step(eae_mlp* m, void* stream, const float* x, const long long* labels, int B, float* logits,
                       float* stats);
 
+/* ------------------------------------------------------------------ scene classification ---------- */
+/* These entry points extend beyond the reference, which has no notebook lines for applying the pipeline to a whole scene.
+ * A model of size P x P (image_h == image_w == patch) runs over windows of a planar scene [C][H][W] held on the device.  Windows
+ * are placed at stride S (1 <= S <= P) on both axes; only whole windows are used: nH = (H - P) / S + 1, nW = (W - P) / S + 1.
+ * Window n = i * nW + j starts at pixel (i * S, j * S).  The input value is (float)v / divisor[c], the eval-mode expression of
+ * eae_stage_bands.  Offsets are 64-bit: scenes may exceed 2^31 elements. */
+#define EAE_SCENE_U8 0
+#define EAE_SCENE_U16 1
+#define EAE_SCENE_F32 2
+typedef struct eae_scene {
+  const void* data;        /* [C][H][W] on the device, dtype EAE_SCENE_* */
+  const float* divisor;    /* [C] on the device */
+  int dtype, C, H, W;
+  int patch, stride;       /* P, S */
+} eae_scene;
+/* fp32 NCHW [B,C,P,P] of windows first_window .. first_window + B - 1: bitwise eae_stage_bands(train = 0) on the same windows. */
+int eae_scene_windows(void* stream, const eae_scene* scene, long long first_window, int B, float* out);
+/* Eval-mode encoder over windows first_window .. + B - 1 (any B: split at max_batch inside), conv1 reading the scene directly
+ * (zero conv padding at every window border): z [B][L].  Invalidates the resident forward (a later backward is refused). */
+int eae_scene_encode(eae_ctx* ctx, void* stream, const eae_scene* scene, long long first_window, int B, float* z);
+/* Encoder -> MLP (eval mode) over windows first_window .. + count - 1, in batches of at most max_batch, no host synchronisation.
+ * probs [K][nH * nW] (softmax) and labels [nH * nW] (int64 argmax, first maximum) receive the windows' columns; the MLP's logits
+ * are those of eae_mlp_eval_step.  Rejects quant = 1 contexts, C != in_channels, patch != image size, a scene smaller than P, S
+ * outside 1..P and a NULL divisor.  Invalidates the resident forward like eae_encoder_forward. */
+int eae_scene_classify(eae_ctx* ctx, eae_mlp* mlp, void* stream, const eae_scene* scene, long long first_window, long long count,
+                       float* probs, long long* labels);
+/* Blending (S divides P, k = P / S): cell map [K][nH + k - 1][nW + k - 1] of S x S cells, each the mean of probs [K][nH][nW] over
+ * the windows that cover it; cell_labels [nH + k - 1][nW + k - 1] = argmax of the blended map (int64). */
+int eae_scene_blend(void* stream, const float* probs, int K, int nH, int nW, int k, float* cell_probs, long long* cell_labels);
+
 #ifdef __cplusplus
 }
 #endif

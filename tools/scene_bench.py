@@ -1,0 +1,91 @@
+#!/usr/bin/env python3
+"""Scene classification throughput (windows/s): classify_scene (conv1 reads the scene, one C call) against the staged composition
+(scene_windows -> eval Encoder -> MLP eval, batch by batch), on two workloads with B = 512 windows per encoder pass:
+  rgb8   RGB uint8 scene at S = 64 (non-overlapping windows)
+  ms16   13-band uint16 scene at S = 32 (Sentinel-2-like, divisor 10000)
+Timed with device events after a warm-up; the staged path also reports its fp32 staging bytes.  Per-kernel times of the fused conv1
+come from a separate `rocprofv3 --kernel-trace --stats -- python tools/scene_bench.py` run (edge_conv_scene_kernel).
+
+    python tools/scene_bench.py [--reps 5] [--warmup 2] [--size 2112]   ->  JSON lines
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import eae_amd  # noqa: E402
+from eae_amd.mlp_engine import mlp_engine_for  # noqa: E402
+
+B, P = 512, 64
+
+
+def _time(fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b) / 1e3)
+    ts.sort()
+    return ts[len(ts) // 2], ts[0], ts[-1]
+
+
+def run(name, c, dtype, stride, divisor, size, reps, warmup):
+    torch.manual_seed(0)
+    model = eae_amd.SupervisedAutoencoder(64, 10, in_channels=c)
+    model._eae_max_batch = B
+    model = model.cuda().eval()
+    mlp = eae_amd.MLP(64, 10).cuda().eval()
+    hi = 256 if dtype == torch.uint8 else 10000
+    scene = torch.randint(0, hi, (c, size, size), dtype=torch.int32, device="cuda").to(dtype)
+    n_h, n_w = eae_amd.window_grid(size, size, P, stride)
+    n = n_h * n_w
+    meng = mlp_engine_for(mlp, max_batch=B)
+
+    def fused():
+        eae_amd.classify_scene(scene, model, mlp, divisor=divisor, stride=stride, batch=B)
+
+    def staged():
+        outs = []
+        with torch.no_grad():
+            for b0 in range(0, n, B):
+                nb = min(B, n - b0)
+                z = model.enc(eae_amd.scene_windows(scene, divisor, P, stride, first=b0, count=nb))
+                outs.append(meng.forward(z))
+        logits = torch.cat(outs)
+        return torch.softmax(logits, 1), logits.argmax(1)
+
+    res = {"workload": name, "C": c, "dtype": str(dtype).replace("torch.", ""), "stride": stride, "scene": [c, size, size],
+           "windows": n, "batch": B, "staging_bytes": n * c * P * P * 4}
+    for tag, fn in (("fused", fused), ("staged", staged)):
+        med, lo, hi_ = _time(fn, reps, warmup)
+        res[tag] = {"s": round(med, 5), "min_s": round(lo, 5), "max_s": round(hi_, 5), "windows_per_s": round(n / med, 1)}
+    res["speedup"] = round(res["staged"]["s"] / res["fused"]["s"], 3)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--size", type=int, default=2112, help="scene height = width in pixels")
+    ap.add_argument("--only", choices=["rgb8", "ms16"], default=None)
+    a = ap.parse_args()
+    work = [("rgb8", 3, torch.uint8, 64, 255.0), ("ms16", 13, torch.uint16, 32, 10000.0)]
+    for name, c, dtype, stride, div in work:
+        if a.only and a.only != name:
+            continue
+        print(json.dumps(run(name, c, dtype, stride, div, a.size, a.reps, a.warmup)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
