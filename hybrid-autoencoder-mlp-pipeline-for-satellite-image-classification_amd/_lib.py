@@ -126,6 +126,11 @@ _PROTOS = {
     "eae_scene_encode": (C.c_int, [vp, vp, C.POINTER(EaeScene), C.c_longlong, C.c_int, vp]),
     "eae_scene_classify": (C.c_int, [vp, vp, vp, C.POINTER(EaeScene), C.c_longlong, C.c_longlong, vp, vp]),
     "eae_scene_blend": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "eae_scene_invalid_counts": (C.c_int, [vp, C.POINTER(EaeScene), C.c_int, C.c_float, C.c_int, vp, vp, vp]),
+    "eae_scene_select": (C.c_int, [vp, vp, C.c_longlong, C.c_int, vp, vp]),
+    "eae_scene_encode_windows": (C.c_int, [vp, vp, C.POINTER(EaeScene), vp, C.c_longlong, vp]),
+    "eae_scene_classify_windows": (C.c_int, [vp, vp, vp, C.POINTER(EaeScene), vp, C.c_longlong, vp, vp]),
+    "eae_scene_blend_valid": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
 }
 
 EXPORTS = tuple(_PROTOS.keys())

@@ -1820,11 +1820,21 @@ int scene_ctx_checks(eae_ctx* c, const eae_scene* s, long long first, long long 
   if (count <= 0 || first < 0 || first + count > *nH * *nW) return eae_set_error(EAE_ERR_ARG, "scene: windows outside the grid");
   return 0;
 }
-// one encoder batch of windows first .. first + B - 1 (B <= max_batch) into c->z (rows of Lp floats)
-int scene_encode_batch(eae_ctx* c, hipStream_t st, const eae_scene* s, long long nW, long long first, int B) {
+// one encoder batch of windows first .. first + B - 1 (B <= max_batch), or of windows index[first ..], into c->z (rows of Lp floats)
+int scene_encode_batch(eae_ctx* c, hipStream_t st, const eae_scene* s, long long nW, long long first, int B,
+                       const long long* index = nullptr, long long nwin = 0) {
   SceneSrc src;
   eae_scene_fill_src(s, nW, first, &src);
+  src.index = index; src.nwin = nwin;
   return run_encoder(c, st, nullptr, B, false, s, &src);
+}
+// checks of the index-driven entry points: the ids themselves stay on the device (no host synchronisation); the kernels read an id
+// outside the grid as an all-zero window and the predict epilogue writes nothing for it
+int scene_index_checks(eae_ctx* c, const eae_scene* s, const long long* windows, long long count, long long* nH, long long* nW) {
+  if (!windows) return eae_set_error(EAE_ERR_ARG, "scene: NULL window list");
+  if (count <= 0) return eae_set_error(EAE_ERR_ARG, "scene: the window list is empty");
+  RC(scene_ctx_checks(c, s, 0, 1, nH, nW));
+  return 0;
 }
 int scene_begin(eae_ctx* c, hipStream_t st) {
   c->fwd_ready = false; c->fwd_eval_ready = false; c->enc_ready = 0; c->dec_ready = 0;
@@ -1862,6 +1872,39 @@ extern "C" int eae_scene_classify(eae_ctx* c, eae_mlp* m, void* stream, const ea
     const int nb = (int)(count - b0 < c->Bm ? count - b0 : c->Bm);
     RC(scene_encode_batch(c, st, s, nW, first + b0, nb));
     RC(eae_mlp_predict(m, st, c->z, c->Lp, nb, first + b0, nH * nW, probs, labels));
+  }
+  return 0;
+}
+
+extern "C" int eae_scene_encode_windows(eae_ctx* c, void* stream, const eae_scene* s, const long long* windows, long long count,
+                                        float* z) {
+  long long nH = 0, nW = 0;
+  RC(scene_index_checks(c, s, windows, count, &nH, &nW));
+  if (!z) return eae_set_error(EAE_ERR_ARG, "scene_encode_windows: NULL z");
+  hipStream_t st = (hipStream_t)stream;
+  RC(scene_begin(c, st));
+  for (long long b0 = 0; b0 < count; b0 += c->Bm) {
+    const int nb = (int)(count - b0 < c->Bm ? count - b0 : c->Bm);
+    RC(scene_encode_batch(c, st, s, nW, b0, nb, windows, nH * nW));
+    RC(copy_latent_out(c, st, z + (size_t)b0 * c->L, c->z, nb));
+  }
+  return 0;
+}
+
+extern "C" int eae_scene_classify_windows(eae_ctx* c, eae_mlp* m, void* stream, const eae_scene* s, const long long* windows,
+                                          long long count, float* probs, long long* labels) {
+  long long nH = 0, nW = 0;
+  RC(scene_index_checks(c, s, windows, count, &nH, &nW));
+  if (!m || !probs || !labels) return eae_set_error(EAE_ERR_ARG, "scene_classify_windows: NULL mlp, probs or labels");
+  int in_dim = 0, classes = 0, mb = 0;
+  RC(eae_mlp_dims(m, &in_dim, &classes, &mb));
+  if (in_dim != c->L) return eae_set_error(EAE_ERR_ARG, "scene_classify_windows: the MLP's input_dim is not the encoder's latent_dim");
+  hipStream_t st = (hipStream_t)stream;
+  RC(scene_begin(c, st));
+  for (long long b0 = 0; b0 < count; b0 += c->Bm) {
+    const int nb = (int)(count - b0 < c->Bm ? count - b0 : c->Bm);
+    RC(scene_encode_batch(c, st, s, nW, b0, nb, windows, nH * nW));
+    RC(eae_mlp_predict(m, st, c->z, c->Lp, nb, b0, nH * nW, probs, labels, windows));
   }
   return 0;
 }

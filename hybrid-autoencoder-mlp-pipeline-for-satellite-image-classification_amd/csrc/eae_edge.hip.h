@@ -27,11 +27,15 @@ template <int SRC3> constexpr bool src3_planar() { return SRC3 != SRC3_NHWCP_BF1
 
 // Scene source of conv1 (eval-mode forward only): image n of the launch is window w = first + n of the grid of P x P windows at
 // stride S (nW per row), whose origin is scene pixel (w / nW * S, w % nW * S).  Offsets are 64-bit: scenes exceed 2^31 elements.
+// Index-driven form (the IDX template flag of the scene kernels): image n is window index[first + n] instead; an id outside
+// [0, nwin) reads as an all-zero window (defence in depth: the callers reject such ids before any launch).
 struct SceneSrc {
   const void* data = nullptr;        // [C][Hs][Ws]
   const float* div = nullptr;        // [C]
   long long first = 0, plane = 0;    // first window of the launch; Hs * Ws
   int Ws = 0, S = 0, nW = 0;
+  const long long* index = nullptr;  // window ids (IDX kernels only)
+  long long nwin = 0;                // nH * nW
 };
 template <typename T> __device__ __forceinline__ float scene_val(T v, float d) { return (float)v / d; }
 // 4 consecutive scene pixels of one band: one vector load where the address allows it (window origins x are not aligned for most
@@ -84,7 +88,7 @@ template <int CP> constexpr int e_halo_row() { return CP == 4 ? 1 : CP / 8; }   
 template <int CP> constexpr int e_nld() { return (E_PH * (e_pieces_row<CP>() + e_halo_row<CP>()) + 255) / 256; }
 template <int SRC3, int CP> struct Patch3Regs { float4 v[EdgeK<CP>::CMAX]; };     // planar fp32: one float4 per band (halo threads: .x only)
 template <int CP> struct Patch3Regs<SRC3_NHWCP_BF16, CP> { uint4 v[e_nld<CP>()]; };   // bf16 NHWC-CP: 16-byte pieces
-template <int SRC3, int CP>
+template <int SRC3, int CP, bool IDX = false>
 __device__ __forceinline__ void patch3_load(const void* src, int C, int n, int H, int W, int iy0, int ix0, Patch3Regs<SRC3, CP>& r,
                                             const SceneSrc* sc = nullptr) {
   const int tid = threadIdx.x;
@@ -93,10 +97,14 @@ __device__ __forceinline__ void patch3_load(const void* src, int C, int n, int H
     using T = typename SceneElem<SRC3>::T;
     const T* x = static_cast<const T*>(sc->data);
     constexpr int CMAX = EdgeK<CP>::CMAX;
-    const long long w = sc->first + n, wi = w / sc->nW, wj = w - wi * sc->nW;
+    long long w = sc->first + n;
+    if constexpr (IDX) w = sc->index[w];                 // one uniform load per workgroup
+    const long long wi = w / sc->nW, wj = w - wi * sc->nW;
     const long long org = wi * sc->S * (long long)sc->Ws + wj * sc->S;
 #pragma unroll
     for (int c = 0; c < CMAX; ++c) r.v[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (IDX)
+      if (w < 0 || w >= sc->nwin) return;
     if (tid < E_PH * 16) {
       const int c4 = tid & 15, rr = tid >> 4;
       const int iy = iy0 + rr, ix = ix0 + 1 + c4 * 4;
@@ -212,11 +220,11 @@ __device__ __forceinline__ void patch3_write(bf16_t* p3, const Patch3Regs<SRC3, 
     }
   }
 }
-template <int SRC3, int CP>
+template <int SRC3, int CP, bool IDX = false>
 __device__ __forceinline__ void stage_patch3(const void* src, int C, bf16_t* p3, int n, int H, int W, int iy0, int ix0,
                                              const SceneSrc* sc = nullptr) {
   Patch3Regs<SRC3, CP> r;
-  patch3_load<SRC3, CP>(src, C, n, H, W, iy0, ix0, r, sc);
+  patch3_load<SRC3, CP, IDX>(src, C, n, H, W, iy0, ix0, r, sc);
   patch3_write<SRC3, CP>(p3, r);
   __syncthreads();
 }
@@ -292,7 +300,7 @@ struct EdgeArgs {
 // consecutive k are whole pixel pieces of the staged [row][col][CP] patch (two pixels for CP = 4, one for 8, half a pixel for 16), so
 // the pixel operand is read straight from the patch.  The weights are the MFMA A operand: an accumulator lane holds 4 consecutive
 // output channels of one pixel (8-byte tile writes instead of 16 two-byte ones).
-template <int SRC3, int EPI, int CP>
+template <int SRC3, int EPI, int CP, bool IDX = false>
 __device__ __forceinline__ void edge_conv_body(const EdgeArgs& a, const SceneSrc* sc = nullptr) {
   constexpr int KP = EdgeK<CP>::KP, KS = EdgeK<CP>::KS;
   __shared__ __attribute__((aligned(16))) bf16_t p3[e_patch<CP>()];
@@ -318,7 +326,7 @@ __device__ __forceinline__ void edge_conv_body(const EdgeArgs& a, const SceneSrc
     for (int ks = 0; ks < KS; ++ks)
       wf[mt][ks] = *reinterpret_cast<const bf16x8*>(a.c.wpack + (mt * 16 + (lane & 15)) * KP + ks * 32 + kgl * 8);
   EDGE_STAMP(16);
-  stage_patch3<SRC3, CP>(a.src3, edge_bands<CP>(a.C), p3, n, a.H, a.W, 2 * tyb * E_TH - 1, 2 * txb * E_TW - 1, sc);  // ends with a barrier
+  stage_patch3<SRC3, CP, IDX>(a.src3, edge_bands<CP>(a.C), p3, n, a.H, a.W, 2 * tyb * E_TH - 1, 2 * txb * E_TW - 1, sc);  // ends with a barrier
   EDGE_STAMP(17);
   f32x4 acc[2][2];
 #pragma unroll
@@ -381,9 +389,10 @@ template <int SRC3, int EPI, int CP>
 __global__ __launch_bounds__(256) void edge_conv_kernel(EdgeArgs a) { edge_conv_body<SRC3, EPI, CP>(a); }
 template <int SRC3, int EPI, int CP>
 __global__ __launch_bounds__(256) void edge_conv_kernel_g(GroupPack<EdgeArgs> p, int gz) { edge_conv_body<SRC3, EPI, CP>(group_args<EdgeArgs>(gz)); }
-// conv1 reading P x P windows of a device-resident scene (eae_scene_encode / eae_scene_classify; eval-mode forward)
-template <int SRC3, int CP>
-__global__ __launch_bounds__(256) void edge_conv_scene_kernel(EdgeArgs a, SceneSrc s) { edge_conv_body<SRC3, EPI_FWD, CP>(a, &s); }
+// conv1 reading P x P windows of a device-resident scene (eae_scene_encode / eae_scene_classify; eval-mode forward); IDX: the windows
+// of the launch come from s.index (eae_scene_encode_windows / eae_scene_classify_windows)
+template <int SRC3, int CP, bool IDX = false>
+__global__ __launch_bounds__(256) void edge_conv_scene_kernel(EdgeArgs a, SceneSrc s) { edge_conv_body<SRC3, EPI_FWD, CP, IDX>(a, &s); }
 
 // ---------------------------------------------------------------------------------------------------------------
 // R[k][c] = sum_m im2col(src)[m][k] * T(side)[m][c]     (weight gradient of conv1 and of deconv4)

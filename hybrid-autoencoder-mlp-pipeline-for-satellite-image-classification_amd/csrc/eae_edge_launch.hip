@@ -32,7 +32,8 @@ int eae_launch_edge_conv(hipStream_t st, int src3_kind, int epi, const EdgeArgs&
   return eae_set_error(-2, "edge_conv: combination not instantiated");
 }
 
-// conv1 over windows of a scene (eval-mode forward): the window gather is the kernel's patch load, no staged [B,C,P,P] batch
+// conv1 over windows of a scene (eval-mode forward): the window gather is the kernel's patch load, no staged [B,C,P,P] batch;
+// windows first + n, or index[first + n] when s.index is set
 int eae_launch_edge_conv_scene(hipStream_t st, int src3_kind, const EdgeArgs& a0, const SceneSrc& s) {
   if (int rc = check_edge_shape(a0.B, a0.H, a0.W)) return rc;
   if (int rc = check_bands(a0.C)) return rc;
@@ -41,7 +42,10 @@ int eae_launch_edge_conv_scene(hipStream_t st, int src3_kind, const EdgeArgs& a0
   dim3 grid(a.B * (a.H / 2 / E_TH) * (a.W / 2 / E_TW));
   a.c.ntiles = (int)grid.x;
   EAE_NO_GROUP("edge_conv_scene_kernel");
-#define CASE1(S, P) if (src3_kind == S && cp == P) { hipLaunchKernelGGL((edge_conv_scene_kernel<S, P>), grid, dim3(256), 0, st, a, s); EAE_LAUNCH_CHECK(); return 0; }
+#define CASE1(S, P) if (src3_kind == S && cp == P) { \
+    if (s.index) hipLaunchKernelGGL((edge_conv_scene_kernel<S, P, true>), grid, dim3(256), 0, st, a, s); \
+    else hipLaunchKernelGGL((edge_conv_scene_kernel<S, P>), grid, dim3(256), 0, st, a, s); \
+    EAE_LAUNCH_CHECK(); return 0; }
 #define CASE(S) CASE1(S, 4) CASE1(S, 8) CASE1(S, 16)
   CASE(SRC3_SCENE_U8)
   CASE(SRC3_SCENE_U16)

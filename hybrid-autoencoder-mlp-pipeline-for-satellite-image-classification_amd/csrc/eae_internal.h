@@ -38,14 +38,16 @@ struct EdgeArgs; struct Deconv4Args; struct WgradArgs; struct FcNtArgs; struct F
 int eae_launch_edge_conv(hipStream_t st, int src3_kind, int epi, const EdgeArgs& a);
 struct SceneSrc;
 int eae_launch_edge_conv_scene(hipStream_t st, int src3_kind, const EdgeArgs& a, const SceneSrc& s);
-// eval-mode MLP over rows x[b * ldx ..] (b < B) of windows win0.. of a scene: probs [K][plane] (column = window), labels [plane] (argmax)
+// eval-mode MLP over rows x[b * ldx ..] (b < B) of windows win0.. of a scene (or windows index[win0 ..]): probs [K][plane] (column =
+// window), labels [plane] (argmax)
 int eae_mlp_predict(eae_mlp* m, hipStream_t st, const float* x, int ldx, int B, long long win0, long long plane, float* probs,
-                    long long* labels);
+                    long long* labels, const long long* index = nullptr);
 int eae_mlp_dims(const eae_mlp* m, int* input_dim, int* classes, int* max_batch);
 // eae_scene.hip: argument checks (-> window grid nH x nW), conv1 source kind and kernel-side description of a scene
 int eae_scene_check(const eae_scene* s, long long* nH, long long* nW);
 int eae_scene_src3_kind(const eae_scene* s);
 void eae_scene_fill_src(const eae_scene* s, long long nW, long long first, SceneSrc* out);
+long long eae_scene_extent(long long n, int patch, int stride);   // (n - 1) * S + P: the pixels a grid of n windows spans on one axis
 int eae_edge_tiles(int B, int H, int W);
 int eae_launch_edge_wgrad(hipStream_t st, int src3_kind, const void* src3, int B, int H, int W, const SrcDesc& side, int smode,
                           float* scratch, long long scratch_floats, float* dw, const EaeProfHook* hook = nullptr,

@@ -33,6 +33,7 @@ struct MlpArgs {
   float* probs;            // eval-mode predict epilogue (scene classification): softmax -> probs[c * plane + win0 + row], or nullptr
   long long* plabels;      // argmax (first maximum) -> plabels[win0 + row]
   long long win0, plane;
+  const long long* index;  // predict epilogue: row r goes to window index[win0 + r] (skipped outside [0, plane)), or nullptr: win0 + r
 };
 
 // Philox4x32-10 (counter-based): keep-mask of nn.Dropout, keyed by (seed, optimisation step), counter = element index
@@ -190,7 +191,11 @@ __global__ EAE_NO_PK __launch_bounds__(T) void mlp_kernel(MlpArgs a) {
       for (int c = 1; c < C; ++c) if (l[c] > mx) { mx = l[c]; am = c; }
       float se = 0.f;
       for (int c = 0; c < C; ++c) se += expf(l[c] - mx);
-      const long long w = a.win0 + r0 + b;
+      long long w = a.win0 + r0 + b;
+      if (a.index) {
+        w = a.index[w];
+        if (w < 0 || w >= a.plane) continue;
+      }
       for (int c = 0; c < C; ++c) a.probs[c * a.plane + w] = expf(l[c] - mx) / se;
       a.plabels[w] = am;
     }
@@ -369,7 +374,7 @@ static int mlp_launch(eae_mlp* m, hipStream_t st, const float* x, const long lon
   }
   a.seed = seed; a.step = (unsigned long long)m->adam_step; a.drop_mask = drop_mask; a.p_drop = 0.3f;
   a.logits = logits; a.stats = stats; a.dlog_in = dlog_in; a.update_running = dlog_in ? 0 : 1;
-  a.ldx = m->IN; a.probs = nullptr; a.plabels = nullptr; a.win0 = 0; a.plane = 0;
+  a.ldx = m->IN; a.probs = nullptr; a.plabels = nullptr; a.win0 = 0; a.plane = 0; a.index = nullptr;
   const int grid = train ? 1 : (B + 63) / 64;
   hipLaunchKernelGGL(mlp_kernel, dim3(grid), dim3(T), 0, st, a);
   EAE_LAUNCH_CHECK();
@@ -404,12 +409,13 @@ int eae_mlp_dims(const eae_mlp* m, int* input_dim, int* classes, int* max_batch)
 }
 
 // Eval-mode pass over B rows of a strided latent (the AE engine's workspace rows, stride Lp): the logits are those of
-// eae_mlp_eval_step; the epilogue writes softmax and argmax at windows win0.. of the scene grid.  B is split at max_batch.
+// eae_mlp_eval_step; the epilogue writes softmax and argmax at windows win0.. of the scene grid, or with an index at windows
+// index[win0 ..] (win0 then counts rows of the index).  B is split at max_batch.
 int eae_mlp_predict(eae_mlp* m, hipStream_t st, const float* x, int ldx, int B, long long win0, long long plane, float* probs,
-                    long long* labels) {
+                    long long* labels, const long long* index) {
   if (!m || !x || !probs || !labels) return eae_set_error(EAE_ERR_ARG, "mlp_predict: NULL argument");
   if (!m->P) return eae_set_error(EAE_ERR_STATE, "eae_mlp_bind has not been called");
-  if (ldx < m->IN || B <= 0 || win0 < 0 || win0 + B > plane) return eae_set_error(EAE_ERR_ARG, "mlp_predict: bad shape");
+  if (ldx < m->IN || B <= 0 || win0 < 0 || (!index && win0 + B > plane)) return eae_set_error(EAE_ERR_ARG, "mlp_predict: bad shape");
   for (int b0 = 0; b0 < B; b0 += m->Bm) {
     const int nb = B - b0 < m->Bm ? B - b0 : m->Bm;
     MlpArgs a;
@@ -422,7 +428,7 @@ int eae_mlp_predict(eae_mlp* m, hipStream_t st, const float* x, int ldx, int B, 
     a.b1 = 0.9f; a.b2 = 0.999f; a.eps = 1e-8f; a.wd = 0.f; a.step_size = 0.f; a.bc2_sqrt = 1.f;
     a.seed = 0; a.step = 0; a.drop_mask = nullptr; a.p_drop = 0.3f;
     a.logits = nullptr; a.stats = nullptr; a.dlog_in = nullptr; a.update_running = 0;
-    a.ldx = ldx; a.probs = probs; a.plabels = labels; a.win0 = win0 + b0; a.plane = plane;
+    a.ldx = ldx; a.probs = probs; a.plabels = labels; a.win0 = win0 + b0; a.plane = plane; a.index = index;
     hipLaunchKernelGGL(mlp_kernel, dim3((nb + 63) / 64), dim3(T), 0, st, a);
     EAE_LAUNCH_CHECK();
   }

@@ -1,6 +1,7 @@
 // Scene classification helpers (include/eae.h, "scene classification"): the window gather (the public way to get patches, and the
-// reference the fused conv1 scene source is tested against) and the cell blend of window probabilities.  Neither uses matrix
-// instructions, so both are built with packed FP32 disabled (EAE_NO_PK, tests/test_isa_guard.py).
+// reference the fused conv1 scene source is tested against), the cell blends of window probabilities, and the nodata / mask path:
+// per-window invalid-pixel counts and the compaction of the valid window ids.  None uses matrix instructions, so all are built with
+// packed FP32 disabled (EAE_NO_PK, tests/test_isa_guard.py).
 #include "eae_internal.h"
 #include "eae_common.hip.h"
 #include "eae_edge.hip.h"
@@ -47,7 +48,215 @@ __global__ EAE_NO_PK __launch_bounds__(256) void scene_blend_kernel(const float*
   cell_labels[p] = am;
 }
 
+// cell (ci, cj) as above, over the valid windows only (labels >= 0): the same (i, then j) summation order, divided by the float count
+// of valid covering windows; a cell without one gets probabilities 0 and label -1
+__global__ EAE_NO_PK __launch_bounds__(256) void scene_blend_valid_kernel(const float* __restrict__ probs, const long long* __restrict__ labels,
+                                                                      int K, int nH, int nW, int k, float* __restrict__ cell,
+                                                                      long long* __restrict__ cell_labels) {
+  const int cH = nH + k - 1, cW = nW + k - 1;
+  const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= (long long)cH * cW) return;
+  const int ci = (int)(p / cW), cj = (int)(p - (long long)ci * cW);
+  const int i0 = ci - k + 1 > 0 ? ci - k + 1 : 0, i1 = ci < nH - 1 ? ci : nH - 1;
+  const int j0 = cj - k + 1 > 0 ? cj - k + 1 : 0, j1 = cj < nW - 1 ? cj : nW - 1;
+  const long long wplane = (long long)nH * nW, cplane = (long long)cH * cW;
+  int nv = 0;
+  for (int i = i0; i <= i1; ++i)
+    for (int j = j0; j <= j1; ++j) nv += labels[(long long)i * nW + j] >= 0;
+  if (nv == 0) {
+    for (int c = 0; c < K; ++c) cell[c * cplane + p] = 0.f;
+    cell_labels[p] = -1;
+    return;
+  }
+  const float cnt = (float)nv;
+  float mx = 0.f;
+  int am = 0;
+  for (int c = 0; c < K; ++c) {
+    const float* q = probs + c * wplane;
+    float s = 0.f;
+    for (int i = i0; i <= i1; ++i)
+      for (int j = j0; j <= j1; ++j)
+        if (labels[(long long)i * nW + j] >= 0) s += q[(long long)i * nW + j];
+    const float v = s / cnt;
+    cell[c * cplane + p] = v;
+    if (c == 0 || v > mx) { mx = v; am = c; }
+  }
+  cell_labels[p] = am;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- invalid-pixel counts
+// Separable count of the invalid pixels of every window, reading each scene element (and mask byte) inside the grid's extent once:
+//   pass 1 (scene_invalid_rows_kernel): one workgroup per (pixel row y, chunk of window columns).  Each thread tests groups of V pixels
+//     (one 16-byte load per band where aligned, else element loads) across the bands in registers and writes one flag byte per pixel
+//     to LDS; a block prefix sum over the chunk's pixels gives every window column its horizontal run sum in O(1) (also for S < P):
+//     rows[y][j] = number of invalid pixels in scene row y, columns j*S .. j*S + P - 1.
+//   pass 2 (scene_invalid_windows_kernel): counts[i][j] = sum of rows[i*S + r][j], r < P (one thread per window, coalesced along j).
+constexpr int INV_NT = 256;               // threads of pass 1
+constexpr int INV_SPAN = INV_NT * 16;     // pixels per pass-1 workgroup (16 per thread), including the alignment shift
+
+__device__ __forceinline__ int wave_incl_scan(int v) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int u = __shfl_up(v, d, 64);
+    if (lane >= d) v += u;
+  }
+  return v;
+}
+// exclusive prefix of v over the NT threads of the block (NT a multiple of 64); *total = the block's sum.  sh: NT / 64 ints of LDS.
+template <int NT>
+__device__ __forceinline__ int block_excl_scan(int v, int* sh, int* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int incl = wave_incl_scan(v);
+  if (lane == 63) sh[wave] = incl;
+  __syncthreads();
+  int base = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < NT / 64; ++w) {
+    const int x = sh[w];
+    base += w < wave ? x : 0;
+    tot += x;
+  }
+  __syncthreads();                        // sh is reused by the next call
+  *total = tot;
+  return base + incl - v;
+}
+
+template <typename T> __device__ __forceinline__ bool inv_match(T v, int mode, T ref, float fref) {
+  if constexpr (sizeof(T) == 4) return mode == EAE_NODATA_NAN ? v != v : v == fref;
+  else return v == ref;
+}
+
+template <typename T>
+__global__ EAE_NO_PK __launch_bounds__(INV_NT) void scene_invalid_rows_kernel(const T* __restrict__ src, long long plane, int C, int Ws,
+                                                                           int P, int S, int nW, int J, int nchunk, int mode, float nodata,
+                                                                           int rule_any, const unsigned char* __restrict__ mask,
+                                                                           int* __restrict__ rows) {
+  constexpr int V = 16 / (int)sizeof(T), G = (int)sizeof(T);   // pixels per 16-byte group, groups per thread (G * V = 16)
+  __shared__ unsigned char fl[INV_SPAN];
+  __shared__ int pre[INV_SPAN + 1];
+  __shared__ int sh[INV_NT / 64];
+  const int tid = threadIdx.x;
+  const long long y = blockIdx.x / nchunk;
+  const int chunk = (int)(blockIdx.x - y * nchunk);
+  const int j0 = chunk * J, jn = nW - j0 < J ? nW - j0 : J;
+  const long long x0 = (long long)j0 * S, x1 = (long long)(j0 + jn - 1) * S + P;     // pixels [x0, x1) of this workgroup
+  const long long rowoff = y * Ws;
+  // groups start at a 16-byte boundary of band 0: xa = x0 - m
+  const int m = (int)((reinterpret_cast<uintptr_t>(src + rowoff + x0) & 15) / sizeof(T));
+  const long long xa = x0 - m;
+  const T ref = (T)(mode == EAE_NODATA_VALUE && sizeof(T) < 4 ? nodata : 0.f);
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    const int q = g * INV_NT + tid;
+    const long long gx = xa + (long long)q * V;
+    const long long lo = gx > x0 ? gx : x0, hi = gx + V < x1 ? gx + V : x1;
+    bool inv[V];
+    const bool any_rule = rule_any != 0;
+#pragma unroll
+    for (int v = 0; v < V; ++v) inv[v] = false;
+    if (lo < hi) {
+      const bool full = lo == gx && hi == gx + V;
+      if (mode != EAE_NODATA_NONE) {
+#pragma unroll
+        for (int v = 0; v < V; ++v) inv[v] = !any_rule;
+#pragma unroll 4
+        for (int c = 0; c < C; ++c) {
+          const T* p = src + c * plane + rowoff + gx;
+          T e[V];
+          if (full && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+            const uint4 u = *reinterpret_cast<const uint4*>(p);
+            __builtin_memcpy(e, &u, 16);
+          } else {
+#pragma unroll
+            for (int v = 0; v < V; ++v) e[v] = (gx + v >= lo && gx + v < hi) ? p[v] : (T)0;
+          }
+#pragma unroll
+          for (int v = 0; v < V; ++v) {
+            const bool mt = inv_match<T>(e[v], mode, ref, nodata);
+            inv[v] = any_rule ? (inv[v] || mt) : (inv[v] && mt);
+          }
+        }
+      }
+      if (mask) {
+        const unsigned char* p = mask + rowoff + gx;
+        unsigned char e[V];
+        if (full && (reinterpret_cast<uintptr_t>(p) & (V - 1)) == 0) {
+          if constexpr (V == 16) { const uint4 u = *reinterpret_cast<const uint4*>(p); __builtin_memcpy(e, &u, 16); }
+          else if constexpr (V == 8) { const uint2 u = *reinterpret_cast<const uint2*>(p); __builtin_memcpy(e, &u, 8); }
+          else { const unsigned u = *reinterpret_cast<const unsigned*>(p); __builtin_memcpy(e, &u, 4); }
+        } else {
+#pragma unroll
+          for (int v = 0; v < V; ++v) e[v] = (gx + v >= lo && gx + v < hi) ? p[v] : (unsigned char)0;
+        }
+#pragma unroll
+        for (int v = 0; v < V; ++v) inv[v] = inv[v] || e[v] != 0;
+      }
+#pragma unroll
+      for (int v = 0; v < V; ++v) inv[v] = inv[v] && gx + v >= lo && gx + v < hi;
+    }
+#pragma unroll
+    for (int v = 0; v < V; ++v) fl[q * V + v] = inv[v] ? 1 : 0;
+  }
+  __syncthreads();
+  // pre[k] = invalid pixels among [xa, xa + k): thread tid owns pixels tid*16 .. tid*16 + 15
+  int loc = 0;
+#pragma unroll
+  for (int v = 0; v < 16; ++v) loc += fl[tid * 16 + v];
+  int tot = 0;
+  int run = block_excl_scan<INV_NT>(loc, sh, &tot);
+  if (tid == 0) pre[0] = 0;
+#pragma unroll
+  for (int v = 0; v < 16; ++v) {
+    run += fl[tid * 16 + v];
+    pre[tid * 16 + v + 1] = run;
+  }
+  __syncthreads();
+  for (int jj = tid; jj < jn; jj += INV_NT) {
+    const int s0 = m + jj * S;
+    rows[y * nW + j0 + jj] = pre[s0 + P] - pre[s0];
+  }
+}
+
+__global__ EAE_NO_PK __launch_bounds__(256) void scene_invalid_windows_kernel(const int* __restrict__ rows, int nH, int nW, int P, int S,
+                                                                          int* __restrict__ counts) {
+  const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= (long long)nH * nW) return;
+  const long long i = p / nW, j = p - i * nW;
+  const int* r = rows + i * S * nW + j;
+  int s = 0;
+  for (int y = 0; y < P; ++y) s += r[(long long)y * nW];
+  counts[p] = s;
+}
+
+// Stable compaction in one workgroup: ids of the windows with counts <= t, ascending, and their number.  Each pass takes 8 consecutive
+// windows per thread (8192 per pass); the output offsets come from a block prefix sum, so the order never depends on scheduling.
+constexpr int SEL_NT = 1024, SEL_PER = 8;
+__global__ EAE_NO_PK __launch_bounds__(SEL_NT) void scene_select_kernel(const int* __restrict__ counts, long long n, int t,
+                                                                    long long* __restrict__ ids, long long* __restrict__ count_out) {
+  __shared__ int sh[SEL_NT / 64];
+  const int tid = threadIdx.x;
+  long long base = 0;
+  for (long long c0 = 0; c0 < n; c0 += (long long)SEL_NT * SEL_PER) {
+    const long long k0 = c0 + (long long)tid * SEL_PER;
+    unsigned ok = 0;
+    int loc = 0;
+#pragma unroll
+    for (int v = 0; v < SEL_PER; ++v)
+      if (k0 + v < n && counts[k0 + v] <= t) { ok |= 1u << v; ++loc; }
+    int tot = 0;
+    long long o = base + block_excl_scan<SEL_NT>(loc, sh, &tot);
+#pragma unroll
+    for (int v = 0; v < SEL_PER; ++v)
+      if (ok & (1u << v)) ids[o++] = k0 + v;
+    base += tot;
+  }
+  if (tid == 0) *count_out = base;
+}
+
 }  // namespace
+
+long long eae_scene_extent(long long n, int patch, int stride) { return (n - 1) * stride + patch; }
 
 int eae_scene_check(const eae_scene* s, long long* nH, long long* nW) {
   if (!s) return eae_set_error(EAE_ERR_ARG, "scene: NULL scene");
@@ -102,6 +311,65 @@ extern "C" int eae_scene_blend(void* stream, const float* probs, int K, int nH, 
   const long long tot = (long long)(nH + k - 1) * (nW + k - 1);
   hipLaunchKernelGGL(scene_blend_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, probs, K, nH, nW, k,
                      cell, cell_labels);
+  EAE_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int eae_scene_blend_valid(void* stream, const float* probs, const long long* labels, int K, int nH, int nW, int k, float* cell,
+                                     long long* cell_labels) {
+  if (!probs || !labels || !cell || !cell_labels) return eae_set_error(EAE_ERR_ARG, "scene_blend_valid: NULL argument");
+  if (K < 1 || nH < 1 || nW < 1 || k < 1) return eae_set_error(EAE_ERR_ARG, "scene_blend_valid: bad shape");
+  EAE_NO_GROUP("scene_blend_valid_kernel");
+  const long long tot = (long long)(nH + k - 1) * (nW + k - 1);
+  hipLaunchKernelGGL(scene_blend_valid_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, probs, labels, K,
+                     nH, nW, k, cell, cell_labels);
+  EAE_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int eae_scene_invalid_counts(void* stream, const eae_scene* s, int nodata_mode, float nodata, int rule,
+                                        const unsigned char* mask, int* rows, int* counts) {
+  long long nH = 0, nW = 0;
+  if (int rc = eae_scene_check(s, &nH, &nW)) return rc;
+  if (!rows || !counts) return eae_set_error(EAE_ERR_ARG, "scene_invalid_counts: NULL rows or counts");
+  if (nodata_mode != EAE_NODATA_NONE && nodata_mode != EAE_NODATA_VALUE && nodata_mode != EAE_NODATA_NAN)
+    return eae_set_error(EAE_ERR_ARG, "scene_invalid_counts: unknown nodata mode");
+  if (rule != EAE_INVALID_ALL && rule != EAE_INVALID_ANY) return eae_set_error(EAE_ERR_ARG, "scene_invalid_counts: unknown rule");
+  if (s->dtype != EAE_SCENE_F32 && nodata_mode == EAE_NODATA_NAN)
+    return eae_set_error(EAE_ERR_ARG, "scene_invalid_counts: a NaN nodata needs an fp32 scene");
+  if (s->dtype != EAE_SCENE_F32 && nodata_mode == EAE_NODATA_VALUE) {
+    const float hi = s->dtype == EAE_SCENE_U8 ? 255.f : 65535.f;
+    if (!(nodata >= 0.f && nodata <= hi) || nodata != (float)(int)nodata)
+      return eae_set_error(EAE_ERR_ARG, "scene_invalid_counts: nodata must be an integer in the scene dtype's range");
+  }
+  if (s->patch > INV_SPAN - 16) return eae_set_error(EAE_ERR_ARG, "scene_invalid_counts: the patch size must be at most 4080");
+  EAE_NO_GROUP("scene_invalid_rows_kernel");
+  const hipStream_t st = (hipStream_t)stream;
+  const long long plane = (long long)s->H * s->W, Hg = eae_scene_extent(nH, s->patch, s->stride);
+  const int J = (INV_SPAN - 15 - s->patch) / s->stride + 1;        // window columns per workgroup: (J - 1) S + P + shift <= INV_SPAN
+  const int nchunk = (int)((nW + J - 1) / J);
+  const long long nblk = Hg * nchunk;
+  if (nblk * INV_NT > 0xffffffffLL) return eae_set_error(EAE_ERR_ARG, "scene_invalid_counts: scene too large");
+  const int rany = rule == EAE_INVALID_ANY;
+#define ROWS(T) hipLaunchKernelGGL(scene_invalid_rows_kernel<T>, dim3((unsigned)nblk), dim3(INV_NT), 0, st, (const T*)s->data, plane, s->C, \
+                                   s->W, s->patch, s->stride, (int)nW, J, nchunk, nodata_mode, nodata, rany, mask, rows)
+  if (s->dtype == EAE_SCENE_U8) ROWS(uint8_t);
+  else if (s->dtype == EAE_SCENE_U16) ROWS(uint16_t);
+  else ROWS(float);
+#undef ROWS
+  EAE_LAUNCH_CHECK();
+  const long long nwin = nH * nW;
+  hipLaunchKernelGGL(scene_invalid_windows_kernel, dim3((unsigned)((nwin + 255) / 256)), dim3(256), 0, st, rows, (int)nH, (int)nW,
+                     s->patch, s->stride, counts);
+  EAE_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int eae_scene_select(void* stream, const int* counts, long long n, int threshold, long long* windows, long long* count) {
+  if (!counts || !windows || !count) return eae_set_error(EAE_ERR_ARG, "scene_select: NULL argument");
+  if (n < 1) return eae_set_error(EAE_ERR_ARG, "scene_select: empty grid");
+  EAE_NO_GROUP("scene_select_kernel");
+  hipLaunchKernelGGL(scene_select_kernel, dim3(1), dim3(SEL_NT), 0, (hipStream_t)stream, counts, n, threshold, windows, count);
   EAE_LAUNCH_CHECK();
   return 0;
 }

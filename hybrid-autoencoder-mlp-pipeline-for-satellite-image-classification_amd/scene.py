@@ -9,10 +9,24 @@ directly (no staged fp32 [B,C,P,P] batch), the MLP reads the engine's latent row
 - `encode_scene` returns the latents z [nH*nW, L] (clustering, retrieval);
 - `classify_scene` returns probabilities [K,nH,nW] and labels [nH,nW], or with ``blend=True`` (S divides P) the map of S x S cells,
   each the mean probability of the windows that cover it, [K,nH+k-1,nW+k-1] with k = P/S.
+
+Nodata and masked windows.  Pixel (y, x) is invalid when it matches ``nodata`` (``rule="all"``, the default and rasterio's
+dataset-mask convention: every band equals it; ``rule="any"``: at least one band does) or when ``mask[y, x] != 0`` (``mask``: a
+[H, W] bool / uint8 tensor on the scene's device).  For uint8 / uint16 scenes ``nodata`` must be an integer in the dtype's range
+(an integral float such as rasterio's 0.0 is accepted); for fp32 scenes ``float("nan")`` matches NaN and any other value matches by
+``==`` after rounding to float32.  Window n is invalid when it holds more than t = floor(max_invalid * P * P) invalid pixels
+(`invalid_threshold`; ``max_invalid`` in [0, 1), default 0: one invalid pixel excludes the window).  A valid window that holds some
+invalid pixels (t > 0) is encoded with those pixels as stored: nothing is filled in.
+- `window_invalid_counts` returns the invalid pixels of every window, `valid_windows` the ascending ids of the valid ones;
+- `classify_scene(nodata=, mask=)` encodes only the valid windows: the others get label -1 and probability 0 for every class, and the
+  blend averages each cell over its valid covering windows only (a cell with none: label -1, probabilities 0);
+- ``windows=`` (`encode_scene`, `classify_scene`) runs the model over a device list of window ids instead of the whole grid.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
+import numbers
 
 import torch
 
@@ -63,7 +77,104 @@ def cell_coverage(n_h, n_w, k):
     return rows[:, None] * cols[None, :]
 
 
+def invalid_threshold(patch, max_invalid):
+    """t = floor(max_invalid * P * P): a window with more than t invalid pixels is excluded (max_invalid in [0, 1))."""
+    patch = int(patch)
+    if patch <= 0:
+        raise RuntimeError(f"the patch size must be positive, got {patch}")
+    if isinstance(max_invalid, bool) or not isinstance(max_invalid, numbers.Real):
+        raise RuntimeError(f"max_invalid must be a number in [0, 1), got {max_invalid!r}")
+    m = float(max_invalid)
+    if not 0.0 <= m < 1.0:                              # also rejects NaN
+        raise RuntimeError(f"max_invalid must be in [0, 1), got {max_invalid}")
+    return math.floor(m * patch * patch)
+
+
+def valid_coverage(valid, k):
+    """Number of valid windows covering each S x S cell: ``valid`` is a boolean [nH, nW] window-validity map, k = P/S; the result is
+    a [nH+k-1, nW+k-1] int64 CPU tensor (`cell_coverage` when every window is valid).  The blend divides by this count."""
+    if not isinstance(valid, torch.Tensor) or valid.dim() != 2 or valid.dtype != torch.bool:
+        raise RuntimeError("valid must be a boolean [nH, nW] tensor")
+    k = int(k)
+    if k < 1:
+        raise RuntimeError(f"k must be positive, got {k}")
+    v = valid.cpu().to(torch.int64)
+    n_h, n_w = v.shape
+    if n_h < 1 or n_w < 1:
+        raise RuntimeError("valid must hold at least one window")
+    # box sums of k x k windows of the zero-padded map: cell (ci, cj) is covered by windows [ci-k+1, ci] x [cj-k+1, cj]
+    pad = torch.zeros((n_h + 2 * (k - 1), n_w + 2 * (k - 1)), dtype=torch.int64)
+    pad[k - 1:k - 1 + n_h, k - 1:k - 1 + n_w] = v
+    ii = pad.cumsum(0).cumsum(1)
+    ii = torch.nn.functional.pad(ii, (1, 0, 1, 0))
+    c_h, c_w = n_h + k - 1, n_w + k - 1
+    return ii[k:k + c_h, k:k + c_w] - ii[0:c_h, k:k + c_w] - ii[k:k + c_h, 0:c_w] + ii[0:c_h, 0:c_w]
+
+
+_RULES = {"all": 0, "any": 1}
+_NODATA_NONE, _NODATA_VALUE, _NODATA_NAN = 0, 1, 2
+_INT_RANGE = {torch.uint8: 255, torch.uint16: 65535}
+
+
 # ---------------------------------------------------------------------------------------------------- argument checks
+def _nodata_arg(dtype, nodata):
+    """(mode, value) of the C call for a nodata value of a scene of this dtype."""
+    if nodata is None:
+        return _NODATA_NONE, 0.0
+    if isinstance(nodata, bool) or not isinstance(nodata, numbers.Real):
+        raise RuntimeError(f"nodata must be a number, got {nodata!r}")
+    if dtype in _INT_RANGE:
+        v = float(nodata)
+        if math.isnan(v) or not v.is_integer() or not 0 <= v <= _INT_RANGE[dtype]:
+            raise RuntimeError(f"nodata of a {str(dtype).replace('torch.', '')} scene must be an integer in 0..{_INT_RANGE[dtype]}, "
+                               f"got {nodata!r}")
+        return _NODATA_VALUE, v
+    v = float(nodata)
+    return (_NODATA_NAN, 0.0) if math.isnan(v) else (_NODATA_VALUE, v)
+
+
+def _mask_arg(scene, mask):
+    """The mask as a contiguous uint8 [H, W] tensor on the scene's device (bool is viewed, not copied), or None."""
+    if mask is None:
+        return None
+    if not isinstance(mask, torch.Tensor) or mask.dim() != 2 or tuple(mask.shape) != tuple(scene.shape[1:]):
+        raise RuntimeError(f"mask must be a [H, W] = {list(scene.shape[1:])} tensor")
+    if mask.dtype not in (torch.bool, torch.uint8):
+        raise RuntimeError(f"mask dtype must be bool or uint8, got {mask.dtype}")
+    if mask.device != scene.device:
+        raise RuntimeError(f"mask is on {mask.device}, the scene on {scene.device}")
+    mask = mask.contiguous()
+    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+
+
+def _invalid_args(scene, nodata, mask, rule):
+    """Validate nodata / mask / rule against the scene: (mode, value, rule id, uint8 mask or None)."""
+    if rule not in _RULES:
+        raise RuntimeError(f"rule must be 'all' or 'any', got {rule!r}")
+    if not isinstance(scene, torch.Tensor) or scene.dim() != 3:
+        raise RuntimeError("scene must be a planar tensor [C,H,W]")
+    if scene.dtype not in _DTYPES:
+        raise RuntimeError(f"scene dtype must be uint8, uint16 or float32, got {scene.dtype}")
+    mode, value = _nodata_arg(scene.dtype, nodata)
+    return mode, value, _RULES[rule], _mask_arg(scene, mask)
+
+
+def _windows_arg(windows, device, n_windows, allow_empty):
+    """Validate a window-id list: 1-D int64 on the scene's device, ids in [0, nH*nW) (one aminmax readback)."""
+    if not isinstance(windows, torch.Tensor) or windows.dim() != 1 or windows.dtype != torch.int64:
+        raise RuntimeError("windows must be a 1-D int64 tensor of window ids")
+    if windows.device != device:
+        raise RuntimeError(f"windows is on {windows.device}, the scene on {device}")
+    if windows.numel() == 0:
+        if not allow_empty:
+            raise RuntimeError("windows is empty")
+        return windows
+    lo, hi = (int(v) for v in torch.aminmax(windows))
+    if lo < 0 or hi >= n_windows:
+        raise RuntimeError(f"window ids {lo}..{hi} are outside the grid of {n_windows}")
+    return windows.contiguous()
+
+
 def _encoder_of(encoder):
     from .modules import Encoder, SupervisedAutoencoder
     if isinstance(encoder, SupervisedAutoencoder):
@@ -96,6 +207,26 @@ def _scene_desc(scene, divisor, patch, stride):
     return desc, (scene, div), n_h, n_w
 
 
+def _invalid_counts(desc, keep, n_h, n_w, mode, value, rule, mask):
+    lib = _lib.load()
+    dev = keep[0].device
+    rows = torch.empty(((n_h - 1) * desc.stride + desc.patch, n_w), dtype=torch.int32, device=dev)
+    counts = torch.empty((n_h, n_w), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.eae_scene_invalid_counts(_stream(), C.byref(desc), mode, value, rule, _ptr(mask), _ptr(rows), _ptr(counts)))
+    return counts
+
+
+def _select(counts, t):
+    lib = _lib.load()
+    n = counts.numel()
+    ids = torch.empty(n, dtype=torch.int64, device=counts.device)
+    cnt = torch.empty(1, dtype=torch.int64, device=counts.device)
+    with torch.cuda.device(counts.device):
+        check(lib.eae_scene_select(_stream(), _ptr(counts), n, int(t), _ptr(ids), _ptr(cnt)))
+    return ids[:int(cnt.item())]
+
+
 def _range(first, count, total):
     first = int(first)
     count = total - first if count is None else int(count)
@@ -116,6 +247,23 @@ def scene_windows(scene, divisor, patch, stride, first=0, count=None):
     return out
 
 
+def window_invalid_counts(scene, patch, stride, nodata=None, mask=None, rule="all"):
+    """Invalid pixels of every P x P window at stride S: int32 [nH, nW] on the scene's device (see the module docstring for what
+    makes a pixel invalid).  Every scene element and mask byte inside the grid's extent is read once."""
+    mode, value, rid, m = _invalid_args(scene, nodata, mask, rule)
+    desc, keep, n_h, n_w = _scene_desc(scene, 1.0, patch, stride)
+    return _invalid_counts(desc, keep + (m,), n_h, n_w, mode, value, rid, m)
+
+
+def valid_windows(scene, patch, stride, nodata=None, mask=None, max_invalid=0.0, rule="all"):
+    """Ascending int64 ids (on the scene's device) of the windows with at most floor(max_invalid * P * P) invalid pixels.
+    The number of valid windows is read back once (``.item()``) to size the result: this is the one host synchronisation of the
+    nodata / mask path."""
+    t = invalid_threshold(patch, max_invalid)
+    counts = window_invalid_counts(scene, patch, stride, nodata=nodata, mask=mask, rule=rule)
+    return _select(counts, t)
+
+
 def _prepare(scene, encoder, divisor, stride, batch):
     enc = _encoder_of(encoder)
     patch = int(enc.image_size)
@@ -134,9 +282,28 @@ def _prepare(scene, encoder, divisor, stride, batch):
     return eng, desc, keep, n_h, n_w, patch, stride
 
 
-def encode_scene(scene, encoder, divisor=1.0, stride=None, batch=512):
+def _grid_of(scene, encoder, stride):
+    """(patch, stride, nH, nW) from shapes alone (no device work), for argument checks ahead of `_prepare`."""
+    enc = _encoder_of(encoder)
+    patch = int(enc.image_size)
+    stride = patch if stride is None else int(stride)
+    if not isinstance(scene, torch.Tensor) or scene.dim() != 3:
+        raise RuntimeError("scene must be a planar tensor [C,H,W]")
+    return (patch, stride) + window_grid(scene.shape[1], scene.shape[2], patch, stride)
+
+
+def encode_scene(scene, encoder, divisor=1.0, stride=None, batch=512, windows=None):
     """Latents z [nH*nW, L] of every window (row n = window i*nW + j), eval-mode encoder, `batch` windows per encoder pass (the
-    engine's max_batch, at least this).  stride=None: the patch size (non-overlapping windows)."""
+    engine's max_batch, at least this).  stride=None: the patch size (non-overlapping windows).
+    windows: a non-empty 1-D int64 device tensor of window ids (any order, duplicates allowed): z [len(windows), L] in that order."""
+    if windows is not None:
+        _, _, n_h, n_w = _grid_of(scene, encoder, stride)
+        windows = _windows_arg(windows, scene.device, n_h * n_w, allow_empty=False)
+        eng, desc, keep, n_h, n_w, _, _ = _prepare(scene, encoder, divisor, stride, batch)
+        z = torch.empty((windows.numel(), eng.latent), dtype=torch.float32, device=eng.device)
+        with torch.cuda.device(eng.device):
+            check(eng.lib.eae_scene_encode_windows(eng.ctx, _stream(), C.byref(desc), _ptr(windows), windows.numel(), _ptr(z)))
+        return z
     eng, desc, keep, n_h, n_w, _, _ = _prepare(scene, encoder, divisor, stride, batch)
     n = n_h * n_w
     z = torch.empty((n, eng.latent), dtype=torch.float32, device=eng.device)
@@ -145,10 +312,16 @@ def encode_scene(scene, encoder, divisor=1.0, stride=None, batch=512):
     return z
 
 
-def classify_scene(scene, encoder, mlp, divisor=1.0, stride=None, batch=512, blend=False):
+def classify_scene(scene, encoder, mlp, divisor=1.0, stride=None, batch=512, blend=False, nodata=None, mask=None, max_invalid=0.0,
+                   rule="all", windows=None):
     """(probs [K,nH,nW] float32 softmax, labels [nH,nW] int64 argmax) of every window: encoder -> MLP in eval mode, one C call.
     blend=True (stride divides the patch size, k = P/S): the map of S x S cells instead, probs [K,nH+k-1,nW+k-1] = mean over the
-    windows covering each cell, labels = argmax of that map."""
+    windows covering each cell, labels = argmax of that map.
+
+    nodata / mask / max_invalid / rule (module docstring): only the valid windows are encoded (`valid_windows`, one host readback);
+    windows: a 1-D int64 device tensor of window ids, the only windows classified (not combined with nodata / mask).  Either way the
+    other windows get label -1 and probability 0, and blend=True averages each cell over its classified windows only (no such
+    window: label -1, probabilities 0).  Without a valid window nothing is launched.  With all of them None the plain path runs."""
     from .mlp_engine import mlp_engine_for
     from .modules import MLP
     if not isinstance(mlp, MLP):
@@ -159,6 +332,18 @@ def classify_scene(scene, encoder, mlp, divisor=1.0, stride=None, batch=512, ble
     if blend:
         patch = int(enc.image_size)
         cell_grid(1, 1, patch, patch if stride is None else int(stride))      # the stride must divide the patch size
+    masked = nodata is not None or mask is not None
+    if rule not in _RULES:
+        raise RuntimeError(f"rule must be 'all' or 'any', got {rule!r}")
+    t = invalid_threshold(enc.image_size, max_invalid)
+    if masked or windows is not None:
+        if windows is not None and masked:
+            raise RuntimeError("windows= cannot be combined with nodata= or mask=")
+        patch, st, n_h, n_w = _grid_of(scene, encoder, stride)
+        inv = _invalid_args(scene, nodata, mask, rule)
+        if windows is not None:
+            windows = _windows_arg(windows, scene.device, n_h * n_w, allow_empty=True)
+        return _classify_subset(scene, encoder, mlp, divisor, stride, batch, blend, inv, t, windows)
     eng, desc, keep, n_h, n_w, patch, stride = _prepare(scene, encoder, divisor, stride, batch)
     if next(mlp.parameters()).device != eng.device:
         raise RuntimeError("the MLP and the encoder must be on the same device")
@@ -174,4 +359,30 @@ def classify_scene(scene, encoder, mlp, divisor=1.0, stride=None, batch=512, ble
         cprobs = torch.empty((k_cls, c_h, c_w), dtype=torch.float32, device=eng.device)
         clabels = torch.empty((c_h, c_w), dtype=torch.int64, device=eng.device)
         check(eng.lib.eae_scene_blend(_stream(), _ptr(probs), k_cls, n_h, n_w, k, _ptr(cprobs), _ptr(clabels)))
+    return cprobs, clabels
+
+
+def _classify_subset(scene, encoder, mlp, divisor, stride, batch, blend, inv, t, windows):
+    """classify_scene over the valid windows (nodata / mask) or the listed ones: pre-filled -1 / 0, index-driven encoder -> MLP."""
+    from .mlp_engine import mlp_engine_for
+    eng, desc, keep, n_h, n_w, patch, stride = _prepare(scene, encoder, divisor, stride, batch)
+    if next(mlp.parameters()).device != eng.device:
+        raise RuntimeError("the MLP and the encoder must be on the same device")
+    meng = mlp_engine_for(mlp)
+    k_cls = int(mlp.num_classes)
+    if windows is None:
+        mode, value, rid, m = inv
+        windows = _select(_invalid_counts(desc, keep + (m,), n_h, n_w, mode, value, rid, m), t)
+    probs = torch.zeros((k_cls, n_h, n_w), dtype=torch.float32, device=eng.device)
+    labels = torch.full((n_h, n_w), -1, dtype=torch.int64, device=eng.device)
+    with torch.cuda.device(eng.device):
+        if windows.numel():
+            check(eng.lib.eae_scene_classify_windows(eng.ctx, meng.ctx, _stream(), C.byref(desc), _ptr(windows), windows.numel(),
+                                                     _ptr(probs), _ptr(labels)))
+        if not blend:
+            return probs, labels
+        c_h, c_w, k = cell_grid(n_h, n_w, patch, stride)
+        cprobs = torch.empty((k_cls, c_h, c_w), dtype=torch.float32, device=eng.device)
+        clabels = torch.empty((c_h, c_w), dtype=torch.int64, device=eng.device)
+        check(eng.lib.eae_scene_blend_valid(_stream(), _ptr(probs), _ptr(labels), k_cls, n_h, n_w, k, _ptr(cprobs), _ptr(clabels)))
     return cprobs, clabels

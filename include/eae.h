@@ -414,6 +414,36 @@ int eae_scene_classify(eae_ctx* ctx, eae_mlp* mlp, void* stream, const eae_scene
  * the windows that cover it; cell_labels [nH + k - 1][nW + k - 1] = argmax of the blended map (int64). */
 int eae_scene_blend(void* stream, const float* probs, int K, int nH, int nW, int k, float* cell_probs, long long* cell_labels);
 
+/* Nodata and masked windows.  Pixel (y, x) is invalid when it matches the nodata value (rule EAE_INVALID_ALL: every band equals it,
+ * rasterio's dataset-mask convention; EAE_INVALID_ANY: at least one band does) or when mask[y * W + x] != 0 (mask: uint8 [H][W] on the
+ * device, or NULL).  nodata_mode EAE_NODATA_NONE ignores nodata; EAE_NODATA_VALUE compares with nodata (for uint8 / uint16 scenes an
+ * integer in the dtype's range, else rejected; for fp32 by ==); EAE_NODATA_NAN matches NaN (fp32 scenes only).
+ * counts [nH][nW] (int32) = invalid pixels of each window.  rows is scratch of Hg * nW ints, Hg = (nH - 1) * S + P.  Every scene
+ * element and mask byte inside the grid's extent is read once; the divisor is not read.  The patch size must be at most 4080. */
+#define EAE_NODATA_NONE 0
+#define EAE_NODATA_VALUE 1
+#define EAE_NODATA_NAN 2
+#define EAE_INVALID_ALL 0
+#define EAE_INVALID_ANY 1
+int eae_scene_invalid_counts(void* stream, const eae_scene* scene, int nodata_mode, float nodata, int rule,
+                             const unsigned char* mask, int* rows, int* counts);
+/* Stable compaction: windows[0 .. *count) = the ascending ids n of counts [n_windows] with counts[n] <= threshold; *count (int64) is
+ * written on the device.  windows must hold n_windows ids.  One workgroup, deterministic; no host synchronisation. */
+int eae_scene_select(void* stream, const int* counts, long long n_windows, int threshold, long long* windows, long long* count);
+/* Index-driven forms of eae_scene_encode / eae_scene_classify: the windows are the ids windows[0 .. count) (device int64, any order,
+ * duplicates allowed), count > 0 passed from the host.  encode: z [count][L] in list order.  classify: probs and labels receive the
+ * listed windows' columns; every other column is left as the caller filled it.  The ids are not checked on the host (no
+ * synchronisation): the kernels read an id outside [0, nH * nW) as an all-zero window and write nothing for it, a guard only; callers
+ * must pass ids inside the grid. */
+int eae_scene_encode_windows(eae_ctx* ctx, void* stream, const eae_scene* scene, const long long* windows, long long count, float* z);
+int eae_scene_classify_windows(eae_ctx* ctx, eae_mlp* mlp, void* stream, const eae_scene* scene, const long long* windows,
+                               long long count, float* probs, long long* labels);
+/* eae_scene_blend over the valid windows only (labels [nH][nW] >= 0, as the index-driven classify leaves behind when labels are
+ * pre-filled with -1): each cell is the mean over its valid covering windows (same summation order, divisor = their float count);
+ * a cell without a valid covering window gets probabilities 0 and label -1.  With every window valid it is bitwise eae_scene_blend. */
+int eae_scene_blend_valid(void* stream, const float* probs, const long long* labels, int K, int nH, int nW, int k, float* cell_probs,
+                          long long* cell_labels);
+
 #ifdef __cplusplus
 }
 #endif
