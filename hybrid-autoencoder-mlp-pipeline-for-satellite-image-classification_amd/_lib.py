@@ -131,6 +131,10 @@ _PROTOS = {
     "eae_scene_encode_windows": (C.c_int, [vp, vp, C.POINTER(EaeScene), vp, C.c_longlong, vp]),
     "eae_scene_classify_windows": (C.c_int, [vp, vp, vp, C.POINTER(EaeScene), vp, C.c_longlong, vp, vp]),
     "eae_scene_blend_valid": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "eae_set_halves": (C.c_int, [vp, C.c_int, C.c_int]),
+    "eae_scene_recon_error": (C.c_int, [vp, vp, C.POINTER(EaeScene), C.c_longlong, C.c_longlong, vp, vp]),
+    "eae_scene_recon_error_windows": (C.c_int, [vp, vp, C.POINTER(EaeScene), vp, C.c_longlong, vp, vp]),
+    "eae_scene_reconstruct": (C.c_int, [vp, vp, C.POINTER(EaeScene), vp, C.c_longlong, vp, vp]),
 }
 
 EXPORTS = tuple(_PROTOS.keys())

@@ -97,6 +97,7 @@ struct eae_ctx {
   bool packed = false;
   bool fwd_ready = false;          // a train-mode forward with gradient staging is resident in the workspace
   bool fwd_eval_ready = false;     // ... or an eval-mode one (BatchNorm with running statistics): eae_ae_backward differentiates that too
+  bool has_enc = true, has_dec = true;   // halves of the model the bound arenas really hold (eae_set_halves; a stand-alone Encoder's engine has no decoder)
   int enc_ready = 0, dec_ready = 0; // stand-alone eae_encoder_forward / eae_decoder_forward resident: 0 no, 1 train mode, 2 eval mode
   bool bwd_eval = false;           // the running backward differentiates an eval-mode forward: BatchNorm is a per-channel affine map
   bool prebn_dirty = false;        // an eval-mode backward wrote the gradients of the biases in front of the BatchNorms (train mode: zero)
@@ -1032,8 +1033,8 @@ int run_encoder(eae_ctx* c, hipStream_t st, const float* x, int B, bool train, c
 
 // ---- decoder: z (fp32 [B][L]) -> d0, u[0..2] -> deconv4 + sigmoid (+ MSE and its gradient)
 
-int run_decoder(eae_ctx* c, hipStream_t st, const float* z, int B, bool train, const float* target, float gscale, float* x_hat,
-                bool want_grad, bool want_loss) {
+// z -> d0 -> u[0..2]: everything in front of deconv4; fills deconv4's arguments except its epilogue outputs
+int run_decoder_trunk(eae_ctx* c, hipStream_t st, const float* z, int B, bool train, Deconv4Args& d) {
   const int H = c->H, W = c->W;
 
   {
@@ -1064,12 +1065,20 @@ int run_decoder(eae_ctx* c, hipStream_t st, const float* z, int B, bool train, c
     RC(sync_fwd(c, st, 4 + i, train));
     RC(bn_fwd_finalize(c, st, 4 + i, eae_conv_s2_ntiles(1, B, a.Hin, a.Win, cin[i]), (long long)B * (a.Hin * 2) * (a.Win * 2), train));
   }
-  Deconv4Args d = Deconv4Args();
+  d = Deconv4Args();
   d.src = src_bnrelu(c->u[2], c->coef_f[6]);
   d.wjoint = (const bf16_t*)(c->pack + c->pk_d4j); d.bias = c->P + c->poff[33];
-  d.x = target; d.x_hat = x_hat; d.g4 = want_grad ? c->g4 : nullptr; d.loss_part = (want_loss || want_grad) ? c->msepart : nullptr;
-  d.gscale = gscale; d.B = B; d.Hin = H / 2; d.Win = W / 2; d.C = c->Cin;
+  d.B = B; d.Hin = H / 2; d.Win = W / 2; d.C = c->Cin;
   fold_consumer(c, d.fold, 6, (long long)B * (H / 2) * (W / 2), train);
+  return 0;
+}
+
+int run_decoder(eae_ctx* c, hipStream_t st, const float* z, int B, bool train, const float* target, float gscale, float* x_hat,
+                bool want_grad, bool want_loss) {
+  Deconv4Args d;
+  RC(run_decoder_trunk(c, st, z, B, train, d));
+  d.x = target; d.x_hat = x_hat; d.g4 = want_grad ? c->g4 : nullptr; d.loss_part = (want_loss || want_grad) ? c->msepart : nullptr;
+  d.gscale = gscale;
   {
     ProfBracket pb(c, EAE_PROF_DECONV4_LOSS, st);
     RC(eae_launch_deconv4_loss(st, SRC_BNRELU, d));
@@ -1907,6 +1916,74 @@ extern "C" int eae_scene_classify_windows(eae_ctx* c, eae_mlp* m, void* stream, 
     RC(eae_mlp_predict(m, st, c->z, c->Lp, nb, b0, nH * nW, probs, labels, windows));
   }
   return 0;
+}
+
+// ---- scene reconstruction: encoder -> decoder over windows, deconv4's MSE target read from the scene itself
+namespace {
+int scene_recon_checks(eae_ctx* c) {
+  if (!c->has_enc || !c->has_dec)
+    return eae_set_error(EAE_ERR_STATE, "scene reconstruction needs both halves bound (the engine of a stand-alone Encoder has no decoder)");
+  return 0;
+}
+// windows first .. first + count - 1, or windows[0 .. count): per batch the encoder, the decoder up to deconv4, the scene-target deconv4
+// and the per-window finalize.  err may be NULL (reconstruct), recon may be NULL (error maps).
+int scene_recon_run(eae_ctx* c, hipStream_t st, const eae_scene* s, long long nH, long long nW, long long first, const long long* windows,
+                    long long count, float* err, float* band_err, float* recon, float* residual) {
+  Deconv4SceneArgs r;
+  r.part = c->msepart;         // [tiles][edge_lp_stride(C)] floats were carved: edge_bp_stride(C) <= edge_lp_stride(C)
+  r.recon = recon; r.residual = residual;
+  r.Wg = (int)eae_scene_extent(nW, s->patch, s->stride);
+  r.gplane = eae_scene_extent(nH, s->patch, s->stride) * r.Wg;
+  r.nH = (int)nH; r.m = (s->patch - s->stride) / 2;
+  RC(scene_begin(c, st));
+  for (long long b0 = 0; b0 < count; b0 += c->Bm) {
+    const int nb = (int)(count - b0 < c->Bm ? count - b0 : c->Bm);
+    SceneSrc src;
+    eae_scene_fill_src(s, nW, first + b0, &src);
+    src.index = windows; src.nwin = nH * nW;
+    RC(run_encoder(c, st, nullptr, nb, false, s, &src));
+    Deconv4Args d;
+    RC(run_decoder_trunk(c, st, c->z, nb, false, d));
+    RC(eae_launch_deconv4_scene(st, eae_scene_src3_kind(s), d, src, r));
+    if (err) RC(eae_launch_scene_err_finalize(st, c->msepart, nb, s->patch, s->C, first + b0, windows, nH * nW, err, band_err));
+  }
+  return 0;
+}
+}  // namespace
+
+extern "C" int eae_set_halves(eae_ctx* c, int encoder, int decoder) {
+  if (!c) return eae_set_error(EAE_ERR_ARG, "set_halves: NULL context");
+  c->has_enc = encoder != 0; c->has_dec = decoder != 0;
+  return 0;
+}
+
+extern "C" int eae_scene_recon_error(eae_ctx* c, void* stream, const eae_scene* s, long long first, long long count, float* err,
+                                     float* band_err) {
+  long long nH = 0, nW = 0;
+  RC(scene_ctx_checks(c, s, first, count, &nH, &nW));
+  RC(scene_recon_checks(c));
+  if (!err) return eae_set_error(EAE_ERR_ARG, "scene_recon_error: NULL err");
+  return scene_recon_run(c, (hipStream_t)stream, s, nH, nW, first, nullptr, count, err, band_err, nullptr, nullptr);
+}
+
+extern "C" int eae_scene_recon_error_windows(eae_ctx* c, void* stream, const eae_scene* s, const long long* windows, long long count,
+                                             float* err, float* band_err) {
+  long long nH = 0, nW = 0;
+  RC(scene_index_checks(c, s, windows, count, &nH, &nW));
+  RC(scene_recon_checks(c));
+  if (!err) return eae_set_error(EAE_ERR_ARG, "scene_recon_error_windows: NULL err");
+  return scene_recon_run(c, (hipStream_t)stream, s, nH, nW, 0, windows, count, err, band_err, nullptr, nullptr);
+}
+
+extern "C" int eae_scene_reconstruct(eae_ctx* c, void* stream, const eae_scene* s, const long long* windows, long long count, float* recon,
+                                     float* residual) {
+  long long nH = 0, nW = 0;
+  if (windows) RC(scene_index_checks(c, s, windows, count, &nH, &nW));
+  else RC(scene_ctx_checks(c, s, 0, count, &nH, &nW));
+  RC(scene_recon_checks(c));
+  if (!recon) return eae_set_error(EAE_ERR_ARG, "scene_reconstruct: NULL recon");
+  if ((s->patch - s->stride) % 2) return eae_set_error(EAE_ERR_ARG, "scene_reconstruct: patch - stride must be even (the owned spans are centred)");
+  return scene_recon_run(c, (hipStream_t)stream, s, nH, nW, 0, windows, count, nullptr, nullptr, recon, residual);
 }
 
 namespace {

@@ -733,3 +733,193 @@ template <int SRC, int CP>
 __global__ __launch_bounds__(256) void deconv4_loss_kernel(Deconv4Args a) { deconv4_loss_body<SRC, CP>(a); }
 template <int SRC, int CP>
 __global__ __launch_bounds__(256) void deconv4_loss_kernel_g(GroupPack<Deconv4Args> p, int gz) { deconv4_loss_body<SRC, CP>(group_args<Deconv4Args>(gz)); }
+
+// ---------------------------------------------------------------------------------------------------------------
+// deconv4 forward + sigmoid against the SCENE (eae_scene_recon_error / eae_scene_reconstruct; eval mode)
+//   image n of the launch is a window of the scene (SceneSrc, as conv1's scene source: first + n, or index[first + n]); the MSE target
+//   is the scene pixel itself, scene_val(v, divisor[c]) -- the expression conv1's patch load uses, so the target is bit-identical to
+//   what the encoder saw.  No [B,C,P,P] x_hat batch and no gradient are written:
+//   part[tile][c] = sum over the tile's 8 x 64 pixels of (x_hat - x)^2 of band c (zero in the padding columns of the row), and with
+//   STITCH x_hat (and optionally the band-mean squared residual of the pixel) goes to a stitched raster, for the pixels the window
+//   OWNS only: with m = (P - S) / 2 window row i owns scene rows [i*S + m, i*S + m + S), extended to 0 for i = 0 and to Hg for
+//   i = nH - 1; columns alike (scene.py owned_span).  Every pixel of the extent has exactly one owner: plain stores, no accumulation.
+//   Summation order of a partial: each thread chains its 2 pixels (fmaf), 6 xor-shuffle levels over the wave, then the four waves in
+//   ascending order; scene_err_finalize_kernel adds a window's tiles, then its bands, in ascending order.  No atomics anywhere.
+// ---------------------------------------------------------------------------------------------------------------
+__host__ __device__ constexpr int edge_bp_stride(int C) { return (C + 3) / 4 * 4; }      // floats of a partial row: C bands, whole float4s
+struct Deconv4SceneArgs {
+  float* part;             // [ntiles][edge_bp_stride(C)]
+  float* recon;            // STITCH: fp32 [C][Hg][Wg]
+  float* residual;         // STITCH: fp32 [Hg][Wg] or nullptr
+  long long gplane = 0;    // Hg * Wg
+  int Wg = 0, nH = 0, m = 0;   // width of the stitched raster, window rows of the grid, (P - S) / 2
+};
+
+// The MFMA part of deconv4_loss_body, line for line: stages the 5 x 33 input patch of this workgroup's tile (image n, input rows iy0..,
+// columns ix0..), multiplies the four phases jointly and leaves the pre-sigmoid tile sl[128][16*NT + 1] (without the bias) in LDS,
+// behind a barrier.  Returns sl.  (Kept beside deconv4_loss_body instead of shared with it: routing the training kernel through this
+// helper changed its instruction schedule, and that kernel's code is tuned and measured as it stands.)
+template <int SRC, int CP>
+__device__ __forceinline__ float* deconv4_presigmoid_tile(const Deconv4Args& a, int& n, int& iy0, int& ix0) {
+  constexpr int PH = E_TH + 1, PW = E_TW + 1, NPIX = PH * PW;       // 5 x 33 input pixels
+  constexpr int NPA = (NPIX * 4 + 255) / 256;
+  constexpr int NT = EdgeK<CP>::NT, SLW = 16 * NT + 1;              // pre-sigmoid tile [128][16*NT + 1] floats
+  constexpr int PATCH_B = (int)sizeof(bf16_t) * NPIX * PIX_STRIDE, SL_B = (int)sizeof(float) * 128 * SLW;
+  // the pre-sigmoid tile `sl` (8.7 KB for CP = 4) reuses the patch (13.2 KB) once every wave has read its fragments: 8 blocks per CU
+  __shared__ __attribute__((aligned(16))) bf16_t patch[(PATCH_B > SL_B ? PATCH_B : SL_B) / 2];
+  float* const sl = reinterpret_cast<float*>(patch);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tiles_x = a.Win / E_TW, tiles_y = a.Hin / E_TH;
+  int t = blockIdx.x;
+  const int txb = t % tiles_x; t /= tiles_x;
+  const int tyb = t % tiles_y; t /= tiles_y;
+  n = t;
+  iy0 = tyb * E_TH; ix0 = txb * E_TW;
+  const int kgs = tid & 3, kgl = lane >> 4;
+  ChanCoef<SRC> cc;
+  BnFoldRegs fr;
+  const bool folded = SRC == SRC_BNRELU && a.fold.acc != nullptr;
+  EDGE_STAMP(0);
+  if (folded) bn_fold_load<32>(a.fold, fr);       // before the patch loads: results return in issue order
+  RawPiece<SRC> raw[NPA];
+  bool val[NPA];
+#pragma unroll
+  for (int i = 0; i < NPA; ++i) {
+    int qq = tid + i * 256;
+    int pix = qq >> 2;
+    int pr = pix / PW, pc = pix % PW;
+    int iy = iy0 + pr, ix = ix0 + pc;
+    val[i] = (pix < NPIX) && (iy < a.Hin) && (ix < a.Win);
+    size_t off = (((size_t)n * a.Hin + iy) * a.Win + ix) * 32 + kgs * 8;
+    load_piece<SRC>(a.src, off, val[i], raw[i]);
+  }
+  {   // coefficient table of the 32-channel source layer (folded BatchNorm finalize) while the loads are in flight
+    __shared__ float coef_tab[4 * 32];
+    const float* coefp = a.src.coef;
+    if (folded) {
+      bn_fold_fwd_finish<32>(a.fold, fr, coef_tab, reinterpret_cast<long long*>(sl), blockIdx.x == 0);
+      coefp = coef_tab;
+    }
+    cc.load(coefp, 32, kgs * 8);
+  }
+  EDGE_STAMP(1);
+#pragma unroll
+  for (int i = 0; i < NPA; ++i) {
+    int qq = tid + i * 256;
+    if (qq < NPIX * 4)
+      *reinterpret_cast<uint4*>(patch + (qq >> 2) * PIX_STRIDE + kgs * 8) = transform_piece<SRC>(raw[i], val[i], cc);
+  }
+  EDGE_STAMP(2);
+  __syncthreads();
+  EDGE_STAMP(3);
+  f32x4 acc[NT][2];
+#pragma unroll
+  for (int j = 0; j < NT; ++j) acc[j][0] = acc[j][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int nb = 0; nb < 4; ++nb) {
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+      bf16x8 bfr = *reinterpret_cast<const bf16x8*>(a.wjoint + (j * 16 + (lane & 15)) * 128 + nb * 32 + kgl * 8);
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi) {
+        int pos = (wave * 2 + mi) * 16 + (lane & 15);
+        int ty = pos / E_TW, tx = pos % E_TW;
+        bf16x8 af = *reinterpret_cast<const bf16x8*>(patch + ((ty + (nb >> 1)) * PW + tx + (nb & 1)) * PIX_STRIDE + kgl * 8);
+        acc[j][mi] = mfma16(af, bfr, acc[j][mi]);
+      }
+    }
+  }
+  EDGE_STAMP(4);
+  __syncthreads();                 // every wave has read its patch fragments: the tiles below overwrite the patch
+#pragma unroll
+  for (int j = 0; j < NT; ++j)
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sl[((wave * 2 + mi) * 16 + (lane >> 4) * 4 + r) * SLW + j * 16 + (lane & 15)] = acc[j][mi][r];
+  __syncthreads();
+  EDGE_STAMP(5);
+  return sl;
+}
+
+template <int SRC3, int CP, bool IDX, bool STITCH>
+__device__ __forceinline__ void deconv4_scene_body(const Deconv4Args& a, const SceneSrc& sc, const Deconv4SceneArgs& r) {
+  using T = typename SceneElem<SRC3>::T;
+  constexpr int NT = EdgeK<CP>::NT, SLW = 16 * NT + 1, CMAX = EdgeK<CP>::CMAX;
+  __shared__ float redb[4][CMAX];
+  const int C = edge_bands<CP>(a.C), BPS = edge_bp_stride(C);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int n, iy0, ix0;
+  const float* const sl = deconv4_presigmoid_tile<SRC_BNRELU, CP>(a, n, iy0, ix0);
+  const int P = a.Win * 2;                          // square windows (scene_ctx_checks)
+  long long w = sc.first + n;
+  if constexpr (IDX) w = sc.index[w];               // one uniform load per workgroup
+  bool inside = true;
+  if constexpr (IDX) inside = w >= 0 && w < sc.nwin;   // an id outside the grid: target zero, nothing written for it
+  const long long wi = inside ? w / sc.nW : 0, wj = inside ? w - wi * sc.nW : 0;
+  const long long org = wi * sc.S * (long long)sc.Ws + wj * sc.S;
+  const T* const x = static_cast<const T*>(sc.data);
+  float bsum[CMAX], bb[CMAX], dv[CMAX];
+#pragma unroll
+  for (int co = 0; co < CMAX; ++co) {
+    bsum[co] = 0.f;
+    bb[co] = co < C ? a.bias[co] : 0.f;
+    dv[co] = co < C ? sc.div[co] : 1.f;
+  }
+  const int ox = tid & 63, lx = 2 * ix0 + ox;       // window-local column of this thread's pixels
+  float xt[2][CMAX];               // the target values of this thread, requested together ahead of the stores (as deconv4_loss_body)
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const T* p = x + org + (long long)(2 * iy0 + (tid >> 6) + 4 * i) * sc.Ws + lx;
+#pragma unroll
+    for (int co = 0; co < CMAX; ++co) xt[i][co] = (inside && co < C) ? scene_val(p[co * sc.plane], dv[co]) : 0.f;
+  }
+  // owned span of the window, window-local (STITCH)
+  int oy_lo = 0, oy_hi = 0, ox_lo = 0, ox_hi = 0;
+  if constexpr (STITCH) {
+    oy_lo = wi == 0 ? 0 : r.m; oy_hi = wi == r.nH - 1 ? P : r.m + sc.S;
+    ox_lo = wj == 0 ? 0 : r.m; ox_hi = wj == sc.nW - 1 ? P : r.m + sc.S;
+  }
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int oy = (tid >> 6) + 4 * i, ly = 2 * iy0 + oy;
+    const int pos = (oy >> 1) * E_TW + (ox >> 1), ph = (oy & 1) * 2 + (ox & 1);
+    const float* sp = sl + pos * SLW + ph * C;
+    bool own = false;
+    long long gp = 0;
+    if constexpr (STITCH) {
+      own = inside && ly >= oy_lo && ly < oy_hi && lx >= ox_lo && lx < ox_hi;
+      gp = (wi * sc.S + ly) * (long long)r.Wg + wj * sc.S + lx;
+    }
+    float rs = 0.f;
+#pragma unroll
+    for (int co = 0; co < CMAX; ++co) {
+      if (co < C) {
+        const float s = sp[co] + bb[co];
+        const float xh = 1.0f / (1.0f + __expf(-s));
+        const float d = xh - xt[i][co];
+        bsum[co] = fmaf(d, d, bsum[co]);
+        if constexpr (STITCH) {
+          rs = fmaf(d, d, rs);
+          if (own) r.recon[co * r.gplane + gp] = xh;
+        }
+      }
+    }
+    if constexpr (STITCH)
+      if (own && r.residual) r.residual[gp] = rs / (float)C;
+  }
+#pragma unroll
+  for (int k = 0; k < CMAX; ++k) {
+    if (k < C) {
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) bsum[k] += __shfl_xor(bsum[k], o);
+      if (lane == 0) redb[wave][k] = bsum[k];
+    }
+  }
+  __syncthreads();
+  if (tid < BPS) r.part[(size_t)blockIdx.x * BPS + tid] = tid < C ? ((redb[0][tid] + redb[1][tid]) + redb[2][tid]) + redb[3][tid] : 0.f;
+}
+template <int SRC3, int CP, bool IDX, bool STITCH>
+__global__ __launch_bounds__(256) void deconv4_scene_kernel(Deconv4Args a, SceneSrc s, Deconv4SceneArgs r) {
+  deconv4_scene_body<SRC3, CP, IDX, STITCH>(a, s, r);
+}

@@ -115,6 +115,65 @@ int eae_launch_deconv4_loss(hipStream_t st, int smode, const Deconv4Args& a) {
   return eae_set_error(-2, "deconv4: source mode not instantiated");
 }
 
+int eae_launch_deconv4_scene(hipStream_t st, int src3_kind, const Deconv4Args& a, const SceneSrc& s, const Deconv4SceneArgs& r) {
+  if (a.B <= 0 || a.Hin % E_TH || a.Win % E_TW) return eae_set_error(-2, "deconv4: input must be a multiple of 4 x 32");
+  if (a.Hin != a.Win) return eae_set_error(-2, "deconv4_scene: windows are square");
+  if (int rc = check_bands(a.C)) return rc;
+  if (!r.part) return eae_set_error(-2, "deconv4_scene: NULL partials");
+  dim3 grid(a.B * (a.Hin / E_TH) * (a.Win / E_TW));
+  const int cp = edge_cp(a.C);
+  EAE_NO_GROUP("deconv4_scene_kernel");
+#define CASE2(S, P, I, T) { hipLaunchKernelGGL((deconv4_scene_kernel<S, P, I, T>), grid, dim3(256), 0, st, a, s, r); EAE_LAUNCH_CHECK(); return 0; }
+#define CASE1(S, P) if (src3_kind == S && cp == P) { \
+    if (s.index) { if (r.recon) CASE2(S, P, true, true) else CASE2(S, P, true, false) } \
+    else { if (r.recon) CASE2(S, P, false, true) else CASE2(S, P, false, false) } }
+#define CASE(S) CASE1(S, 4) CASE1(S, 8) CASE1(S, 16)
+  CASE(SRC3_SCENE_U8)
+  CASE(SRC3_SCENE_U16)
+  CASE(SRC3_SCENE_F32)
+#undef CASE
+#undef CASE1
+#undef CASE2
+  return eae_set_error(-2, "deconv4_scene: source kind not instantiated");
+}
+
+// One (window, band) per thread, 16 lanes per window: the thread of band c adds the window's tiles in ascending order; the band sums
+// are then added in ascending order (every lane of the group walks them, lane 0 writes) and divided by C * P * P.  The result depends
+// on the window alone, never on the batch it ran in.
+__global__ EAE_NO_PK __launch_bounds__(256) void scene_err_finalize_kernel(const float* __restrict__ part, int B, int tiles, int C, int bps,
+                                                                       float npix, long long first, const long long* __restrict__ index,
+                                                                       long long nwin, float* __restrict__ err,
+                                                                       float* __restrict__ band_err) {
+  const int t = blockIdx.x * 256 + threadIdx.x, n = t >> 4, c = t & 15;
+  const bool live = n < B;
+  float s = 0.f;
+  if (live && c < C) {
+    const float* q = part + (size_t)n * tiles * bps + c;
+    for (int k = 0; k < tiles; ++k) s += q[(size_t)k * bps];
+  }
+  const int base = threadIdx.x & 48;          // first lane of this window's group inside the wave
+  float tot = 0.f;
+  for (int k = 0; k < C; ++k) tot += __shfl(s, base + k);
+  if (!live) return;
+  long long w = first + n;
+  if (index) w = index[w];
+  if (w < 0 || w >= nwin) return;
+  if (band_err && c < C) band_err[c * nwin + w] = s / npix;
+  if (c == 0) err[w] = tot / (npix * (float)C);
+}
+
+int eae_launch_scene_err_finalize(hipStream_t st, const float* part, int B, int P, int C, long long first, const long long* index,
+                                  long long nwin, float* err, float* band_err) {
+  if (int rc = check_bands(C)) return rc;
+  if (!part || !err || B <= 0) return eae_set_error(-2, "scene_err_finalize: NULL argument");
+  EAE_NO_GROUP("scene_err_finalize_kernel");
+  const int tiles = (P / 2 / E_TH) * (P / 2 / E_TW);
+  hipLaunchKernelGGL(scene_err_finalize_kernel, dim3((unsigned)((B * 16 + 255) / 256)), dim3(256), 0, st, part, B, tiles, C,
+                     edge_bp_stride(C), (float)P * (float)P, first, index, nwin, err, band_err);
+  EAE_LAUNCH_CHECK();
+  return 0;
+}
+
 // g4[n,oy,ox,c] = bf16(dx_hat * x_hat * (1 - x_hat))   (backward of nn.Sigmoid, R.md:383, for an externally supplied dL/dx_hat)
 // fp32 NCHW [B,C,H,W] in, bf16 NHWC-CP out; part[block][edge_lp_stride(C)] = {0, sum g(c) for c < C, zero padding} (bias gradient of
 // deconv4)

@@ -54,6 +54,14 @@ int eae_launch_edge_wgrad(hipStream_t st, int src3_kind, const void* src3, int B
                           const struct BnBwdFold* bfold = nullptr, unsigned* sig = nullptr, unsigned sig_val = 0,
                           int (*mid)(void*, GateArgs*) = nullptr, void* mid_user = nullptr, int C = 3);
 int eae_launch_deconv4_loss(hipStream_t st, int smode, const Deconv4Args& a);
+// deconv4 + sigmoid against windows of a scene (eval mode, BNRELU source): per-tile per-band squared-error partials into r.part, and
+// with r.recon set the owned pixels of the stitched x_hat (and residual) raster; windows s.first + n, or s.index[s.first + n]
+struct Deconv4SceneArgs;
+int eae_launch_deconv4_scene(hipStream_t st, int src3_kind, const Deconv4Args& a, const SceneSrc& s, const Deconv4SceneArgs& r);
+// err[w] = mean over the C * P * P elements of window w of the launch (w = first + n, or index[first + n]; n < B), band_err[c][w] (or
+// nullptr) the mean over band c; part as eae_launch_deconv4_scene left it.  An id outside [0, nwin) is skipped.
+int eae_launch_scene_err_finalize(hipStream_t st, const float* part, int B, int P, int C, long long first, const long long* index,
+                                  long long nwin, float* err, float* band_err);
 int eae_launch_wgrad_s2(hipStream_t st, const WgradArgs& a, int cs, int cb, int smode, int bmode, float* scratch,
                         long long scratch_floats, float* dw, const EaeProfHook* hook = nullptr);
 int eae_launch_fc_nt(hipStream_t st, const FcNtArgs& a, int amode, int epi, int ksplit);

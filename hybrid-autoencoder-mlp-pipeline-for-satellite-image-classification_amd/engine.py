@@ -117,6 +117,7 @@ class AEEngine:
             self.ctx = h
             check(self.lib.eae_bind(self.ctx, _ptr(self.params), _ptr(self.grads), _ptr(self.adam_m), _ptr(self.adam_v),
                                     _ptr(self.bn_running), _ptr(self.bn_nbt)))
+            check(self.lib.eae_set_halves(self.ctx, int(enc is not None), int(dec is not None)))
         self._finalizer = weakref.finalize(self, _destroy, self.lib, self.ctx, self.device)
         # one hook per module, reaching whichever engine currently serves it (a rebuilt engine must not keep the old one alive)
         if not getattr(root, "_eae_hooked", False):

@@ -21,6 +21,16 @@ invalid pixels (t > 0) is encoded with those pixels as stored: nothing is filled
 - `classify_scene(nodata=, mask=)` encodes only the valid windows: the others get label -1 and probability 0 for every class, and the
   blend averages each cell over its valid covering windows only (a cell with none: label -1, probabilities 0);
 - ``windows=`` (`encode_scene`, `classify_scene`) runs the model over a device list of window ids instead of the whole grid.
+
+Reconstruction (the decoder half: what the model cannot explain -- anomaly and change screening, quality control of a trained
+encoder, choosing windows worth labelling).  The autoencoder runs encoder -> decoder over the windows and deconv4's epilogue reads its
+MSE target from the scene itself, by the expression conv1 read it with: no [B,C,P,P] batch of windows or of x_hat is written.
+- `scene_reconstruction_error` returns err [nH,nW], the mean of (x_hat - x)^2 over each window's C*P*P elements (``per_band=True``:
+  also band_err [C,nH,nW]); windows that are not run (invalid under nodata / mask, or absent from ``windows=``) hold NaN;
+- `reconstruct_scene` returns the stitched x_hat [C,Hg,Wg] over the grid's extent (`owned_span`: every pixel is written by the one
+  window that owns it, the centre S x S of each window extended to the extent's edges, so nothing is accumulated and the windows'
+  border artefacts are dropped), in the units of ``scene / divisor``; ``residual=True`` adds the per-pixel band mean of
+  (x_hat - x)^2 [Hg,Wg].  Pixels owned by a window that is not run hold NaN.
 """
 from __future__ import annotations
 
@@ -54,6 +64,23 @@ def window_origin(n, n_w, stride):
     """Top-left pixel (y, x) of window n of a grid with n_w windows per row."""
     i, j = divmod(int(n), int(n_w))
     return i * int(stride), j * int(stride)
+
+
+def owned_span(i, n, patch, stride):
+    """(lo, hi): the pixels [lo, hi) of one axis of the grid's extent [0, (n-1)*S + P) that window i of n OWNS in a stitched raster.
+    With m = (P - S) / 2 window i owns [i*S + m, i*S + m + S), extended to 0 for i = 0 and to the extent's end for i = n - 1: the
+    spans of the n windows partition the extent.  P - S must be even."""
+    i, n, patch, stride = int(i), int(n), int(patch), int(stride)
+    if patch <= 0 or not 1 <= stride <= patch:
+        raise RuntimeError(f"stride must be in 1..{patch} (the patch size), got {stride}")
+    if (patch - stride) % 2:
+        raise RuntimeError(f"a stitched raster needs an even patch - stride (centred owned spans), got {patch} - {stride}")
+    if n < 1 or not 0 <= i < n:
+        raise RuntimeError(f"window {i} is outside 0..{n - 1}")
+    m = (patch - stride) // 2
+    lo = 0 if i == 0 else i * stride + m
+    hi = (n - 1) * stride + patch if i == n - 1 else i * stride + m + stride
+    return lo, hi
 
 
 def cell_grid(n_h, n_w, patch, stride):
@@ -386,3 +413,83 @@ def _classify_subset(scene, encoder, mlp, divisor, stride, batch, blend, inv, t,
         clabels = torch.empty((c_h, c_w), dtype=torch.int64, device=eng.device)
         check(eng.lib.eae_scene_blend_valid(_stream(), _ptr(probs), _ptr(labels), k_cls, n_h, n_w, k, _ptr(cprobs), _ptr(clabels)))
     return cprobs, clabels
+
+
+# ---------------------------------------------------------------------------------------------------- reconstruction
+def _recon_args(scene, autoencoder, stride, nodata, mask, max_invalid, rule, windows, stitched):
+    """The checks of the reconstruction functions that need no device; returns (masked, t, inv, windows)."""
+    from .modules import SupervisedAutoencoder
+    if not isinstance(autoencoder, SupervisedAutoencoder):
+        raise RuntimeError(f"autoencoder must be a SupervisedAutoencoder (the decoder is needed), got {type(autoencoder).__name__}")
+    masked = nodata is not None or mask is not None
+    if windows is not None and masked:
+        raise RuntimeError("windows= cannot be combined with nodata= or mask=")
+    if rule not in _RULES:
+        raise RuntimeError(f"rule must be 'all' or 'any', got {rule!r}")
+    patch = int(autoencoder.enc.image_size)
+    t = invalid_threshold(patch, max_invalid)
+    if stitched:
+        owned_span(0, 1, patch, patch if stride is None else int(stride))      # patch - stride must be even
+    inv = None
+    if masked or windows is not None:
+        _, _, n_h, n_w = _grid_of(scene, autoencoder, stride)
+        inv = _invalid_args(scene, nodata, mask, rule)
+        if windows is not None:
+            windows = _windows_arg(windows, scene.device, n_h * n_w, allow_empty=True)
+    return masked, t, inv, windows
+
+
+def scene_reconstruction_error(scene, autoencoder, divisor=1.0, stride=None, batch=512, per_band=False, nodata=None, mask=None,
+                               max_invalid=0.0, rule="all", windows=None):
+    """err [nH,nW] float32: the mean of (x_hat - x)^2 over the C*P*P elements of every window, x = scene / divisor as the encoder
+    read it, x_hat = the eval-mode autoencoder's reconstruction of the window; one C call, no staged batch (module docstring).
+    per_band=True: (err, band_err [C,nH,nW]), the mean over each band.  The sums are deterministic and do not depend on ``batch``.
+
+    nodata / mask / max_invalid / rule: only the valid windows are run (`valid_windows`, one host readback); windows: a 1-D int64
+    device tensor of window ids, the only windows run (not combined with nodata / mask).  Either way the other windows hold NaN;
+    without a window to run nothing is launched.  A valid window that holds some invalid pixels is scored with them as stored."""
+    masked, t, inv, windows = _recon_args(scene, autoencoder, stride, nodata, mask, max_invalid, rule, windows, stitched=False)
+    eng, desc, keep, n_h, n_w, _, _ = _prepare(scene, autoencoder, divisor, stride, batch)
+    subset = masked or windows is not None
+    if masked:
+        mode, value, rid, m = inv
+        windows = _select(_invalid_counts(desc, keep + (m,), n_h, n_w, mode, value, rid, m), t)
+    make = (lambda shape: torch.full(shape, float("nan"), dtype=torch.float32, device=eng.device)) if subset else \
+        (lambda shape: torch.empty(shape, dtype=torch.float32, device=eng.device))
+    err = make((n_h, n_w))
+    band = make((desc.C, n_h, n_w)) if per_band else None
+    with torch.cuda.device(eng.device):
+        if not subset:
+            check(eng.lib.eae_scene_recon_error(eng.ctx, _stream(), C.byref(desc), 0, n_h * n_w, _ptr(err), _ptr(band)))
+        elif windows.numel():
+            check(eng.lib.eae_scene_recon_error_windows(eng.ctx, _stream(), C.byref(desc), _ptr(windows), windows.numel(), _ptr(err),
+                                                        _ptr(band)))
+    return (err, band) if per_band else err
+
+
+def reconstruct_scene(scene, autoencoder, divisor=1.0, stride=None, batch=512, residual=False, nodata=None, mask=None,
+                      max_invalid=0.0, rule="all", windows=None):
+    """recon [C,Hg,Wg] float32 over the grid's extent (Hg = (nH-1)*S + P): the eval-mode autoencoder's x_hat of every window, each
+    pixel taken from the one window that owns it (`owned_span`; patch - stride must be even), in the units of ``scene / divisor``.
+    residual=True: (recon, residual [Hg,Wg]), the mean over the bands of (x_hat - x)^2 of each pixel.
+
+    nodata / mask / max_invalid / rule / windows as for `scene_reconstruction_error`: pixels owned by a window that is not run hold
+    NaN (in both outputs)."""
+    masked, t, inv, windows = _recon_args(scene, autoencoder, stride, nodata, mask, max_invalid, rule, windows, stitched=True)
+    eng, desc, keep, n_h, n_w, patch, stride = _prepare(scene, autoencoder, divisor, stride, batch)
+    subset = masked or windows is not None
+    if masked:
+        mode, value, rid, m = inv
+        windows = _select(_invalid_counts(desc, keep + (m,), n_h, n_w, mode, value, rid, m), t)
+    h_g, w_g = (n_h - 1) * stride + patch, (n_w - 1) * stride + patch
+    make = (lambda shape: torch.full(shape, float("nan"), dtype=torch.float32, device=eng.device)) if subset else \
+        (lambda shape: torch.empty(shape, dtype=torch.float32, device=eng.device))
+    recon = make((desc.C, h_g, w_g))
+    res = make((h_g, w_g)) if residual else None
+    with torch.cuda.device(eng.device):
+        if not subset:
+            check(eng.lib.eae_scene_reconstruct(eng.ctx, _stream(), C.byref(desc), None, n_h * n_w, _ptr(recon), _ptr(res)))
+        elif windows.numel():
+            check(eng.lib.eae_scene_reconstruct(eng.ctx, _stream(), C.byref(desc), _ptr(windows), windows.numel(), _ptr(recon),
+                                                _ptr(res)))
+    return (recon, res) if residual else recon

@@ -444,6 +444,36 @@ int eae_scene_classify_windows(eae_ctx* ctx, eae_mlp* mlp, void* stream, const e
 int eae_scene_blend_valid(void* stream, const float* probs, const long long* labels, int K, int nH, int nW, int k, float* cell_probs,
                           long long* cell_labels);
 
+
+/* Scene reconstruction (eval mode, bf16 contexts, both halves bound): encoder -> decoder over windows of the scene, with deconv4's
+ * MSE target read from the scene itself by the expression conv1 reads it with, (float)v / divisor[c]: no [B,C,P,P] batch of windows,
+ * of x_hat or of gradients is written.  x_hat is bitwise eae_decoder_forward(train = 0) on the windows' latents.  All three split at
+ * max_batch inside, synchronise nothing on the host, apply the checks of eae_scene_encode / eae_scene_encode_windows and invalidate
+ * the resident forward.  The sums are deterministic (fixed order, no atomics) and do not depend on how windows are batched.
+ *
+ * eae_set_halves: which halves of the model the bound arenas hold (default: both).  The engine of a stand-alone Encoder or Decoder
+ * binds arenas whose other half is zero; the three calls below return EAE_ERR_STATE unless both halves are declared present.
+ *
+ * eae_scene_recon_error: err [nH * nW] receives, at the ids of windows first_window .. + count - 1, the mean of (x_hat - x)^2 over
+ * the window's C * P * P elements; band_err [C][nH * nW] (or NULL) the mean over each band's P * P.
+ * eae_scene_recon_error_windows: the same for the ids windows[0 .. count) (device int64, any order, duplicates allowed); every other
+ * entry of err / band_err is left as the caller filled it.  An id outside [0, nH * nW) is read as zeros and nothing is written for it
+ * (a guard only, as for eae_scene_encode_windows).
+ *
+ * eae_scene_reconstruct: the stitched reconstruction recon [C][Hg][Wg] (fp32, the units of v / divisor) of the grid's extent, Hg =
+ * (nH - 1) * S + P, Wg alike, and (residual != NULL) residual [Hg][Wg], the mean over the bands of (x_hat - x)^2 of each pixel.
+ * Every pixel of the extent is OWNED by exactly one window and is written by that window alone (plain stores, no accumulation): with
+ * m = (P - S) / 2, window row i owns scene rows [i * S + m, i * S + m + S), extended to 0 for i = 0 and to Hg for i = nH - 1; columns
+ * alike.  P - S must be even.  windows == NULL: windows 0 .. count - 1 (count = nH * nW: the whole extent); else the listed ids, and
+ * the pixels owned by other windows are left as the caller filled them. */
+int eae_set_halves(eae_ctx* ctx, int encoder, int decoder);
+int eae_scene_recon_error(eae_ctx* ctx, void* stream, const eae_scene* scene, long long first_window, long long count, float* err,
+                          float* band_err);
+int eae_scene_recon_error_windows(eae_ctx* ctx, void* stream, const eae_scene* scene, const long long* windows, long long count,
+                                  float* err, float* band_err);
+int eae_scene_reconstruct(eae_ctx* ctx, void* stream, const eae_scene* scene, const long long* windows, long long count, float* recon,
+                          float* residual);
+
 #ifdef __cplusplus
 }
 #endif
