@@ -22,7 +22,7 @@ struct MlpArgs {
   long long* nbt;          // [2]
   float *h1, *a1, *h2, *a2, *dlog, *g2, *g1;   // workspace
   int train, backward, adam;
-  float step_size, bc2_sqrt, b1, b2, eps, wd;
+  float step_size, bc2_sqrt, b1, b2, omb1, omb2, eps, wd;   // omb = 1 - beta, rounded from double as torch does
   unsigned long long seed, step;
   const float* drop_mask;
   const float* dlog_in;    // externally supplied dL/dlogits [B][C] (autograd path) or nullptr
@@ -218,9 +218,11 @@ __global__ EAE_NO_PK __launch_bounds__(T) void mlp_kernel(MlpArgs a) {
   red[tid] = loss; red[T + tid] = corr;
   __syncthreads();
   if (tid == 0 && a.stats) {
-    float s = 0.f, cr = 0.f;
+    double sd = 0.0;         // up to 1024 partial sums: a serial fp32 sum loses sqrt(lim) ulps of the mean loss
+    float cr = 0.f;
     const int lim = nb < T ? nb : T;
-    for (int i = 0; i < lim; ++i) { s += red[i]; cr += red[T + i]; }
+    for (int i = 0; i < lim; ++i) { sd += (double)red[i]; cr += red[T + i]; }
+    const float s = (float)sd;
     if (a.train) { a.stats[0] += s; a.stats[1] += (float)nb; a.stats[2] += cr; }   // sum_b CE_b = mean CE * B
     else { atomicAdd(&a.stats[0], s); atomicAdd(&a.stats[1], (float)nb); atomicAdd(&a.stats[2], cr); }
   }
@@ -289,8 +291,8 @@ __global__ EAE_NO_PK __launch_bounds__(T) void mlp_kernel(MlpArgs a) {
   // ---- Adam with coupled L2 weight decay (torch.optim.Adam(lr, weight_decay=1e-4), R.md:2625)
   for (long i = tid; i < a.off[10]; i += T) {
     float p = a.P[i], g = G[i] + a.wd * p, m = a.M[i], v = a.V[i];
-    m = m + (1.f - a.b1) * (g - m);
-    v = a.b2 * v + (1.f - a.b2) * g * g;
+    m = m + a.omb1 * (g - m);
+    v = a.b2 * v + a.omb2 * g * g;
     a.P[i] = p - a.step_size * (m / (sqrtf(v) / a.bc2_sqrt + a.eps));
     a.M[i] = m; a.V[i] = v;
   }
@@ -366,7 +368,7 @@ static int mlp_launch(eae_mlp* m, hipStream_t st, const float* x, const long lon
   a.bnrun = m->bnrun; a.nbt = train ? m->nbt : nullptr;
   a.h1 = m->h1; a.a1 = m->a1; a.h2 = m->h2; a.a2 = m->a2; a.dlog = m->dlog; a.g2 = m->g2; a.g1 = m->g1;
   a.train = train; a.backward = backward; a.adam = adam;
-  a.b1 = 0.9f; a.b2 = 0.999f; a.eps = 1e-8f; a.wd = wd; a.step_size = 0.f; a.bc2_sqrt = 1.f;
+  a.b1 = 0.9f; a.b2 = 0.999f; a.omb1 = (float)(1.0 - 0.9); a.omb2 = (float)(1.0 - 0.999); a.eps = 1e-8f; a.wd = wd; a.step_size = 0.f; a.bc2_sqrt = 1.f;
   if (adam) {
     m->adam_step += 1;
     double bc1 = 1.0 - std::pow(0.9, (double)m->adam_step), bc2 = 1.0 - std::pow(0.999, (double)m->adam_step);
@@ -425,7 +427,7 @@ int eae_mlp_predict(eae_mlp* m, hipStream_t st, const float* x, int ldx, int B, 
     a.bnrun = m->bnrun; a.nbt = nullptr;
     a.h1 = m->h1; a.a1 = m->a1; a.h2 = m->h2; a.a2 = m->a2; a.dlog = m->dlog; a.g2 = m->g2; a.g1 = m->g1;
     a.train = 0; a.backward = 0; a.adam = 0;
-    a.b1 = 0.9f; a.b2 = 0.999f; a.eps = 1e-8f; a.wd = 0.f; a.step_size = 0.f; a.bc2_sqrt = 1.f;
+    a.b1 = 0.9f; a.b2 = 0.999f; a.omb1 = 0.1f; a.omb2 = 0.001f; a.eps = 1e-8f; a.wd = 0.f; a.step_size = 0.f; a.bc2_sqrt = 1.f;
     a.seed = 0; a.step = 0; a.drop_mask = nullptr; a.p_drop = 0.3f;
     a.logits = nullptr; a.stats = nullptr; a.dlog_in = nullptr; a.update_running = 0;
     a.ldx = ldx; a.probs = probs; a.plabels = labels; a.win0 = win0 + b0; a.plane = plane; a.index = index;

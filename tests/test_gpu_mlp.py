@@ -94,6 +94,28 @@ def test_mlp_dropout_philox_rate():
         b = eng.forward(_cuda(x), train=True)
     assert torch.equal(a, b)              # same (seed, step) -> same mask: counter-based RNG
     assert torch.isfinite(a).all()
+    # the rate: the logits are those of the float64 reference under the Philox keep mask of (seed, step) with threshold
+    # u >= 0.3 and scale 1/0.7, within 8 x the fp32 oracle's own deviation; that mask keeps 0.7 of the units within 4 sigma;
+    # and a mask of any other rate (threshold 0.31: 1 % of the bits) is far outside the same bound
+    import mlp_ref as R
+    from oracle import ae_numpy as O
+    p0 = mlp_state_np(perturb=False)
+    step = 0                              # forward keys on the current optimisation step of a fresh engine
+    u = R.philox_uniform(eng.seed, step, 64 * 128).reshape(64, 128)
+    mask = R.philox_keep_mask(eng.seed, step, 64)
+    assert abs(float(mask.mean()) - 0.7) <= 4 * np.sqrt(0.21 / (128 * 64))
+    ref = R.forward(p0, x, True, drop_mask=mask)["logits"]
+    bound = R.bound(R.deviation(O.mlp_forward(p0, x, train=True, drop_mask=mask)["logits"], ref), float(np.abs(ref).max()))
+    assert R.deviation(a.cpu().numpy(), ref) <= bound
+    for other in ((u >= np.float32(0.31)).astype(np.float32), (u > np.float32(0.3 + 1e-3)).astype(np.float32),
+                  R.philox_keep_mask(eng.seed, step + 1, 64)):
+        assert not np.array_equal(other, mask)
+        assert R.deviation(R.forward(p0, x, True, drop_mask=other)["logits"], ref) > 100 * bound
+    # the kept units carry 1/0.7.  The BatchNorm behind the second Linear removes most of a common scale, so a missing scale
+    # shows in the logits only through net.4.bias and eps: still 12 x the bound here (the gradients of
+    # test_gpu_mlp_shapes.py::test_kernel_dropout_train_step see it in full)
+    unscaled = R.forward(p0, x, True, drop_mask=mask * np.float32(0.7))["logits"]
+    assert R.deviation(unscaled, ref) > 10 * bound
 
 
 def test_extract_features_and_module_forward(golden):
