@@ -23,50 +23,31 @@ __global__ EAE_NO_PK __launch_bounds__(256) void scene_windows_kernel(const T* _
   for (int c = 0; c < C; ++c) out[(b * C + c) * pp + r] = scene_val(q[c * plane], divisor[c]);
 }
 
-// cell (ci, cj) of the [nH + k - 1][nW + k - 1] map: mean over windows i in [ci - k + 1, ci] x j in [cj - k + 1, cj] inside the grid
+// cell (ci, cj) of the [nH + k - 1][nW + k - 1] map: mean over windows i in [ci - k + 1, ci] x j in [cj - k + 1, cj] inside the grid.
+// VALID: over the valid ones of them only (labels >= 0): the same (i, then j) summation order, divided by the float count of valid
+// covering windows; a cell without one gets probabilities 0 and label -1.  (labels is the last argument, read by VALID only: the plain
+// form keeps the argument block it had as a kernel of its own.)
+template <bool VALID>
 __global__ EAE_NO_PK __launch_bounds__(256) void scene_blend_kernel(const float* __restrict__ probs, int K, int nH, int nW, int k,
-                                                                float* __restrict__ cell, long long* __restrict__ cell_labels) {
+                                                                float* __restrict__ cell, long long* __restrict__ cell_labels,
+                                                                const long long* __restrict__ labels) {
   const int cH = nH + k - 1, cW = nW + k - 1;
   const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
   if (p >= (long long)cH * cW) return;
   const int ci = (int)(p / cW), cj = (int)(p - (long long)ci * cW);
   const int i0 = ci - k + 1 > 0 ? ci - k + 1 : 0, i1 = ci < nH - 1 ? ci : nH - 1;
   const int j0 = cj - k + 1 > 0 ? cj - k + 1 : 0, j1 = cj < nW - 1 ? cj : nW - 1;
-  const float cnt = (float)((i1 - i0 + 1) * (j1 - j0 + 1));
   const long long wplane = (long long)nH * nW, cplane = (long long)cH * cW;
-  float mx = 0.f;
-  int am = 0;
-  for (int c = 0; c < K; ++c) {
-    const float* q = probs + c * wplane;
-    float s = 0.f;
+  int nv = (i1 - i0 + 1) * (j1 - j0 + 1);
+  if constexpr (VALID) {
+    nv = 0;
     for (int i = i0; i <= i1; ++i)
-      for (int j = j0; j <= j1; ++j) s += q[(long long)i * nW + j];
-    const float v = s / cnt;
-    cell[c * cplane + p] = v;
-    if (c == 0 || v > mx) { mx = v; am = c; }
-  }
-  cell_labels[p] = am;
-}
-
-// cell (ci, cj) as above, over the valid windows only (labels >= 0): the same (i, then j) summation order, divided by the float count
-// of valid covering windows; a cell without one gets probabilities 0 and label -1
-__global__ EAE_NO_PK __launch_bounds__(256) void scene_blend_valid_kernel(const float* __restrict__ probs, const long long* __restrict__ labels,
-                                                                      int K, int nH, int nW, int k, float* __restrict__ cell,
-                                                                      long long* __restrict__ cell_labels) {
-  const int cH = nH + k - 1, cW = nW + k - 1;
-  const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (p >= (long long)cH * cW) return;
-  const int ci = (int)(p / cW), cj = (int)(p - (long long)ci * cW);
-  const int i0 = ci - k + 1 > 0 ? ci - k + 1 : 0, i1 = ci < nH - 1 ? ci : nH - 1;
-  const int j0 = cj - k + 1 > 0 ? cj - k + 1 : 0, j1 = cj < nW - 1 ? cj : nW - 1;
-  const long long wplane = (long long)nH * nW, cplane = (long long)cH * cW;
-  int nv = 0;
-  for (int i = i0; i <= i1; ++i)
-    for (int j = j0; j <= j1; ++j) nv += labels[(long long)i * nW + j] >= 0;
-  if (nv == 0) {
-    for (int c = 0; c < K; ++c) cell[c * cplane + p] = 0.f;
-    cell_labels[p] = -1;
-    return;
+      for (int j = j0; j <= j1; ++j) nv += labels[(long long)i * nW + j] >= 0;
+    if (nv == 0) {
+      for (int c = 0; c < K; ++c) cell[c * cplane + p] = 0.f;
+      cell_labels[p] = -1;
+      return;
+    }
   }
   const float cnt = (float)nv;
   float mx = 0.f;
@@ -75,8 +56,12 @@ __global__ EAE_NO_PK __launch_bounds__(256) void scene_blend_valid_kernel(const 
     const float* q = probs + c * wplane;
     float s = 0.f;
     for (int i = i0; i <= i1; ++i)
-      for (int j = j0; j <= j1; ++j)
-        if (labels[(long long)i * nW + j] >= 0) s += q[(long long)i * nW + j];
+      for (int j = j0; j <= j1; ++j) {
+        if constexpr (VALID) {
+          if (labels[(long long)i * nW + j] < 0) continue;
+        }
+        s += q[(long long)i * nW + j];
+      }
     const float v = s / cnt;
     cell[c * cplane + p] = v;
     if (c == 0 || v > mx) { mx = v; am = c; }
@@ -282,6 +267,13 @@ void eae_scene_fill_src(const eae_scene* s, long long nW, long long first, Scene
   out->Ws = s->W; out->S = s->stride; out->nW = (int)nW;
 }
 
+// the one u8 / u16 / f32 dispatch: f(tag) with tag a null pointer of the scene's element type
+template <typename F> void scene_dtype_dispatch(const eae_scene* s, F f) {
+  if (s->dtype == EAE_SCENE_U8) f((const uint8_t*)nullptr);
+  else if (s->dtype == EAE_SCENE_U16) f((const uint16_t*)nullptr);
+  else f((const float*)nullptr);
+}
+
 extern "C" int eae_scene_windows(void* stream, const eae_scene* s, long long first, int B, float* out) {
   long long nH = 0, nW = 0;
   if (int rc = eae_scene_check(s, &nH, &nW)) return rc;
@@ -291,40 +283,34 @@ extern "C" int eae_scene_windows(void* stream, const eae_scene* s, long long fir
   const hipStream_t st = (hipStream_t)stream;
   const long long plane = (long long)s->H * s->W, tot = (long long)B * s->patch * s->patch;
   const dim3 grid((unsigned)((tot + 255) / 256));
-  if (s->dtype == EAE_SCENE_U8)
-    hipLaunchKernelGGL(scene_windows_kernel<uint8_t>, grid, dim3(256), 0, st, (const uint8_t*)s->data, s->divisor, s->C, plane, s->W,
-                       s->patch, s->stride, (int)nW, first, B, out);
-  else if (s->dtype == EAE_SCENE_U16)
-    hipLaunchKernelGGL(scene_windows_kernel<uint16_t>, grid, dim3(256), 0, st, (const uint16_t*)s->data, s->divisor, s->C, plane, s->W,
-                       s->patch, s->stride, (int)nW, first, B, out);
-  else
-    hipLaunchKernelGGL(scene_windows_kernel<float>, grid, dim3(256), 0, st, (const float*)s->data, s->divisor, s->C, plane, s->W,
-                       s->patch, s->stride, (int)nW, first, B, out);
+  scene_dtype_dispatch(s, [&](auto* t) {
+    using T = std::remove_cv_t<std::remove_pointer_t<decltype(t)>>;
+    hipLaunchKernelGGL(scene_windows_kernel<T>, grid, dim3(256), 0, st, (const T*)s->data, s->divisor, s->C, plane, s->W, s->patch,
+                       s->stride, (int)nW, first, B, out);
+  });
   EAE_LAUNCH_CHECK();
   return 0;
 }
 
-extern "C" int eae_scene_blend(void* stream, const float* probs, int K, int nH, int nW, int k, float* cell, long long* cell_labels) {
-  if (!probs || !cell || !cell_labels) return eae_set_error(EAE_ERR_ARG, "scene_blend: NULL argument");
+// both blends: the plain one passes labels = NULL, which its kernel never reads
+template <bool VALID>
+static int scene_blend(void* stream, const float* probs, const long long* labels, int K, int nH, int nW, int k, float* cell,
+                       long long* cell_labels) {
+  if (!probs || (VALID && !labels) || !cell || !cell_labels) return eae_set_error(EAE_ERR_ARG, "scene_blend: NULL argument");
   if (K < 1 || nH < 1 || nW < 1 || k < 1) return eae_set_error(EAE_ERR_ARG, "scene_blend: bad shape");
   EAE_NO_GROUP("scene_blend_kernel");
   const long long tot = (long long)(nH + k - 1) * (nW + k - 1);
-  hipLaunchKernelGGL(scene_blend_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, probs, K, nH, nW, k,
-                     cell, cell_labels);
+  hipLaunchKernelGGL(scene_blend_kernel<VALID>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, probs, K, nH, nW, k, cell, cell_labels, labels);
   EAE_LAUNCH_CHECK();
   return 0;
 }
-
+extern "C" int eae_scene_blend(void* stream, const float* probs, int K, int nH, int nW, int k, float* cell, long long* cell_labels) {
+  return scene_blend<false>(stream, probs, nullptr, K, nH, nW, k, cell, cell_labels);
+}
 extern "C" int eae_scene_blend_valid(void* stream, const float* probs, const long long* labels, int K, int nH, int nW, int k, float* cell,
                                      long long* cell_labels) {
-  if (!probs || !labels || !cell || !cell_labels) return eae_set_error(EAE_ERR_ARG, "scene_blend_valid: NULL argument");
-  if (K < 1 || nH < 1 || nW < 1 || k < 1) return eae_set_error(EAE_ERR_ARG, "scene_blend_valid: bad shape");
-  EAE_NO_GROUP("scene_blend_valid_kernel");
-  const long long tot = (long long)(nH + k - 1) * (nW + k - 1);
-  hipLaunchKernelGGL(scene_blend_valid_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, probs, labels, K,
-                     nH, nW, k, cell, cell_labels);
-  EAE_LAUNCH_CHECK();
-  return 0;
+  return scene_blend<true>(stream, probs, labels, K, nH, nW, k, cell, cell_labels);
 }
 
 extern "C" int eae_scene_invalid_counts(void* stream, const eae_scene* s, int nodata_mode, float nodata, int rule,
@@ -351,12 +337,11 @@ extern "C" int eae_scene_invalid_counts(void* stream, const eae_scene* s, int no
   const long long nblk = Hg * nchunk;
   if (nblk * INV_NT > 0xffffffffLL) return eae_set_error(EAE_ERR_ARG, "scene_invalid_counts: scene too large");
   const int rany = rule == EAE_INVALID_ANY;
-#define ROWS(T) hipLaunchKernelGGL(scene_invalid_rows_kernel<T>, dim3((unsigned)nblk), dim3(INV_NT), 0, st, (const T*)s->data, plane, s->C, \
-                                   s->W, s->patch, s->stride, (int)nW, J, nchunk, nodata_mode, nodata, rany, mask, rows)
-  if (s->dtype == EAE_SCENE_U8) ROWS(uint8_t);
-  else if (s->dtype == EAE_SCENE_U16) ROWS(uint16_t);
-  else ROWS(float);
-#undef ROWS
+  scene_dtype_dispatch(s, [&](auto* t) {
+    using T = std::remove_cv_t<std::remove_pointer_t<decltype(t)>>;
+    hipLaunchKernelGGL(scene_invalid_rows_kernel<T>, dim3((unsigned)nblk), dim3(INV_NT), 0, st, (const T*)s->data, plane, s->C, s->W,
+                       s->patch, s->stride, (int)nW, J, nchunk, nodata_mode, nodata, rany, mask, rows);
+  });
   EAE_LAUNCH_CHECK();
   const long long nwin = nH * nW;
   hipLaunchKernelGGL(scene_invalid_windows_kernel, dim3((unsigned)((nwin + 255) / 256)), dim3(256), 0, st, rows, (int)nH, (int)nW,

@@ -37,6 +37,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import numbers
+from typing import NamedTuple
 
 import torch
 
@@ -174,16 +175,26 @@ def _mask_arg(scene, mask):
     return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
 
 
-def _invalid_args(scene, nodata, mask, rule):
-    """Validate nodata / mask / rule against the scene: (mode, value, rule id, uint8 mask or None)."""
+def _rule_arg(rule):
     if rule not in _RULES:
         raise RuntimeError(f"rule must be 'all' or 'any', got {rule!r}")
+    return _RULES[rule]
+
+
+def _check_scene(scene):
+    """The one check of the scene tensor's rank and dtype."""
     if not isinstance(scene, torch.Tensor) or scene.dim() != 3:
         raise RuntimeError("scene must be a planar tensor [C,H,W]")
     if scene.dtype not in _DTYPES:
         raise RuntimeError(f"scene dtype must be uint8, uint16 or float32, got {scene.dtype}")
+
+
+def _invalid_args(scene, nodata, mask, rule):
+    """Validate nodata / mask / rule against the scene: (mode, value, rule id, uint8 mask or None)."""
+    rid = _rule_arg(rule)
+    _check_scene(scene)
     mode, value = _nodata_arg(scene.dtype, nodata)
-    return mode, value, _RULES[rule], _mask_arg(scene, mask)
+    return mode, value, rid, _mask_arg(scene, mask)
 
 
 def _windows_arg(windows, device, n_windows, allow_empty):
@@ -212,11 +223,8 @@ def _encoder_of(encoder):
 
 
 def _scene_desc(scene, divisor, patch, stride):
-    """Validate the scene (before any device work) and return (EaeScene, keep-alive tensors, nH, nW)."""
-    if not isinstance(scene, torch.Tensor) or scene.dim() != 3:
-        raise RuntimeError("scene must be a planar tensor [C,H,W]")
-    if scene.dtype not in _DTYPES:
-        raise RuntimeError(f"scene dtype must be uint8, uint16 or float32, got {scene.dtype}")
+    """(EaeScene, keep-alive tensors, nH, nW) of a scene that has passed `_check_scene`: device, band count, grid and divisor are
+    validated here, before any kernel."""
     _require_gpu(scene.device)
     c, h, w = (int(v) for v in scene.shape)
     if not 1 <= c <= 16:
@@ -265,6 +273,7 @@ def _range(first, count, total):
 # ---------------------------------------------------------------------------------------------------- public functions
 def scene_windows(scene, divisor, patch, stride, first=0, count=None):
     """fp32 NCHW [count,C,P,P] of windows first .. first+count-1 (count=None: to the end of the grid)."""
+    _check_scene(scene)
     desc, keep, n_h, n_w = _scene_desc(scene, divisor, patch, stride)
     first, count = _range(first, count, n_h * n_w)
     lib = _lib.load()
@@ -291,11 +300,8 @@ def valid_windows(scene, patch, stride, nodata=None, mask=None, max_invalid=0.0,
     return _select(counts, t)
 
 
-def _prepare(scene, encoder, divisor, stride, batch):
-    enc = _encoder_of(encoder)
-    patch = int(enc.image_size)
-    stride = patch if stride is None else int(stride)
-    desc, keep, n_h, n_w = _scene_desc(scene, divisor, patch, stride)
+def _prepare(enc, desc, keep, batch):
+    """The engine of the encoder for this scene: band count, device, bf16 only, parameters re-read."""
     if desc.C != int(enc.in_channels):
         raise RuntimeError(f"scene has {desc.C} bands, the encoder takes in_channels={enc.in_channels}")
     if int(batch) < 1:
@@ -306,36 +312,75 @@ def _prepare(scene, encoder, divisor, stride, batch):
     if eng.quant != 0:
         raise RuntimeError("scene classification supports bf16 engines only (quant=1 / fp8 is not supported)")
     eng.params_changed()
-    return eng, desc, keep, n_h, n_w, patch, stride
+    return eng
 
 
-def _grid_of(scene, encoder, stride):
-    """(patch, stride, nH, nW) from shapes alone (no device work), for argument checks ahead of `_prepare`."""
+class _Plan(NamedTuple):
+    """What a model-running scene function works from (`_plan`).  windows: None = every window of the grid (the range entry points of
+    the C library, no id list), else the int64 ids of the windows to run (the index-driven entry points; may be empty)."""
+    eng: object
+    desc: object
+    keep: tuple
+    n_h: int
+    n_w: int
+    patch: int
+    stride: int
+    windows: object
+
+    def out(self, shape, fill, dtype=torch.float32):
+        """An output over the grid: every element is written when the whole grid runs, a subset leaves `fill` elsewhere."""
+        if self.windows is None:
+            return torch.empty(shape, dtype=dtype, device=self.eng.device)
+        return torch.full(shape, fill, dtype=dtype, device=self.eng.device)
+
+    def run(self, range_fn, index_fn, *outs, head=()):
+        """The one C call over the window set, writing `outs`: the range entry point for the whole grid, the index-driven one for a
+        list of ids, none for an empty list (the forward generation stays put).  head: arguments between the context and the stream."""
+        eng, w = self.eng, self.windows
+        with torch.cuda.device(eng.device):
+            if w is None:
+                check(range_fn(eng.ctx, *head, _stream(), C.byref(self.desc), 0, self.n_h * self.n_w, *map(_ptr, outs)))
+            elif w.numel():
+                check(index_fn(eng.ctx, *head, _stream(), C.byref(self.desc), _ptr(w), w.numel(), *map(_ptr, outs)))
+
+
+def _plan(scene, encoder, divisor, stride, batch, nodata=None, mask=None, max_invalid=0.0, rule="all", windows=None, allow_empty=True,
+          blend=False, stitched=False):
+    """Every model-running function starts here: (1) all host-side validation, before an engine exists or a kernel runs; (2) `_prepare`;
+    (3) the window set -- None for the whole grid, the given ids, or under nodata / mask the valid ids (`_select`: the one ``.item()``)."""
+    rid = _rule_arg(rule)
     enc = _encoder_of(encoder)
     patch = int(enc.image_size)
     stride = patch if stride is None else int(stride)
-    if not isinstance(scene, torch.Tensor) or scene.dim() != 3:
-        raise RuntimeError("scene must be a planar tensor [C,H,W]")
-    return (patch, stride) + window_grid(scene.shape[1], scene.shape[2], patch, stride)
+    t = invalid_threshold(patch, max_invalid)
+    masked = nodata is not None or mask is not None
+    if windows is not None and masked:
+        raise RuntimeError("windows= cannot be combined with nodata= or mask=")
+    _check_scene(scene)
+    desc, keep, n_h, n_w = _scene_desc(scene, divisor, patch, stride)
+    if blend:
+        cell_grid(n_h, n_w, patch, stride)               # the stride must divide the patch size
+    if stitched:
+        owned_span(0, n_h, patch, stride)                # patch - stride must be even
+    mode, value = _nodata_arg(scene.dtype, nodata)
+    m = _mask_arg(scene, mask)
+    if windows is not None:
+        windows = _windows_arg(windows, scene.device, n_h * n_w, allow_empty)
+    eng = _prepare(enc, desc, keep, batch)
+    if masked:
+        windows = _select(_invalid_counts(desc, keep + (m,), n_h, n_w, mode, value, rid, m), t)
+    return _Plan(eng, desc, keep, n_h, n_w, patch, stride, windows)
 
 
 def encode_scene(scene, encoder, divisor=1.0, stride=None, batch=512, windows=None):
     """Latents z [nH*nW, L] of every window (row n = window i*nW + j), eval-mode encoder, `batch` windows per encoder pass (the
     engine's max_batch, at least this).  stride=None: the patch size (non-overlapping windows).
     windows: a non-empty 1-D int64 device tensor of window ids (any order, duplicates allowed): z [len(windows), L] in that order."""
-    if windows is not None:
-        _, _, n_h, n_w = _grid_of(scene, encoder, stride)
-        windows = _windows_arg(windows, scene.device, n_h * n_w, allow_empty=False)
-        eng, desc, keep, n_h, n_w, _, _ = _prepare(scene, encoder, divisor, stride, batch)
-        z = torch.empty((windows.numel(), eng.latent), dtype=torch.float32, device=eng.device)
-        with torch.cuda.device(eng.device):
-            check(eng.lib.eae_scene_encode_windows(eng.ctx, _stream(), C.byref(desc), _ptr(windows), windows.numel(), _ptr(z)))
-        return z
-    eng, desc, keep, n_h, n_w, _, _ = _prepare(scene, encoder, divisor, stride, batch)
-    n = n_h * n_w
+    p = _plan(scene, encoder, divisor, stride, batch, windows=windows, allow_empty=False)
+    eng = p.eng
+    n = p.n_h * p.n_w if p.windows is None else p.windows.numel()
     z = torch.empty((n, eng.latent), dtype=torch.float32, device=eng.device)
-    with torch.cuda.device(eng.device):
-        check(eng.lib.eae_scene_encode(eng.ctx, _stream(), C.byref(desc), 0, n, _ptr(z)))
+    p.run(eng.lib.eae_scene_encode, eng.lib.eae_scene_encode_windows, z)
     return z
 
 
@@ -356,87 +401,33 @@ def classify_scene(scene, encoder, mlp, divisor=1.0, stride=None, batch=512, ble
     enc = _encoder_of(encoder)
     if int(mlp.input_dim) != int(enc.latent_dim):
         raise RuntimeError(f"the MLP takes input_dim={mlp.input_dim}, the encoder's latent_dim is {enc.latent_dim}")
-    if blend:
-        patch = int(enc.image_size)
-        cell_grid(1, 1, patch, patch if stride is None else int(stride))      # the stride must divide the patch size
-    masked = nodata is not None or mask is not None
-    if rule not in _RULES:
-        raise RuntimeError(f"rule must be 'all' or 'any', got {rule!r}")
-    t = invalid_threshold(enc.image_size, max_invalid)
-    if masked or windows is not None:
-        if windows is not None and masked:
-            raise RuntimeError("windows= cannot be combined with nodata= or mask=")
-        patch, st, n_h, n_w = _grid_of(scene, encoder, stride)
-        inv = _invalid_args(scene, nodata, mask, rule)
-        if windows is not None:
-            windows = _windows_arg(windows, scene.device, n_h * n_w, allow_empty=True)
-        return _classify_subset(scene, encoder, mlp, divisor, stride, batch, blend, inv, t, windows)
-    eng, desc, keep, n_h, n_w, patch, stride = _prepare(scene, encoder, divisor, stride, batch)
+    p = _plan(scene, encoder, divisor, stride, batch, nodata, mask, max_invalid, rule, windows, blend=blend)
+    eng, n_h, n_w = p.eng, p.n_h, p.n_w
     if next(mlp.parameters()).device != eng.device:
         raise RuntimeError("the MLP and the encoder must be on the same device")
     meng = mlp_engine_for(mlp)
     k_cls = int(mlp.num_classes)
-    probs = torch.empty((k_cls, n_h, n_w), dtype=torch.float32, device=eng.device)
-    labels = torch.empty((n_h, n_w), dtype=torch.int64, device=eng.device)
+    probs = p.out((k_cls, n_h, n_w), 0.0)
+    labels = p.out((n_h, n_w), -1, torch.int64)
+    p.run(eng.lib.eae_scene_classify, eng.lib.eae_scene_classify_windows, probs, labels, head=(meng.ctx,))
+    if not blend:
+        return probs, labels
+    c_h, c_w, k = cell_grid(n_h, n_w, p.patch, p.stride)
+    cprobs = torch.empty((k_cls, c_h, c_w), dtype=torch.float32, device=eng.device)
+    clabels = torch.empty((c_h, c_w), dtype=torch.int64, device=eng.device)
     with torch.cuda.device(eng.device):
-        check(eng.lib.eae_scene_classify(eng.ctx, meng.ctx, _stream(), C.byref(desc), 0, n_h * n_w, _ptr(probs), _ptr(labels)))
-        if not blend:
-            return probs, labels
-        c_h, c_w, k = cell_grid(n_h, n_w, patch, stride)
-        cprobs = torch.empty((k_cls, c_h, c_w), dtype=torch.float32, device=eng.device)
-        clabels = torch.empty((c_h, c_w), dtype=torch.int64, device=eng.device)
-        check(eng.lib.eae_scene_blend(_stream(), _ptr(probs), k_cls, n_h, n_w, k, _ptr(cprobs), _ptr(clabels)))
-    return cprobs, clabels
-
-
-def _classify_subset(scene, encoder, mlp, divisor, stride, batch, blend, inv, t, windows):
-    """classify_scene over the valid windows (nodata / mask) or the listed ones: pre-filled -1 / 0, index-driven encoder -> MLP."""
-    from .mlp_engine import mlp_engine_for
-    eng, desc, keep, n_h, n_w, patch, stride = _prepare(scene, encoder, divisor, stride, batch)
-    if next(mlp.parameters()).device != eng.device:
-        raise RuntimeError("the MLP and the encoder must be on the same device")
-    meng = mlp_engine_for(mlp)
-    k_cls = int(mlp.num_classes)
-    if windows is None:
-        mode, value, rid, m = inv
-        windows = _select(_invalid_counts(desc, keep + (m,), n_h, n_w, mode, value, rid, m), t)
-    probs = torch.zeros((k_cls, n_h, n_w), dtype=torch.float32, device=eng.device)
-    labels = torch.full((n_h, n_w), -1, dtype=torch.int64, device=eng.device)
-    with torch.cuda.device(eng.device):
-        if windows.numel():
-            check(eng.lib.eae_scene_classify_windows(eng.ctx, meng.ctx, _stream(), C.byref(desc), _ptr(windows), windows.numel(),
-                                                     _ptr(probs), _ptr(labels)))
-        if not blend:
-            return probs, labels
-        c_h, c_w, k = cell_grid(n_h, n_w, patch, stride)
-        cprobs = torch.empty((k_cls, c_h, c_w), dtype=torch.float32, device=eng.device)
-        clabels = torch.empty((c_h, c_w), dtype=torch.int64, device=eng.device)
-        check(eng.lib.eae_scene_blend_valid(_stream(), _ptr(probs), _ptr(labels), k_cls, n_h, n_w, k, _ptr(cprobs), _ptr(clabels)))
+        if p.windows is None:
+            check(eng.lib.eae_scene_blend(_stream(), _ptr(probs), k_cls, n_h, n_w, k, _ptr(cprobs), _ptr(clabels)))
+        else:
+            check(eng.lib.eae_scene_blend_valid(_stream(), _ptr(probs), _ptr(labels), k_cls, n_h, n_w, k, _ptr(cprobs), _ptr(clabels)))
     return cprobs, clabels
 
 
 # ---------------------------------------------------------------------------------------------------- reconstruction
-def _recon_args(scene, autoencoder, stride, nodata, mask, max_invalid, rule, windows, stitched):
-    """The checks of the reconstruction functions that need no device; returns (masked, t, inv, windows)."""
+def _autoencoder_arg(autoencoder):
     from .modules import SupervisedAutoencoder
     if not isinstance(autoencoder, SupervisedAutoencoder):
         raise RuntimeError(f"autoencoder must be a SupervisedAutoencoder (the decoder is needed), got {type(autoencoder).__name__}")
-    masked = nodata is not None or mask is not None
-    if windows is not None and masked:
-        raise RuntimeError("windows= cannot be combined with nodata= or mask=")
-    if rule not in _RULES:
-        raise RuntimeError(f"rule must be 'all' or 'any', got {rule!r}")
-    patch = int(autoencoder.enc.image_size)
-    t = invalid_threshold(patch, max_invalid)
-    if stitched:
-        owned_span(0, 1, patch, patch if stride is None else int(stride))      # patch - stride must be even
-    inv = None
-    if masked or windows is not None:
-        _, _, n_h, n_w = _grid_of(scene, autoencoder, stride)
-        inv = _invalid_args(scene, nodata, mask, rule)
-        if windows is not None:
-            windows = _windows_arg(windows, scene.device, n_h * n_w, allow_empty=True)
-    return masked, t, inv, windows
 
 
 def scene_reconstruction_error(scene, autoencoder, divisor=1.0, stride=None, batch=512, per_band=False, nodata=None, mask=None,
@@ -448,22 +439,11 @@ def scene_reconstruction_error(scene, autoencoder, divisor=1.0, stride=None, bat
     nodata / mask / max_invalid / rule: only the valid windows are run (`valid_windows`, one host readback); windows: a 1-D int64
     device tensor of window ids, the only windows run (not combined with nodata / mask).  Either way the other windows hold NaN;
     without a window to run nothing is launched.  A valid window that holds some invalid pixels is scored with them as stored."""
-    masked, t, inv, windows = _recon_args(scene, autoencoder, stride, nodata, mask, max_invalid, rule, windows, stitched=False)
-    eng, desc, keep, n_h, n_w, _, _ = _prepare(scene, autoencoder, divisor, stride, batch)
-    subset = masked or windows is not None
-    if masked:
-        mode, value, rid, m = inv
-        windows = _select(_invalid_counts(desc, keep + (m,), n_h, n_w, mode, value, rid, m), t)
-    make = (lambda shape: torch.full(shape, float("nan"), dtype=torch.float32, device=eng.device)) if subset else \
-        (lambda shape: torch.empty(shape, dtype=torch.float32, device=eng.device))
-    err = make((n_h, n_w))
-    band = make((desc.C, n_h, n_w)) if per_band else None
-    with torch.cuda.device(eng.device):
-        if not subset:
-            check(eng.lib.eae_scene_recon_error(eng.ctx, _stream(), C.byref(desc), 0, n_h * n_w, _ptr(err), _ptr(band)))
-        elif windows.numel():
-            check(eng.lib.eae_scene_recon_error_windows(eng.ctx, _stream(), C.byref(desc), _ptr(windows), windows.numel(), _ptr(err),
-                                                        _ptr(band)))
+    _autoencoder_arg(autoencoder)
+    p = _plan(scene, autoencoder, divisor, stride, batch, nodata, mask, max_invalid, rule, windows)
+    err = p.out((p.n_h, p.n_w), float("nan"))
+    band = p.out((p.desc.C, p.n_h, p.n_w), float("nan")) if per_band else None
+    p.run(p.eng.lib.eae_scene_recon_error, p.eng.lib.eae_scene_recon_error_windows, err, band)
     return (err, band) if per_band else err
 
 
@@ -475,21 +455,11 @@ def reconstruct_scene(scene, autoencoder, divisor=1.0, stride=None, batch=512, r
 
     nodata / mask / max_invalid / rule / windows as for `scene_reconstruction_error`: pixels owned by a window that is not run hold
     NaN (in both outputs)."""
-    masked, t, inv, windows = _recon_args(scene, autoencoder, stride, nodata, mask, max_invalid, rule, windows, stitched=True)
-    eng, desc, keep, n_h, n_w, patch, stride = _prepare(scene, autoencoder, divisor, stride, batch)
-    subset = masked or windows is not None
-    if masked:
-        mode, value, rid, m = inv
-        windows = _select(_invalid_counts(desc, keep + (m,), n_h, n_w, mode, value, rid, m), t)
-    h_g, w_g = (n_h - 1) * stride + patch, (n_w - 1) * stride + patch
-    make = (lambda shape: torch.full(shape, float("nan"), dtype=torch.float32, device=eng.device)) if subset else \
-        (lambda shape: torch.empty(shape, dtype=torch.float32, device=eng.device))
-    recon = make((desc.C, h_g, w_g))
-    res = make((h_g, w_g)) if residual else None
-    with torch.cuda.device(eng.device):
-        if not subset:
-            check(eng.lib.eae_scene_reconstruct(eng.ctx, _stream(), C.byref(desc), None, n_h * n_w, _ptr(recon), _ptr(res)))
-        elif windows.numel():
-            check(eng.lib.eae_scene_reconstruct(eng.ctx, _stream(), C.byref(desc), _ptr(windows), windows.numel(), _ptr(recon),
-                                                _ptr(res)))
+    _autoencoder_arg(autoencoder)
+    p = _plan(scene, autoencoder, divisor, stride, batch, nodata, mask, max_invalid, rule, windows, stitched=True)
+    h_g, w_g = (p.n_h - 1) * p.stride + p.patch, (p.n_w - 1) * p.stride + p.patch
+    recon = p.out((p.desc.C, h_g, w_g), float("nan"))
+    res = p.out((h_g, w_g), float("nan")) if residual else None
+    fn = p.eng.lib.eae_scene_reconstruct                 # one entry point: windows = NULL is the whole grid
+    p.run(lambda ctx, st, desc, first, n, *outs: fn(ctx, st, desc, None, n, *outs), fn, recon, res)
     return (recon, res) if residual else recon

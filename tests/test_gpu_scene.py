@@ -12,24 +12,9 @@ from eae_amd import _lib
 from eae_amd.engine import engine_for, _stream, _ptr
 from eae_amd.mlp_engine import mlp_engine_for
 from helpers import ae_state_np, mlp_state_np, load_state_np
+from scene_util import _scene, _divisor, _model as _encoder, _mlp, _desc
 
 pytestmark = pytest.mark.gpu
-
-_MAX = {torch.uint8: 256, torch.uint16: 65536}
-
-
-def _scene(c, h, w, dtype, seed):
-    g = torch.Generator().manual_seed(seed)
-    if dtype == torch.float32:
-        s = torch.rand((c, h, w), generator=g) * 3.0
-    else:
-        s = torch.randint(0, _MAX[dtype], (c, h, w), generator=g, dtype=torch.int64).to(dtype)
-    return s.cuda()
-
-
-def _divisor(c, dtype):
-    base = {torch.uint8: 255.0, torch.uint16: 10000.0, torch.float32: 1.5}[dtype]
-    return [base * (1.0 + 0.1 * i) for i in range(c)]
 
 
 def _host_windows(scene, p, s):
@@ -38,18 +23,6 @@ def _host_windows(scene, p, s):
     c, h, w = x.shape
     n_h, n_w = (h - p) // s + 1, (w - p) // s + 1
     return torch.stack([x[:, i * s:i * s + p, j * s:j * s + p] for i in range(n_h) for j in range(n_w)]), n_h, n_w
-
-
-def _encoder(c, seed=0, latent=64, batch=512):
-    torch.manual_seed(seed)
-    m = eae_amd.SupervisedAutoencoder(latent, 10, in_channels=c)
-    m._eae_max_batch = batch                   # the engine's max_batch: the fused path's batch, and the staged path's below
-    with torch.no_grad():                      # non-trivial running statistics: eval mode must use them
-        for mod in m.enc.modules():
-            if hasattr(mod, "running_mean") and mod.running_mean is not None:
-                mod.running_mean.uniform_(-0.2, 0.2)
-                mod.running_var.uniform_(0.5, 2.0)
-    return m.cuda().eval()
 
 
 def _staged_z(scene, div, model, stride, batch, first=0, count=None):
@@ -130,16 +103,6 @@ def test_encode_scene_halo_stays_zero(dtype):
 
 
 # ---------------------------------------------------------------------------------------------------------------- predict
-def _mlp(latent=64, classes=10, seed=3):
-    torch.manual_seed(seed)
-    m = eae_amd.MLP(latent, classes)
-    with torch.no_grad():
-        for bn in (m.net[1], m.net[5]):
-            bn.running_mean.uniform_(-0.3, 0.3)
-            bn.running_var.uniform_(0.5, 2.0)
-    return m.cuda().eval()
-
-
 @pytest.mark.parametrize("dtype,c,s,classes", [(torch.uint8, 3, 20, 10), (torch.uint16, 13, 32, 16), (torch.float32, 4, 16, 3)])
 def test_classify_scene_matches_staged_logits(dtype, c, s, classes):
     scene = _scene(c, 150, 203, dtype, seed=200 + c)
@@ -243,12 +206,6 @@ def test_scene_beyond_2g_elements():
 
 
 # ---------------------------------------------------------------------------------------------------------------- errors
-def _desc(scene, div, patch=64, stride=64, dtype=None):
-    return _lib.EaeScene(C.c_void_p(scene.data_ptr()), C.c_void_p(0 if div is None else div.data_ptr()),
-                         {torch.uint8: 0, torch.uint16: 1, torch.float32: 2}[scene.dtype] if dtype is None else dtype,
-                         scene.shape[0], scene.shape[1], scene.shape[2], patch, stride)
-
-
 def test_rejected_arguments_raise():
     model, mlp = _encoder(3, seed=51), _mlp(64, 10)
     ok = _scene(3, 100, 100, torch.uint8, seed=1)
@@ -284,6 +241,39 @@ def test_rejected_arguments_raise():
     with pytest.raises(RuntimeError):
         _lib.check(lib.eae_scene_windows(_stream(), C.byref(_desc(ok, None)), 0, 1, _ptr(z)))
     torch.cuda.synchronize()
+
+
+def test_range_entry_points_from_a_later_first_window():
+    """The range form with first > 0 (the Python layer always passes 0): windows 5..11 of a 3 x 4 grid at max_batch 4, two batch
+    boundaries and a ragged last batch of 3.  They equal the whole-grid call's rows bitwise (eval mode mixes no rows), nothing in
+    front of them is written, and the index form over the same ids agrees."""
+    model, mlp = _encoder(3, seed=71, batch=4), _mlp(64, 10)
+    scene = _scene(3, 128, 160, torch.uint8, seed=11)
+    eng, meng = engine_for(model.enc), mlp_engine_for(mlp)
+    assert eng.max_batch == 4 and eae_amd.window_grid(128, 160, 64, 32) == (3, 4)
+    d = _desc(scene, torch.full((3,), 255.0, device="cuda"), stride=32)
+    lib, n = eng.lib, 12
+
+    def run(first, count):
+        z = torch.full((count, 64), -7.0, device="cuda")
+        probs, err = torch.full((10, n), -7.0, device="cuda"), torch.full((n,), -7.0, device="cuda")
+        labels = torch.full((n,), -7, dtype=torch.int64, device="cuda")
+        _lib.check(lib.eae_scene_encode(eng.ctx, _stream(), C.byref(d), first, count, _ptr(z)))
+        _lib.check(lib.eae_scene_classify(eng.ctx, meng.ctx, _stream(), C.byref(d), first, count, _ptr(probs), _ptr(labels)))
+        _lib.check(lib.eae_scene_recon_error(eng.ctx, _stream(), C.byref(d), first, count, _ptr(err), None))
+        return z, probs, labels, err
+
+    z0, p0, l0, e0 = run(0, n)
+    z1, p1, l1, e1 = run(5, 7)
+    assert torch.isfinite(z0).all() and (z0.std(0) > 0).any() and (e0 > 0).all() and (l0 >= 0).all()
+    assert torch.equal(z1, z0[5:])
+    assert torch.equal(p1[:, 5:], p0[:, 5:]) and torch.equal(l1[5:], l0[5:])
+    assert (p1[:, :5] == -7).all() and (l1[:5] == -7).all()
+    assert torch.equal(e1[5:], e0[5:]) and (e1[:5] == -7).all()
+    ids = torch.arange(5, n, dtype=torch.int64, device="cuda")
+    zi = torch.empty((7, 64), device="cuda")
+    _lib.check(lib.eae_scene_encode_windows(eng.ctx, _stream(), C.byref(d), _ptr(ids), 7, _ptr(zi)))
+    assert torch.equal(zi, z0[5:])
 
 
 def test_quant_fp8_context_rejected():

@@ -8,50 +8,12 @@ import torch
 import eae_amd
 from eae_amd import scene as S
 from eae_amd.engine import engine_for
+from scene_util import _MAX, _scene, _divisor, _model as _encoder, _mlp
 
 pytestmark = pytest.mark.gpu
 
 P = 64
 _NP = {torch.uint8: np.uint8, torch.uint16: np.uint16, torch.float32: np.float32}
-_MAX = {torch.uint8: 256, torch.uint16: 65536}
-
-
-# ---------------------------------------------------------------------------------------------------------------- fixtures (copied
-# from tests/test_gpu_scene.py: a test module is not imported)
-def _scene(c, h, w, dtype, seed):
-    g = torch.Generator().manual_seed(seed)
-    if dtype == torch.float32:
-        s = torch.rand((c, h, w), generator=g) * 3.0
-    else:
-        s = torch.randint(0, _MAX[dtype], (c, h, w), generator=g, dtype=torch.int64).to(dtype)
-    return s.cuda()
-
-
-def _divisor(c, dtype):
-    base = {torch.uint8: 255.0, torch.uint16: 10000.0, torch.float32: 1.5}[dtype]
-    return [base * (1.0 + 0.1 * i) for i in range(c)]
-
-
-def _encoder(c, seed=0, latent=64, batch=512):
-    torch.manual_seed(seed)
-    m = eae_amd.SupervisedAutoencoder(latent, 10, in_channels=c)
-    m._eae_max_batch = batch
-    with torch.no_grad():
-        for mod in m.enc.modules():
-            if hasattr(mod, "running_mean") and mod.running_mean is not None:
-                mod.running_mean.uniform_(-0.2, 0.2)
-                mod.running_var.uniform_(0.5, 2.0)
-    return m.cuda().eval()
-
-
-def _mlp(latent=64, classes=10, seed=3):
-    torch.manual_seed(seed)
-    m = eae_amd.MLP(latent, classes)
-    with torch.no_grad():
-        for bn in (m.net[1], m.net[5]):
-            bn.running_mean.uniform_(-0.3, 0.3)
-            bn.running_var.uniform_(0.5, 2.0)
-    return m.cuda().eval()
 
 
 # ---------------------------------------------------------------------------------------------------------------- scenes with holes

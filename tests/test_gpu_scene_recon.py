@@ -2,6 +2,7 @@
 against the staged composition of public pieces (scene_windows -> eval-mode SupervisedAutoencoder -> a float64 MSE), batch
 independence, the NumPy oracle, nodata / mask / window lists, the stitched raster's ownership rule, 64-bit offsets and refusals."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -11,37 +12,12 @@ import eae_amd
 from eae_amd import _lib
 from eae_amd.engine import engine_for, _stream, _ptr
 from helpers import ae_state_np, load_state_np
+from scene_util import _scene, _divisor, _desc, _model as _build
 
 pytestmark = pytest.mark.gpu
 
-_MAX = {torch.uint8: 256, torch.uint16: 65536}
 U = 2.0 ** -24                                     # unit roundoff of fp32
-
-
-def _scene(c, h, w, dtype, seed):
-    g = torch.Generator().manual_seed(seed)
-    if dtype == torch.float32:
-        s = torch.rand((c, h, w), generator=g) * 3.0
-    else:
-        s = torch.randint(0, _MAX[dtype], (c, h, w), generator=g, dtype=torch.int64).to(dtype)
-    return s.cuda()
-
-
-def _divisor(c, dtype):
-    base = {torch.uint8: 255.0, torch.uint16: 10000.0, torch.float32: 1.5}[dtype]
-    return [base * (1.0 + 0.1 * i) for i in range(c)]
-
-
-def _model(c, seed=0, batch=512, p=64):
-    torch.manual_seed(seed)
-    m = eae_amd.SupervisedAutoencoder(64, 10, image_size=p, in_channels=c)
-    m._eae_max_batch = batch                   # the engine's max_batch: the fused path's batch, and the staged path's below
-    with torch.no_grad():                      # non-trivial running statistics in BOTH halves: eval mode must use them
-        for mod in m.modules():
-            if hasattr(mod, "running_mean") and mod.running_mean is not None:
-                mod.running_mean.uniform_(-0.2, 0.2)
-                mod.running_var.uniform_(0.5, 2.0)
-    return m.cuda().eval()
+_model = functools.partial(_build, all_halves=True)    # non-trivial running statistics in BOTH halves
 
 
 def _staged(scene, div, model, stride, batch, first=0, count=None):
@@ -85,7 +61,7 @@ def test_error_maps_match_staged_float64(dtype, c, s, batch, p):
     h, w = (157, 211) if p == 64 else (300, 333)
     scene = _scene(c, h, w, dtype, seed=100 + c + s)
     div = _divisor(c, dtype)
-    model = _model(c, seed=c, batch=batch, p=p)
+    model = _model(c, seed=c, batch=batch, image_size=p)
     err, band = eae_amd.scene_reconstruction_error(scene, model, divisor=div, stride=s, batch=batch, per_band=True)
     n_h, n_w = eae_amd.window_grid(h, w, p, s)
     assert err.shape == (n_h, n_w) and band.shape == (c, n_h, n_w) and err.dtype == torch.float32
@@ -291,12 +267,6 @@ def test_error_map_beyond_2g_elements():
 
 
 # ---------------------------------------------------------------------------------------------------------------- refusals
-def _desc(scene, div, patch=64, stride=64):
-    return _lib.EaeScene(C.c_void_p(scene.data_ptr()), C.c_void_p(0 if div is None else div.data_ptr()),
-                         {torch.uint8: 0, torch.uint16: 1, torch.float32: 2}[scene.dtype], scene.shape[0], scene.shape[1],
-                         scene.shape[2], patch, stride)
-
-
 def test_rejected_arguments_raise():
     model = _model(3, seed=51, batch=8)
     ok = _scene(3, 100, 100, torch.uint8, seed=1)
