@@ -19,14 +19,18 @@ constexpr int HC = 64;  // logits row stride in LDS = largest class count
 //   dW1   [128][L]  = dh^T z        thread = 4 j x 4 k tiles (strided over [32][L/4]), r = 0..HR-1
 // Row strides are padded to L + 4 / 132 floats: 16-byte aligned rows whose float4 reads by 16 consecutive lanes fall on 16 different
 // bank slots.  Arithmetic stays fp32 fmaf chains (the head is fp32 end to end: <= 5e-5 vs the reference's goldens).
-template <int HR_>
+// W2G: W2 is read from global memory instead of a staged copy.  W1 at L = 256 takes 130 KB; with more than 20 classes the staged W2
+// ([C][132] floats, 33 KB at C = 64) no longer fits beside it in the CU's 160 KB (eae_launch_head picks the variant).
+template <int HR_, bool W2G = false>
 __device__ __forceinline__ EAE_NO_PK void head_body(const HeadArgs& a) {     // <= 96 VGPRs: the kernel runs beside the decoder on a side stream, and a wave-specialised igemm2 workgroup (2 x 200 registers per SIMD lane) must still fit beside one of its waves -- at 132 registers dec.deconv1's forward waited for the head's 32 CUs (15 -> 28 us)
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int L = a.L, C = a.C, LS = L + 4, HS = 132;
   float* w1 = sm;                    // [128][LS]
   float* zt = w1 + 128 * LS;         // [HR_][LS]
-  float* w2 = zt + HR_ * LS;         // [C][HS]
-  float* hp = w2 + ((C * HS + 3) & ~3);   // [HR_][HS]  pre-activation
+  float* w2s = zt + HR_ * LS;        // [C][HS]  (W2G: absent)
+  float* hp = w2s + (W2G ? 0 : ((C * HS + 3) & ~3));   // [HR_][HS]  pre-activation
+  const float* w2 = W2G ? a.w2 : w2s;
+  const int WS = W2G ? 128 : HS;     // row stride of w2
   float* dh = hp + HR_ * HS;         // [HR_][HS]
   float* lg = dh + HR_ * HS;         // [HR_][HC]   logits, then dlogits
   float* b1 = lg + HR_ * HC;         // [128]
@@ -45,10 +49,11 @@ __device__ __forceinline__ EAE_NO_PK void head_body(const HeadArgs& a) {     // 
     if (r0 + r < a.B) v = *reinterpret_cast<const float4*>(a.z + (size_t)(r0 + r) * L + k4 * 4);
     *reinterpret_cast<float4*>(zt + r * LS + k4 * 4) = v;
   }
-  for (int i = tid; i < C * 32; i += 256) {
-    const int c = i >> 5, j4 = i & 31;
-    *reinterpret_cast<float4*>(w2 + c * HS + j4 * 4) = *reinterpret_cast<const float4*>(a.w2 + (size_t)c * 128 + j4 * 4);
-  }
+  if (!W2G)
+    for (int i = tid; i < C * 32; i += 256) {
+      const int c = i >> 5, j4 = i & 31;
+      *reinterpret_cast<float4*>(w2s + c * HS + j4 * 4) = *reinterpret_cast<const float4*>(a.w2 + (size_t)c * 128 + j4 * 4);
+    }
   if (tid < 128) b1[tid] = a.b1[tid];
   if (tid < C) b2[tid] = a.b2[tid];
   __syncthreads();
@@ -81,7 +86,7 @@ __device__ __forceinline__ EAE_NO_PK void head_body(const HeadArgs& a) {     // 
     float s = b2[c];
 #pragma unroll 4
     for (int j = 0; j < 128; j += 4) {
-      const float4 h = *reinterpret_cast<const float4*>(hp + r * HS + j), w = *reinterpret_cast<const float4*>(w2 + c * HS + j);
+      const float4 h = *reinterpret_cast<const float4*>(hp + r * HS + j), w = *reinterpret_cast<const float4*>(w2 + c * WS + j);
       s = fmaf(relu_nan(h.x), w.x, s); s = fmaf(relu_nan(h.y), w.y, s); s = fmaf(relu_nan(h.z), w.z, s); s = fmaf(relu_nan(h.w), w.w, s);
     }
     lg[r * HC + c] = s;
@@ -126,7 +131,7 @@ __device__ __forceinline__ EAE_NO_PK void head_body(const HeadArgs& a) {     // 
     const int r = i >> 7, j = i & 127;
     float s = 0.f;
 #pragma unroll 8
-    for (int c = 0; c < C; ++c) s = fmaf(lg[r * HC + c], w2[c * HS + j], s);
+    for (int c = 0; c < C; ++c) s = fmaf(lg[r * HC + c], w2[c * WS + j], s);
     dh[r * HS + j] = hp[r * HS + j] > 0.f ? s : 0.f;
   }
   __syncthreads();
@@ -189,6 +194,9 @@ template <int HR_>
 __global__ EAE_NO_PK __launch_bounds__(256, 5) void head_kernel(HeadArgs a) { head_body<HR_>(a); }
 template <int HR_>
 __global__ EAE_NO_PK __launch_bounds__(256, 5) void head_kernel_g(GroupPack<HeadArgs> p, int gz) { head_body<HR_>(group_args<HeadArgs>(gz)); }
+__global__ EAE_NO_PK __launch_bounds__(256) void head_kernel_w2g(HeadArgs a) { head_body<8, true>(a); }
+__global__ EAE_NO_PK __launch_bounds__(256) void head_kernel_w2g_g(GroupPack<HeadArgs> p, int gz) { head_body<8, true>(group_args<HeadArgs>(gz)); }
+constexpr size_t HEAD_LDS_MAX = 160 * 1024;     // LDS of a gfx950 CU = the most one workgroup can ask for
 
 static int head_rows(int L) { return L <= 128 ? 16 : 8; }
 int eae_head_blocks(int B, int L) { const int hr = head_rows(L); return (B + hr - 1) / hr; }
@@ -196,11 +204,14 @@ int eae_head_blocks(int B, int L) { const int hr = head_rows(L); return (B + hr 
 int eae_launch_head(hipStream_t st, const HeadArgs& a) {
   if (a.L > 256 || a.C > HC || a.L % 4) return eae_set_error(-2, "head: latent_dim must be <= 256 (multiple of 4), classes <= 64");
   const int hr = head_rows(a.L);
-  const size_t smem = sizeof(float) * ((size_t)128 * (a.L + 4) + (size_t)hr * (a.L + 4) + ((a.C * 132 + 3) & ~3) + 2 * hr * 132 + hr * HC + 128 + HC + 2 * hr);
+  const size_t smem_rest = sizeof(float) * ((size_t)128 * (a.L + 4) + (size_t)hr * (a.L + 4) + 2 * hr * 132 + hr * HC + 128 + HC + 2 * hr);
+  const size_t smem_w2 = sizeof(float) * ((a.C * 132 + 3) & ~3);
+  const bool w2g = hr == 8 && smem_rest + smem_w2 > HEAD_LDS_MAX;     // wide latent and many classes: W2 stays in global memory
+  const size_t smem = smem_rest + (w2g ? 0 : smem_w2);
   // the dynamic-LDS limit is an attribute of the kernel ON ONE DEVICE and the request grows with the latent width: keep the
   // largest size granted per (kernel, device) (a process-wide static skipped the attribute for an engine on a second device)
-  void (*kern)(HeadArgs) = hr == 16 ? head_kernel<16> : head_kernel<8>;
-  void (*kern_g)(GroupPack<HeadArgs>, int) = hr == 16 ? head_kernel_g<16> : head_kernel_g<8>;
+  void (*kern)(HeadArgs) = w2g ? head_kernel_w2g : hr == 16 ? head_kernel<16> : head_kernel<8>;
+  void (*kern_g)(GroupPack<HeadArgs>, int) = w2g ? head_kernel_w2g_g : hr == 16 ? head_kernel_g<16> : head_kernel_g<8>;
   {
     static thread_local std::vector<std::pair<std::pair<const void*, int>, size_t>> granted;
     int dev = 0;
