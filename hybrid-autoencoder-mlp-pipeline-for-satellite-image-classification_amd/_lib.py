@@ -31,7 +31,8 @@ class EaeSrc(C.Structure):
 
 class EaeScene(C.Structure):
     _fields_ = [("data", vp), ("divisor", vp), ("dtype", C.c_int), ("C", C.c_int), ("H", C.c_int), ("W", C.c_int),
-                ("patch", C.c_int), ("stride", C.c_int)]
+                ("patch", C.c_int), ("stride", C.c_int), ("border", C.c_int), ("pad_top", C.c_int), ("pad_bottom", C.c_int),
+                ("pad_left", C.c_int), ("pad_right", C.c_int), ("fill", C.c_float)]
 
 
 _PROTOS = {

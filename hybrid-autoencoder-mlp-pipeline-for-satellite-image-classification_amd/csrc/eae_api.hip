@@ -1897,6 +1897,7 @@ int scene_recon(eae_ctx* c, void* stream, const eae_scene* s, long long first, c
   r.recon = recon; r.residual = residual;
   r.Wg = (int)eae_scene_extent(nW, s->patch, s->stride);
   r.gplane = eae_scene_extent(nH, s->patch, s->stride) * r.Wg;
+  if (s->border) { r.Wg = s->W; r.gplane = (long long)s->H * s->W; }      // the stitched raster of a bordered scene is the real scene
   r.nH = (int)nH; r.m = (s->patch - s->stride) / 2;
   hipStream_t st = (hipStream_t)stream;
   return scene_run(c, st, s, nH, nW, first, windows, count, [&](long long b0, int nb, const SceneSrc& src) {

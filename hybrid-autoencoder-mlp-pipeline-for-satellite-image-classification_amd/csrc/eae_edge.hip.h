@@ -29,7 +29,9 @@ template <int SRC3> constexpr bool src3_planar() { return SRC3 != SRC3_NHWCP_BF1
 // stride S (nW per row), whose origin is scene pixel (w / nW * S, w % nW * S).  Offsets are 64-bit: scenes exceed 2^31 elements.
 // Index-driven form (the IDX template flag of the scene kernels): image n is window index[first + n] instead; an id outside
 // [0, nwin) reads as an all-zero window (defence in depth: the callers reject such ids before any launch).
-struct SceneSrc {
+// (SceneSrcCore is the part every scene kernel takes; SceneSrc adds the border fields behind it.  Kernels with arguments after the
+// scene take the two parts apart, the border last, so that the argument block of the borderless forms stays as it was.)
+struct SceneSrcCore {
   const void* data = nullptr;        // [C][Hs][Ws]
   const float* div = nullptr;        // [C]
   long long first = 0, plane = 0;    // first window of the launch; Hs * Ws
@@ -37,7 +39,29 @@ struct SceneSrc {
   const long long* index = nullptr;  // window ids (IDX kernels only)
   long long nwin = 0;                // nH * nW
 };
+// border (BORDER kernels only; eae.h, "Border modes"): the grid lies over the virtual scene, window (i, j) starts at virtual pixel
+// (i * S, j * S) = scene pixel (i * S - pt, j * S - pl), and a pixel outside the Hs x Ws scene is resolved when it is loaded
+struct SceneBorder {
+  int mode = 0, pt = 0, pl = 0, Hs = 0, Ws = 0;
+  float fill = 0.f;
+};
+struct SceneSrc : SceneSrcCore { SceneBorder b; };
 template <typename T> __device__ __forceinline__ float scene_val(T v, float d) { return (float)v / d; }
+// The one border resolver: source index on an axis of length n of virtual coordinate v behind a leading pad p, or -1 for a constant
+// pixel (whose stored value is fill).  s = v - p inside [0, n) is the pixel itself; EDGE clamps; REFLECT mirrors about the edge pixel
+// without repeating it (one reflection: the pads are at most n - 1, eae_scene_check).
+__device__ __forceinline__ int scene_resolve(int v, int p, int n, int mode) {
+  const int s = v - p;
+  if ((unsigned)s < (unsigned)n) return s;
+  if (mode == EAE_BORDER_EDGE) return s < 0 ? 0 : n - 1;
+  if (mode == EAE_BORDER_REFLECT) return s < 0 ? -s : 2 * (n - 1) - s;
+  return -1;
+}
+// value of virtual pixel (vy, vx) of band plane x, as conv1 and deconv4's target both read it
+template <typename T> __device__ __forceinline__ float scene_border_val(const T* x, const SceneBorder& b, int vy, int vx, float d) {
+  const int sy = scene_resolve(vy, b.pt, b.Hs, b.mode), sx = scene_resolve(vx, b.pl, b.Ws, b.mode);
+  return scene_val(sy < 0 || sx < 0 ? (T)b.fill : x[(long long)sy * b.Ws + sx], d);
+}
 // 4 consecutive scene pixels of one band: one vector load where the address allows it (window origins x are not aligned for most
 // strides and scene widths), else 4 element loads
 template <typename T> __device__ __forceinline__ float4 scene_load4(const T* p, float d) {
@@ -88,7 +112,7 @@ template <int CP> constexpr int e_halo_row() { return CP == 4 ? 1 : CP / 8; }   
 template <int CP> constexpr int e_nld() { return (E_PH * (e_pieces_row<CP>() + e_halo_row<CP>()) + 255) / 256; }
 template <int SRC3, int CP> struct Patch3Regs { float4 v[EdgeK<CP>::CMAX]; };     // planar fp32: one float4 per band (halo threads: .x only)
 template <int CP> struct Patch3Regs<SRC3_NHWCP_BF16, CP> { uint4 v[e_nld<CP>()]; };   // bf16 NHWC-CP: 16-byte pieces
-template <int SRC3, int CP, bool IDX = false>
+template <int SRC3, int CP, bool IDX = false, bool BORDER = false>
 __device__ __forceinline__ void patch3_load(const void* src, int C, int n, int H, int W, int iy0, int ix0, Patch3Regs<SRC3, CP>& r,
                                             const SceneSrc* sc = nullptr) {
   const int tid = threadIdx.x;
@@ -105,6 +129,47 @@ __device__ __forceinline__ void patch3_load(const void* src, int C, int n, int H
     for (int c = 0; c < CMAX; ++c) r.v[c] = make_float4(0.f, 0.f, 0.f, 0.f);
     if constexpr (IDX)
       if (w < 0 || w >= sc->nwin) return;
+    if constexpr (BORDER) {
+      // virtual coordinates (vy, vx) of the window's pixels.  The row resolves once per thread; a thread whose four virtual columns are
+      // real ones takes the vector path of the borderless form, else four resolved element loads (or the fill): only the workgroups
+      // of windows at the border diverge.
+      const int vy0 = (int)wi * sc->S, vx0 = (int)wj * sc->S;
+      if (tid < E_PH * 16) {
+        const int c4 = tid & 15, rr = tid >> 4;
+        const int iy = iy0 + rr, ix = ix0 + 1 + c4 * 4;
+        if (iy >= 0 && iy < H) {
+          const int sy = scene_resolve(vy0 + iy, sc->b.pt, sc->b.Hs, sc->b.mode), sx0 = vx0 + ix - sc->b.pl;
+          if (sy >= 0 && sx0 >= 0 && sx0 + 3 < sc->Ws) {
+            const T* p = x + (long long)sy * sc->Ws + sx0;
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c)
+              if (c < C) r.v[c] = scene_load4<T>(p + c * sc->plane, sc->div[c]);
+          } else {
+            int sx[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) sx[e] = sy < 0 ? -1 : scene_resolve(vx0 + ix + e, sc->b.pl, sc->Ws, sc->b.mode);
+            const T* p = x + (long long)(sy < 0 ? 0 : sy) * sc->Ws;
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c)
+              if (c < C) {
+                const T* q = p + c * sc->plane;
+                const float d = sc->div[c];
+                const T f = (T)sc->b.fill;
+                r.v[c] = make_float4(scene_val(sx[0] < 0 ? f : q[sx[0]], d), scene_val(sx[1] < 0 ? f : q[sx[1]], d),
+                                     scene_val(sx[2] < 0 ? f : q[sx[2]], d), scene_val(sx[3] < 0 ? f : q[sx[3]], d));
+              }
+          }
+        }
+      } else if (tid < E_PH * 16 + E_PH) {
+        const int iy = iy0 + tid - E_PH * 16;
+        if (ix0 >= 0 && iy >= 0 && iy < H) {
+#pragma unroll
+          for (int c = 0; c < CMAX; ++c)
+            if (c < C) r.v[c].x = scene_border_val<T>(x + c * sc->plane, sc->b, vy0 + iy, vx0 + ix0, sc->div[c]);
+        }
+      }
+      return;
+    }
     if (tid < E_PH * 16) {
       const int c4 = tid & 15, rr = tid >> 4;
       const int iy = iy0 + rr, ix = ix0 + 1 + c4 * 4;
@@ -220,11 +285,11 @@ __device__ __forceinline__ void patch3_write(bf16_t* p3, const Patch3Regs<SRC3, 
     }
   }
 }
-template <int SRC3, int CP, bool IDX = false>
+template <int SRC3, int CP, bool IDX = false, bool BORDER = false>
 __device__ __forceinline__ void stage_patch3(const void* src, int C, bf16_t* p3, int n, int H, int W, int iy0, int ix0,
                                              const SceneSrc* sc = nullptr) {
   Patch3Regs<SRC3, CP> r;
-  patch3_load<SRC3, CP, IDX>(src, C, n, H, W, iy0, ix0, r, sc);
+  patch3_load<SRC3, CP, IDX, BORDER>(src, C, n, H, W, iy0, ix0, r, sc);
   patch3_write<SRC3, CP>(p3, r);
   __syncthreads();
 }
@@ -300,7 +365,7 @@ struct EdgeArgs {
 // consecutive k are whole pixel pieces of the staged [row][col][CP] patch (two pixels for CP = 4, one for 8, half a pixel for 16), so
 // the pixel operand is read straight from the patch.  The weights are the MFMA A operand: an accumulator lane holds 4 consecutive
 // output channels of one pixel (8-byte tile writes instead of 16 two-byte ones).
-template <int SRC3, int EPI, int CP, bool IDX = false>
+template <int SRC3, int EPI, int CP, bool IDX = false, bool BORDER = false>
 __device__ __forceinline__ void edge_conv_body(const EdgeArgs& a, const SceneSrc* sc = nullptr) {
   constexpr int KP = EdgeK<CP>::KP, KS = EdgeK<CP>::KS;
   __shared__ __attribute__((aligned(16))) bf16_t p3[e_patch<CP>()];
@@ -326,7 +391,7 @@ __device__ __forceinline__ void edge_conv_body(const EdgeArgs& a, const SceneSrc
     for (int ks = 0; ks < KS; ++ks)
       wf[mt][ks] = *reinterpret_cast<const bf16x8*>(a.c.wpack + (mt * 16 + (lane & 15)) * KP + ks * 32 + kgl * 8);
   EDGE_STAMP(16);
-  stage_patch3<SRC3, CP, IDX>(a.src3, edge_bands<CP>(a.C), p3, n, a.H, a.W, 2 * tyb * E_TH - 1, 2 * txb * E_TW - 1, sc);  // ends with a barrier
+  stage_patch3<SRC3, CP, IDX, BORDER>(a.src3, edge_bands<CP>(a.C), p3, n, a.H, a.W, 2 * tyb * E_TH - 1, 2 * txb * E_TW - 1, sc);  // ends with a barrier
   EDGE_STAMP(17);
   f32x4 acc[2][2];
 #pragma unroll
@@ -390,9 +455,10 @@ __global__ __launch_bounds__(256) void edge_conv_kernel(EdgeArgs a) { edge_conv_
 template <int SRC3, int EPI, int CP>
 __global__ __launch_bounds__(256) void edge_conv_kernel_g(GroupPack<EdgeArgs> p, int gz) { edge_conv_body<SRC3, EPI, CP>(group_args<EdgeArgs>(gz)); }
 // conv1 reading P x P windows of a device-resident scene (eae_scene_encode / eae_scene_classify; eval-mode forward); IDX: the windows
-// of the launch come from s.index (eae_scene_encode_windows / eae_scene_classify_windows)
-template <int SRC3, int CP, bool IDX = false>
-__global__ __launch_bounds__(256) void edge_conv_scene_kernel(EdgeArgs a, SceneSrc s) { edge_conv_body<SRC3, EPI_FWD, CP, IDX>(a, &s); }
+// of the launch come from s.index (eae_scene_encode_windows / eae_scene_classify_windows); BORDER: the grid lies over the virtual
+// padded scene (s.border and the fields behind it).  The flag keeps the borderless instantiations the code they were.
+template <int SRC3, int CP, bool IDX = false, bool BORDER = false>
+__global__ __launch_bounds__(256) void edge_conv_scene_kernel(EdgeArgs a, SceneSrc s) { edge_conv_body<SRC3, EPI_FWD, CP, IDX, BORDER>(a, &s); }
 
 // ---------------------------------------------------------------------------------------------------------------
 // R[k][c] = sum_m im2col(src)[m][k] * T(side)[m][c]     (weight gradient of conv1 and of deconv4)
@@ -749,10 +815,10 @@ __global__ __launch_bounds__(256) void deconv4_loss_kernel_g(GroupPack<Deconv4Ar
 __host__ __device__ constexpr int edge_bp_stride(int C) { return (C + 3) / 4 * 4; }      // floats of a partial row: C bands, whole float4s
 struct Deconv4SceneArgs {
   float* part;             // [ntiles][edge_bp_stride(C)]
-  float* recon;            // STITCH: fp32 [C][Hg][Wg]
-  float* residual;         // STITCH: fp32 [Hg][Wg] or nullptr
-  long long gplane = 0;    // Hg * Wg
-  int Wg = 0, nH = 0, m = 0;   // width of the stitched raster, window rows of the grid, (P - S) / 2
+  float* recon;            // STITCH: fp32 [C][Hg][Wg]; BORDER: [C][Hs][Ws], the real scene
+  float* residual;         // STITCH: fp32 [Hg][Wg] or nullptr; BORDER: [Hs][Ws]
+  long long gplane = 0;    // Hg * Wg; BORDER: Hs * Ws
+  int Wg = 0, nH = 0, m = 0;   // width of the stitched raster (BORDER: Ws), window rows of the grid, (P - S) / 2
 };
 
 // The MFMA part of deconv4_loss_body, line for line: stages the 5 x 33 input patch of this workgroup's tile (image n, input rows iy0..,
@@ -842,8 +908,9 @@ __device__ __forceinline__ float* deconv4_presigmoid_tile(const Deconv4Args& a, 
   return sl;
 }
 
-template <int SRC3, int CP, bool IDX, bool STITCH>
-__device__ __forceinline__ void deconv4_scene_body(const Deconv4Args& a, const SceneSrc& sc, const Deconv4SceneArgs& r) {
+template <int SRC3, int CP, bool IDX, bool STITCH, bool BORDER = false>
+__device__ __forceinline__ void deconv4_scene_body(const Deconv4Args& a, const SceneSrcCore& sc, const Deconv4SceneArgs& r,
+                                                   const SceneBorder& sb) {
   using T = typename SceneElem<SRC3>::T;
   constexpr int NT = EdgeK<CP>::NT, SLW = 16 * NT + 1, CMAX = EdgeK<CP>::CMAX;
   __shared__ float redb[4][CMAX];
@@ -870,9 +937,16 @@ __device__ __forceinline__ void deconv4_scene_body(const Deconv4Args& a, const S
   float xt[2][CMAX];               // the target values of this thread, requested together ahead of the stores (as deconv4_loss_body)
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
-    const T* p = x + org + (long long)(2 * iy0 + (tid >> 6) + 4 * i) * sc.Ws + lx;
+    if constexpr (BORDER) {          // the resolver conv1's patch load used: target and input stay bit-identical
+      const int vy = (int)wi * sc.S + 2 * iy0 + (tid >> 6) + 4 * i, vx = (int)wj * sc.S + lx;
 #pragma unroll
-    for (int co = 0; co < CMAX; ++co) xt[i][co] = (inside && co < C) ? scene_val(p[co * sc.plane], dv[co]) : 0.f;
+      for (int co = 0; co < CMAX; ++co)
+        xt[i][co] = (inside && co < C) ? scene_border_val<T>(x + co * sc.plane, sb, vy, vx, dv[co]) : 0.f;
+    } else {
+      const T* p = x + org + (long long)(2 * iy0 + (tid >> 6) + 4 * i) * sc.Ws + lx;
+#pragma unroll
+      for (int co = 0; co < CMAX; ++co) xt[i][co] = (inside && co < C) ? scene_val(p[co * sc.plane], dv[co]) : 0.f;
+    }
   }
   // owned span of the window, window-local (STITCH)
   int oy_lo = 0, oy_hi = 0, ox_lo = 0, ox_hi = 0;
@@ -889,7 +963,13 @@ __device__ __forceinline__ void deconv4_scene_body(const Deconv4Args& a, const S
     long long gp = 0;
     if constexpr (STITCH) {
       own = inside && ly >= oy_lo && ly < oy_hi && lx >= ox_lo && lx < ox_hi;
-      gp = (wi * sc.S + ly) * (long long)r.Wg + wj * sc.S + lx;
+      if constexpr (BORDER) {        // spans in virtual coordinates; a store lands only where the virtual pixel is a real one
+        const long long ry = wi * sc.S + ly - sb.pt, rx = wj * sc.S + lx - sb.pl;
+        own = own && ry >= 0 && ry < sb.Hs && rx >= 0 && rx < sb.Ws;
+        gp = ry * r.Wg + rx;
+      } else {
+        gp = (wi * sc.S + ly) * (long long)r.Wg + wj * sc.S + lx;
+      }
     }
     float rs = 0.f;
 #pragma unroll
@@ -919,7 +999,7 @@ __device__ __forceinline__ void deconv4_scene_body(const Deconv4Args& a, const S
   __syncthreads();
   if (tid < BPS) r.part[(size_t)blockIdx.x * BPS + tid] = tid < C ? ((redb[0][tid] + redb[1][tid]) + redb[2][tid]) + redb[3][tid] : 0.f;
 }
-template <int SRC3, int CP, bool IDX, bool STITCH>
-__global__ __launch_bounds__(256) void deconv4_scene_kernel(Deconv4Args a, SceneSrc s, Deconv4SceneArgs r) {
-  deconv4_scene_body<SRC3, CP, IDX, STITCH>(a, s, r);
+template <int SRC3, int CP, bool IDX, bool STITCH, bool BORDER = false>
+__global__ __launch_bounds__(256) void deconv4_scene_kernel(Deconv4Args a, SceneSrcCore s, Deconv4SceneArgs r, SceneBorder sb) {
+  deconv4_scene_body<SRC3, CP, IDX, STITCH, BORDER>(a, s, r, sb);
 }

@@ -33,7 +33,7 @@ int eae_launch_edge_conv(hipStream_t st, int src3_kind, int epi, const EdgeArgs&
 }
 
 // conv1 over windows of a scene (eval-mode forward): the window gather is the kernel's patch load, no staged [B,C,P,P] batch;
-// windows first + n, or index[first + n] when s.index is set
+// windows first + n, or index[first + n] when s.index is set; the BORDER forms when s.b.mode is
 int eae_launch_edge_conv_scene(hipStream_t st, int src3_kind, const EdgeArgs& a0, const SceneSrc& s) {
   if (int rc = check_edge_shape(a0.B, a0.H, a0.W)) return rc;
   if (int rc = check_bands(a0.C)) return rc;
@@ -43,7 +43,10 @@ int eae_launch_edge_conv_scene(hipStream_t st, int src3_kind, const EdgeArgs& a0
   a.c.ntiles = (int)grid.x;
   EAE_NO_GROUP("edge_conv_scene_kernel");
 #define CASE1(S, P) if (src3_kind == S && cp == P) { \
-    if (s.index) hipLaunchKernelGGL((edge_conv_scene_kernel<S, P, true>), grid, dim3(256), 0, st, a, s); \
+    if (s.b.mode) { \
+      if (s.index) hipLaunchKernelGGL((edge_conv_scene_kernel<S, P, true, true>), grid, dim3(256), 0, st, a, s); \
+      else hipLaunchKernelGGL((edge_conv_scene_kernel<S, P, false, true>), grid, dim3(256), 0, st, a, s); \
+    } else if (s.index) hipLaunchKernelGGL((edge_conv_scene_kernel<S, P, true>), grid, dim3(256), 0, st, a, s); \
     else hipLaunchKernelGGL((edge_conv_scene_kernel<S, P>), grid, dim3(256), 0, st, a, s); \
     EAE_LAUNCH_CHECK(); return 0; }
 #define CASE(S) CASE1(S, 4) CASE1(S, 8) CASE1(S, 16)
@@ -123,7 +126,8 @@ int eae_launch_deconv4_scene(hipStream_t st, int src3_kind, const Deconv4Args& a
   dim3 grid(a.B * (a.Hin / E_TH) * (a.Win / E_TW));
   const int cp = edge_cp(a.C);
   EAE_NO_GROUP("deconv4_scene_kernel");
-#define CASE2(S, P, I, T) { hipLaunchKernelGGL((deconv4_scene_kernel<S, P, I, T>), grid, dim3(256), 0, st, a, s, r); EAE_LAUNCH_CHECK(); return 0; }
+#define CASE3(S, P, I, T, D) { hipLaunchKernelGGL((deconv4_scene_kernel<S, P, I, T, D>), grid, dim3(256), 0, st, a, (const SceneSrcCore&)s, r, s.b); EAE_LAUNCH_CHECK(); return 0; }
+#define CASE2(S, P, I, T) { if (s.b.mode) CASE3(S, P, I, T, true) else CASE3(S, P, I, T, false) }
 #define CASE1(S, P) if (src3_kind == S && cp == P) { \
     if (s.index) { if (r.recon) CASE2(S, P, true, true) else CASE2(S, P, true, false) } \
     else { if (r.recon) CASE2(S, P, false, true) else CASE2(S, P, false, false) } }
@@ -134,6 +138,7 @@ int eae_launch_deconv4_scene(hipStream_t st, int src3_kind, const Deconv4Args& a
 #undef CASE
 #undef CASE1
 #undef CASE2
+#undef CASE3
   return eae_set_error(-2, "deconv4_scene: source kind not instantiated");
 }
 

@@ -9,16 +9,22 @@
 namespace {
 
 // out[b][c][y][x] = scene[c][oy + y][ox + x] / divisor[c] for window first + b; one thread per output pixel, all bands
-template <typename T>
+// BORDER: (oy + y, ox + x) is a virtual pixel, resolved by scene_border_val (bs: the border fields of the scene; read by BORDER only)
+template <typename T, bool BORDER>
 __global__ EAE_NO_PK __launch_bounds__(256) void scene_windows_kernel(const T* __restrict__ src, const float* __restrict__ divisor, int C,
                                                                   long long plane, int Ws, int P, int S, int nW, long long first, int B,
-                                                                  float* __restrict__ out) {
+                                                                  float* __restrict__ out, SceneBorder bs) {
   const long long pp = (long long)P * P;
   const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
   if (p >= pp * B) return;
   const long long b = p / pp, r = p - b * pp;
   const int y = (int)(r / P), x = (int)(r - (long long)y * P);
   const long long w = first + b, wi = w / nW, wj = w - wi * nW;
+  if constexpr (BORDER) {
+    for (int c = 0; c < C; ++c)
+      out[(b * C + c) * pp + r] = scene_border_val<T>(src + c * plane, bs, (int)wi * S + y, (int)wj * S + x, divisor[c]);
+    return;
+  }
   const T* q = src + (wi * S + y) * (long long)Ws + wj * S + x;
   for (int c = 0; c < C; ++c) out[(b * C + c) * pp + r] = scene_val(q[c * plane], divisor[c]);
 }
@@ -76,6 +82,14 @@ __global__ EAE_NO_PK __launch_bounds__(256) void scene_blend_kernel(const float*
 //     to LDS; a block prefix sum over the chunk's pixels gives every window column its horizontal run sum in O(1) (also for S < P):
 //     rows[y][j] = number of invalid pixels in scene row y, columns j*S .. j*S + P - 1.
 //   pass 2 (scene_invalid_windows_kernel): counts[i][j] = sum of rows[i*S + r][j], r < P (one thread per window, coalesced along j).
+// BORDER (the grid over the virtual padded scene; the mapping virtual -> source pixel is separable, so the split stays): y and the
+//   columns of pass 1 are virtual coordinates, rows[] holds the virtual rows and pass 2 is unchanged.  The workgroup of virtual row y
+//   reads the row's source row; a group of V whose virtual columns are all real takes the vector path, any other group loads resolved
+//   elements, a constant pixel being the fill value itself (so it is invalid exactly when the fill matches nodata; its mask byte is 0).
+//   Reads: a real element is read once for every virtual pixel inside the extent that resolves to it.  Per axis that is 1 for constant,
+//   at most 3 for reflect (itself, a leading and a trailing mirror image) and, for edge, 1 except the first and the last row / column,
+//   which are read 1 + their pad (<= P) times: at most 9 reads of an element under reflect, P * P of a corner pixel under edge, and
+//   over the scene at most (H + pad_top + pad_bottom) x (W + pad_left + pad_right) element reads per band.
 constexpr int INV_NT = 256;               // threads of pass 1
 constexpr int INV_SPAN = INV_NT * 16;     // pixels per pass-1 workgroup (16 per thread), including the alignment shift
 
@@ -112,11 +126,11 @@ template <typename T> __device__ __forceinline__ bool inv_match(T v, int mode, T
   else return v == ref;
 }
 
-template <typename T>
+template <typename T, bool BORDER>
 __global__ EAE_NO_PK __launch_bounds__(INV_NT) void scene_invalid_rows_kernel(const T* __restrict__ src, long long plane, int C, int Ws,
                                                                            int P, int S, int nW, int J, int nchunk, int mode, float nodata,
                                                                            int rule_any, const unsigned char* __restrict__ mask,
-                                                                           int* __restrict__ rows) {
+                                                                           int* __restrict__ rows, SceneBorder bs) {
   constexpr int V = 16 / (int)sizeof(T), G = (int)sizeof(T);   // pixels per 16-byte group, groups per thread (G * V = 16)
   __shared__ unsigned char fl[INV_SPAN];
   __shared__ int pre[INV_SPAN + 1];
@@ -126,9 +140,12 @@ __global__ EAE_NO_PK __launch_bounds__(INV_NT) void scene_invalid_rows_kernel(co
   const int chunk = (int)(blockIdx.x - y * nchunk);
   const int j0 = chunk * J, jn = nW - j0 < J ? nW - j0 : J;
   const long long x0 = (long long)j0 * S, x1 = (long long)(j0 + jn - 1) * S + P;     // pixels [x0, x1) of this workgroup
-  const long long rowoff = y * Ws;
+  // BORDER: y, x0, x1, gx, lo, hi are virtual coordinates; virtual column v of this row is element rowoff + v of a band when real
+  const int pl = BORDER ? bs.pl : 0;
+  const int sy = BORDER ? scene_resolve((int)y, bs.pt, bs.Hs, bs.mode) : 0;     // source row; -1: a row of constant pixels
+  const long long rowoff = (BORDER ? (long long)(sy < 0 ? 0 : sy) : y) * Ws - pl;
   // groups start at a 16-byte boundary of band 0: xa = x0 - m
-  const int m = (int)((reinterpret_cast<uintptr_t>(src + rowoff + x0) & 15) / sizeof(T));
+  const int m = (int)(((reinterpret_cast<uintptr_t>(src) + (uintptr_t)((rowoff + x0) * (long long)sizeof(T))) & 15) / sizeof(T));
   const long long xa = x0 - m;
   const T ref = (T)(mode == EAE_NODATA_VALUE && sizeof(T) < 4 ? nodata : 0.f);
 #pragma unroll
@@ -140,8 +157,13 @@ __global__ EAE_NO_PK __launch_bounds__(INV_NT) void scene_invalid_rows_kernel(co
     const bool any_rule = rule_any != 0;
 #pragma unroll
     for (int v = 0; v < V; ++v) inv[v] = false;
+    int sx[V];                          // BORDER: source columns of the group's virtual ones, -1 = a constant pixel
+    if constexpr (BORDER) {
+#pragma unroll
+      for (int v = 0; v < V; ++v) sx[v] = sy < 0 ? -1 : scene_resolve((int)gx + v, pl, Ws, bs.mode);
+    }
     if (lo < hi) {
-      const bool full = lo == gx && hi == gx + V;
+      const bool full = lo == gx && hi == gx + V && (!BORDER || (sy >= 0 && gx >= pl && gx + V <= pl + Ws));
       if (mode != EAE_NODATA_NONE) {
 #pragma unroll
         for (int v = 0; v < V; ++v) inv[v] = !any_rule;
@@ -152,6 +174,10 @@ __global__ EAE_NO_PK __launch_bounds__(INV_NT) void scene_invalid_rows_kernel(co
           if (full && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
             const uint4 u = *reinterpret_cast<const uint4*>(p);
             __builtin_memcpy(e, &u, 16);
+          } else if constexpr (BORDER) {
+            const T* pr = src + c * plane + rowoff + pl;      // the real row
+#pragma unroll
+            for (int v = 0; v < V; ++v) e[v] = (gx + v >= lo && gx + v < hi) ? (sx[v] < 0 ? (T)bs.fill : pr[sx[v]]) : (T)0;
           } else {
 #pragma unroll
             for (int v = 0; v < V; ++v) e[v] = (gx + v >= lo && gx + v < hi) ? p[v] : (T)0;
@@ -170,6 +196,10 @@ __global__ EAE_NO_PK __launch_bounds__(INV_NT) void scene_invalid_rows_kernel(co
           if constexpr (V == 16) { const uint4 u = *reinterpret_cast<const uint4*>(p); __builtin_memcpy(e, &u, 16); }
           else if constexpr (V == 8) { const uint2 u = *reinterpret_cast<const uint2*>(p); __builtin_memcpy(e, &u, 8); }
           else { const unsigned u = *reinterpret_cast<const unsigned*>(p); __builtin_memcpy(e, &u, 4); }
+        } else if constexpr (BORDER) {
+          const unsigned char* pr = mask + rowoff + pl;
+#pragma unroll
+          for (int v = 0; v < V; ++v) e[v] = (gx + v >= lo && gx + v < hi && sx[v] >= 0) ? pr[sx[v]] : (unsigned char)0;
         } else {
 #pragma unroll
           for (int v = 0; v < V; ++v) e[v] = (gx + v >= lo && gx + v < hi) ? p[v] : (unsigned char)0;
@@ -251,10 +281,27 @@ int eae_scene_check(const eae_scene* s, long long* nH, long long* nW) {
     return eae_set_error(EAE_ERR_ARG, "scene: dtype must be EAE_SCENE_U8, EAE_SCENE_U16 or EAE_SCENE_F32");
   if (s->C < 1 || s->C > 16) return eae_set_error(EAE_ERR_ARG, "scene: in_channels must be in 1..16");
   if (s->patch <= 0 || s->patch % 64) return eae_set_error(EAE_ERR_ARG, "scene: the patch size must be a positive multiple of 64");
-  if (s->H < s->patch || s->W < s->patch) return eae_set_error(EAE_ERR_ARG, "scene: smaller than one window");
+  if (s->border < EAE_BORDER_NONE || s->border > EAE_BORDER_REFLECT) return eae_set_error(EAE_ERR_ARG, "scene: unknown border mode");
+  const int pads[4] = {s->pad_top, s->pad_bottom, s->pad_left, s->pad_right};
+  for (int p : pads) {
+    if (s->border == EAE_BORDER_NONE && p != 0) return eae_set_error(EAE_ERR_ARG, "scene: pads need a border mode");
+    if (p < 0 || p >= s->patch) return eae_set_error(EAE_ERR_ARG, "scene: every pad must be in 0..patch - 1");
+  }
+  if (s->border != EAE_BORDER_NONE && (s->H < 1 || s->W < 1)) return eae_set_error(EAE_ERR_ARG, "scene: empty scene");
+  if (s->border == EAE_BORDER_REFLECT &&
+      (s->pad_top > s->H - 1 || s->pad_bottom > s->H - 1 || s->pad_left > s->W - 1 || s->pad_right > s->W - 1))
+    return eae_set_error(EAE_ERR_ARG, "scene: a reflect pad must be smaller than the scene (one reflection)");
+  if (s->border == EAE_BORDER_CONSTANT && s->dtype != EAE_SCENE_F32) {
+    const float hi = s->dtype == EAE_SCENE_U8 ? 255.f : 65535.f;
+    if (!(s->fill >= 0.f && s->fill <= hi) || s->fill != (float)(int)s->fill)
+      return eae_set_error(EAE_ERR_ARG, "scene: fill must be an integer in the scene dtype's range");
+  }
+  // the grid lies over the virtual scene (border = NONE: the scene itself, every pad being 0)
+  const long long Hv = (long long)s->H + s->pad_top + s->pad_bottom, Wv = (long long)s->W + s->pad_left + s->pad_right;
+  if (Hv < s->patch || Wv < s->patch) return eae_set_error(EAE_ERR_ARG, "scene: smaller than one window");
   if (s->stride < 1 || s->stride > s->patch) return eae_set_error(EAE_ERR_ARG, "scene: stride must be in 1..patch");
-  *nH = (s->H - s->patch) / s->stride + 1;
-  *nW = (s->W - s->patch) / s->stride + 1;
+  *nH = (Hv - s->patch) / s->stride + 1;
+  *nW = (Wv - s->patch) / s->stride + 1;
   return 0;
 }
 
@@ -265,13 +312,18 @@ int eae_scene_src3_kind(const eae_scene* s) {
 void eae_scene_fill_src(const eae_scene* s, long long nW, long long first, SceneSrc* out) {
   out->data = s->data; out->div = s->divisor; out->first = first; out->plane = (long long)s->H * s->W;
   out->Ws = s->W; out->S = s->stride; out->nW = (int)nW;
+  out->b.mode = s->border; out->b.pt = s->pad_top; out->b.pl = s->pad_left; out->b.Hs = s->H; out->b.Ws = s->W; out->b.fill = s->fill;
 }
 
-// the one u8 / u16 / f32 dispatch: f(tag) with tag a null pointer of the scene's element type
+// the one u8 / u16 / f32 x borderless / border dispatch: f(tag, border) with tag a null pointer of the scene's element type and
+// border a std::bool_constant
 template <typename F> void scene_dtype_dispatch(const eae_scene* s, F f) {
-  if (s->dtype == EAE_SCENE_U8) f((const uint8_t*)nullptr);
-  else if (s->dtype == EAE_SCENE_U16) f((const uint16_t*)nullptr);
-  else f((const float*)nullptr);
+  auto g = [&](auto border) {
+    if (s->dtype == EAE_SCENE_U8) f((const uint8_t*)nullptr, border);
+    else if (s->dtype == EAE_SCENE_U16) f((const uint16_t*)nullptr, border);
+    else f((const float*)nullptr, border);
+  };
+  if (s->border) g(std::true_type()); else g(std::false_type());
 }
 
 extern "C" int eae_scene_windows(void* stream, const eae_scene* s, long long first, int B, float* out) {
@@ -283,10 +335,12 @@ extern "C" int eae_scene_windows(void* stream, const eae_scene* s, long long fir
   const hipStream_t st = (hipStream_t)stream;
   const long long plane = (long long)s->H * s->W, tot = (long long)B * s->patch * s->patch;
   const dim3 grid((unsigned)((tot + 255) / 256));
-  scene_dtype_dispatch(s, [&](auto* t) {
+  SceneSrc bs;
+  eae_scene_fill_src(s, nW, first, &bs);
+  scene_dtype_dispatch(s, [&](auto* t, auto border) {
     using T = std::remove_cv_t<std::remove_pointer_t<decltype(t)>>;
-    hipLaunchKernelGGL(scene_windows_kernel<T>, grid, dim3(256), 0, st, (const T*)s->data, s->divisor, s->C, plane, s->W, s->patch,
-                       s->stride, (int)nW, first, B, out);
+    hipLaunchKernelGGL((scene_windows_kernel<T, decltype(border)::value>), grid, dim3(256), 0, st, (const T*)s->data, s->divisor, s->C,
+                       plane, s->W, s->patch, s->stride, (int)nW, first, B, out, bs.b);
   });
   EAE_LAUNCH_CHECK();
   return 0;
@@ -337,10 +391,13 @@ extern "C" int eae_scene_invalid_counts(void* stream, const eae_scene* s, int no
   const long long nblk = Hg * nchunk;
   if (nblk * INV_NT > 0xffffffffLL) return eae_set_error(EAE_ERR_ARG, "scene_invalid_counts: scene too large");
   const int rany = rule == EAE_INVALID_ANY;
-  scene_dtype_dispatch(s, [&](auto* t) {
+  SceneSrc bs;
+  eae_scene_fill_src(s, nW, 0, &bs);
+  scene_dtype_dispatch(s, [&](auto* t, auto border) {
     using T = std::remove_cv_t<std::remove_pointer_t<decltype(t)>>;
-    hipLaunchKernelGGL(scene_invalid_rows_kernel<T>, dim3((unsigned)nblk), dim3(INV_NT), 0, st, (const T*)s->data, plane, s->C, s->W,
-                       s->patch, s->stride, (int)nW, J, nchunk, nodata_mode, nodata, rany, mask, rows);
+    hipLaunchKernelGGL((scene_invalid_rows_kernel<T, decltype(border)::value>), dim3((unsigned)nblk), dim3(INV_NT), 0, st,
+                       (const T*)s->data, plane, s->C, s->W, s->patch, s->stride, (int)nW, J, nchunk, nodata_mode, nodata, rany, mask,
+                       rows, bs.b);
   });
   EAE_LAUNCH_CHECK();
   const long long nwin = nH * nW;

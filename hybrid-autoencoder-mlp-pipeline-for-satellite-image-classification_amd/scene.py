@@ -31,6 +31,17 @@ MSE target from the scene itself, by the expression conv1 read it with: no [B,C,
   window that owns it, the centre S x S of each window extended to the extent's edges, so nothing is accumulated and the windows'
   border artefacts are dropped), in the units of ``scene / divisor``; ``residual=True`` adds the per-pixel band mean of
   (x_hat - x)^2 [Hg,Wg].  Pixels owned by a window that is not run hold NaN.
+
+Borders (``border="constant" | "edge" | "reflect"``, every function above): the grid is laid over a VIRTUAL padded scene that covers
+the whole raster (`border_grid`: as many windows as it takes, the excess split around the scene with ``anchor="center"`` or put
+behind it with ``anchor="origin"``), and a virtual pixel outside the scene is resolved when a kernel loads it (`border_source`): no
+padded copy is made.  Every function returns bitwise what it returns with ``border=None`` on
+``np.pad(scene, ((0,0),(pt,pb),(pl,pr)), mode)`` (``"constant"``: ``constant_values=fill``; ``"reflect"`` does not repeat the edge
+pixel) with the mask padded alike (0 in constant mode): mirrored and replicated pixels are as valid as their source, constant ones
+are invalid when ``fill`` matches ``nodata``; the error maps average over the window as the model saw it.  Window (i, j) starts at
+scene pixel (i*S - pt, j*S - pl), so with ``anchor="origin"`` cell (ci, cj) of a blended map starts at pixel (ci*S, cj*S).  Window
+and cell maps have the shapes of the virtual grid; `reconstruct_scene` returns the real scene, [C,H,W] and [H,W].  The scene may be
+smaller than one patch.
 """
 from __future__ import annotations
 
@@ -59,6 +70,54 @@ def window_grid(height, width, patch, stride):
     if height < patch or width < patch:
         raise RuntimeError(f"scene {height} x {width} is smaller than one {patch} x {patch} window")
     return (height - patch) // stride + 1, (width - patch) // stride + 1
+
+
+_BORDERS = {None: 0, "constant": 1, "edge": 2, "reflect": 3}
+
+
+def border_grid(height, width, patch, stride, anchor="center"):
+    """(nH, nW, (pt, pb, pl, pr)): the grid that covers an H x W scene and the pads of its virtual scene.  Per axis
+    n = max(0, ceil((len - P) / S)) + 1 windows span (n-1)*S + P pixels; the excess over len (< P) is split excess//2 in front and
+    the rest behind (``anchor="center"``) or put behind (``anchor="origin"``: window (i, j) starts at pixel (i*S, j*S))."""
+    height, width, patch, stride = int(height), int(width), int(patch), int(stride)
+    if patch <= 0 or patch % 64:
+        raise RuntimeError(f"the patch size must be a positive multiple of 64, got {patch}")
+    if not 1 <= stride <= patch:
+        raise RuntimeError(f"stride must be in 1..{patch} (the patch size), got {stride}")
+    if height < 1 or width < 1:
+        raise RuntimeError(f"scene {height} x {width} is empty")
+    if anchor not in ("center", "origin"):
+        raise RuntimeError(f"anchor must be 'center' or 'origin', got {anchor!r}")
+
+    def axis(n_px):
+        n = max(0, -((patch - n_px) // stride)) + 1          # -(-a // b) = ceil(a / b)
+        excess = (n - 1) * stride + patch - n_px
+        lead = excess // 2 if anchor == "center" else 0
+        return n, lead, excess - lead
+
+    n_h, pt, pb = axis(height)
+    n_w, pl, pr = axis(width)
+    return n_h, n_w, (pt, pb, pl, pr)
+
+
+def border_source(v, pad, n, mode):
+    """Source index on an axis of length n of virtual coordinate v behind a leading pad, as ``np.pad`` places it; None for a pixel
+    of the constant fill.  s = v - pad inside [0, n) is the pixel itself; "edge" clamps s to [0, n-1]; "reflect" is -s for s < 0 and
+    2(n-1) - s for s >= n (one reflection: the pads are at most n - 1)."""
+    if mode not in ("constant", "edge", "reflect"):
+        raise RuntimeError(f"border must be 'constant', 'edge' or 'reflect', got {mode!r}")
+    v, pad, n = int(v), int(pad), int(n)
+    s = v - pad
+    if 0 <= s < n:
+        return s
+    if mode == "constant":
+        return None
+    if mode == "edge":
+        return 0 if s < 0 else n - 1
+    s = -s if s < 0 else 2 * (n - 1) - s
+    if not 0 <= s < n:
+        raise RuntimeError(f"coordinate {v} needs more than one reflection of an axis of length {n} behind a pad of {pad}")
+    return s
 
 
 def window_origin(n, n_w, stride):
@@ -181,6 +240,32 @@ def _rule_arg(rule):
     return _RULES[rule]
 
 
+def _border_arg(scene, patch, stride, border, fill, anchor):
+    """(mode id, fill, nH, nW, pads) for a scene that has passed `_check_scene`: the grid of whole windows for border=None, else
+    `border_grid` and the checks of the mode."""
+    h, w = int(scene.shape[1]), int(scene.shape[2])
+    if border not in _BORDERS:
+        raise RuntimeError(f"border must be None, 'constant', 'edge' or 'reflect', got {border!r}")
+    if anchor not in ("center", "origin"):
+        raise RuntimeError(f"anchor must be 'center' or 'origin', got {anchor!r}")
+    if isinstance(fill, bool) or not isinstance(fill, numbers.Real):
+        raise RuntimeError(f"fill must be a number, got {fill!r}")
+    fill = float(fill)
+    if border != "constant":
+        if fill != 0.0:
+            raise RuntimeError(f"fill is the value of border='constant' pixels; got fill={fill!r} with border={border!r}")
+        if border is None:
+            return (0, 0.0) + window_grid(h, w, patch, stride) + ((0, 0, 0, 0),)
+    elif scene.dtype in _INT_RANGE and (math.isnan(fill) or not fill.is_integer() or not 0 <= fill <= _INT_RANGE[scene.dtype]):
+        raise RuntimeError(f"fill of a {str(scene.dtype).replace('torch.', '')} scene must be an integer in "
+                           f"0..{_INT_RANGE[scene.dtype]}, got {fill!r}")
+    n_h, n_w, pads = border_grid(h, w, patch, stride, anchor)
+    if border == "reflect" and (max(pads[:2]) > h - 1 or max(pads[2:]) > w - 1):
+        raise RuntimeError(f"border='reflect' mirrors once: the pads {pads} (top, bottom, left, right) must stay below the scene's "
+                           f"{h} x {w}")
+    return _BORDERS[border], fill, n_h, n_w, pads
+
+
 def _check_scene(scene):
     """The one check of the scene tensor's rank and dtype."""
     if not isinstance(scene, torch.Tensor) or scene.dim() != 3:
@@ -222,14 +307,14 @@ def _encoder_of(encoder):
     raise RuntimeError(f"encoder must be an Encoder or a SupervisedAutoencoder, got {type(encoder).__name__}")
 
 
-def _scene_desc(scene, divisor, patch, stride):
-    """(EaeScene, keep-alive tensors, nH, nW) of a scene that has passed `_check_scene`: device, band count, grid and divisor are
-    validated here, before any kernel."""
-    _require_gpu(scene.device)
+def _scene_desc(scene, divisor, patch, stride, border=None, fill=0, anchor="center"):
+    """(EaeScene, keep-alive tensors, nH, nW) of a scene that has passed `_check_scene`: device, band count, grid (of the virtual
+    scene under a border), border arguments and divisor are validated here, before any kernel."""
     c, h, w = (int(v) for v in scene.shape)
+    mode, fill, n_h, n_w, pads = _border_arg(scene, patch, stride, border, fill, anchor)
+    _require_gpu(scene.device)
     if not 1 <= c <= 16:
         raise RuntimeError(f"scene: in_channels must be in 1..16, got {c}")
-    n_h, n_w = window_grid(h, w, patch, stride)
     div = torch.as_tensor(divisor, dtype=torch.float32).reshape(-1)
     if div.numel() == 1:
         div = div.expand(c)
@@ -238,7 +323,7 @@ def _scene_desc(scene, divisor, patch, stride):
     div = div.to(scene.device).contiguous()
     scene = scene.contiguous()
     desc = _lib.EaeScene(C.c_void_p(scene.data_ptr()), C.c_void_p(div.data_ptr()), _DTYPES[scene.dtype], c, h, w, int(patch),
-                         int(stride))
+                         int(stride), mode, *pads, fill)
     return desc, (scene, div), n_h, n_w
 
 
@@ -271,10 +356,11 @@ def _range(first, count, total):
 
 
 # ---------------------------------------------------------------------------------------------------- public functions
-def scene_windows(scene, divisor, patch, stride, first=0, count=None):
-    """fp32 NCHW [count,C,P,P] of windows first .. first+count-1 (count=None: to the end of the grid)."""
+def scene_windows(scene, divisor, patch, stride, first=0, count=None, border=None, fill=0, anchor="center"):
+    """fp32 NCHW [count,C,P,P] of windows first .. first+count-1 (count=None: to the end of the grid).  border / fill / anchor:
+    module docstring, "Borders"."""
     _check_scene(scene)
-    desc, keep, n_h, n_w = _scene_desc(scene, divisor, patch, stride)
+    desc, keep, n_h, n_w = _scene_desc(scene, divisor, patch, stride, border, fill, anchor)
     first, count = _range(first, count, n_h * n_w)
     lib = _lib.load()
     out = torch.empty((count, keep[0].shape[0], int(patch), int(patch)), dtype=torch.float32, device=keep[0].device)
@@ -283,20 +369,21 @@ def scene_windows(scene, divisor, patch, stride, first=0, count=None):
     return out
 
 
-def window_invalid_counts(scene, patch, stride, nodata=None, mask=None, rule="all"):
+def window_invalid_counts(scene, patch, stride, nodata=None, mask=None, rule="all", border=None, fill=0, anchor="center"):
     """Invalid pixels of every P x P window at stride S: int32 [nH, nW] on the scene's device (see the module docstring for what
-    makes a pixel invalid).  Every scene element and mask byte inside the grid's extent is read once."""
+    makes a pixel invalid).  Every scene element and mask byte inside the grid's extent is read once (under a border: once per
+    virtual pixel that resolves to it)."""
     mode, value, rid, m = _invalid_args(scene, nodata, mask, rule)
-    desc, keep, n_h, n_w = _scene_desc(scene, 1.0, patch, stride)
+    desc, keep, n_h, n_w = _scene_desc(scene, 1.0, patch, stride, border, fill, anchor)
     return _invalid_counts(desc, keep + (m,), n_h, n_w, mode, value, rid, m)
 
 
-def valid_windows(scene, patch, stride, nodata=None, mask=None, max_invalid=0.0, rule="all"):
+def valid_windows(scene, patch, stride, nodata=None, mask=None, max_invalid=0.0, rule="all", border=None, fill=0, anchor="center"):
     """Ascending int64 ids (on the scene's device) of the windows with at most floor(max_invalid * P * P) invalid pixels.
     The number of valid windows is read back once (``.item()``) to size the result: this is the one host synchronisation of the
     nodata / mask path."""
     t = invalid_threshold(patch, max_invalid)
-    counts = window_invalid_counts(scene, patch, stride, nodata=nodata, mask=mask, rule=rule)
+    counts = window_invalid_counts(scene, patch, stride, nodata=nodata, mask=mask, rule=rule, border=border, fill=fill, anchor=anchor)
     return _select(counts, t)
 
 
@@ -345,7 +432,7 @@ class _Plan(NamedTuple):
 
 
 def _plan(scene, encoder, divisor, stride, batch, nodata=None, mask=None, max_invalid=0.0, rule="all", windows=None, allow_empty=True,
-          blend=False, stitched=False):
+          blend=False, stitched=False, border=None, fill=0, anchor="center"):
     """Every model-running function starts here: (1) all host-side validation, before an engine exists or a kernel runs; (2) `_prepare`;
     (3) the window set -- None for the whole grid, the given ids, or under nodata / mask the valid ids (`_select`: the one ``.item()``)."""
     rid = _rule_arg(rule)
@@ -357,7 +444,7 @@ def _plan(scene, encoder, divisor, stride, batch, nodata=None, mask=None, max_in
     if windows is not None and masked:
         raise RuntimeError("windows= cannot be combined with nodata= or mask=")
     _check_scene(scene)
-    desc, keep, n_h, n_w = _scene_desc(scene, divisor, patch, stride)
+    desc, keep, n_h, n_w = _scene_desc(scene, divisor, patch, stride, border, fill, anchor)
     if blend:
         cell_grid(n_h, n_w, patch, stride)               # the stride must divide the patch size
     if stitched:
@@ -372,11 +459,12 @@ def _plan(scene, encoder, divisor, stride, batch, nodata=None, mask=None, max_in
     return _Plan(eng, desc, keep, n_h, n_w, patch, stride, windows)
 
 
-def encode_scene(scene, encoder, divisor=1.0, stride=None, batch=512, windows=None):
+def encode_scene(scene, encoder, divisor=1.0, stride=None, batch=512, windows=None, border=None, fill=0, anchor="center"):
     """Latents z [nH*nW, L] of every window (row n = window i*nW + j), eval-mode encoder, `batch` windows per encoder pass (the
     engine's max_batch, at least this).  stride=None: the patch size (non-overlapping windows).
-    windows: a non-empty 1-D int64 device tensor of window ids (any order, duplicates allowed): z [len(windows), L] in that order."""
-    p = _plan(scene, encoder, divisor, stride, batch, windows=windows, allow_empty=False)
+    windows: a non-empty 1-D int64 device tensor of window ids (any order, duplicates allowed): z [len(windows), L] in that order.
+    border / fill / anchor: module docstring, "Borders" (the grid is then `border_grid`'s)."""
+    p = _plan(scene, encoder, divisor, stride, batch, windows=windows, allow_empty=False, border=border, fill=fill, anchor=anchor)
     eng = p.eng
     n = p.n_h * p.n_w if p.windows is None else p.windows.numel()
     z = torch.empty((n, eng.latent), dtype=torch.float32, device=eng.device)
@@ -385,7 +473,7 @@ def encode_scene(scene, encoder, divisor=1.0, stride=None, batch=512, windows=No
 
 
 def classify_scene(scene, encoder, mlp, divisor=1.0, stride=None, batch=512, blend=False, nodata=None, mask=None, max_invalid=0.0,
-                   rule="all", windows=None):
+                   rule="all", windows=None, border=None, fill=0, anchor="center"):
     """(probs [K,nH,nW] float32 softmax, labels [nH,nW] int64 argmax) of every window: encoder -> MLP in eval mode, one C call.
     blend=True (stride divides the patch size, k = P/S): the map of S x S cells instead, probs [K,nH+k-1,nW+k-1] = mean over the
     windows covering each cell, labels = argmax of that map.
@@ -393,7 +481,10 @@ def classify_scene(scene, encoder, mlp, divisor=1.0, stride=None, batch=512, ble
     nodata / mask / max_invalid / rule (module docstring): only the valid windows are encoded (`valid_windows`, one host readback);
     windows: a 1-D int64 device tensor of window ids, the only windows classified (not combined with nodata / mask).  Either way the
     other windows get label -1 and probability 0, and blend=True averages each cell over its classified windows only (no such
-    window: label -1, probabilities 0).  Without a valid window nothing is launched.  With all of them None the plain path runs."""
+    window: label -1, probabilities 0).  Without a valid window nothing is launched.  With all of them None the plain path runs.
+
+    border / fill / anchor (module docstring, "Borders"): the grid covers the whole scene (`border_grid`), so every pixel lies in a
+    window and, with blend=True, in a cell of the virtual grid's cell map."""
     from .mlp_engine import mlp_engine_for
     from .modules import MLP
     if not isinstance(mlp, MLP):
@@ -401,7 +492,8 @@ def classify_scene(scene, encoder, mlp, divisor=1.0, stride=None, batch=512, ble
     enc = _encoder_of(encoder)
     if int(mlp.input_dim) != int(enc.latent_dim):
         raise RuntimeError(f"the MLP takes input_dim={mlp.input_dim}, the encoder's latent_dim is {enc.latent_dim}")
-    p = _plan(scene, encoder, divisor, stride, batch, nodata, mask, max_invalid, rule, windows, blend=blend)
+    p = _plan(scene, encoder, divisor, stride, batch, nodata, mask, max_invalid, rule, windows, blend=blend, border=border, fill=fill,
+              anchor=anchor)
     eng, n_h, n_w = p.eng, p.n_h, p.n_w
     if next(mlp.parameters()).device != eng.device:
         raise RuntimeError("the MLP and the encoder must be on the same device")
@@ -431,16 +523,18 @@ def _autoencoder_arg(autoencoder):
 
 
 def scene_reconstruction_error(scene, autoencoder, divisor=1.0, stride=None, batch=512, per_band=False, nodata=None, mask=None,
-                               max_invalid=0.0, rule="all", windows=None):
+                               max_invalid=0.0, rule="all", windows=None, border=None, fill=0, anchor="center"):
     """err [nH,nW] float32: the mean of (x_hat - x)^2 over the C*P*P elements of every window, x = scene / divisor as the encoder
     read it, x_hat = the eval-mode autoencoder's reconstruction of the window; one C call, no staged batch (module docstring).
     per_band=True: (err, band_err [C,nH,nW]), the mean over each band.  The sums are deterministic and do not depend on ``batch``.
 
     nodata / mask / max_invalid / rule: only the valid windows are run (`valid_windows`, one host readback); windows: a 1-D int64
     device tensor of window ids, the only windows run (not combined with nodata / mask).  Either way the other windows hold NaN;
-    without a window to run nothing is launched.  A valid window that holds some invalid pixels is scored with them as stored."""
+    without a window to run nothing is launched.  A valid window that holds some invalid pixels is scored with them as stored.
+    border / fill / anchor (module docstring, "Borders"): the mean runs over the window as the model saw it, padded pixels included."""
     _autoencoder_arg(autoencoder)
-    p = _plan(scene, autoencoder, divisor, stride, batch, nodata, mask, max_invalid, rule, windows)
+    p = _plan(scene, autoencoder, divisor, stride, batch, nodata, mask, max_invalid, rule, windows, border=border, fill=fill,
+              anchor=anchor)
     err = p.out((p.n_h, p.n_w), float("nan"))
     band = p.out((p.desc.C, p.n_h, p.n_w), float("nan")) if per_band else None
     p.run(p.eng.lib.eae_scene_recon_error, p.eng.lib.eae_scene_recon_error_windows, err, band)
@@ -448,16 +542,22 @@ def scene_reconstruction_error(scene, autoencoder, divisor=1.0, stride=None, bat
 
 
 def reconstruct_scene(scene, autoencoder, divisor=1.0, stride=None, batch=512, residual=False, nodata=None, mask=None,
-                      max_invalid=0.0, rule="all", windows=None):
+                      max_invalid=0.0, rule="all", windows=None, border=None, fill=0, anchor="center"):
     """recon [C,Hg,Wg] float32 over the grid's extent (Hg = (nH-1)*S + P): the eval-mode autoencoder's x_hat of every window, each
     pixel taken from the one window that owns it (`owned_span`; patch - stride must be even), in the units of ``scene / divisor``.
     residual=True: (recon, residual [Hg,Wg]), the mean over the bands of (x_hat - x)^2 of each pixel.
 
     nodata / mask / max_invalid / rule / windows as for `scene_reconstruction_error`: pixels owned by a window that is not run hold
-    NaN (in both outputs)."""
+    NaN (in both outputs).
+
+    border / fill / anchor (module docstring, "Borders"): recon [C,H,W] and residual [H,W] of the REAL scene.  The owned spans are
+    those of the virtual grid, which covers the scene, so every pixel has an owner; a window stores the real pixels of its span."""
     _autoencoder_arg(autoencoder)
-    p = _plan(scene, autoencoder, divisor, stride, batch, nodata, mask, max_invalid, rule, windows, stitched=True)
+    p = _plan(scene, autoencoder, divisor, stride, batch, nodata, mask, max_invalid, rule, windows, stitched=True, border=border,
+              fill=fill, anchor=anchor)
     h_g, w_g = (p.n_h - 1) * p.stride + p.patch, (p.n_w - 1) * p.stride + p.patch
+    if border is not None:
+        h_g, w_g = p.desc.H, p.desc.W
     recon = p.out((p.desc.C, h_g, w_g), float("nan"))
     res = p.out((h_g, w_g), float("nan")) if residual else None
     fn = p.eng.lib.eae_scene_reconstruct                 # one entry point: windows = NULL is the whole grid

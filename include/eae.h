@@ -398,7 +398,26 @@ typedef struct eae_scene {
   const float* divisor;    /* [C] on the device */
   int dtype, C, H, W;
   int patch, stride;       /* P, S */
+  int border;              /* EAE_BORDER_*; every field from here on zero: the grid of whole windows described above */
+  int pad_top, pad_bottom, pad_left, pad_right;
+  float fill;              /* the stored value of an EAE_BORDER_CONSTANT pixel */
 } eae_scene;
+/* Border modes.  With border != EAE_BORDER_NONE the window grid is laid over the VIRTUAL scene of (pad_top + H + pad_bottom) x
+ * (pad_left + W + pad_right) pixels: nH = (pad_top + H + pad_bottom - P) / S + 1, nW alike, and window (i, j) starts at scene pixel
+ * (i * S - pad_top, j * S - pad_left).  Every call that takes an eae_scene returns bitwise what it returns for border = NONE on
+ * numpy.pad(scene, ((0, 0), (pad_top, pad_bottom), (pad_left, pad_right)), mode) (and the mask padded alike, with 0 in constant mode);
+ * no padded copy is made: the kernels resolve a virtual pixel when they load it.  With s = v - pad the source index of virtual
+ * coordinate v on an axis of length n is s inside [0, n); EDGE clamps s to [0, n - 1]; REFLECT takes -s for s < 0 and 2 (n - 1) - s
+ * for s >= n (numpy's "reflect": the edge pixel is not repeated); a CONSTANT pixel has the value (float)fill / divisor[c], and is
+ * invalid for eae_scene_invalid_counts when fill matches the nodata value.  Replicated and mirrored pixels are as valid as their source.
+ * Rejected (EAE_ERR_ARG): a pad outside 0..P - 1, a virtual size below P, REFLECT with pad_top or pad_bottom > H - 1 or pad_left or
+ * pad_right > W - 1 (one reflection only), a fill of a uint8 / uint16 scene that is no integer of the dtype's range, an unknown mode, and
+ * border = NONE with a non-zero pad.  The real scene may be smaller than P.  Window and cell maps keep their shapes, of the virtual
+ * grid; eae_scene_reconstruct writes the REAL scene (see there). */
+#define EAE_BORDER_NONE 0
+#define EAE_BORDER_CONSTANT 1
+#define EAE_BORDER_EDGE 2
+#define EAE_BORDER_REFLECT 3
 /* fp32 NCHW [B,C,P,P] of windows first_window .. first_window + B - 1: bitwise eae_stage_bands(train = 0) on the same windows. */
 int eae_scene_windows(void* stream, const eae_scene* scene, long long first_window, int B, float* out);
 /* Eval-mode encoder over windows first_window .. + B - 1 (any B: split at max_batch inside), conv1 reading the scene directly
@@ -418,8 +437,10 @@ int eae_scene_blend(void* stream, const float* probs, int K, int nH, int nW, int
  * rasterio's dataset-mask convention; EAE_INVALID_ANY: at least one band does) or when mask[y * W + x] != 0 (mask: uint8 [H][W] on the
  * device, or NULL).  nodata_mode EAE_NODATA_NONE ignores nodata; EAE_NODATA_VALUE compares with nodata (for uint8 / uint16 scenes an
  * integer in the dtype's range, else rejected; for fp32 by ==); EAE_NODATA_NAN matches NaN (fp32 scenes only).
- * counts [nH][nW] (int32) = invalid pixels of each window.  rows is scratch of Hg * nW ints, Hg = (nH - 1) * S + P.  Every scene
- * element and mask byte inside the grid's extent is read once; the divisor is not read.  The patch size must be at most 4080. */
+ * counts [nH][nW] (int32) = invalid pixels of each window.  rows is scratch of Hg * nW ints, Hg = (nH - 1) * S + P (with a border:
+ * nH and nW of the virtual grid, so Hg is the virtual extent).  Every scene element and mask byte inside the grid's extent is read
+ * once (with a border: once for every virtual pixel inside the extent that resolves to it); the divisor is not
+ * read.  The patch size must be at most 4080. */
 #define EAE_NODATA_NONE 0
 #define EAE_NODATA_VALUE 1
 #define EAE_NODATA_NAN 2
@@ -465,7 +486,9 @@ int eae_scene_blend_valid(void* stream, const float* probs, const long long* lab
  * Every pixel of the extent is OWNED by exactly one window and is written by that window alone (plain stores, no accumulation): with
  * m = (P - S) / 2, window row i owns scene rows [i * S + m, i * S + m + S), extended to 0 for i = 0 and to Hg for i = nH - 1; columns
  * alike.  P - S must be even.  windows == NULL: windows 0 .. count - 1 (count = nH * nW: the whole extent); else the listed ids, and
- * the pixels owned by other windows are left as the caller filled them. */
+ * the pixels owned by other windows are left as the caller filled them.  With a border the spans are those of the virtual grid and
+ * recon is [C][H][W], residual [H][W], of the real scene: a window stores the pixels it owns that are real ones, and every real
+ * pixel has an owner because the virtual extent covers the scene when the pads are those of a full grid. */
 int eae_set_halves(eae_ctx* ctx, int encoder, int decoder);
 int eae_scene_recon_error(eae_ctx* ctx, void* stream, const eae_scene* scene, long long first_window, long long count, float* err,
                           float* band_err);
