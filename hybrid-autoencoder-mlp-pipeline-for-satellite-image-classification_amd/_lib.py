@@ -136,6 +136,9 @@ _PROTOS = {
     "eae_scene_recon_error": (C.c_int, [vp, vp, C.POINTER(EaeScene), C.c_longlong, C.c_longlong, vp, vp]),
     "eae_scene_recon_error_windows": (C.c_int, [vp, vp, C.POINTER(EaeScene), vp, C.c_longlong, vp, vp]),
     "eae_scene_reconstruct": (C.c_int, [vp, vp, C.POINTER(EaeScene), vp, C.c_longlong, vp, vp]),
+    "eae_scene_stage_windows": (C.c_int, [vp, C.POINTER(EaeScene), vp, C.c_int, vp, C.c_int, C.c_float, C.c_ulonglong, C.c_ulonglong,
+                                          vp, vp, C.c_int]),
+    "eae_scene_window_labels": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
 }
 
 EXPORTS = tuple(_PROTOS.keys())

@@ -696,18 +696,6 @@ int eae_launch_adam_scaled(hipStream_t st, float* p, const float* g, float* m, f
 // Per-image (flip, top, left) and the noise come from a counter-based Philox4x32-10 stream keyed by (seed, step) unless
 // explicit `params` [B][3] / `noise` [B,3,H,W] are supplied (parity tests).
 // ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox4(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t* o) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-    uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-    uint32_t n0 = h1 ^ c1 ^ k0, n1 = l1, n2 = h0 ^ c3 ^ k1, n3 = l0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
-
 __global__ EAE_NO_PK __launch_bounds__(256) void augment_kernel(const uint8_t* __restrict__ in, float* __restrict__ out, int B, int H, int W,
                                                        int train, float std, unsigned long long seed, unsigned long long step,
                                                        const int* __restrict__ params, const float* __restrict__ noise) {
@@ -774,11 +762,7 @@ __global__ EAE_NO_PK __launch_bounds__(256) void stage_bands_kernel(const T* __r
   int flip = 0, top = 4, left = 4;
   if (train) {
     if (params) { flip = params[b * 3]; top = params[b * 3 + 1]; left = params[b * 3 + 2]; }
-    else {
-      uint32_t o[4];
-      philox4((uint32_t)b, 0x5eedu, (uint32_t)step, (uint32_t)(step >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), o);
-      flip = o[0] >> 31; top = (int)(((unsigned long long)o[1] * 9) >> 32); left = (int)(((unsigned long long)o[2] * 9) >> 32);
-    }
+    else stage_draw_params(b, seed, step, flip, top, left);
   }
   const int sy = y + top - 4;
   int sx = x + left - 4;
@@ -787,16 +771,7 @@ __global__ EAE_NO_PK __launch_bounds__(256) void stage_bands_kernel(const T* __r
   const T* q = src + (inside ? (((size_t)n * C * H + sy) * W + sx) : (size_t)0);
   for (int c0 = 0; c0 < C; c0 += 4) {
     float z[4] = {0.f, 0.f, 0.f, 0.f};
-    if (train && std != 0.f && !noise) {
-      uint32_t o[4];
-      philox4((uint32_t)p, ((uint32_t)(p >> 32) ^ 0xA5A5u) + ((uint32_t)c0 << 16), (uint32_t)step, (uint32_t)(step >> 32), (uint32_t)seed,
-              ~(uint32_t)(seed >> 32), o);
-      const float u1 = ((o[0] >> 8) + 1) * (1.0f / 16777216.0f), u2 = (o[1] >> 8) * (1.0f / 16777216.0f);
-      const float u3 = ((o[2] >> 8) + 1) * (1.0f / 16777216.0f), u4 = (o[3] >> 8) * (1.0f / 16777216.0f);
-      const float r1 = sqrtf(-2.0f * __logf(u1)), r2 = sqrtf(-2.0f * __logf(u3));
-      z[0] = r1 * __cosf(6.28318530718f * u2); z[1] = r1 * __sinf(6.28318530718f * u2);
-      z[2] = r2 * __cosf(6.28318530718f * u4); z[3] = r2 * __sinf(6.28318530718f * u4);
-    }
+    if (train && std != 0.f && !noise) stage_draw_noise4(p, c0, seed, step, z);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int c = c0 + j;

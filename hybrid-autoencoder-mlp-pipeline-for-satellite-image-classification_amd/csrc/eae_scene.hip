@@ -1,7 +1,8 @@
 // Scene classification helpers (include/eae.h, "scene classification"): the window gather (the public way to get patches, and the
 // reference the fused conv1 scene source is tested against), the cell blends of window probabilities, and the nodata / mask path:
-// per-window invalid-pixel counts and the compaction of the valid window ids.  None uses matrix instructions, so all are built with
-// packed FP32 disabled (EAE_NO_PK, tests/test_isa_guard.py).
+// per-window invalid-pixel counts and the compaction of the valid window ids; and training from a scene (include/eae.h, "training from
+// a scene"): augmented window batches and a label for every window from a label raster.  None uses matrix instructions, so all are
+// built with packed FP32 disabled (EAE_NO_PK, tests/test_isa_guard.py).
 #include "eae_internal.h"
 #include "eae_common.hip.h"
 #include "eae_edge.hip.h"
@@ -269,18 +270,120 @@ __global__ EAE_NO_PK __launch_bounds__(SEL_NT) void scene_select_kernel(const in
   if (tid == 0) *count_out = base;
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------- training from a scene
+// stage_bands_kernel (eae_misc.hip) with the image of batch position b gathered from the scene: window windows[b], origin (oy, ox).
+//   out[b,c,y,x] = scene[c, oy + sy, ox + sx] / divisor[c] (or 0) + std * N(0,1),  sy = y + top - 4, sx = x + left - 4, flipped: P-1-sx
+// One thread per output pixel, all bands; p is the flat index over [B][P][P], the index stage_bands_kernel has for [B,C,P,P] images, so
+// stage_draw_params(b) and stage_draw_noise4(p, c0) (eae_misc.h) are the draws that kernel makes.  CROP_SCENE = false: (sy, unflipped
+// sx) outside [0, P) reads 0, which keeps every read inside the window.  CROP_SCENE = true: the read is bounds-checked against the
+// scene instead, so the crop slides the window over its real neighbourhood.  An id outside [0, nwin) gives NaN and reads nothing.
+template <typename T, bool CROP_SCENE>
+__global__ EAE_NO_PK __launch_bounds__(256) void scene_stage_windows_kernel(const T* __restrict__ src, const float* __restrict__ divisor,
+                                                                        int C, long long plane, int Hs, int Ws, int P, int S, int nW,
+                                                                        long long nwin, const long long* __restrict__ windows, int B,
+                                                                        float* __restrict__ out, int train, float std,
+                                                                        unsigned long long seed, unsigned long long step,
+                                                                        const int* __restrict__ params, const float* __restrict__ noise) {
+  const long long pp = (long long)P * P;
+  const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= pp * B) return;
+  const int b = (int)(p / pp);
+  const long long r = p - b * pp;
+  const int y = (int)(r / P), x = (int)(r - (long long)y * P);
+  const long long w = windows[b];
+  const bool valid = w >= 0 && w < nwin;
+  int flip = 0, top = 4, left = 4;
+  if (train) {
+    if (params) { flip = params[b * 3]; top = params[b * 3 + 1]; left = params[b * 3 + 2]; }
+    else stage_draw_params(b, seed, step, flip, top, left);
+  }
+  const long long sy = (long long)y + top - 4;
+  long long sx = (long long)x + left - 4;
+  bool inside = valid;
+  if constexpr (!CROP_SCENE) inside = inside && sy >= 0 && sy < P && sx >= 0 && sx < P;
+  if (flip) sx = P - 1 - sx;
+  const long long wi = valid ? w / nW : 0, wj = valid ? w - wi * nW : 0;
+  const long long gy = wi * S + sy, gx = wj * S + sx;                  // scene pixel
+  if constexpr (CROP_SCENE) inside = inside && gy >= 0 && gy < Hs && gx >= 0 && gx < Ws;
+  const T* q = src + (inside ? gy * Ws + gx : 0);
+  for (int c0 = 0; c0 < C; c0 += 4) {
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+    if (train && std != 0.f && !noise) stage_draw_noise4(p, c0, seed, step, z);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int c = c0 + j;
+      if (c >= C) break;
+      float v = inside ? scene_val(q[c * plane], divisor[c]) : 0.f;
+      if (!valid) v = __builtin_nanf("");
+      if (train && std != 0.f) v = fmaf(std, noise ? noise[((long long)b * C + c) * pp + r] : z[j], v);
+      out[((long long)b * C + c) * pp + r] = v;
+    }
+  }
+}
+
+// One workgroup per window: every wave counts the labelled pixels (values in [0, K)) it reads into its own K-bin LDS histogram, a
+// thread adding a run of equal classes with one atomic (land-cover windows are mostly one class: a run is usually the thread's whole
+// share); wave 0 then sums the waves' bins in wave order, lane = class, and reduces (count, class) to the largest count, the lowest
+// class on a tie.  Integer counts: exact and identical from run to run.
+constexpr int LBL_NT = 256;
+template <typename T>
+__global__ EAE_NO_PK __launch_bounds__(LBL_NT) void scene_window_labels_kernel(const T* __restrict__ raster, int W, int P, int S, int nW,
+                                                                            int K, long long* __restrict__ label,
+                                                                            int* __restrict__ count, int* __restrict__ labelled) {
+  __shared__ int hist[LBL_NT / 64][64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long n = blockIdx.x, wi = n / nW, wj = n - wi * nW;
+  hist[wave][lane] = 0;
+  __syncthreads();
+  const T* q = raster + wi * S * (long long)W + wj * S;
+  int cur = -1, run = 0;
+  for (int i = tid; i < P * P; i += LBL_NT) {
+    const int y = i / P, x = i - y * P;
+    const long long v = (long long)q[(long long)y * W + x];
+    const int k = v >= 0 && v < K ? (int)v : -1;
+    if (k != cur) {
+      if (cur >= 0) atomicAdd(&hist[wave][cur], run);
+      cur = k;
+      run = 0;
+    }
+    ++run;
+  }
+  if (cur >= 0) atomicAdd(&hist[wave][cur], run);
+  __syncthreads();
+  if (wave != 0) return;
+  int best = 0;
+#pragma unroll
+  for (int w = 0; w < LBL_NT / 64; ++w) best += hist[w][lane];       // lanes K .. 63 hold 0
+  int tot = best, cls = lane;
+#pragma unroll
+  for (int d = 32; d; d >>= 1) {
+    tot += __shfl_xor(tot, d, 64);
+    const int ob = __shfl_xor(best, d, 64), oc = __shfl_xor(cls, d, 64);
+    if (ob > best || (ob == best && oc < cls)) { best = ob; cls = oc; }
+  }
+  if (lane == 0) {
+    label[n] = tot ? cls : -1;
+    if (count) count[n] = tot ? best : 0;
+    if (labelled) labelled[n] = tot;
+  }
+}
+
 }  // namespace
 
 long long eae_scene_extent(long long n, int patch, int stride) { return (n - 1) * stride + patch; }
 
-int eae_scene_check(const eae_scene* s, long long* nH, long long* nW) {
+// model: the windows feed the model, whose image size is a multiple of 64; the model-free calls (eae_scene_windows, training from a
+// scene) take any patch size
+static int scene_check(const eae_scene* s, long long* nH, long long* nW, bool model) {
   if (!s) return eae_set_error(EAE_ERR_ARG, "scene: NULL scene");
   if (!s->data) return eae_set_error(EAE_ERR_ARG, "scene: NULL data");
   if (!s->divisor) return eae_set_error(EAE_ERR_ARG, "scene: NULL divisor");
   if (s->dtype != EAE_SCENE_U8 && s->dtype != EAE_SCENE_U16 && s->dtype != EAE_SCENE_F32)
     return eae_set_error(EAE_ERR_ARG, "scene: dtype must be EAE_SCENE_U8, EAE_SCENE_U16 or EAE_SCENE_F32");
   if (s->C < 1 || s->C > 16) return eae_set_error(EAE_ERR_ARG, "scene: in_channels must be in 1..16");
-  if (s->patch <= 0 || s->patch % 64) return eae_set_error(EAE_ERR_ARG, "scene: the patch size must be a positive multiple of 64");
+  if (s->patch <= 0 || (model && s->patch % 64))
+    return eae_set_error(EAE_ERR_ARG, model ? "scene: the patch size must be a positive multiple of 64" : "scene: the patch size must be positive");
   if (s->border < EAE_BORDER_NONE || s->border > EAE_BORDER_REFLECT) return eae_set_error(EAE_ERR_ARG, "scene: unknown border mode");
   const int pads[4] = {s->pad_top, s->pad_bottom, s->pad_left, s->pad_right};
   for (int p : pads) {
@@ -304,6 +407,7 @@ int eae_scene_check(const eae_scene* s, long long* nH, long long* nW) {
   *nW = (Wv - s->patch) / s->stride + 1;
   return 0;
 }
+int eae_scene_check(const eae_scene* s, long long* nH, long long* nW) { return scene_check(s, nH, nW, true); }
 
 int eae_scene_src3_kind(const eae_scene* s) {
   return s->dtype == EAE_SCENE_U8 ? SRC3_SCENE_U8 : s->dtype == EAE_SCENE_U16 ? SRC3_SCENE_U16 : SRC3_SCENE_F32;
@@ -328,7 +432,7 @@ template <typename F> void scene_dtype_dispatch(const eae_scene* s, F f) {
 
 extern "C" int eae_scene_windows(void* stream, const eae_scene* s, long long first, int B, float* out) {
   long long nH = 0, nW = 0;
-  if (int rc = eae_scene_check(s, &nH, &nW)) return rc;
+  if (int rc = scene_check(s, &nH, &nW, false)) return rc;
   if (!out) return eae_set_error(EAE_ERR_ARG, "scene_windows: NULL output");
   if (B <= 0 || first < 0 || first + B > nH * nW) return eae_set_error(EAE_ERR_ARG, "scene_windows: windows outside the grid");
   EAE_NO_GROUP("scene_windows_kernel");
@@ -412,6 +516,55 @@ extern "C" int eae_scene_select(void* stream, const int* counts, long long n, in
   if (n < 1) return eae_set_error(EAE_ERR_ARG, "scene_select: empty grid");
   EAE_NO_GROUP("scene_select_kernel");
   hipLaunchKernelGGL(scene_select_kernel, dim3(1), dim3(SEL_NT), 0, (hipStream_t)stream, counts, n, threshold, windows, count);
+  EAE_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int eae_scene_stage_windows(void* stream, const eae_scene* s, const long long* windows, int B, float* out, int train,
+                                       float noise_std, unsigned long long seed, unsigned long long step, const int* params,
+                                       const float* noise, int crop) {
+  long long nH = 0, nW = 0;
+  if (int rc = scene_check(s, &nH, &nW, false)) return rc;
+  if (s->border != EAE_BORDER_NONE) return eae_set_error(EAE_ERR_ARG, "scene_stage_windows: border modes are not supported");
+  if (!windows || !out) return eae_set_error(EAE_ERR_ARG, "scene_stage_windows: NULL windows or output");
+  if (B <= 0) return eae_set_error(EAE_ERR_ARG, "scene_stage_windows: B must be positive");
+  if (crop != EAE_CROP_WINDOW && crop != EAE_CROP_SCENE) return eae_set_error(EAE_ERR_ARG, "scene_stage_windows: unknown crop mode");
+  const long long plane = (long long)s->H * s->W, nblk = ((long long)B * s->patch * s->patch + 255) / 256;
+  if (nblk > 0x7fffffffLL) return eae_set_error(EAE_ERR_ARG, "scene_stage_windows: batch too large");
+  EAE_NO_GROUP("scene_stage_windows_kernel");
+  const hipStream_t st = (hipStream_t)stream;
+  auto launch = [&](auto* t, auto scene_crop) {
+    using T = std::remove_cv_t<std::remove_pointer_t<decltype(t)>>;
+    hipLaunchKernelGGL((scene_stage_windows_kernel<T, decltype(scene_crop)::value>), dim3((unsigned)nblk), dim3(256), 0, st,
+                       (const T*)s->data, s->divisor, s->C, plane, s->H, s->W, s->patch, s->stride, (int)nW, nH * nW, windows, B, out,
+                       train, noise_std, seed, step, params, noise);
+  };
+  scene_dtype_dispatch(s, [&](auto* t, auto) {          // border = NONE: one instance per dtype and crop mode
+    if (crop == EAE_CROP_SCENE) launch(t, std::true_type()); else launch(t, std::false_type());
+  });
+  EAE_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int eae_scene_window_labels(void* stream, const void* raster, int elem_bytes, int H, int W, int patch, int stride, int K,
+                                       long long* label, int* count, int* labelled) {
+  if (!raster || !label) return eae_set_error(EAE_ERR_ARG, "scene_window_labels: NULL raster or label");
+  if (elem_bytes != 1 && elem_bytes != 4) return eae_set_error(EAE_ERR_ARG, "scene_window_labels: raster must be uint8 or int32 (elem_bytes 1 or 4)");
+  if (K < 1 || K > 64) return eae_set_error(EAE_ERR_ARG, "scene_window_labels: the number of classes must be in 1..64");
+  if (patch < 1 || patch > INV_SPAN - 16) return eae_set_error(EAE_ERR_ARG, "scene_window_labels: the patch size must be in 1..4080");
+  if (stride < 1 || stride > patch) return eae_set_error(EAE_ERR_ARG, "scene_window_labels: stride must be in 1..patch");
+  if (H < patch || W < patch) return eae_set_error(EAE_ERR_ARG, "scene_window_labels: raster smaller than one window");
+  const long long nH = (H - patch) / stride + 1, nW = (W - patch) / stride + 1;
+  if (nH * nW > 0x7fffffffLL) return eae_set_error(EAE_ERR_ARG, "scene_window_labels: raster too large");
+  EAE_NO_GROUP("scene_window_labels_kernel");
+  const hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)(nH * nW));
+  if (elem_bytes == 1)
+    hipLaunchKernelGGL(scene_window_labels_kernel<uint8_t>, grid, dim3(LBL_NT), 0, st, (const uint8_t*)raster, W, patch, stride, (int)nW, K,
+                       label, count, labelled);
+  else
+    hipLaunchKernelGGL(scene_window_labels_kernel<int32_t>, grid, dim3(LBL_NT), 0, st, (const int32_t*)raster, W, patch, stride, (int)nW, K,
+                       label, count, labelled);
   EAE_LAUNCH_CHECK();
   return 0;
 }

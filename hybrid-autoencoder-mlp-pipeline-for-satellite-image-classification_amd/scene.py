@@ -42,6 +42,19 @@ are invalid when ``fill`` matches ``nodata``; the error maps average over the wi
 scene pixel (i*S - pt, j*S - pl), so with ``anchor="origin"`` cell (ci, cj) of a blended map starts at pixel (ci*S, cj*S).  Window
 and cell maps have the shapes of the virtual grid; `reconstruct_scene` returns the real scene, [C,H,W] and [H,W].  The scene may be
 smaller than one patch.
+
+Training from a scene (the loader side: the model is trained by `fit_autoencoder`, `fit_mlp` and their kin, which take any iterable of
+(imgs, labels) with a ``batch_size``).  No patch dataset is cut -- with overlapping windows it would be (P/S)^2 times the scene -- and no
+per-patch label is made on the host; no model runs, so P is any positive size; the grid is that of whole windows (no border).
+- `window_labels` turns a label raster [H,W] (a land-cover map, rasterised polygons; values in [0,K) are classes, everything else is
+  unlabelled) into the majority class of every window, with its purity and the window's labelled share;
+- `stage_scene_windows` returns the augmented fp32 batch [B,C,P,P] of a list of window ids: `stage_bands`' transform and random
+  stream, the windows gathered from the scene.  ``crop="window"`` is bitwise `stage_bands` on the materialised windows (the pad-4
+  crop reads 0 outside the window); ``crop="scene"`` lets the crop slide the window over its real neighbourhood (0 only outside the
+  scene), so no black frame appears;
+- `SceneLoader` is the iterable over (x, y) batches of the labelled windows: epoch e orders the ids by
+  ``torch.randperm(n, generator=torch.Generator().manual_seed(seed + e))`` (`window_schedule`) and batch i is
+  ``stage_scene_windows(ids, seed=seed, step=e * len(loader) + i)``; nothing inside an epoch synchronises the host.
 """
 from __future__ import annotations
 
@@ -60,10 +73,14 @@ _DTYPES = {torch.uint8: 0, torch.uint16: 1, torch.float32: 2}
 
 
 # ---------------------------------------------------------------------------------------------------- grid arithmetic (pure Python)
-def window_grid(height, width, patch, stride):
-    """(nH, nW): whole P x P windows at stride S in an H x W scene.  Window n = i*nW + j starts at pixel (i*S, j*S)."""
+def window_grid(height, width, patch, stride, any_patch=False):
+    """(nH, nW): whole P x P windows at stride S in an H x W scene.  Window n = i*nW + j starts at pixel (i*S, j*S).  P is a
+    multiple of 64, a model's image size; any_patch=True takes every positive P (the calls that run no model: `scene_windows`
+    without a border, `stage_scene_windows`, `window_labels`, `SceneLoader`)."""
     height, width, patch, stride = int(height), int(width), int(patch), int(stride)
-    if patch <= 0 or patch % 64:
+    if any_patch and patch <= 0:
+        raise RuntimeError(f"the patch size must be positive, got {patch}")
+    if not any_patch and (patch <= 0 or patch % 64):
         raise RuntimeError(f"the patch size must be a positive multiple of 64, got {patch}")
     if not 1 <= stride <= patch:
         raise RuntimeError(f"stride must be in 1..{patch} (the patch size), got {stride}")
@@ -240,9 +257,9 @@ def _rule_arg(rule):
     return _RULES[rule]
 
 
-def _border_arg(scene, patch, stride, border, fill, anchor):
-    """(mode id, fill, nH, nW, pads) for a scene that has passed `_check_scene`: the grid of whole windows for border=None, else
-    `border_grid` and the checks of the mode."""
+def _border_arg(scene, patch, stride, border, fill, anchor, any_patch=False):
+    """(mode id, fill, nH, nW, pads) for a scene that has passed `_check_scene`: the grid of whole windows for border=None (any_patch:
+    `window_grid`), else `border_grid` and the checks of the mode."""
     h, w = int(scene.shape[1]), int(scene.shape[2])
     if border not in _BORDERS:
         raise RuntimeError(f"border must be None, 'constant', 'edge' or 'reflect', got {border!r}")
@@ -255,7 +272,7 @@ def _border_arg(scene, patch, stride, border, fill, anchor):
         if fill != 0.0:
             raise RuntimeError(f"fill is the value of border='constant' pixels; got fill={fill!r} with border={border!r}")
         if border is None:
-            return (0, 0.0) + window_grid(h, w, patch, stride) + ((0, 0, 0, 0),)
+            return (0, 0.0) + window_grid(h, w, patch, stride, any_patch) + ((0, 0, 0, 0),)
     elif scene.dtype in _INT_RANGE and (math.isnan(fill) or not fill.is_integer() or not 0 <= fill <= _INT_RANGE[scene.dtype]):
         raise RuntimeError(f"fill of a {str(scene.dtype).replace('torch.', '')} scene must be an integer in "
                            f"0..{_INT_RANGE[scene.dtype]}, got {fill!r}")
@@ -282,8 +299,9 @@ def _invalid_args(scene, nodata, mask, rule):
     return mode, value, rid, _mask_arg(scene, mask)
 
 
-def _windows_arg(windows, device, n_windows, allow_empty):
-    """Validate a window-id list: 1-D int64 on the scene's device, ids in [0, nH*nW) (one aminmax readback)."""
+def _windows_arg(windows, device, n_windows, allow_empty, check_range=True):
+    """Validate a window-id list: 1-D int64 on the scene's device, ids in [0, nH*nW) (one aminmax readback; check_range=False
+    leaves the ids unread)."""
     if not isinstance(windows, torch.Tensor) or windows.dim() != 1 or windows.dtype != torch.int64:
         raise RuntimeError("windows must be a 1-D int64 tensor of window ids")
     if windows.device != device:
@@ -292,6 +310,8 @@ def _windows_arg(windows, device, n_windows, allow_empty):
         if not allow_empty:
             raise RuntimeError("windows is empty")
         return windows
+    if not check_range:
+        return windows.contiguous()
     lo, hi = (int(v) for v in torch.aminmax(windows))
     if lo < 0 or hi >= n_windows:
         raise RuntimeError(f"window ids {lo}..{hi} are outside the grid of {n_windows}")
@@ -307,11 +327,11 @@ def _encoder_of(encoder):
     raise RuntimeError(f"encoder must be an Encoder or a SupervisedAutoencoder, got {type(encoder).__name__}")
 
 
-def _scene_desc(scene, divisor, patch, stride, border=None, fill=0, anchor="center"):
+def _scene_desc(scene, divisor, patch, stride, border=None, fill=0, anchor="center", any_patch=False):
     """(EaeScene, keep-alive tensors, nH, nW) of a scene that has passed `_check_scene`: device, band count, grid (of the virtual
     scene under a border), border arguments and divisor are validated here, before any kernel."""
     c, h, w = (int(v) for v in scene.shape)
-    mode, fill, n_h, n_w, pads = _border_arg(scene, patch, stride, border, fill, anchor)
+    mode, fill, n_h, n_w, pads = _border_arg(scene, patch, stride, border, fill, anchor, any_patch)
     _require_gpu(scene.device)
     if not 1 <= c <= 16:
         raise RuntimeError(f"scene: in_channels must be in 1..16, got {c}")
@@ -358,9 +378,9 @@ def _range(first, count, total):
 # ---------------------------------------------------------------------------------------------------- public functions
 def scene_windows(scene, divisor, patch, stride, first=0, count=None, border=None, fill=0, anchor="center"):
     """fp32 NCHW [count,C,P,P] of windows first .. first+count-1 (count=None: to the end of the grid).  border / fill / anchor:
-    module docstring, "Borders"."""
+    module docstring, "Borders".  No model runs: without a border P is any positive size."""
     _check_scene(scene)
-    desc, keep, n_h, n_w = _scene_desc(scene, divisor, patch, stride, border, fill, anchor)
+    desc, keep, n_h, n_w = _scene_desc(scene, divisor, patch, stride, border, fill, anchor, any_patch=True)
     first, count = _range(first, count, n_h * n_w)
     lib = _lib.load()
     out = torch.empty((count, keep[0].shape[0], int(patch), int(patch)), dtype=torch.float32, device=keep[0].device)
@@ -563,3 +583,224 @@ def reconstruct_scene(scene, autoencoder, divisor=1.0, stride=None, batch=512, r
     fn = p.eng.lib.eae_scene_reconstruct                 # one entry point: windows = NULL is the whole grid
     p.run(lambda ctx, st, desc, first, n, *outs: fn(ctx, st, desc, None, n, *outs), fn, recon, res)
     return (recon, res) if residual else recon
+
+
+# ---------------------------------------------------------------------------------------------------- training from a scene
+_CROPS = {"window": 0, "scene": 1}
+_MAX_LABEL_PATCH = 4080
+
+
+def _crop_arg(crop):
+    if crop not in _CROPS:
+        raise RuntimeError(f"crop must be 'window' or 'scene', got {crop!r}")
+    return _CROPS[crop]
+
+
+def stage_scene_windows(scene, divisor, patch, stride, windows, train=True, noise_std=0.03, seed=0, step=0, params=None, noise=None,
+                        crop="window"):
+    """fp32 NCHW [B,C,P,P]: `stage_bands`' transform of the windows ``windows`` (1-D int64 ids on the scene's device, any order,
+    duplicates allowed) of the grid of whole P x P windows at stride S: flip -> pad-4 crop -> / divisor[c] -> + noise_std * N(0,1)
+    (train=False: the division only, bitwise `scene_windows`).  Randomness as `stage_bands`: Philox keyed by (seed, step), the same
+    stream, or explicit ``params`` int32 [B,3] = (flip, top, left) and ``noise`` [B,C,P,P].
+    crop="window": outside the window the crop reads 0 -- bitwise `stage_bands` on the materialised windows; crop="scene": it reads
+    the scene's own pixels around the window (0 outside the scene).  The ids are not read on the host (no synchronisation): an id
+    outside the grid gives a NaN image, as an index outside the dataset does in `stage_bands`."""
+    cid = _crop_arg(crop)
+    _check_scene(scene)
+    windows = _windows_arg(windows, scene.device, 0, allow_empty=False, check_range=False)
+    b, c, p = windows.numel(), int(scene.shape[0]), int(patch)
+    if params is not None:
+        if not isinstance(params, torch.Tensor) or tuple(params.shape) != (b, 3):
+            raise RuntimeError(f"params must be int32 [B,3] = (flip, top, left) with B = {b}")
+    if noise is not None:
+        if not isinstance(noise, torch.Tensor) or tuple(noise.shape) != (b, c, p, p):
+            raise RuntimeError(f"noise must be [B,C,P,P] = {(b, c, p, p)}")
+    desc, keep, _, _ = _scene_desc(scene, divisor, patch, stride, any_patch=True)        # grid, device, bands, divisor
+    return _stage_windows(desc, keep, windows, train, noise_std, seed, step, params, noise, cid)
+
+
+def _stage_windows(desc, keep, windows, train, noise_std, seed, step, params, noise, cid):
+    """The C call of `stage_scene_windows` on a validated scene descriptor (`_scene_desc`) and id list: what a `SceneLoader` runs
+    per batch."""
+    dev, b = keep[0].device, windows.numel()
+    if params is not None:
+        params = params.to(device=dev, dtype=torch.int32).contiguous()
+    if noise is not None:
+        noise = noise.to(device=dev, dtype=torch.float32).contiguous()
+    lib = _lib.load()
+    out = torch.empty((b, desc.C, desc.patch, desc.patch), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.eae_scene_stage_windows(_stream(), C.byref(desc), _ptr(windows), b, _ptr(out), int(bool(train)), float(noise_std),
+                                          int(seed) & (2**64 - 1), int(step) & (2**64 - 1), _ptr(params), _ptr(noise), cid))
+    return out
+
+
+def window_labels(raster, patch, stride, num_classes, ignore=None):
+    """(label int64 [nH,nW], purity float32 [nH,nW], labelled float32 [nH,nW]) of every whole P x P window at stride S over a label
+    raster [H,W] on the device (any integer dtype; uint8 and int32 are read as they are, the others converted to int32).  A pixel is
+    labelled when its value is in [0, num_classes), num_classes in 1..64; every other value (255, negatives, >= K) is unlabelled, and
+    so are the values of ``ignore`` (one value or a list).  label = the class with the most labelled pixels (the lowest on a tie), -1
+    for a window without a labelled pixel; purity = that class's pixels / P^2; labelled = labelled pixels / P^2.  Exact integer
+    counts underneath: identical from run to run."""
+    k = int(num_classes)
+    if not 1 <= k <= 64:
+        raise RuntimeError(f"num_classes must be in 1..64, got {num_classes}")
+    if not isinstance(raster, torch.Tensor) or raster.dim() != 2:
+        raise RuntimeError("raster must be a [H, W] tensor of class ids")
+    if raster.dtype.is_floating_point or raster.dtype.is_complex or raster.dtype == torch.bool:
+        raise RuntimeError(f"raster must have an integer dtype, got {raster.dtype}")
+    patch, stride = int(patch), int(stride)
+    if patch > _MAX_LABEL_PATCH:
+        raise RuntimeError(f"the patch size must be at most {_MAX_LABEL_PATCH}, got {patch}")
+    h, w = (int(v) for v in raster.shape)
+    n_h, n_w = window_grid(h, w, patch, stride, any_patch=True)
+    if ignore is None:
+        ignore = []
+    elif isinstance(ignore, numbers.Integral) and not isinstance(ignore, bool):
+        ignore = [int(ignore)]
+    else:
+        ignore = list(ignore)
+        if any(isinstance(v, bool) or not isinstance(v, numbers.Integral) for v in ignore):
+            raise RuntimeError(f"ignore must be an integer or a list of integers, got {ignore!r}")
+    ignore = sorted({int(v) for v in ignore if 0 <= int(v) < k})          # any other value is unlabelled already
+    _require_gpu(raster.device)
+    if raster.dtype not in (torch.uint8, torch.int32):
+        wide = raster.to(torch.int64)
+        raster = torch.where((wide >= 0) & (wide < k), wide, -1).to(torch.int32)
+    if ignore:
+        hit = raster == ignore[0]
+        for v in ignore[1:]:
+            hit = hit | (raster == v)
+        raster = raster.masked_fill(hit, 255 if raster.dtype == torch.uint8 else -1)          # K <= 64: 255 is never a class
+    raster = raster.contiguous()
+    dev = raster.device
+    label = torch.empty((n_h, n_w), dtype=torch.int64, device=dev)
+    count = torch.empty((n_h, n_w), dtype=torch.int32, device=dev)
+    labelled = torch.empty((n_h, n_w), dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        check(lib.eae_scene_window_labels(_stream(), _ptr(raster), raster.element_size(), h, w, patch, stride, k, _ptr(label),
+                                          _ptr(count), _ptr(labelled)))
+    pp = float(patch * patch)
+    return label, count.to(torch.float32) / pp, labelled.to(torch.float32) / pp
+
+
+def window_schedule(n, batch_size, epoch, seed=0, shuffle=True, drop_last=False):
+    """The batches of one epoch over n drawable windows, as a list of 1-D int64 CPU tensors of POSITIONS in 0..n-1 (pure host
+    arithmetic).  shuffle: the order is ``torch.randperm(n, generator=torch.Generator().manual_seed(seed + epoch))``, else ascending;
+    consecutive runs of batch_size, the short last one dropped with drop_last."""
+    n, batch_size, epoch = int(n), int(batch_size), int(epoch)
+    if n < 1:
+        raise RuntimeError(f"no window to draw from (n = {n})")
+    if batch_size < 1:
+        raise RuntimeError(f"batch_size must be positive, got {batch_size}")
+    if epoch < 0:
+        raise RuntimeError(f"epoch must not be negative, got {epoch}")
+    order = torch.randperm(n, generator=torch.Generator().manual_seed(int(seed) + epoch)) if shuffle else torch.arange(n)
+    stop = n - n % batch_size if drop_last else n
+    return [order[i:min(i + batch_size, stop)] for i in range(0, stop, batch_size)]
+
+
+def schedule_len(n, batch_size, drop_last=False):
+    """Number of batches `window_schedule` yields."""
+    n, batch_size = int(n), int(batch_size)
+    if batch_size < 1:
+        raise RuntimeError(f"batch_size must be positive, got {batch_size}")
+    return n // batch_size if drop_last else -(-n // batch_size)
+
+
+def drawable_windows(label, windows=None, purity=None, min_purity=0.0):
+    """The ids a `SceneLoader` draws from, in the order given: ``windows`` (1-D int64; None = every window of the
+    label map, ascending) restricted to ``label >= 0`` and, when ``purity`` is given, to ``purity >= min_purity``.  Works on the
+    tensors' own device (one readback of the number kept)."""
+    if not isinstance(label, torch.Tensor) or label.dim() != 2 or label.dtype != torch.int64:
+        raise RuntimeError("label must be an int64 [nH, nW] map of window labels (`window_labels`)")
+    flat = label.reshape(-1)
+    if windows is None:
+        windows = torch.arange(flat.numel(), dtype=torch.int64, device=label.device)
+    else:
+        windows = _windows_arg(windows, label.device, flat.numel(), allow_empty=True)
+    keep = flat[windows] >= 0
+    if purity is not None:
+        if not isinstance(purity, torch.Tensor) or tuple(purity.shape) != tuple(label.shape):
+            raise RuntimeError(f"purity must be a [nH, nW] = {list(label.shape)} tensor")
+        if purity.device != label.device:
+            raise RuntimeError(f"purity is on {purity.device}, label on {label.device}")
+        keep = keep & (purity.reshape(-1)[windows] >= float(min_purity))
+    elif float(min_purity) > 0.0:
+        raise RuntimeError("min_purity needs the purity map (`window_labels`)")
+    return windows[keep]
+
+
+class SceneLoader:
+    """Iterable of (x [b,C,P,P] float32, y [b] int64) batches of the labelled windows of a scene, both on the scene's device: what
+    `fit_autoencoder`, `fit_autoencoder_group`, `grid_search_autoencoder`, `extract_features`, `fit_mlp` and `evaluate` take as a
+    loader.  ``label`` (and ``purity``) are `window_labels`' maps [nH,nW] of the scene's grid at (patch, stride; None: the patch size).
+
+    The drawable ids (``.windows``) are ``windows`` (default: all) restricted to label >= 0 and, with ``purity``, to
+    purity >= min_purity (`drawable_windows`); two loaders over disjoint ``windows`` make a train / validation split.  Epoch e
+    (counted per ``__iter__``, or set with `set_epoch`) takes the ids in `window_schedule`'s order -- shuffled when ``shuffle``
+    (default: ``train``) -- and batch i is ``stage_scene_windows(ids, train=train, seed=seed, step=e * len(self) + i, noise_std=,
+    crop=)`` with ``y = label.reshape(-1)[ids]``.  The epoch's order is uploaded once when the iterator starts; nothing inside an
+    epoch synchronises the host."""
+
+    def __init__(self, scene, label, divisor=1.0, patch=64, stride=None, batch_size=64, windows=None, min_purity=0.0, purity=None,
+                 train=True, shuffle=None, drop_last=False, noise_std=0.03, crop="window", seed=0):
+        _crop_arg(crop)
+        _check_scene(scene)
+        self.patch = int(patch)
+        self.stride = self.patch if stride is None else int(stride)
+        self.batch_size = int(batch_size)
+        if self.batch_size < 1:
+            raise RuntimeError(f"batch_size must be positive, got {batch_size}")
+        n_h, n_w = window_grid(scene.shape[1], scene.shape[2], self.patch, self.stride, any_patch=True)
+        if not isinstance(label, torch.Tensor) or label.dtype != torch.int64 or tuple(label.shape) != (n_h, n_w):
+            got = tuple(label.shape) if isinstance(label, torch.Tensor) else type(label).__name__
+            raise RuntimeError(f"label must be the int64 [nH, nW] = {[n_h, n_w]} map `window_labels` returns for a raster of the "
+                               f"scene's {scene.shape[1]} x {scene.shape[2]} pixels at this patch and stride, got {got}")
+        if label.device != scene.device:
+            raise RuntimeError(f"label is on {label.device}, the scene on {scene.device}")
+        self.windows = drawable_windows(label, windows, purity, min_purity)
+        if self.windows.numel() == 0:
+            raise RuntimeError("no window to draw from: none of the given windows is labelled (and pure enough)")
+        # device, band count and divisor are checked here, before the first epoch; the divisor stays on the device as fp32 [C]
+        self._desc, self._keep, _, _ = _scene_desc(scene, divisor, self.patch, self.stride, any_patch=True)
+        self.scene, self.divisor = self._keep
+        self.labels = label.reshape(-1)[self.windows]
+        self.train = bool(train)
+        self.shuffle = self.train if shuffle is None else bool(shuffle)
+        self.drop_last = bool(drop_last)
+        self.noise_std, self.crop, self.seed = float(noise_std), crop, int(seed)
+        if len(self) == 0:
+            raise RuntimeError(f"drop_last leaves no batch: {self.windows.numel()} windows, batch_size {self.batch_size}")
+        self.epoch = 0
+
+    def __len__(self):
+        return schedule_len(self.windows.numel(), self.batch_size, self.drop_last)
+
+    def set_epoch(self, epoch):
+        """The epoch the next ``__iter__`` runs (it then goes on counting from there)."""
+        if int(epoch) < 0:
+            raise RuntimeError(f"epoch must not be negative, got {epoch}")
+        self.epoch = int(epoch)
+
+    def schedule(self, epoch):
+        """`window_schedule` of this loader for an epoch: positions in ``.windows``, on the host."""
+        return window_schedule(self.windows.numel(), self.batch_size, epoch, self.seed, self.shuffle, self.drop_last)
+
+    def __iter__(self):
+        e = self.epoch                                       # taken here, not at the first next(): one epoch per __iter__
+        self.epoch = e + 1
+        return self._batches(e)
+
+    def _batches(self, e):
+        batches = self.schedule(e)
+        dev = self.windows.device
+        order = torch.cat(batches).pin_memory().to(dev, non_blocking=True)             # one upload per epoch
+        ids, ys = self.windows[order], self.labels[order]
+        base, at, cid = e * len(self), 0, _CROPS[self.crop]
+        for i, b in enumerate(batches):
+            w = ids[at:at + b.numel()]
+            x = _stage_windows(self._desc, self._keep, w, self.train, self.noise_std, self.seed, base + i, None, None, cid)
+            yield x, ys[at:at + b.numel()]
+            at += b.numel()

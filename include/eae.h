@@ -418,7 +418,8 @@ typedef struct eae_scene {
 #define EAE_BORDER_CONSTANT 1
 #define EAE_BORDER_EDGE 2
 #define EAE_BORDER_REFLECT 3
-/* fp32 NCHW [B,C,P,P] of windows first_window .. first_window + B - 1: bitwise eae_stage_bands(train = 0) on the same windows. */
+/* fp32 NCHW [B,C,P,P] of windows first_window .. first_window + B - 1: bitwise eae_stage_bands(train = 0) on the same windows.  No
+ * model runs, so P is any positive size here (every call that runs a model wants a multiple of 64, its image size). */
 int eae_scene_windows(void* stream, const eae_scene* scene, long long first_window, int B, float* out);
 /* Eval-mode encoder over windows first_window .. + B - 1 (any B: split at max_batch inside), conv1 reading the scene directly
  * (zero conv padding at every window border): z [B][L].  Invalidates the resident forward (a later backward is refused). */
@@ -496,6 +497,37 @@ int eae_scene_recon_error_windows(eae_ctx* ctx, void* stream, const eae_scene* s
                                   float* err, float* band_err);
 int eae_scene_reconstruct(eae_ctx* ctx, void* stream, const eae_scene* scene, const long long* windows, long long count, float* recon,
                           float* residual);
+
+/* ------------------------------------------------------------------ training from a scene ---------- */
+/* The loader side of training, from a scene and a label raster held on the device: no [N,C,P,P] patch dataset is cut (with
+ * overlapping windows that dataset is (P/S)^2 times the scene) and no per-patch label is made on the host.  No model runs here: P is
+ * any positive size, S in 1..P, C in 1..16, the grid is that of whole windows (border = EAE_BORDER_NONE; any other mode is rejected).
+ *
+ * eae_scene_stage_windows: out [B,C,P,P] (fp32 NCHW) = the transform of eae_stage_bands applied to windows[0 .. B) (device int64 ids of
+ * the grid, any order, duplicates allowed): flip -> pad-4 crop -> (float)v / divisor[c] (a true division) -> fmaf(noise_std, n, v).
+ * (flip, top, left) of batch position b and the noise come from params int32 [B][3] / noise [B,C,P,P] when given, else from the
+ * Philox stream of eae_stage_bands, keyed alike (batch position b; flat pixel index over [B][P][P]; band group; seed; step): the two
+ * calls draw the same values.  train = 0: the division only, bitwise eae_scene_windows.  With the window's origin (oy, ox),
+ * sy = y + top - 4, sx = x + left - 4 and, after a flip, sx <- P - 1 - sx:
+ *   EAE_CROP_WINDOW: a position with sy or the unflipped sx outside [0, P) reads 0, as in eae_stage_bands; out is bitwise
+ *     eae_stage_bands on the materialised windows [B,C,P,P] with the same arguments.
+ *   EAE_CROP_SCENE: the value is scene pixel (oy + sy, ox + sx) wherever that pixel lies inside the scene, 0 outside it: the crop
+ *     jitters the window over its real neighbourhood and no black frame appears.  This is EAE_CROP_WINDOW with params (flip, 4, 4) on
+ *     the window of origin (oy + top - 4, ox + (flip ? -(left - 4) : left - 4)) cut from the scene zero-padded by 4.
+ * An id outside [0, nH * nW) gives NaN for that image and reads nothing (as an index outside 0..N-1 does in eae_stage_bands).  Rejected
+ * (EAE_ERR_ARG): what eae_scene_windows rejects, a border mode, NULL windows / out, B <= 0, an unknown crop.  No host synchronisation. */
+#define EAE_CROP_WINDOW 0
+#define EAE_CROP_SCENE 1
+int eae_scene_stage_windows(void* stream, const eae_scene* scene, const long long* windows, int B, float* out, int train,
+                            float noise_std, unsigned long long seed, unsigned long long step, const int* params, const float* noise,
+                            int crop);
+/* A label for every window of the grid of whole P x P windows at stride S over a label raster [H][W] on the device, uint8
+ * (elem_bytes 1) or int32 (4).  A pixel is labelled when its value is in [0, K), K in 1..64; every other value (255, negatives,
+ * >= K) is unlabelled.  For window n: label[n] (int64) = the class with the most labelled pixels, the lowest class on a tie, -1 when
+ * the window has none; count[n] (int32, or NULL) = that class's pixels (0 without one); labelled[n] (int32, or NULL) = the labelled
+ * pixels.  Integer counts: exact, and identical from run to run.  The patch size must be at most 4080. */
+int eae_scene_window_labels(void* stream, const void* raster, int elem_bytes, int H, int W, int patch, int stride, int K,
+                            long long* label, int* count, int* labelled);
 
 #ifdef __cplusplus
 }
