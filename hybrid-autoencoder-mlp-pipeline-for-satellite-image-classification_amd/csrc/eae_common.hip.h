@@ -3,31 +3,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "eae_args.h"      // bf16_t, SRC_* / EPI_*, SrcDesc, BnAcc / BnFold / BnBwdFold
 #include "eae_group.h"
 
-typedef uint16_t bf16_t;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;   // one MFMA A/B fragment (4 VGPRs)
 typedef __attribute__((ext_vector_type(4))) float f32x4;     // one 16x16 accumulator fragment
 typedef __attribute__((ext_vector_type(4))) short s16x4;
-
-// activation "sources": how a logical NHWC activation tensor is materialised when it is loaded
-enum { SRC_RAW = 0,      // bf16 tensor as stored
-       SRC_BNRELU = 1,   // max(0, s[c]*y + t[c])            (BatchNorm apply + ReLU fused into the consumer's load)
-       SRC_BNBWD = 2,    // A[c]*g + B[c]*y + C[c]           (BatchNorm backward apply fused into the consumer's load)
-       SRC_F32 = 3,      // fp32 tensor, converted to bf16 on load
-       SRC_RAWG = 4 };   // bf16 GRADIENT tensor as stored (the BatchNorm-backward-applied dy a backward-data kernel wrote while it staged
-                         // its patch, ConvArgs::dy_out): loads like SRC_RAW; the fp8 variants convert it to e5m2 like SRC_BNBWD
-
-// epilogues of the conv-like kernels
-enum { EPI_FWD = 0,      // + bias, store raw bf16, per-channel sum / sum-of-squares partials (BatchNorm batch statistics)
-       EPI_MASK = 1,     // ReLU mask from the previous layer's BN output, store masked grad, sum g / sum g*xhat partials
-       EPI_PLAIN = 2 };  // store bf16
-
-struct SrcDesc {
-  const bf16_t* p0;    // RAW: tensor; BNRELU: raw pre-BN tensor y; BNBWD: masked gradient g
-  const bf16_t* p1;    // BNBWD: raw pre-BN tensor y
-  const float* coef;   // BNRELU: [4][C] = s, t, mean, invstd ; BNBWD: [3][C] = A, B, C
-};
 
 __device__ __forceinline__ float bf2f(uint32_t h) { return __uint_as_float(h << 16); }
 __device__ __forceinline__ uint32_t f2bf(float f) {           // round-to-nearest-even (v_cvt_pk_bf16_f32 on gfx950)
@@ -163,22 +144,6 @@ __device__ __forceinline__ bf16x8 tr_frag(const bf16_t* row_ptr_lo, const bf16_t
 //             over 256 threads) and builds the coefficient table in LDS; workgroup 0 also stores the table for the kernels
 //             that need it later and updates the running statistics.
 // ---------------------------------------------------------------------------------------------------------------
-struct BnAcc {
-  unsigned long long* acc;   // [copies][2][C]; zero before the producer runs; nullptr: per-tile partials + finalize kernel
-  int copies;                // power of two
-  float scale;               // fixed-point scale
-  unsigned long long* flag;  // [C] sticky "a non-finite partial of this channel was seen" words (cleared with the accumulators)
-};
-struct BnFold {
-  const unsigned long long* acc;   // nullptr: the coefficients come from SrcDesc::coef
-  int copies;
-  float inv_scale, count, momentum, eps;
-  const float* gamma; const float* beta;
-  float* rm; float* rv; long long* nbt;
-  float* coef_out;           // [4][C]: s, t, mean, invstd
-  const unsigned long long* flag;  // [C] the layer's non-finite flags (BnAcc::flag)
-  unsigned* poison;          // step-wide sticky word (cleared with the accumulators): the writer workgroup sets it when a channel is flagged
-};
 __device__ __forceinline__ void bn_acc_add(const BnAcc& b, int C, int tile_id, int which, int ch, float v) {
   unsigned long long* p = b.acc + ((size_t)(tile_id & (b.copies - 1)) * 2 + which) * C + ch;
   // a non-finite partial (diverged run) must poison the statistics like it does in floating point.  It cannot travel inside the
@@ -191,8 +156,6 @@ __device__ __forceinline__ void bn_acc_add(const BnAcc& b, int C, int tile_id, i
 // Split in two so that the accumulator loads can be ISSUED before the kernel's own first loads (vector-memory results return in
 // issue order: a prologue whose loads queue behind the patch loads would wait for all of them) and CONSUMED after those are in
 // flight.  copies <= 4 * (256 / C)  (at most 4 accumulator sets per thread).
-constexpr int BN_FOLD_K = 4;
-constexpr int BN_FOLD_KB = 2;      // backward tables: the consumers hold two source tensors' raw pieces in registers meanwhile
 template <int K> struct BnFoldRegsT { long long v[2][K]; unsigned long long flag; };
 typedef BnFoldRegsT<BN_FOLD_K> BnFoldRegs;
 typedef BnFoldRegsT<BN_FOLD_KB> BnFoldRegsB;
@@ -272,16 +235,6 @@ __device__ __forceinline__ void bn_fold_fwd(const BnFold& f, float* table, long 
 // (A "last workgroup of the producer finalizes" variant was measured first: waiting for the atomics' return values and drawing a
 // ticket cost every producer workgroup two device-scope round trips at its end: 0.558 vs 0.5225 ms per step.)
 // ---------------------------------------------------------------------------------------------------------------
-struct BnBwdFold {
-  const unsigned long long* acc;   // nullptr: the coefficients come from SrcDesc::coef (bn_bwd_finalize_kernel wrote them)
-  int copies;
-  float inv_scale, count;
-  const float* gamma; const float* coef_fwd;       // [C], [4][C]
-  float* dgamma; float* dbeta; float* coef_out;    // [C], [C], [3][C]: written by the `writer` workgroup (each may be nullptr)
-  float* dbias;              // eval-mode backward only: gradient of the bias in FRONT of this BatchNorm, A[c] * sum g (train mode: zero)
-  const unsigned long long* flag;  // [C] the layer's non-finite flags (BnAcc::flag of the backward accumulators)
-  unsigned* poison;          // step-wide sticky word, as in BnFold
-};
 template <int C>
 __device__ __forceinline__ void bn_fold_bwd_load(const BnBwdFold& f, BnFoldRegsB& r, int tid = threadIdx.x) {
   bn_fold_load_acc<C, BN_FOLD_KB>(f.acc, f.copies, f.flag, r, tid);     // copies <= BN_FOLD_KB * (256 / C)
@@ -331,5 +284,3 @@ __device__ __forceinline__ void eae_signal(unsigned* sig, unsigned val) {
 __device__ __forceinline__ void eae_signal_first(unsigned* sig, unsigned val, bool first) {
   if (sig != nullptr && first && threadIdx.x == 0) __hip_atomic_store(sig, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-
-#define EAE_LAUNCH_CHECK() do { hipError_t e__ = hipGetLastError(); if (e__ != hipSuccess) return eae_set_error(-3, hipGetErrorString(e__)); } while (0)

@@ -8,6 +8,7 @@
 #pragma once
 #include "eae_common.hip.h"
 #include "eae_igemm.hip.h"
+// (argument blocks EdgeArgs / Deconv4Args / Deconv4SceneArgs / SceneSrc, the SRC3_* kinds, edge_cp and edge_lp_stride: eae_args.h)
 
 #ifdef EAE_STAMPS          // diagnostic build: s_memtime stamps of one workgroup of the edge kernels (tools/kstamp3.py)
 __device__ unsigned long long* g_edge_dbg = nullptr;
@@ -18,34 +19,8 @@ __device__ int g_edge_dbg_block = 0;
 #define EDGE_STAMP(i) do {} while (0)
 #endif
 
-enum { SRC3_NCHW_F32 = 0,     // fp32 planar image (the loader contract)
-       SRC3_NHWCP_BF16 = 1,   // bf16 pixels padded to CP channels (gradient of the pre-sigmoid output)
-       SRC3_SCENE_U8 = 2,     // P x P windows of a planar uint8 / uint16 / fp32 scene [C][Hs][Ws], value / divisor[c] (eae_scene)
-       SRC3_SCENE_U16 = 3,
-       SRC3_SCENE_F32 = 4 };
 template <int SRC3> constexpr bool src3_planar() { return SRC3 != SRC3_NHWCP_BF16; }
 
-// Scene source of conv1 (eval-mode forward only): image n of the launch is window w = first + n of the grid of P x P windows at
-// stride S (nW per row), whose origin is scene pixel (w / nW * S, w % nW * S).  Offsets are 64-bit: scenes exceed 2^31 elements.
-// Index-driven form (the IDX template flag of the scene kernels): image n is window index[first + n] instead; an id outside
-// [0, nwin) reads as an all-zero window (defence in depth: the callers reject such ids before any launch).
-// (SceneSrcCore is the part every scene kernel takes; SceneSrc adds the border fields behind it.  Kernels with arguments after the
-// scene take the two parts apart, the border last, so that the argument block of the borderless forms stays as it was.)
-struct SceneSrcCore {
-  const void* data = nullptr;        // [C][Hs][Ws]
-  const float* div = nullptr;        // [C]
-  long long first = 0, plane = 0;    // first window of the launch; Hs * Ws
-  int Ws = 0, S = 0, nW = 0;
-  const long long* index = nullptr;  // window ids (IDX kernels only)
-  long long nwin = 0;                // nH * nW
-};
-// border (BORDER kernels only; eae.h, "Border modes"): the grid lies over the virtual scene, window (i, j) starts at virtual pixel
-// (i * S, j * S) = scene pixel (i * S - pt, j * S - pl), and a pixel outside the Hs x Ws scene is resolved when it is loaded
-struct SceneBorder {
-  int mode = 0, pt = 0, pl = 0, Hs = 0, Ws = 0;
-  float fill = 0.f;
-};
-struct SceneSrc : SceneSrcCore { SceneBorder b; };
 template <typename T> __device__ __forceinline__ float scene_val(T v, float d) { return (float)v / d; }
 // The one border resolver: source index on an axis of length n of virtual coordinate v behind a leading pad p, or -1 for a constant
 // pixel (whose stored value is fill).  s = v - p inside [0, n) is the pixel itself; EDGE clamps; REFLECT mirrors about the edge pixel
@@ -80,11 +55,6 @@ template <int SRC3> struct SceneElem { using T = float; };
 template <> struct SceneElem<SRC3_SCENE_U8> { using T = uint8_t; };
 template <> struct SceneElem<SRC3_SCENE_U16> { using T = uint16_t; };
 
-// Band counts: C (1..16, a run-time argument) image bands are staged as CP = 4, 8 or 16 (the trailing template argument of every
-// edge kernel).  CP = 4 is the RGB form: C = 3 is a compile-time constant there (edge_bands), so it compiles to the registers,
-// arithmetic and summation order of the 3-band kernels.  Generic forms with a run-time C measured 3-5 % slower on the RGB step
-// (DESIGN.md section 10).  C = 1, 2 and 4..8 -> CP = 8, C = 9..16 -> CP = 16.
-constexpr int edge_cp(int C) { return C == 3 ? 4 : C <= 8 ? 8 : 16; }
 template <int CP> __device__ __forceinline__ int edge_bands(int C) { return CP == 4 ? 3 : C; }
 template <int CP> struct EdgeK {
   static constexpr int CMAX = CP == 4 ? 3 : CP;       // most bands a CP form takes
@@ -93,8 +63,6 @@ template <int CP> struct EdgeK {
   static constexpr int KC = (9 * CMAX + 31) / 32;     // 32-wide im2col chunks of the weight gradient (k = tap*C + c): at most 1, 3, 5
   static constexpr int NT = CP / 4;                   // deconv4: 16-column MFMA tiles of the 4 phases x C outputs
 };
-// loss partial row of deconv4 / sigmoid backward: {sum diff^2, sum g(c) for c < C}, padded to whole float4s (4 floats for C = 3)
-__host__ __device__ constexpr int edge_lp_stride(int C) { return (C + 4) / 4 * 4; }
 
 constexpr int E_TH = 4, E_TW = 32;                 // 128 output pixels (conv view) / 128 input positions (deconv view)
 constexpr int E_PH = 2 * E_TH + 1, E_PW = 2 * E_TW + 1;   // 9 x 65 patch of the C-band tensor
@@ -354,12 +322,6 @@ __device__ __forceinline__ void build_im2col(const bf16_t* p3, bf16_t* at, const
 // ---------------------------------------------------------------------------------------------------------------
 // out[m][32] = im2col(src)[m][9C] . Wp[32][9C]^T      (conv1 forward; backward-data of deconv4)
 // ---------------------------------------------------------------------------------------------------------------
-struct EdgeArgs {
-  const void* src3;        // fp32 NCHW [B,C,H,W] or bf16 NHWC-CP [B,H,W,CP]
-  int B, H, W;             // spatial size of the C-band tensor
-  ConvArgs c;              // wpack [32][KP] (k = tap*CP + c, zero where c >= C or k >= 9*CP), bias, out [B,H/2,W/2,32], stat_part, yprev, prev_coef
-  int C = 3;               // bands (1..16; edge_cp(C) == CP)
-};
 
 // No im2col tile: with k = tap*CP + c (bands >= C and k >= 9*CP are zero in the weights: K = KP, 2 / 3 / 5 MFMA k-steps) a lane's 8
 // consecutive k are whole pixel pieces of the staged [row][col][CP] patch (two pixels for CP = 4, one for 8, half a pixel for 16), so
@@ -622,19 +584,6 @@ __global__ __launch_bounds__(256) void edge_wgrad_kernel_g(GroupPack<EdgeWgradAr
 //   s[n,oy,ox,co] = b[co] + sum over the 2x2 input neighbourhood ;  x_hat = sigmoid(s)
 //   loss partial  = sum (x_hat - x)^2 ;  g = gscale * (x_hat - x) * x_hat * (1 - x_hat)   (gscale = alpha*2/numel)
 // ---------------------------------------------------------------------------------------------------------------
-struct Deconv4Args {
-  SrcDesc src;             // a3 = BNRELU(u3)  [B,Hin,Win,32]
-  const bf16_t* wjoint;    // [16*NT][128]  n = phase*C+co, k = nb*32+ci
-  const float* bias;       // [C]
-  const float* x;          // target fp32 NCHW [B,C,2Hin,2Win] or nullptr (forward only)
-  float* x_hat;            // fp32 NCHW or nullptr
-  bf16_t* g4;              // bf16 NHWC-CP [B,2Hin,2Win,CP] or nullptr
-  float* loss_part;        // [ntiles][edge_lp_stride(C)]: sum diff^2, sum g (co = 0..C-1), zero padding   or nullptr
-  float gscale;
-  int B, Hin, Win;
-  BnFold fold;             // BNRELU source: coefficient table of deconv3's BatchNorm from its accumulators
-  int C = 3;               // bands (1..16; edge_cp(C) == CP)
-};
 
 template <int SRC, int CP>
 __device__ __forceinline__ void deconv4_loss_body(const Deconv4Args& a) {
@@ -813,13 +762,6 @@ __global__ __launch_bounds__(256) void deconv4_loss_kernel_g(GroupPack<Deconv4Ar
 //   ascending order; scene_err_finalize_kernel adds a window's tiles, then its bands, in ascending order.  No atomics anywhere.
 // ---------------------------------------------------------------------------------------------------------------
 __host__ __device__ constexpr int edge_bp_stride(int C) { return (C + 3) / 4 * 4; }      // floats of a partial row: C bands, whole float4s
-struct Deconv4SceneArgs {
-  float* part;             // [ntiles][edge_bp_stride(C)]
-  float* recon;            // STITCH: fp32 [C][Hg][Wg]; BORDER: [C][Hs][Ws], the real scene
-  float* residual;         // STITCH: fp32 [Hg][Wg] or nullptr; BORDER: [Hs][Ws]
-  long long gplane = 0;    // Hg * Wg; BORDER: Hs * Ws
-  int Wg = 0, nH = 0, m = 0;   // width of the stitched raster (BORDER: Ws), window rows of the grid, (P - S) / 2
-};
 
 // The MFMA part of deconv4_loss_body, line for line: stages the 5 x 33 input patch of this workgroup's tile (image n, input rows iy0..,
 // columns ix0..), multiplies the four phases jointly and leaves the pre-sigmoid tile sl[128][16*NT + 1] (without the bias) in LDS,

@@ -9,21 +9,6 @@
 #include "eae_common.hip.h"
 #include "eae_igemm.hip.h"
 
-enum { FCE_PARTIAL = 0,    // fp32 partial [kslice][M][N]       (split-K)
-       FCE_BIAS_BF16 = 1,  // bf16(acc + bias[n]) -> [M][N]
-       FCE_MASK = 2 };     // ReLU mask of the BN output at the same position + BN-backward partial sums
-
-struct FcNtArgs {
-  SrcDesc a;               // A [M][K]; SRC_F32: p0 is a float*; BNRELU: channel = k % 256
-  const bf16_t* w;         // [N][K]
-  int M, N, K;
-  int klen;                // K-range per grid.z slice (multiple of 64)
-  float* part;             // FCE_PARTIAL
-  ConvArgs c;              // FCE_BIAS_BF16 / FCE_MASK: out, bias ([N]), stat_part, yprev, prev_coef ([4][256]);
-                           // c.fold: BNRELU source -- coefficient table of the 256-channel source layer from its accumulators
-                           // (no field of its own: eight of these blocks must fit one grouped launch, eae_group.h)
-};
-
 constexpr int FC_KC = 64;
 constexpr int FC_LS = FC_KC + 8;   // LDS row stride (bf16)
 
@@ -270,14 +255,6 @@ static __global__ EAE_NO_PK __launch_bounds__(256) void fc_splitk_reduce_kernel_
 // out_mode 0: R is [I][J] row-major, row index permuted   i' = p*256+c  ->  c*Pn + p   (dec.fc weight [4096][L])
 // out_mode 1: R is [I][J] row-major, column index permuted j' = p*256+c ->  c*Pn + p   (enc.fc weight [L][4096])
 // ---------------------------------------------------------------------------------------------------------------
-struct FcTnArgs {
-  SrcDesc p, q;            // P [Bt][I], Q [Bt][J]   (F32: p0 is float*; BNRELU: channel = col % 256)
-  int Bt, I, J;
-  float* out;              // reference-layout weight gradient
-  float* colsum;           // bias gradient (reference order) or nullptr
-  int out_mode, Pn;        // Pn = pixels per image of the flattened map
-};
-
 
 // The reduction runs over the batch in chunks of 64 rows; one block walks ALL chunks, so its time used to be (number of chunks) x
 // (memory latency + staging + a handful of MFMAs): 8 exposed round trips at B=512 (22 us inside the step for 8 MB of operands).  The raw

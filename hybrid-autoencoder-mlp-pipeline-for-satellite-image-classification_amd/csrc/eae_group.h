@@ -80,7 +80,7 @@ struct GroupRec {
   void clear() { items.clear(); argbuf.clear(); error = 0; }
 };
 
-extern thread_local GroupRec* eae_rec;     // non-null: launches made by this thread are recorded (eae_api.hip)
+extern thread_local GroupRec* eae_rec;     // non-null: launches made by this thread are recorded (eae_group.hip)
 // Launchers that pick a tile geometry by the size of the grid (eae_conv_launch.hip) see batch x eae_geo_mult: the members of a grouped
 // step run as ONE launch.  Thread-local, 1 outside eae_group_train_step; eae_set_geometry_mult() sets it for a context run alone
 // (the bitwise group-vs-alone test).

@@ -20,43 +20,7 @@
 //   * BatchNorm reductions (forward: sum y, sum y^2; backward: sum g, sum g*xhat) are taken from the values actually
 //     stored, accumulated over all phases, and written as ONE deterministic partial per workgroup (no atomics).
 #pragma once
-#include "eae_common.hip.h"
-
-struct ConvArgs {
-  SrcDesc src;
-  const bf16_t* wpack;     // [COUT][9][CIN] bf16 (tap = ky*3+kx)
-  const float* bias;       // [COUT] (EPI_FWD) or nullptr
-  bf16_t* out;             // NHWC bf16
-  float* stat_part;        // [2][COUT][ntiles] (channel-major: the finalize kernels read one channel contiguously) or nullptr
-  int ntiles;              // number of statistics partials per channel = workgroups along grid.x (set by the launcher)
-  const bf16_t* yprev;     // EPI_MASK: raw pre-BN tensor at the output positions
-  const float* prev_coef;  // EPI_MASK: [4][COUT] s,t,mean,invstd of that BN
-  int B, Hin, Win;         // input spatial size (conv: out = Hin/2; deconv: out = 2*Hin)
-  // Progress word of the caller's stream: the first thread of the grid stores `sig_val` there when the kernel STARTS (i.e. after
-  // everything enqueued before it on its stream has completed).  Gate kernels on the engine's side streams poll that word, so a
-  // hand-over to a side stream needs no event record on the dependency chain (each one cost it ~5 us of bubble).
-  unsigned* sig;
-  unsigned sig_val;
-  BnAcc bacc;              // statistics go to fixed-point accumulators instead of stat_part (finalize folded into the consumer)
-  BnFold fold;             // SRC_BNRELU: build the source layer's coefficient table from its accumulators
-  BnBwdFold bfold;         // SRC_BNBWD: build the source layer's backward coefficient table from its accumulators
-  // fp8 variant (igemm8_s2_kernel, BASELINE config 5): wpack = e4m3 bytes [COUT][9][CIN];  qs[0] = 1 / (scale of the pixel
-  // operand) -- the fragments are converted bf16 -> e4m3 (activations) / e5m2 (gradients) with v_cvt_scalef32_pk_*_bf16, which
-  // DIVIDES by its scale operand --, qs[1] = 1 / (pixel scale * weight scale), applied to the accumulators;  amax: the largest
-  // |staged value| (bf16 bits << 16, atomicMax) for the next step's scale (delayed scaling, eae_fp8.hip)
-  const float* qs;
-  unsigned* amax;
-  int amax_mask;          // amax is an array of amax_mask + 1 slots (a power of two): workgroup t reports into slot t & amax_mask
-  int amax_stride;        // words between two slots (the engine: 32 = one 128-byte line per slot; per-op calls: 0 slots -> unused)
-  // SRC_BNBWD only: the BatchNorm-backward-applied gradient dy = A*g + B*y + C, exactly as staged (bf16, the source tensor's NHWC
-  // layout), is ALSO stored here by channel block 0 of every tile, so that the layer's weight-gradient kernel reads ONE plain
-  // tensor instead of transforming g and y again (SRC_RAWG, eae_wgrad.hip.h).  nullptr: off
-  bf16_t* dy_out;
-#ifdef EAE_STAMPS
-  unsigned long long* dbg; // diagnostic build only: s_memtime stamps of workgroup `dbg_block`, wave 0
-  int dbg_block;
-#endif
-};
+#include "eae_common.hip.h"      // (ConvArgs, KIND_*: eae_args.h)
 
 #ifdef EAE_STAMPS
 #define EAE_STAMP(i) do { if (a.dbg && (int)blockIdx.x == a.dbg_block && blockIdx.y == 0 && threadIdx.x == 0) { \
@@ -75,7 +39,6 @@ struct ConvArgs {
 #define EAE_STAMP_T(i, t) do {} while (0)
 #endif
 
-enum { KIND_CONV = 0, KIND_DECONV = 1 };
 constexpr int PIX_STRIDE = 40;       // edge / wgrad kernels: bf16 elements per staged pixel, 32 channels + 8 pad (80 B)
 // igemm patch: 2-D image [img][row][PWS pixels][32 ch], 64 B per pixel and no padding bytes (a 16x8 conv tile then fits
 // 4 workgroups per CU).  Inside every 256-byte group of 4 pixels of a row the pixel slot j and the 16-byte chunk c are permuted so
@@ -399,7 +362,7 @@ __device__ __forceinline__ void igemm_body(const ConvArgs& a, const int li_given
   rs.init<SRC>(a.src);
   // The 32 <-> 64-channel instances run at 3-4 workgroups per CU on 128-168 registers with 72 of them holding raw pieces: keeping the
   // piece offsets alive until the staging loop cost them 100-290 bytes of scratch (dec.deconv3's backward-data: 35 -> 53 us in the
-  // step).  They are built without the store; the engine never asks them for dy (eae_api.hip: dy_mask).
+  // step).  They are built without the store; the engine never asks them for dy (eae_step.hip: dy_mask).
   constexpr bool DY = SRC == SRC_BNBWD && CIN * COUT > 2048;
   const bool wr_dy = DY && a.dy_out != nullptr && nblk == 0;
   // (a workgroup that does not store dy -- no dy_out, or not channel block 0 -- gets a descriptor of ZERO bytes: its stores are all

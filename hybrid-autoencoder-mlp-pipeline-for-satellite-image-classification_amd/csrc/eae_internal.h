@@ -12,6 +12,7 @@ int eae_launch_deconv_s2(const ConvArgs& a, int cin, int cout, int src, int epi,
 int eae_conv_s2_ntiles(int kind, int B, int Hin, int Win, int cin = 0);   // statistics partials per channel = workgroups along grid.x
 
 #define EAE_HIP(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) return eae_set_error(-3, hipGetErrorString(e__)); } while (0)
+#define EAE_LAUNCH_CHECK() do { hipError_t e__ = hipGetLastError(); if (e__ != hipSuccess) return eae_set_error(-3, hipGetErrorString(e__)); } while (0)
 
 // Raise a kernel's dynamic-LDS limit once per (kernel, device): the attribute belongs to the device's code object, so a
 // process-wide "done" flag would skip it for a context created later on another device.
@@ -64,6 +65,8 @@ int eae_launch_scene_err_finalize(hipStream_t st, const float* part, int B, int 
                                   long long nwin, float* err, float* band_err);
 int eae_launch_wgrad_s2(hipStream_t st, const WgradArgs& a, int cs, int cb, int smode, int bmode, float* scratch,
                         long long scratch_floats, float* dw, const EaeProfHook* hook = nullptr);
+// out[i] = scale * sum_s part[s][i] over float4 elements i < n4 (reduce_slices_kernel, eae_wgrad.hip.h), for callers outside the kernel units
+int eae_launch_reduce_slices(hipStream_t st, const float* part, int nslices, long n4, float* out, float scale);
 int eae_launch_fc_nt(hipStream_t st, const FcNtArgs& a, int amode, int epi, int ksplit);
 int eae_launch_fc_reduce(hipStream_t st, const float* part, int nsl, int M, int N, const float* bias, const float* addend,
                          const float* addend2, float* out);

@@ -4,6 +4,7 @@
 // a scene"): augmented window batches and a label for every window from a label raster.  None uses matrix instructions, so all are
 // built with packed FP32 disabled (EAE_NO_PK, tests/test_isa_guard.py).
 #include "eae_internal.h"
+#include "eae_ctx.h"
 #include "eae_common.hip.h"
 #include "eae_edge.hip.h"
 
@@ -567,4 +568,129 @@ extern "C" int eae_scene_window_labels(void* stream, const void* raster, int ele
                        label, count, labelled);
   EAE_LAUNCH_CHECK();
   return 0;
+}
+
+// ---- scene calls: one checked window set and one batch driver under the seven entry points
+namespace {
+// The window set of a scene call.  windows == NULL: the range first .. first + count - 1 of the grid; otherwise the ids windows[0 .. count)
+// (first must be 0).  The ids stay on the device (no host synchronisation): the kernels read an id outside the grid as an all-zero window
+// and the epilogues write nothing for it.  Returns the grid (nH, nW).
+int scene_set_checks(eae_ctx* c, const eae_scene* s, long long first, const long long* windows, long long count, long long* nH,
+                     long long* nW) {
+  if (windows && count <= 0) return eae_set_error(EAE_ERR_ARG, "scene: the window list is empty");
+  if (!c) return eae_set_error(EAE_ERR_ARG, "scene: NULL context");
+  if (!c->P || !c->bnrun) return eae_set_error(EAE_ERR_STATE, "eae_bind has not been called");
+  if (c->fp8) return eae_set_error(EAE_ERR_ARG, "scene: quant=1 (fp8) contexts are not supported");
+  RC(eae_scene_check(s, nH, nW));
+  if (s->C != c->Cin) return eae_set_error(EAE_ERR_ARG, "scene: band count does not match the encoder's in_channels");
+  if (c->H != c->W || s->patch != c->H) return eae_set_error(EAE_ERR_ARG, "scene: the patch must be the (square) image size of the model");
+  if (windows ? first != 0 : count <= 0 || first < 0 || first + count > *nH * *nW)
+    return eae_set_error(EAE_ERR_ARG, "scene: windows outside the grid");
+  return 0;
+}
+int scene_list_check(const long long* windows) { return windows ? 0 : eae_set_error(EAE_ERR_ARG, "scene: NULL window list"); }
+
+// The batch driver: the checked window set in batches of max_batch, each encoded into c->z (rows of Lp floats) by conv1 reading the scene,
+// then handed to body(b0, nb, src): b0 = the batch's offset in the set, nb its size, src the scene source the encoder read.
+template <typename Body>
+int scene_run(eae_ctx* c, hipStream_t st, const eae_scene* s, long long nH, long long nW, long long first, const long long* windows,
+              long long count, Body body) {
+  invalidate_forward(c);
+  c->fwd_gen += 1;          // scene activations are never differentiated: a backward of an earlier forward is refused
+  RC(ensure_packed(c, st));
+  RC(prep_accumulators(c, st, false));
+  for (long long b0 = 0; b0 < count; b0 += c->Bm) {
+    const int nb = (int)(count - b0 < c->Bm ? count - b0 : c->Bm);
+    SceneSrc src;
+    eae_scene_fill_src(s, nW, first + b0, &src);
+    src.index = windows; src.nwin = nH * nW;
+    RC(run_encoder(c, st, nullptr, nb, false, s, &src));
+    RC(body(b0, nb, src));
+  }
+  return 0;
+}
+
+int scene_encode(eae_ctx* c, void* stream, const eae_scene* s, long long first, const long long* windows, long long count, float* z) {
+  long long nH = 0, nW = 0;
+  RC(scene_set_checks(c, s, first, windows, count, &nH, &nW));
+  if (!z) return eae_set_error(EAE_ERR_ARG, "scene_encode: NULL z");
+  hipStream_t st = (hipStream_t)stream;
+  return scene_run(c, st, s, nH, nW, first, windows, count,
+                   [&](long long b0, int nb, const SceneSrc&) { return copy_latent_out(c, st, z + (size_t)b0 * c->L, c->z, nb); });
+}
+
+int scene_classify(eae_ctx* c, eae_mlp* m, void* stream, const eae_scene* s, long long first, const long long* windows, long long count,
+                   float* probs, long long* labels) {
+  long long nH = 0, nW = 0;
+  RC(scene_set_checks(c, s, first, windows, count, &nH, &nW));
+  if (!m || !probs || !labels) return eae_set_error(EAE_ERR_ARG, "scene_classify: NULL mlp, probs or labels");
+  int in_dim = 0, classes = 0, mb = 0;
+  RC(eae_mlp_dims(m, &in_dim, &classes, &mb));
+  if (in_dim != c->L) return eae_set_error(EAE_ERR_ARG, "scene_classify: the MLP's input_dim is not the encoder's latent_dim");
+  hipStream_t st = (hipStream_t)stream;
+  return scene_run(c, st, s, nH, nW, first, windows, count, [&](long long b0, int nb, const SceneSrc&) {
+    return eae_mlp_predict(m, st, c->z, c->Lp, nb, first + b0, nH * nW, probs, labels, windows);
+  });
+}
+
+// scene reconstruction: encoder -> decoder over the window set, deconv4's MSE target read from the scene itself.  Per batch the decoder up to
+// deconv4, the scene-target deconv4 and the per-window finalize.  err may be NULL (reconstruct), recon may be NULL (error maps).
+int scene_recon(eae_ctx* c, void* stream, const eae_scene* s, long long first, const long long* windows, long long count, float* err,
+                float* band_err, float* recon, float* residual) {
+  long long nH = 0, nW = 0;
+  RC(scene_set_checks(c, s, first, windows, count, &nH, &nW));
+  if (!c->has_enc || !c->has_dec)
+    return eae_set_error(EAE_ERR_STATE, "scene reconstruction needs both halves bound (the engine of a stand-alone Encoder has no decoder)");
+  if (!err && !recon) return eae_set_error(EAE_ERR_ARG, "scene reconstruction: NULL output");
+  if (recon && (s->patch - s->stride) % 2)
+    return eae_set_error(EAE_ERR_ARG, "scene_reconstruct: patch - stride must be even (the owned spans are centred)");
+  Deconv4SceneArgs r;
+  r.part = c->msepart;         // [tiles][edge_lp_stride(C)] floats were carved: edge_bp_stride(C) <= edge_lp_stride(C)
+  r.recon = recon; r.residual = residual;
+  r.Wg = (int)eae_scene_extent(nW, s->patch, s->stride);
+  r.gplane = eae_scene_extent(nH, s->patch, s->stride) * r.Wg;
+  if (s->border) { r.Wg = s->W; r.gplane = (long long)s->H * s->W; }      // the stitched raster of a bordered scene is the real scene
+  r.nH = (int)nH; r.m = (s->patch - s->stride) / 2;
+  hipStream_t st = (hipStream_t)stream;
+  return scene_run(c, st, s, nH, nW, first, windows, count, [&](long long b0, int nb, const SceneSrc& src) {
+    Deconv4Args d;
+    RC(run_decoder_trunk(c, st, c->z, nb, false, d));
+    RC(eae_launch_deconv4_scene(st, eae_scene_src3_kind(s), d, src, r));
+    if (err) RC(eae_launch_scene_err_finalize(st, c->msepart, nb, s->patch, s->C, first + b0, windows, nH * nW, err, band_err));
+    return 0;
+  });
+}
+}  // namespace
+
+extern "C" int eae_scene_encode(eae_ctx* c, void* stream, const eae_scene* s, long long first, int B, float* z) {
+  return scene_encode(c, stream, s, first, nullptr, B, z);
+}
+extern "C" int eae_scene_encode_windows(eae_ctx* c, void* stream, const eae_scene* s, const long long* windows, long long count,
+                                        float* z) {
+  RC(scene_list_check(windows));
+  return scene_encode(c, stream, s, 0, windows, count, z);
+}
+
+extern "C" int eae_scene_classify(eae_ctx* c, eae_mlp* m, void* stream, const eae_scene* s, long long first, long long count, float* probs,
+                                  long long* labels) {
+  return scene_classify(c, m, stream, s, first, nullptr, count, probs, labels);
+}
+extern "C" int eae_scene_classify_windows(eae_ctx* c, eae_mlp* m, void* stream, const eae_scene* s, const long long* windows,
+                                          long long count, float* probs, long long* labels) {
+  RC(scene_list_check(windows));
+  return scene_classify(c, m, stream, s, 0, windows, count, probs, labels);
+}
+
+extern "C" int eae_scene_recon_error(eae_ctx* c, void* stream, const eae_scene* s, long long first, long long count, float* err,
+                                     float* band_err) {
+  return scene_recon(c, stream, s, first, nullptr, count, err, band_err, nullptr, nullptr);
+}
+extern "C" int eae_scene_recon_error_windows(eae_ctx* c, void* stream, const eae_scene* s, const long long* windows, long long count,
+                                             float* err, float* band_err) {
+  RC(scene_list_check(windows));
+  return scene_recon(c, stream, s, 0, windows, count, err, band_err, nullptr, nullptr);
+}
+extern "C" int eae_scene_reconstruct(eae_ctx* c, void* stream, const eae_scene* s, const long long* windows, long long count, float* recon,
+                                     float* residual) {
+  return scene_recon(c, stream, s, 0, windows, count, nullptr, nullptr, recon, residual);
 }

@@ -30,15 +30,6 @@
 #include "eae_common.hip.h"
 #include "eae_igemm.hip.h"
 
-struct WgradArgs {
-  SrcDesc small, big;
-  float* part;            // [nslices][CS][CB][9]
-  int B, Hs, Ws;          // small-map spatial size (big map = 2Hs x 2Ws)
-  int tiles_per_block, ntiles, nslices;
-  BnBwdFold bfold;        // the SRC_BNBWD operand's coefficient table from the layer's backward accumulators (eae_common.hip.h)
-  const float* qs;        // fp8 variant (wgrad8_s2_kernel): 1/scale of the small operand, 1/scale of the big operand, 1/(product)
-};
-
 constexpr int S_STRIDE = 72;   // bf16 elements per staged S row: 64 channels + 8 pad (144 B)
 constexpr int WG_EP_STRIDE = 292;   // floats per cs row of the epilogue image [64][32*9 (+4)]: 16-byte rows, conflict-free 4-byte writes
 constexpr int WG_THREADS = 768, WG_PRODUCERS = 512;

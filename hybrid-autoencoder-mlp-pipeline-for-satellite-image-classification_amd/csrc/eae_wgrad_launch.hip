@@ -67,6 +67,12 @@ int geo(const WgradArgs& a, float* scratch, long long sf, float* dw, hipStream_t
 }
 }  // namespace
 
+int eae_launch_reduce_slices(hipStream_t st, const float* part, int nslices, long n4, float* out, float scale) {
+  launch_reduce_slices(st, part, nslices, n4, out, scale);
+  EAE_LAUNCH_CHECK();
+  return 0;
+}
+
 // instantiations used by the path
 //   conv2/3/4   : small = dy  (BNBWD), big = input activation (BNRELU): (64,32) (128,64) (256,128)
 //   deconv3/2   : small = input activation (BNRELU), big = dOut (BNBWD): (64,32) (128,64)

@@ -211,7 +211,7 @@ class DataParallelTrainer:
         after the second half.  The 1/world scaling is folded into the Adam kernel."""
         eng = self.eng
         if self.sync_bn is not None:
-            # SyncBN multiplies the per-rank element count by the world size (eae_api.hip fold_consumer / bn_bwd_fin): every rank must
+            # SyncBN multiplies the per-rank element count by the world size (eae_step.hip fold_consumer / bn_bwd_fin): every rank must
             # feed the same number of images, or mean / variance / the backward terms are silently wrong (ADVICE r2).  One tiny
             # collective more in a mode that already issues 14 per step.
             b = int(x.shape[0])

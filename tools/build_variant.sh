@@ -7,11 +7,13 @@ PKG=$(dirname "$0")/../hybrid-autoencoder-mlp-pipeline-for-satellite-image-class
 PKG=$(cd "$PKG" && pwd)
 OBJ=$PKG/csrc/_obj_$TAG
 mkdir -p "$OBJ"
-pids=()
-for s in eae_api eae_conv_launch eae_edge_launch eae_wgrad_launch eae_fc_launch eae_misc eae_head eae_mlp; do
+# the translation units are the product library's (build.SOURCES)
+SOURCES=$(cd "$PKG" && python3 -c "import build; print(' '.join(s[:-len('.hip')] for s in build.SOURCES))")
+pids=(); objs=()
+for s in $SOURCES; do
   hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wno-unused-result "$@" -c "$PKG/csrc/$s.hip" -o "$OBJ/$s.o" &
-  pids+=($!)
+  pids+=($!); objs+=("$OBJ/$s.o")
 done
 for p in "${pids[@]}"; do wait $p; done
-hipcc --offload-arch=gfx950 -shared -fPIC -o "$PKG/libeae_$TAG.so" "$OBJ"/*.o
+hipcc --offload-arch=gfx950 -shared -fPIC -o "$PKG/libeae_$TAG.so" "${objs[@]}"
 echo "$PKG/libeae_$TAG.so"
