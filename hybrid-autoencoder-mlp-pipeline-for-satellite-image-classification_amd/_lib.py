@@ -51,6 +51,8 @@ _PROTOS = {
     "eae_fp8_scales": (C.c_int, [vp, vp]),
     "eae_params_changed": (C.c_int, [vp]),
     "eae_set_graph": (C.c_int, [vp, C.c_int]),
+    "eae_set_class_weights": (C.c_int, [vp, vp, C.c_longlong]),
+    "eae_set_valid_counter": (C.c_int, [vp, vp]),
     "eae_set_adam_step": (C.c_int, [vp, C.c_longlong]),
     "eae_get_adam_step": (C.c_longlong, [vp]),
     "eae_ae_forward": (C.c_int, [vp, vp, C.POINTER(EaeStepIO)]),
@@ -104,6 +106,7 @@ _PROTOS = {
     "eae_op_fc_wgrad": (C.c_int, [vp, C.c_int, EaeSrc, EaeSrc, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "eae_op_head_scratch_floats": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
     "eae_op_head_ce": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_longlong]),
+    "eae_op_head_ce_w": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_longlong, vp, C.c_longlong]),
     "eae_op_sigmoid_bwd": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "eae_op_pack_edge": (C.c_int, [vp, vp, C.c_int, vp, vp]),
     "eae_op_edge_conv_c": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp]),
@@ -123,6 +126,8 @@ _PROTOS = {
     "eae_mlp_backward": (C.c_int, [vp, vp, vp, C.c_int, C.c_ulonglong, vp, vp]),
     "eae_mlp_train_step": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_float, C.c_float, C.c_ulonglong, vp, vp, vp]),
     "eae_mlp_eval_step": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, vp]),
+    "eae_mlp_set_class_weights": (C.c_int, [vp, vp, C.c_longlong]),
+    "eae_mlp_set_valid_counter": (C.c_int, [vp, vp]),
     "eae_scene_windows": (C.c_int, [vp, C.POINTER(EaeScene), C.c_longlong, C.c_int, vp]),
     "eae_scene_encode": (C.c_int, [vp, vp, C.POINTER(EaeScene), C.c_longlong, C.c_int, vp]),
     "eae_scene_classify": (C.c_int, [vp, vp, vp, C.POINTER(EaeScene), C.c_longlong, C.c_longlong, vp, vp]),
@@ -142,6 +147,7 @@ _PROTOS = {
 }
 
 EXPORTS = tuple(_PROTOS.keys())
+NO_IGNORE = -2 ** 63          # EAE_NO_IGNORE (include/eae.h)
 _lib = None
 
 

@@ -147,6 +147,11 @@ struct eae_ctx {
   int ngraphs = 0;
   bool use_graph = true;
   bool capturing = false;
+  // class-weighted CrossEntropyLoss with ignored labels (eae_set_class_weights): the head runs its weighted kernels when either is set
+  const float* class_w = nullptr;  // caller-owned device fp32 [C], or nullptr (all ones)
+  long long ignore_index = EAE_NO_IGNORE;
+  bool wce() const { return class_w != nullptr || ignore_index != EAE_NO_IGNORE; }
+  long long* valid_acc = nullptr;  // eae_set_valid_counter: caller-owned device word, += counted rows of every step that accumulates its loss
   float* dyn = nullptr;            // device: lr/bc1, sqrt(bc2), weight decay of the current Adam step
   // optional in-situ timing of ONE launch site (eae_profile_enable(ctx, site); sites: include/eae.h) with HIP events on the
   // stream that launch goes to

@@ -293,16 +293,14 @@ extern "C" int eae_profile_read2(eae_ctx* c, double* total_ms, double* empty_ms,
 }
 extern "C" int eae_profile_read(eae_ctx* c, double* total_ms, long long* count) { return eae_profile_read2(c, total_ms, nullptr, count); }
 
+static int drop_graphs(eae_ctx* c, bool drain);
 extern "C" int eae_destroy(eae_ctx* c) {
   if (!c) return 0;
   hipDeviceSynchronize();
   streams_forget(c);
   eae_dp_destroy(c);
   if (c->prof_ev[0]) for (int i = 0; i < 3 * eae_ctx::PROF_RING; ++i) hipEventDestroy(c->prof_ev[i]);
-  for (int i = 0; i < c->ngraphs; ++i) {
-    if (c->graphs[i].exec) hipGraphExecDestroy(c->graphs[i].exec);
-    if (c->graphs[i].graph) hipGraphDestroy(c->graphs[i].graph);
-  }
+  drop_graphs(c, false);           // (the device has drained above)
   if (c->side) {
     for (int i = 0; i < eae_ctx::NEV; ++i) hipEventDestroy(c->ev_fork[i]);
     hipEventDestroy(c->ev_join);
@@ -376,6 +374,34 @@ extern "C" long long eae_gate_timeouts(eae_ctx* c) {
 extern "C" int eae_set_graph(eae_ctx* c, int on) {
   if (!c) return eae_set_error(EAE_ERR_ARG, "ctx is NULL");
   c->use_graph = on != 0;
+  return 0;
+}
+// A captured step graph holds the head kernel and the pointers of the setting it was captured under: dropped (after the device has
+// drained: one may be in flight) whenever the setting changes; the next steps capture again.
+static int drop_graphs(eae_ctx* c, bool drain) {
+  if (!c->ngraphs) return 0;
+  if (drain) EAE_HIP(hipDeviceSynchronize());
+  for (int i = 0; i < c->ngraphs; ++i) {
+    if (c->graphs[i].exec) EAE_HIP(hipGraphExecDestroy(c->graphs[i].exec));
+    if (c->graphs[i].graph) EAE_HIP(hipGraphDestroy(c->graphs[i].graph));
+    c->graphs[i] = eae_ctx::GraphEntry();
+  }
+  c->ngraphs = 0;
+  return 0;
+}
+// Class weights / ignore_index of the fused CrossEntropyLoss (include/eae.h).
+extern "C" int eae_set_class_weights(eae_ctx* c, const float* weights, long long ignore_index) {
+  if (!c) return eae_set_error(EAE_ERR_ARG, "ctx is NULL");
+  if (c->capturing) return eae_set_error(EAE_ERR_STATE, "set_class_weights: a step is being captured");
+  RC(drop_graphs(c, true));
+  c->class_w = weights; c->ignore_index = ignore_index;
+  return 0;
+}
+extern "C" int eae_set_valid_counter(eae_ctx* c, long long* counter) {
+  if (!c) return eae_set_error(EAE_ERR_ARG, "ctx is NULL");
+  if (c->capturing) return eae_set_error(EAE_ERR_STATE, "set_valid_counter: a step is being captured");
+  RC(drop_graphs(c, true));
+  c->valid_acc = counter;
   return 0;
 }
 extern "C" int eae_params_changed(eae_ctx* c) { if (!c) return eae_set_error(EAE_ERR_ARG, "ctx is NULL"); c->packed = false; invalidate_forward(c); return 0; }

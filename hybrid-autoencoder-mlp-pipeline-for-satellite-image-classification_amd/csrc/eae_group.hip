@@ -51,6 +51,8 @@ int group_run(int what, eae_ctx* const* ctxs, int n, int mult, void* stream, con
     if (c->prof_on || c->fp8 || c->dp_comm || c->use_gates != c0->use_gates || c->use_side != c0->use_side || c->nx != c0->nx)
       return eae_set_error(EAE_ERR_STATE, "group call: members must share the stream layout, with profiling, fp8 and data parallel off");
     if (c->Cin != c0->Cin) return eae_set_error(EAE_ERR_ARG, "group call: members must share in_channels");
+    if (c->wce() != c0->wce())       // one head kernel serves the whole group (each member with its own vector and ignore_index)
+      return eae_set_error(EAE_ERR_ARG, "group call: class weights / ignore_index must be set on every member or on none");
     for (int j = 0; j < k; ++j) if (ctxs[j] == c) return eae_set_error(EAE_ERR_ARG, "group call: a context appears twice");
   }
   RC(streams_distinct(c0, user));

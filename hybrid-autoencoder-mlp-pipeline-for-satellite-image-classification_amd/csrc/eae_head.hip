@@ -21,8 +21,16 @@ constexpr int HC = 64;  // logits row stride in LDS = largest class count
 // bank slots.  Arithmetic stays fp32 fmaf chains (the head is fp32 end to end: <= 5e-5 vs the reference's goldens).
 // W2G: W2 is read from global memory instead of a staged copy.  W1 at L = 256 takes 130 KB; with more than 20 classes the staged W2
 // ([C][132] floats, 33 KB at C = 64) no longer fits beside it in the CU's 160 KB (eae_launch_head picks the variant).
-template <int HR_, bool W2G = false>
-__device__ __forceinline__ EAE_NO_PK void head_body(const HeadArgs& a) {     // <= 96 VGPRs: the kernel runs beside the decoder on a side stream, and a wave-specialised igemm2 workgroup (2 x 200 registers per SIMD lane) must still fit beside one of its waves -- at 132 registers dec.deconv1's forward waited for the head's 32 CUs (15 -> 28 us)
+// WCE: class-weighted CrossEntropyLoss with ignored labels (include/eae.h, eae_set_class_weights).  A row counts when its label is
+// not `ign` and lies in [0, C); W = sum of cw[label] over the counted rows of the WHOLE batch, summed by every block in one fixed
+// order (thread t takes rows t, t + 256, ..; xor butterfly inside each wave; the four wave sums added in wave order), so every block
+// holds the same bits without a hand-over between blocks.  dlogits = (softmax - onehot) * cw[label] / W, an exact zero row for a row
+// that does not count; the block's loss partial carries B / W so that the unchanged finalize kernels' "/ B" yields the weighted mean.
+// W == 0 (nothing counted): loss and gradients are zero.  The same pass counts the counted rows; block 0 adds the count to the device
+// word `valid` (eae_set_valid_counter): the labelled-sample count costs no launch.  The instantiations with WCE = false are instruction for instruction the
+// kernels they were before the flag existed.
+template <int HR_, bool W2G = false, bool WCE = false>
+__device__ __forceinline__ EAE_NO_PK void head_body(const HeadArgs& a, const float* cw = nullptr, long long ign = 0, long long* valid = nullptr) {     // <= 96 VGPRs: the kernel runs beside the decoder on a side stream, and a wave-specialised igemm2 workgroup (2 x 200 registers per SIMD lane) must still fit beside one of its waves -- at 132 registers dec.deconv1's forward waited for the head's 32 CUs (15 -> 28 us)
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int L = a.L, C = a.C, LS = L + 4, HS = 132;
   float* w1 = sm;                    // [128][LS]
@@ -36,6 +44,8 @@ __device__ __forceinline__ EAE_NO_PK void head_body(const HeadArgs& a) {     // 
   float* b1 = lg + HR_ * HC;         // [128]
   float* b2 = b1 + 128;              // [HC]
   float* rl = b2 + HC;               // [HR_] per-row loss, [HR_] per-row correct
+  float* cws = rl + 2 * HR_;         // WCE: [HC] class weights (ones without a vector)
+  float* wsum = cws + HC;            // WCE: [4] per-wave sums of cw[label] over the batch, [4] per-wave counts of counted rows (int)
   const int tid = threadIdx.x;
   const int r0 = blockIdx.x * HR_;
   const int L4 = L >> 2;
@@ -56,7 +66,19 @@ __device__ __forceinline__ EAE_NO_PK void head_body(const HeadArgs& a) {     // 
     }
   if (tid < 128) b1[tid] = a.b1[tid];
   if (tid < C) b2[tid] = a.b2[tid];
+  if (WCE && tid < C) cws[tid] = cw ? cw[tid] : 1.f;
   __syncthreads();
+  if (WCE) {
+    float s = 0.f;
+    int n = 0;
+    for (int r = tid; r < a.B; r += 256) {          // (a weighted kernel is launched with labels and without an external dlogits only)
+      const long long lab = a.labels[r];
+      if (lab != ign && lab >= 0 && lab < C) { s += cws[(int)lab]; ++n; }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { s += __shfl_xor(s, o, 64); n += __shfl_xor(n, o, 64); }
+    if ((tid & 63) == 0) { wsum[tid >> 6] = s; reinterpret_cast<int*>(wsum)[4 + (tid >> 6)] = n; }      // read behind the next two barriers
+  }
   {   // h_pre[r][j]: 2 rows x 4 columns per thread
     constexpr int RT = HR_ / 2;                 // row pairs
     const int ct = tid & 31, rt = tid >> 5;     // 8 row groups x 32 column groups
@@ -105,6 +127,23 @@ __device__ __forceinline__ EAE_NO_PK void head_body(const HeadArgs& a) {     // 
       if (a.logits) for (int c = 0; c < C; ++c) a.logits[(size_t)r * C + c] = lg[tid * HC + c];
       if (a.dlogits_in) {
         for (int c = 0; c < C; ++c) lg[tid * HC + c] = a.dlogits_in[(size_t)r * C + c];
+      } else if (WCE) {
+        const long long lab64 = a.labels[r];
+        const float wtot = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+        const float inv_w = wtot > 0.f ? 1.0f / wtot : 0.f;
+        if (lab64 != ign && lab64 >= 0 && lab64 < C) {
+          const int lab = (int)lab64;
+          const float wl = cws[lab];
+          loss = wl * (lse - lg[tid * HC + lab]) * ((float)a.B * inv_w);
+          correct = (am == lab) ? 1.f : 0.f;
+          const float sc = wl * inv_w;
+          for (int c = 0; c < C; ++c) {
+            float pr = expf(lg[tid * HC + c] - lse);
+            lg[tid * HC + c] = (pr - (c == lab ? 1.f : 0.f)) * sc;
+          }
+        } else {
+          for (int c = 0; c < C; ++c) lg[tid * HC + c] = 0.f;
+        }
       } else if (a.labels) {
         int lab = (int)a.labels[r];
         loss = lse - lg[tid * HC + lab];
@@ -124,6 +163,10 @@ __device__ __forceinline__ EAE_NO_PK void head_body(const HeadArgs& a) {     // 
     float s = 0.f, cr = 0.f;
     for (int r = 0; r < HR_; ++r) { s += rl[r]; cr += rl[HR_ + r]; }
     a.loss_part[blockIdx.x * 2] = s; a.loss_part[blockIdx.x * 2 + 1] = cr;
+  }
+  if (WCE && tid == 0 && blockIdx.x == 0 && valid) {      // one writer per launch; launches of a context are ordered by its streams
+    const int* wn = reinterpret_cast<const int*>(wsum) + 4;
+    *valid += (long long)(wn[0] + wn[1] + wn[2] + wn[3]);
   }
   if ((!a.labels && !a.dlogits_in) || !a.grad_part) return;
   // dh[r][j] = (h_pre > 0) * sum_c dlogits[r][c] * W2[c][j]
@@ -196,22 +239,37 @@ template <int HR_>
 __global__ EAE_NO_PK __launch_bounds__(256, 5) void head_kernel_g(GroupPack<HeadArgs> p, int gz) { head_body<HR_>(group_args<HeadArgs>(gz)); }
 __global__ EAE_NO_PK __launch_bounds__(256) void head_kernel_w2g(HeadArgs a) { head_body<8, true>(a); }
 __global__ EAE_NO_PK __launch_bounds__(256) void head_kernel_w2g_g(GroupPack<HeadArgs> p, int gz) { head_body<8, true>(group_args<HeadArgs>(gz)); }
+template <int HR_>
+__global__ EAE_NO_PK __launch_bounds__(256, 5) void head_kernel_wce(HeadArgsW a) { head_body<HR_, false, true>(a.h, a.class_w, a.ignore_index, a.valid); }
+template <int HR_>
+__global__ EAE_NO_PK __launch_bounds__(256, 5) void head_kernel_wce_g(GroupPack<HeadArgsW> p, int gz) {
+  const HeadArgsW a = group_args<HeadArgsW>(gz);
+  head_body<HR_, false, true>(a.h, a.class_w, a.ignore_index, a.valid);
+}
+__global__ EAE_NO_PK __launch_bounds__(256) void head_kernel_w2g_wce(HeadArgsW a) { head_body<8, true, true>(a.h, a.class_w, a.ignore_index, a.valid); }
+__global__ EAE_NO_PK __launch_bounds__(256) void head_kernel_w2g_wce_g(GroupPack<HeadArgsW> p, int gz) {
+  const HeadArgsW a = group_args<HeadArgsW>(gz);
+  head_body<8, true, true>(a.h, a.class_w, a.ignore_index, a.valid);
+}
 constexpr size_t HEAD_LDS_MAX = 160 * 1024;     // LDS of a gfx950 CU = the most one workgroup can ask for
 
 static int head_rows(int L) { return L <= 128 ? 16 : 8; }
 int eae_head_blocks(int B, int L) { const int hr = head_rows(L); return (B + hr - 1) / hr; }
 
-int eae_launch_head(hipStream_t st, const HeadArgs& a) {
+// A = HeadArgs (k*: the plain kernels) or HeadArgsW (the weighted ones, `extra` more floats of LDS): full = what the kernel receives
+template <class A>
+static int head_launch(hipStream_t st, const HeadArgs& a, const A& full, size_t extra, void (*k16)(A), void (*k8)(A), void (*kw2g)(A),
+                       void (*g16)(GroupPack<A>, int), void (*g8)(GroupPack<A>, int), void (*gw2g)(GroupPack<A>, int)) {
   if (a.L > 256 || a.C > HC || a.L % 4) return eae_set_error(-2, "head: latent_dim must be <= 256 (multiple of 4), classes <= 64");
   const int hr = head_rows(a.L);
-  const size_t smem_rest = sizeof(float) * ((size_t)128 * (a.L + 4) + (size_t)hr * (a.L + 4) + 2 * hr * 132 + hr * HC + 128 + HC + 2 * hr);
+  const size_t smem_rest = sizeof(float) * ((size_t)128 * (a.L + 4) + (size_t)hr * (a.L + 4) + 2 * hr * 132 + hr * HC + 128 + HC + 2 * hr + extra);
   const size_t smem_w2 = sizeof(float) * ((a.C * 132 + 3) & ~3);
   const bool w2g = hr == 8 && smem_rest + smem_w2 > HEAD_LDS_MAX;     // wide latent and many classes: W2 stays in global memory
   const size_t smem = smem_rest + (w2g ? 0 : smem_w2);
   // the dynamic-LDS limit is an attribute of the kernel ON ONE DEVICE and the request grows with the latent width: keep the
   // largest size granted per (kernel, device) (a process-wide static skipped the attribute for an engine on a second device)
-  void (*kern)(HeadArgs) = w2g ? head_kernel_w2g : hr == 16 ? head_kernel<16> : head_kernel<8>;
-  void (*kern_g)(GroupPack<HeadArgs>, int) = w2g ? head_kernel_w2g_g : hr == 16 ? head_kernel_g<16> : head_kernel_g<8>;
+  void (*kern)(A) = w2g ? kw2g : hr == 16 ? k16 : k8;
+  void (*kern_g)(GroupPack<A>, int) = w2g ? gw2g : hr == 16 ? g16 : g8;
   {
     static thread_local std::vector<std::pair<std::pair<const void*, int>, size_t>> granted;
     int dev = 0;
@@ -224,9 +282,19 @@ int eae_launch_head(hipStream_t st, const HeadArgs& a) {
       if (have) *have = smem; else granted.push_back({{f, dev}, smem});
     }
   }
-  eae_launch(kern, kern_g, dim3((a.B + hr - 1) / hr), dim3(256), (unsigned)smem, st, a);
+  eae_launch(kern, kern_g, dim3((a.B + hr - 1) / hr), dim3(256), (unsigned)smem, st, full);
   EAE_LAUNCH_CHECK();
   return 0;
+}
+int eae_launch_head(hipStream_t st, const HeadArgs& a) {
+  return head_launch<HeadArgs>(st, a, a, 0, head_kernel<16>, head_kernel<8>, head_kernel_w2g, head_kernel_g<16>, head_kernel_g<8>, head_kernel_w2g_g);
+}
+// the weighted kernels; labels NULL or an external dlogits: nothing to weight, the plain kernels run
+int eae_launch_head_w(hipStream_t st, const HeadArgs& a, const float* class_w, long long ignore_index, long long* valid) {
+  if (!a.labels || a.dlogits_in) return eae_launch_head(st, a);
+  const HeadArgsW w = {a, class_w, ignore_index, valid};
+  return head_launch<HeadArgsW>(st, a, w, HC + 8, head_kernel_wce<16>, head_kernel_wce<8>, head_kernel_w2g_wce, head_kernel_wce_g<16>,
+                                head_kernel_wce_g<8>, head_kernel_w2g_wce_g);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -152,9 +152,9 @@ static long long head_stride_of(int L, int C) { return r4(128LL * L) + 128 + r4(
 extern "C" long long eae_op_head_scratch_floats(int B, int L, int C) {
   return (long long)eae_head_blocks(B, L) * (head_stride_of(L, C) + 2) + 64;
 }
-extern "C" int eae_op_head_ce(void* stream, const float* z, const float* w1, const float* b1, const float* w2, const float* b2,
-                              const long long* labels, int B, int L, int C, float* logits, float* dz, float* grads, float* loss2,
-                              float* scratch, long long scratch_floats) {
+static int op_head_ce(void* stream, const float* z, const float* w1, const float* b1, const float* w2, const float* b2,
+                      const long long* labels, int B, int L, int C, float* logits, float* dz, float* grads, float* loss2,
+                      float* scratch, long long scratch_floats, bool wce, const float* class_w, long long ignore_index) {
   if (!z || !w1 || !b1 || !w2 || !b2 || !scratch) return eae_set_error(EAE_ERR_ARG, "head_ce: NULL argument");
   if (scratch_floats < eae_op_head_scratch_floats(B, L, C)) return eae_set_error(EAE_ERR_ARG, "head_ce: scratch too small");
   hipStream_t st = (hipStream_t)stream;
@@ -165,10 +165,22 @@ extern "C" int eae_op_head_ce(void* stream, const float* z, const float* w1, con
   HeadArgs h = HeadArgs();
   h.z = z; h.w1 = w1; h.b1 = b1; h.w2 = w2; h.b2 = b2; h.labels = labels; h.B = B; h.L = L; h.C = C; h.inv_batch = 1.0f / (float)B;
   h.logits = logits; h.dz = dz; h.grad_part = (labels && grads) ? gpart : nullptr; h.grad_stride = stride; h.loss_part = ce_part;
-  RC(eae_launch_head(st, h));
+  if (wce) RC(eae_launch_head_w(st, h, class_w, ignore_index));
+  else RC(eae_launch_head(st, h));
   if (labels && grads) RC(eae_launch_reduce_slices(st, gpart, nb, (long)(stride / 4), grads, 1.0f));
   if (labels && loss2) RC(eae_launch_ce_mean(st, ce_part, nb, B, loss2));
   return 0;
+}
+extern "C" int eae_op_head_ce(void* stream, const float* z, const float* w1, const float* b1, const float* w2, const float* b2,
+                              const long long* labels, int B, int L, int C, float* logits, float* dz, float* grads, float* loss2,
+                              float* scratch, long long scratch_floats) {
+  return op_head_ce(stream, z, w1, b1, w2, b2, labels, B, L, C, logits, dz, grads, loss2, scratch, scratch_floats, false, nullptr, 0);
+}
+extern "C" int eae_op_head_ce_w(void* stream, const float* z, const float* w1, const float* b1, const float* w2, const float* b2,
+                                const long long* labels, int B, int L, int C, float* logits, float* dz, float* grads, float* loss2,
+                                float* scratch, long long scratch_floats, const float* class_w, long long ignore_index) {
+  return op_head_ce(stream, z, w1, b1, w2, b2, labels, B, L, C, logits, dz, grads, loss2, scratch, scratch_floats,
+                    class_w != nullptr || ignore_index != EAE_NO_IGNORE, class_w, ignore_index);
 }
 extern "C" int eae_op_pack3x3(void* stream, const float* w, int A, int B, void* p1, void* p2) {
   // one-off helper for tests: builds a 2-entry descriptor table on the fly (synchronous upload)

@@ -175,13 +175,15 @@ int run_decoder(eae_ctx* c, hipStream_t st, const float* z, int B, bool train, c
   return 0;
 }
 
-int run_head(eae_ctx* c, hipStream_t st, int B, const long long* labels, float* logits, bool want_grad, const float* dlogits_in) {
+int run_head(eae_ctx* c, hipStream_t st, int B, const long long* labels, float* logits, bool want_grad, const float* dlogits_in,
+             bool count_valid = false) {
   HeadArgs h = HeadArgs();
   h.dlogits_in = dlogits_in;
   h.z = c->z; h.w1 = c->lpad ? (const float*)(c->pack + c->pk_w1p) : c->P + c->poff[34]; h.b1 = c->P + c->poff[35]; h.w2 = c->P + c->poff[36]; h.b2 = c->P + c->poff[37];
   h.labels = labels; h.B = B; h.L = c->Lp; h.C = c->C; h.inv_batch = 1.0f / (float)B;
   h.logits = logits; h.dz = c->dzc; h.grad_part = want_grad ? c->headpart : nullptr; h.grad_stride = c->head_stride;
   h.loss_part = c->cepart;
+  if (c->wce()) return eae_launch_head_w(st, h, c->class_w, c->ignore_index, count_valid ? c->valid_acc : nullptr);     // (labels NULL or external dlogits: the plain kernels)
   return eae_launch_head(st, h);
 }
 
@@ -342,15 +344,16 @@ int forward_impl(eae_ctx* c, hipStream_t st, const eae_step_io* io, bool want_gr
     if (want_grad && c->use_side) {
       const long long* labels = io->labels;
       float* logits = io->logits;
+      const bool count = io->loss_accum != nullptr;      // the labelled-sample count goes with the loss accumulators
       sq_push(c, [=](hipStream_t hs, float*) {
-        RC(run_head(c, hs, B, labels, logits, true, nullptr));
+        RC(run_head(c, hs, B, labels, logits, true, nullptr, count));
         EAE_HIP(eae_event_record(c->ev_head, hs));
         return 0;
       }, 0);
       sq_fork(c);                  // released by the decoder's first kernel (run_decoder commits behind it)
       c->head_pending = true;
     } else {
-      RC(run_head(c, st, B, io->labels, io->logits, want_grad, nullptr));
+      RC(run_head(c, st, B, io->labels, io->logits, want_grad, nullptr, io->loss_accum != nullptr));
     }
   }
   RC(run_decoder(c, st, c->z, B, train, (want_loss || want_grad) ? io->x : nullptr, gscale, io->x_hat, want_grad, want_loss));

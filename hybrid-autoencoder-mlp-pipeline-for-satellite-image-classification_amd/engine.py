@@ -47,6 +47,26 @@ def _require_gpu(device):
         raise RuntimeError("the autoencoder engine runs on a HIP device only (model.to('cuda')); there is no CPU path")
 
 
+def class_weight_args(weights, ignore_index, classes, device):
+    """(fp32 device copy of the class weights or None, ignore_index as the C ABI takes it) for `set_class_weights` of the two engines.
+    Rejects a wrong length, negative or non-finite weights and an all-zero vector."""
+    w = None
+    if weights is not None:
+        w = torch.as_tensor(weights).detach().to(dtype=torch.float32, device="cpu").reshape(-1)
+        if w.numel() != int(classes):
+            raise RuntimeError(f"class weights must have one entry per class ({classes}), got {w.numel()}")
+        if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+            raise RuntimeError("class weights must be finite and >= 0")
+        if not bool((w > 0).any()):
+            raise RuntimeError("class weights must not all be zero")
+        w = w.to(device).contiguous()
+    if ignore_index is None:
+        return w, _lib.NO_IGNORE
+    if isinstance(ignore_index, bool) or int(ignore_index) != ignore_index or not -2 ** 63 < int(ignore_index) < 2 ** 63:
+        raise RuntimeError(f"ignore_index must be an integer or None, got {ignore_index!r}")
+    return w, int(ignore_index)
+
+
 class AEEngine:
     """Owns the arenas + C context of one SupervisedAutoencoder (or a stand-alone Encoder / Decoder)."""
 
@@ -87,6 +107,8 @@ class AEEngine:
             self.bn_nbt = torch.zeros(7, dtype=torch.int64, device=self.device)
             self.loss_accum = torch.zeros(8, dtype=torch.float32, device=self.device)
             self.loss_last = torch.zeros(4, dtype=torch.float32, device=self.device)
+            self.valid = torch.zeros((), dtype=torch.int64, device=self.device)
+        self.class_weights, self.ignore_index = None, None
         # slots: (module attribute path) in named_parameters() order of SupervisedAutoencoder
         self._slots = []      # (param tensor holder, index)
         self._bn_slots = []   # (bn module, l)
@@ -118,6 +140,7 @@ class AEEngine:
             check(self.lib.eae_bind(self.ctx, _ptr(self.params), _ptr(self.grads), _ptr(self.adam_m), _ptr(self.adam_v),
                                     _ptr(self.bn_running), _ptr(self.bn_nbt)))
             check(self.lib.eae_set_halves(self.ctx, int(enc is not None), int(dec is not None)))
+            check(self.lib.eae_set_valid_counter(self.ctx, _ptr(self.valid)))     # written by the head kernel while class weights / ignore_index are set
         self._finalizer = weakref.finalize(self, _destroy, self.lib, self.ctx, self.device)
         # one hook per module, reaching whichever engine currently serves it (a rebuilt engine must not keep the old one alive)
         if not getattr(root, "_eae_hooked", False):
@@ -170,6 +193,30 @@ class AEEngine:
         """Replay train_step from a captured hipGraph (one host call per step) instead of ~70 eager launches: for host-bound use,
         i.e. several small configurations stepped concurrently (train.run_concurrent)."""
         check(self.lib.eae_set_graph(self.ctx, int(bool(on))))
+
+    @_on_device
+    def set_class_weights(self, weights=None, ignore_index=None):
+        """CrossEntropyLoss(weight=weights, ignore_index=ignore_index) in every fused step of this engine (include/eae.h
+        eae_set_class_weights): weights = a [num_classes] tensor or sequence (finite, >= 0, not all zero; an fp32 device copy is kept
+        alive here) or None; ignore_index = an integer or None.  With either set, every label outside [0, num_classes) is ignored too,
+        and the head kernel counts the labelled samples of every accumulating step into a device word (`read_valid`; no extra
+        launch).  Both None switch the feature off."""
+        w, ign = class_weight_args(weights, ignore_index, self.classes, self.device)
+        check(self.lib.eae_set_class_weights(self.ctx, _ptr(w), ign))
+        self.class_weights, self.ignore_index = w, (None if ignore_index is None else int(ignore_index))
+        self.valid.zero_()          # the count starts with the setting (a reset while the feature is off leaves the word alone)
+
+    @property
+    def weighted(self):
+        return self.class_weights is not None or self.ignore_index is not None
+
+    def read_valid(self):
+        """Number of counted (labelled) samples in the steps accumulated since reset_loss(), for an accuracy over the labelled samples
+        (read_loss()[4] / read_valid()); the engine-owned data-parallel step counts too.  With the feature off every sample counts:
+        read_loss()[3].  One D2H sync."""
+        if not self.weighted:
+            return int(self.loss_accum[3].item())
+        return int(self.valid.item())
 
     def gate_timeouts(self):
         """0, or the progress value a side-stream gate gave up waiting for (diagnostic; synchronises the device)."""
@@ -352,6 +399,8 @@ class AEEngine:
 
     def reset_loss(self):
         self.loss_accum.zero_()
+        if self.weighted:
+            self.valid.zero_()
 
     def read_loss(self):
         """(mean loss, mean mse, mean ce, n samples, n correct) accumulated since reset_loss(); one D2H sync."""
@@ -419,6 +468,10 @@ def _engine_for_locked(module, max_batch, quant):
                 eng.adam_m.copy_(old.adam_m)
                 eng.adam_v.copy_(old.adam_v)
                 eng.loss_accum.copy_(old.loss_accum)
+            if old.weighted:
+                eng.set_class_weights(old.class_weights, old.ignore_index)
+            with torch.no_grad():
+                eng.valid.copy_(old.valid)
             check(eng.lib.eae_set_adam_step(eng.ctx, old.lib.eae_get_adam_step(old.ctx)))
         _ENGINES[root] = eng
     return eng

@@ -8,7 +8,7 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .engine import _ptr, _stream, _require_gpu
+from .engine import _ptr, _stream, _require_gpu, class_weight_args
 
 _ENGINES = weakref.WeakKeyDictionary()
 
@@ -33,6 +33,8 @@ class MLPEngine:
         self.bn_running = torch.zeros(self.boff[4], dtype=torch.float32, device=dev)
         self.bn_nbt = torch.zeros(2, dtype=torch.int64, device=dev)
         self.stats = torch.zeros(8, dtype=torch.float32, device=dev)
+        self.valid = torch.zeros((), dtype=torch.int64, device=dev)
+        self.class_weights, self.ignore_index = None, None
         net = mlp.net
         self._slots = [(net[0].weight, 0), (net[0].bias, 1), (net[1].weight, 2), (net[1].bias, 3), (net[4].weight, 4),
                        (net[4].bias, 5), (net[5].weight, 6), (net[5].bias, 7), (net[7].weight, 8), (net[7].bias, 9)]
@@ -57,6 +59,7 @@ class MLPEngine:
         self.ctx = h
         check(self.lib.eae_mlp_bind(self.ctx, _ptr(self.params), _ptr(self.grads), _ptr(self.adam_m), _ptr(self.adam_v),
                                     _ptr(self.bn_running), _ptr(self.bn_nbt)))
+        check(self.lib.eae_mlp_set_valid_counter(self.ctx, _ptr(self.valid)))       # written by the kernel while class weights / ignore_index are set
         self._finalizer = weakref.finalize(self, _destroy, self.lib, self.ctx)
         self.seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
 
@@ -73,6 +76,25 @@ class MLPEngine:
         if labels is not None and (labels.dtype != torch.int64 or labels.shape != (x.shape[0],) or labels.device != self.device):
             raise RuntimeError("labels must be int64 [B] on the model's device")
         return x.contiguous(), (None if labels is None else labels.contiguous())
+
+    def set_class_weights(self, weights=None, ignore_index=None):
+        """CrossEntropyLoss(weight=weights, ignore_index=ignore_index) in train_step and eval_step (include/eae.h
+        eae_mlp_set_class_weights); arguments and the labelled-sample count as for AEEngine.set_class_weights."""
+        w, ign = class_weight_args(weights, ignore_index, self.classes, self.device)
+        check(self.lib.eae_mlp_set_class_weights(self.ctx, _ptr(w), ign))
+        self.class_weights, self.ignore_index = w, (None if ignore_index is None else int(ignore_index))
+        self.valid.zero_()          # the count starts with the setting (a reset while the feature is off leaves the word alone)
+
+    @property
+    def weighted(self):
+        return self.class_weights is not None or self.ignore_index is not None
+
+    def read_valid(self):
+        """Number of counted (labelled) samples since reset_stats(), counted by the kernel (accuracy over them: read_stats()[1] *
+        read_stats()[2] / read_valid()); with the feature off every sample counts: read_stats()[2].  One D2H sync."""
+        if not self.weighted:
+            return int(self.stats[1].item())
+        return int(self.valid.item())
 
     def forward(self, x, train=False, drop_mask=None):
         x, _ = self._check(x)
@@ -101,6 +123,8 @@ class MLPEngine:
 
     def reset_stats(self):
         self.stats.zero_()
+        if self.weighted:
+            self.valid.zero_()
 
     def read_stats(self):
         """(mean loss, accuracy, n) since reset_stats(); one D2H sync."""
@@ -121,10 +145,13 @@ def mlp_engine_for(mlp, max_batch=None):
     dev = next(mlp.parameters()).device
     _require_gpu(dev)
     want = max_batch or 256
+    old = None
     if eng is not None and (not eng.attached() or eng.device != dev or eng.max_batch < want):
-        eng = None
+        old, eng = eng, None
     if eng is None:
         eng = MLPEngine(mlp, max_batch=want)
+        if old is not None and old.device == dev and (old.class_weights is not None or old.ignore_index is not None):
+            eng.set_class_weights(old.class_weights, old.ignore_index)      # the criterion's setting survives a bigger workspace
         _ENGINES[mlp] = eng
     return eng
 

@@ -709,10 +709,39 @@ def schedule_len(n, batch_size, drop_last=False):
     return n // batch_size if drop_last else -(-n // batch_size)
 
 
-def drawable_windows(label, windows=None, purity=None, min_purity=0.0):
+def class_weights(labels, num_classes, scheme="balanced"):
+    """Class weights [num_classes] float32 (on the tensor's device; CPU tensors work) from the class counts of an integer tensor of
+    any shape -- a `window_labels` map, a loader's ``.labels``, a label raster.  Values outside [0, K) do not count (-1, 255).
+    "balanced": n / (K_present * count_c), scikit-learn's class_weight="balanced" over the classes present; "inverse_sqrt":
+    proportional to 1 / sqrt(count_c), scaled like "balanced" so that sum_c count_c * w_c = n (a sample's mean weight is 1).  A class
+    without a sample gets weight 0.  For `set_class_weights` of the engines and ``class_weight=`` of the fit functions."""
+    k = int(num_classes)
+    if k < 1:
+        raise RuntimeError(f"num_classes must be positive, got {num_classes}")
+    if not isinstance(labels, torch.Tensor) or labels.dtype.is_floating_point or labels.dtype.is_complex or labels.dtype == torch.bool:
+        raise RuntimeError("labels must be an integer tensor of class ids")
+    if scheme not in ("balanced", "inverse_sqrt"):
+        raise RuntimeError(f"scheme must be 'balanced' or 'inverse_sqrt', got {scheme!r}")
+    flat = labels.reshape(-1).to(torch.int64)
+    ok = (flat >= 0) & (flat < k)
+    count = torch.bincount(torch.where(ok, flat, k), minlength=k + 1)[:k].to(torch.float64)       # bin K takes what does not count
+    n = count.sum()
+    if float(n) == 0.0:
+        raise RuntimeError("no label in [0, num_classes): nothing to weight")
+    present = count > 0
+    safe = torch.where(present, count, torch.ones_like(count))
+    if scheme == "balanced":
+        w = n / (present.sum() * safe)
+    else:
+        w = safe.rsqrt() * (n / torch.where(present, count.sqrt(), torch.zeros_like(count)).sum())
+    return torch.where(present, w, torch.zeros_like(w)).to(torch.float32)
+
+
+def drawable_windows(label, windows=None, purity=None, min_purity=0.0, unlabelled=False):
     """The ids a `SceneLoader` draws from, in the order given: ``windows`` (1-D int64; None = every window of the
-    label map, ascending) restricted to ``label >= 0`` and, when ``purity`` is given, to ``purity >= min_purity``.  Works on the
-    tensors' own device (one readback of the number kept)."""
+    label map, ascending) restricted to ``label >= 0`` and, when ``purity`` is given, to ``purity >= min_purity``.  unlabelled=True
+    keeps the windows with label -1 too (their purity passes): with ``ignore_index=-1`` in the fit they train the reconstruction
+    only.  Works on the tensors' own device (one readback of the number kept)."""
     if not isinstance(label, torch.Tensor) or label.dim() != 2 or label.dtype != torch.int64:
         raise RuntimeError("label must be an int64 [nH, nW] map of window labels (`window_labels`)")
     flat = label.reshape(-1)
@@ -720,13 +749,15 @@ def drawable_windows(label, windows=None, purity=None, min_purity=0.0):
         windows = torch.arange(flat.numel(), dtype=torch.int64, device=label.device)
     else:
         windows = _windows_arg(windows, label.device, flat.numel(), allow_empty=True)
-    keep = flat[windows] >= 0
+    lab = flat[windows]
+    keep = torch.ones_like(lab, dtype=torch.bool) if unlabelled else lab >= 0
     if purity is not None:
         if not isinstance(purity, torch.Tensor) or tuple(purity.shape) != tuple(label.shape):
             raise RuntimeError(f"purity must be a [nH, nW] = {list(label.shape)} tensor")
         if purity.device != label.device:
             raise RuntimeError(f"purity is on {purity.device}, label on {label.device}")
-        keep = keep & (purity.reshape(-1)[windows] >= float(min_purity))
+        pure = purity.reshape(-1)[windows] >= float(min_purity)
+        keep = keep & ((pure | (lab < 0)) if unlabelled else pure)
     elif float(min_purity) > 0.0:
         raise RuntimeError("min_purity needs the purity map (`window_labels`)")
     return windows[keep]
@@ -742,10 +773,15 @@ class SceneLoader:
     (counted per ``__iter__``, or set with `set_epoch`) takes the ids in `window_schedule`'s order -- shuffled when ``shuffle``
     (default: ``train``) -- and batch i is ``stage_scene_windows(ids, train=train, seed=seed, step=e * len(self) + i, noise_std=,
     crop=)`` with ``y = label.reshape(-1)[ids]``.  The epoch's order is uploaded once when the iterator starts; nothing inside an
-    epoch synchronises the host."""
+    epoch synchronises the host.
+
+    unlabelled=True keeps the windows without a label as well (``y = -1``; ``windows`` and ``min_purity`` still apply to the labelled
+    ones): fit with ``ignore_index=-1`` and the whole scene trains the reconstruction while only the labelled windows train the
+    classifier ("imbalanced / partly labelled scene").  ``.labels`` then holds the -1 entries, which
+    `class_weights` and ``class_weight="balanced"`` do not count."""
 
     def __init__(self, scene, label, divisor=1.0, patch=64, stride=None, batch_size=64, windows=None, min_purity=0.0, purity=None,
-                 train=True, shuffle=None, drop_last=False, noise_std=0.03, crop="window", seed=0):
+                 train=True, shuffle=None, drop_last=False, noise_std=0.03, crop="window", seed=0, unlabelled=False):
         _crop_arg(crop)
         _check_scene(scene)
         self.patch = int(patch)
@@ -760,7 +796,8 @@ class SceneLoader:
                                f"scene's {scene.shape[1]} x {scene.shape[2]} pixels at this patch and stride, got {got}")
         if label.device != scene.device:
             raise RuntimeError(f"label is on {label.device}, the scene on {scene.device}")
-        self.windows = drawable_windows(label, windows, purity, min_purity)
+        self.unlabelled = bool(unlabelled)
+        self.windows = drawable_windows(label, windows, purity, min_purity, unlabelled=self.unlabelled)
         if self.windows.numel() == 0:
             raise RuntimeError("no window to draw from: none of the given windows is labelled (and pure enough)")
         # device, band count and divisor are checked here, before the first epoch; the divisor stays on the device as fp32 [C]

@@ -17,14 +17,45 @@ from .modules import SupervisedAutoencoder, MLP
 
 
 # ------------------------------------------------------------------------------------------------ steppers
+def resolve_class_weight(class_weight, loader, num_classes):
+    """The `class_weight` argument of the fit functions as what the engines take: None, a [num_classes] tensor / sequence (passed on),
+    or the name of a `scene.class_weights` scheme ("balanced", "inverse_sqrt") computed from the labels of the train loader, which
+    then must expose them as ``.labels`` (`scene.SceneLoader` does; unlabelled windows, -1, do not count)."""
+    if class_weight is None or not isinstance(class_weight, str):
+        return class_weight
+    labels = getattr(loader, "labels", None)
+    if not isinstance(labels, torch.Tensor):
+        raise RuntimeError(f"class_weight={class_weight!r} needs a train loader that exposes its labels as a tensor `.labels` "
+                           "(scene.SceneLoader); pass a weight vector instead")
+    from .scene import class_weights
+    return class_weights(labels, num_classes, scheme=class_weight)
+
+
+def _apply_class_weight(eng, class_weight, ignore_index):
+    # (an engine is cached per model: a stepper without the arguments switches off what an earlier one set)
+    if class_weight is not None or ignore_index is not None or eng.weighted:
+        eng.set_class_weights(class_weight, ignore_index)
+
+
+def _criterion_kw(class_weight, ignore_index):
+    """The two arguments as keywords for a fit function, only when set (a custom fit_fn without them keeps working)."""
+    kw = {}
+    if class_weight is not None:
+        kw["class_weight"] = class_weight
+    if ignore_index is not None:
+        kw["ignore_index"] = ignore_index
+    return kw
+
+
 class AEStepper:
     """HIP-engine stepper for SupervisedAutoencoder: train_step / eval_step / read_loss."""
 
-    def __init__(self, model, alpha, lr, head=True, max_batch=None, graph=None):
+    def __init__(self, model, alpha, lr, head=True, max_batch=None, graph=None, class_weight=None, ignore_index=None):
         from .engine import engine_for
         self.model, self.alpha, self.lr, self.head = model, float(alpha), float(lr), head
         self.eng = engine_for(model, max_batch=max_batch)
         self.eng.reset_optimizer()
+        _apply_class_weight(self.eng, class_weight, ignore_index)     # CrossEntropyLoss(weight=, ignore_index=) of train and eval steps
         if graph is not None:
             self.eng.set_graph(graph)
         self.graph = bool(graph)
@@ -59,12 +90,13 @@ class GroupAEStepper:
     include/eae.h eae_group_train_step).  `active` = indices of the members that have not stopped early; the tile geometries stay
     those of the full group, so a member's arithmetic does not depend on which other members are still training."""
 
-    def __init__(self, models, alphas, lrs, head=True, max_batch=None):
+    def __init__(self, models, alphas, lrs, head=True, max_batch=None, class_weight=None, ignore_index=None):
         from .engine import engine_for
         self.models, self.alphas, self.lrs, self.head = list(models), [float(a) for a in alphas], [float(v) for v in lrs], head
         self.engs = [engine_for(m, max_batch=max_batch) for m in self.models]
         for e in self.engs:
             e.reset_optimizer()
+            _apply_class_weight(e, class_weight, ignore_index)        # the same criterion for every member (a group is all on or all off)
         self.mult = len(self.engs)
         self.device = self.engs[0].device
 
@@ -95,11 +127,12 @@ class GroupAEStepper:
 
 
 class MLPStepper:
-    def __init__(self, clf, lr, weight_decay=1e-4, max_batch=None):
+    def __init__(self, clf, lr, weight_decay=1e-4, max_batch=None, class_weight=None, ignore_index=None):
         from .mlp_engine import mlp_engine_for
         self.clf, self.lr, self.wd = clf, float(lr), float(weight_decay)
         self.eng = mlp_engine_for(clf, max_batch=max_batch)
         self.eng.reset_optimizer()
+        _apply_class_weight(self.eng, class_weight, ignore_index)
         self.device = self.eng.device
 
     def begin(self):
@@ -127,19 +160,26 @@ def _first_batch_size(loader, default=64):
 # ------------------------------------------------------------------------------------------------ autoencoder
 def fit_autoencoder(train_loader, val_loader, alpha, lr, latent_dim=64, num_classes=10, num_epochs=80, patience=15,
                     device="cuda", model=None, stepper=None, head=True, verbose=True, log=print, graph=None, side_streams=None,
-                    in_channels=3):
+                    in_channels=3, class_weight=None, ignore_index=None):
     """One (alpha, lr) configuration of the reference's AE loop (R.md:619-697).
 
     Returns dict(model, train_curve, val_curve, best_val_loss, epochs).  As in the reference, `model` holds the weights of
     the LAST epoch run (R.md:705 keeps a live reference, not the best epoch's weights).  in_channels: image bands of the model built
-    here (1..16; the loaders yield [B,in_channels,H,W])."""
+    here (1..16; the loaders yield [B,in_channels,H,W]).
+
+    class_weight / ignore_index: the criterion becomes CrossEntropyLoss(weight=, ignore_index=) in the train and the validation steps
+    (engine.AEEngine.set_class_weights) -- for an imbalanced or partly labelled scene.  class_weight = a [num_classes] vector, or
+    "balanced" / "inverse_sqrt" (`scene.class_weights` over ``train_loader.labels``); with ignore_index=-1 and a
+    ``SceneLoader(unlabelled=True)`` every window trains the reconstruction and the labelled ones the classifier.  They configure the
+    stepper built here (a custom `stepper` brings its own criterion)."""
     if model is None and stepper is None:
         model = SupervisedAutoencoder(latent_dim=latent_dim, num_classes=num_classes, in_channels=in_channels).to(device)
         if side_streams is not None:
             model._eae_side_streams = side_streams      # read when the model's engine is first built (engine.engine_for)
     if stepper is None:
         stepper = AEStepper(model, alpha, lr, head=head, graph=graph,
-                            max_batch=max(_first_batch_size(train_loader), _first_batch_size(val_loader)))
+                            max_batch=max(_first_batch_size(train_loader), _first_batch_size(val_loader)),
+                            class_weight=resolve_class_weight(class_weight, train_loader, num_classes), ignore_index=ignore_index)
     dev = getattr(stepper, "device", None)
     counter, best_val_loss = 0, float("inf")
     train_curve, val_curve = [], []
@@ -179,13 +219,14 @@ def fit_autoencoder(train_loader, val_loader, alpha, lr, latent_dim=64, num_clas
 
 
 def fit_autoencoder_group(train_loader, val_loader, configs, latent_dim=64, num_classes=10, num_epochs=80, patience=15,
-                          device="cuda", models=None, stepper=None, head=True, verbose=True, logs=None, in_channels=3):
+                          device="cuda", models=None, stepper=None, head=True, verbose=True, logs=None, in_channels=3,
+                          class_weight=None, ignore_index=None):
     """fit_autoencoder for SEVERAL (alpha, lr) configurations at once: the members share every batch of the two loaders (one pass of
     the loader per epoch for the whole group) and each keeps its own curves, best loss and early-stopping counter exactly as the
     reference's loop does for it alone (R.md:619-697); a member that stops early drops out, the others go on.
 
     Returns one fit_autoencoder-style dict per configuration.  logs: optional list of per-configuration line lists.  in_channels: image
-    bands of the models built here (1..16)."""
+    bands of the models built here (1..16).  class_weight / ignore_index: as for `fit_autoencoder`, the same criterion for every member."""
     n = len(configs)
     if models is None and stepper is None:
         models = [SupervisedAutoencoder(latent_dim=latent_dim, num_classes=num_classes, in_channels=in_channels).to(device)
@@ -194,7 +235,8 @@ def fit_autoencoder_group(train_loader, val_loader, configs, latent_dim=64, num_
             m._eae_side_streams = 2              # a grouped step is fastest with two side streams (the engine's default is three)
     if stepper is None:
         stepper = GroupAEStepper(models, [a for a, _ in configs], [l for _, l in configs], head=head,
-                                 max_batch=max(_first_batch_size(train_loader), _first_batch_size(val_loader)))
+                                 max_batch=max(_first_batch_size(train_loader), _first_batch_size(val_loader)),
+                                 class_weight=resolve_class_weight(class_weight, train_loader, num_classes), ignore_index=ignore_index)
     dev = getattr(stepper, "device", None)
     lines = logs if logs is not None else [[] for _ in range(n)]
     counter, best = [0] * n, [float("inf")] * n
@@ -342,7 +384,8 @@ def run_concurrent(jobs, concurrent, device="cuda", static=False):
 def grid_search_autoencoder(train_loader, val_loader, alpha_values=(20, 25, 30, 35, 40),
                             lr_values=(1e-4, 2e-4, 5e-4, 1e-3, 2e-3, 5e-3, 1e-2, 5e-2, 1e-1), latent_dim=64, num_epochs=80,
                             patience=15, out_dir="models_best", device="cuda", verbose=True, log=print, fit_fn=None, concurrent=1,
-                            grouped=0, group_fit_fn=None, concurrent_groups=1, in_channels=3):
+                            grouped=0, group_fit_fn=None, concurrent_groups=1, in_channels=3, class_weight=None, ignore_index=None,
+                            num_classes=10):
     """The reference's alpha x lr grid (R.md:599-729): trains every configuration, keeps the global best, writes
     `out_dir/AE_GLOBAL_BEST.pt` (plain state_dict) and `out_dir/validation_losses.json` (keys "alpha={a}, lr={lr}").
 
@@ -369,9 +412,16 @@ def grid_search_autoencoder(train_loader, val_loader, alpha_values=(20, 25, 30, 
     stream: 2 x 2 streams are the GPU's four hardware queues, and one group's forward pass -- a chain of latency-bound kernels that
     leaves most CUs idle -- runs beside the other group's backward pass (bench.py `configs.grid_b64`: 16 configurations at 0.89-0.92 M
     images/s against 0.83-0.85 M for one group of 8).  The models are built in grid order on the calling thread, a configuration's
-    results do not depend on what runs beside it."""
+    results do not depend on what runs beside it.
+
+    class_weight / ignore_index: the criterion of every configuration, as for `fit_autoencoder` (sequential, `concurrent` and `grouped`
+    drivers alike); a scheme name is resolved once, from ``train_loader.labels``, for `num_classes` classes.  A custom fit_fn / group_fit_fn sees
+    them only when set.  num_classes: classes of the models built here and of the weight vector (passed on when it is not 10)."""
     os.makedirs(out_dir, exist_ok=True)
     fit_fn = fit_fn or fit_autoencoder
+    crit = _criterion_kw(resolve_class_weight(class_weight, train_loader, num_classes), ignore_index)
+    if int(num_classes) != 10:
+        crit["num_classes"] = int(num_classes)          # like in_channels: a custom fit function sees it only when it is not the default
     results, best = {}, {"loss": float("inf"), "info": None, "state": None, "train": None, "val": None}
     grid = [(alpha, lr) for alpha in alpha_values for lr in lr_values]
     fitted = None
@@ -386,7 +436,7 @@ def grid_search_autoencoder(train_loader, val_loader, alpha_values=(20, 25, 30, 
             # parameter initialisation draws from torch's global generator: in grid order, on this thread (as for `concurrent`)
             prebuilt = []
             for cfgs in chunks:
-                ms = [SupervisedAutoencoder(latent_dim=latent_dim, num_classes=10, in_channels=in_channels).to(device) for _ in cfgs]
+                ms = [SupervisedAutoencoder(latent_dim=latent_dim, num_classes=int(num_classes), in_channels=in_channels).to(device) for _ in cfgs]
                 for m in ms:
                     m._eae_side_streams = 1          # two groups x (caller's stream + one side stream) = the four hardware queues
                 prebuilt.append(ms)
@@ -397,7 +447,7 @@ def grid_search_autoencoder(train_loader, val_loader, alpha_values=(20, 25, 30, 
                 lines = [[] for _ in cfgs]
                 extra = {"models": prebuilt[gi]} if prebuilt is not None else {}
                 rs = gfit(train_loader, val_loader, cfgs, latent_dim=latent_dim, num_epochs=num_epochs, patience=patience, device=device,
-                          verbose=verbose, logs=lines, **bands, **extra)
+                          verbose=verbose, logs=lines, **bands, **crit, **extra)
                 out = []
                 for r, ln in zip(rs, lines):
                     r = dict(r)
@@ -415,7 +465,7 @@ def grid_search_autoencoder(train_loader, val_loader, alpha_values=(20, 25, 30, 
         prebuilt = {}
         if fit_fn is fit_autoencoder:
             for (alpha, lr) in grid:
-                m = SupervisedAutoencoder(latent_dim=latent_dim, num_classes=10, in_channels=in_channels).to(device)
+                m = SupervisedAutoencoder(latent_dim=latent_dim, num_classes=int(num_classes), in_channels=in_channels).to(device)
                 if int(concurrent) >= 3:
                     m._eae_side_streams = -1
                 prebuilt[(alpha, lr)] = m
@@ -429,7 +479,7 @@ def grid_search_autoencoder(train_loader, val_loader, alpha_values=(20, 25, 30, 
                 # at K = 4.  hipGraph replay of each step is slower than eager (0.7-0.8x), more hardware queues or several processes far slower.
                 extra = {"model": prebuilt.pop((alpha, lr))} if fit_fn is fit_autoencoder else {}
                 r = fit_fn(train_loader, val_loader, alpha, lr, latent_dim=latent_dim, num_epochs=num_epochs, patience=patience,
-                           device=device, verbose=verbose, log=lines.append, **bands, **extra)
+                           device=device, verbose=verbose, log=lines.append, **bands, **crit, **extra)
                 r = dict(r)
                 # only the state_dict of a finished configuration is needed below: release its engine (workspace, streams) now
                 r["state"] = None if r.get("model") is None else {k: v.detach().cpu().clone() for k, v in r["model"].state_dict().items()}
@@ -449,7 +499,7 @@ def grid_search_autoencoder(train_loader, val_loader, alpha_values=(20, 25, 30, 
                         log(ln)
             else:
                 r = fit_fn(train_loader, val_loader, alpha, lr, latent_dim=latent_dim, num_epochs=num_epochs, patience=patience,
-                           device=device, verbose=verbose, log=log, **bands)
+                           device=device, verbose=verbose, log=log, **bands, **crit)
             results[(alpha, lr)] = r["best_val_loss"]
             if r["best_val_loss"] < best["loss"]:
                 state = r.get("state")
@@ -484,17 +534,22 @@ def extract_features(loader, encoder):
 
 # ------------------------------------------------------------------------------------------------ MLP
 def fit_mlp(train_dl, val_dl, test_dl, lr, input_dim=64, num_classes=10, num_epochs=30, weight_decay=1e-4, device="cuda",
-            clf=None, stepper=None, alias_best=True, verbose=True, log=print):
+            clf=None, stepper=None, alias_best=True, verbose=True, log=print, class_weight=None, ignore_index=None):
     """One learning rate of the reference's MLP loop (R.md:2619-2697): Adam(lr, weight_decay), CE, accuracy tracking,
     best-validation snapshot, test accuracy.
 
     alias_best=True reproduces the reference's `clf.state_dict().copy()` (R.md:2683): a shallow copy that aliases the
     live tensors, so the "best" state -- and the test accuracy measured after `load_state_dict` -- are those of the
-    final epoch.  alias_best=False snapshots real copies of the best-validation epoch instead."""
+    final epoch.  alias_best=False snapshots real copies of the best-validation epoch instead.
+
+    class_weight / ignore_index: CrossEntropyLoss(weight=, ignore_index=) in the train, validation and test steps
+    (mlp_engine.MLPEngine.set_class_weights); class_weight = a vector or a `scene.class_weights` scheme name over ``train_dl.labels``.
+    The accuracies stay correct / all samples; `stepper.eng.read_valid()` gives the labelled count of the last phase."""
     if clf is None and stepper is None:
         clf = MLP(input_dim=input_dim, num_classes=num_classes).to(device)
     if stepper is None:
-        stepper = MLPStepper(clf, lr, weight_decay, max_batch=max(256, _first_batch_size(train_dl)))
+        stepper = MLPStepper(clf, lr, weight_decay, max_batch=max(256, _first_batch_size(train_dl)),
+                             class_weight=resolve_class_weight(class_weight, train_dl, num_classes), ignore_index=ignore_index)
     dev = getattr(stepper, "device", None)
     curves = {"train_acc": [], "val_acc": [], "train_loss": [], "val_loss": []}
     best_val_acc, best_state = 0, None
@@ -533,17 +588,24 @@ def fit_mlp(train_dl, val_dl, test_dl, lr, input_dim=64, num_classes=10, num_epo
 
 
 def grid_search_mlp(train_dl, val_dl, test_dl, lr_values=(1e-6, 5e-6, 1e-5, 5e-5, 1e-4, 5e-4, 1e-3, 5e-3, 1e-2, 5e-2, 1e-1),
-                    input_dim=64, num_epochs=30, out_dir="mlp_best", device="cuda", verbose=True, log=print, fit_fn=None):
-    """The reference's MLP learning-rate grid (R.md:2611-2732); saves `out_dir/MLP_GLOBAL_BEST.pt`."""
+                    input_dim=64, num_epochs=30, out_dir="mlp_best", device="cuda", verbose=True, log=print, fit_fn=None,
+                    class_weight=None, ignore_index=None, num_classes=10):
+    """The reference's MLP learning-rate grid (R.md:2611-2732); saves `out_dir/MLP_GLOBAL_BEST.pt`.  class_weight / ignore_index: the
+    criterion of every learning rate, as for `fit_mlp` (a custom fit_fn sees them only when set); num_classes: classes of the classifier and
+    of the weight vector (passed on when it is not 10)."""
     os.makedirs(out_dir, exist_ok=True)
     fit_fn = fit_fn or fit_mlp
+    crit = _criterion_kw(resolve_class_weight(class_weight, train_dl, num_classes), ignore_index)
+    if int(num_classes) != 10:
+        crit["num_classes"] = int(num_classes)          # a custom fit function sees it only when it is not the default
     best = {"val": 0, "test": 0, "lr": None, "state": None, "curves": None}
     for lr in lr_values:
         if verbose:
             log("\n=====================================")
             log(f"   Training MLP with LR = {lr}")
             log("=====================================")
-        r = fit_fn(train_dl, val_dl, test_dl, lr, input_dim=input_dim, num_epochs=num_epochs, device=device, verbose=verbose, log=log)
+        r = fit_fn(train_dl, val_dl, test_dl, lr, input_dim=input_dim, num_epochs=num_epochs, device=device, verbose=verbose, log=log,
+                   **crit)
         if r["best_val_acc"] > best["val"]:
             state = r["best_state"]
             best.update(val=r["best_val_acc"], test=r["test_acc"], lr=lr,

@@ -96,6 +96,34 @@ int eae_gate_timeouts_clear(eae_ctx* ctx);
  * eagerly (default; EAE_GRAPH=1 in the environment turns replay on at creation).  Replay pays when the HOST is the limit: several small
  * configurations stepped concurrently (train.py run_concurrent, R.md:599-711 at batch 64). */
 int eae_set_graph(eae_ctx* ctx, int on);
+/* Class-weighted cross-entropy with ignored labels in the fused steps: torch's CrossEntropyLoss(weight=w, ignore_index=i, reduction=
+ * "mean") for imbalanced or partly labelled data (a scene's window labels: -1 = unlabelled, scene.py).
+ * weights: device fp32 [num_classes] (finite, >= 0), caller-owned and kept until replaced, or NULL (all ones).  weights == NULL and
+ * ignore_index == EAE_NO_IGNORE switch the feature off: the kernels and the contract of before (every label in [0, C)).
+ * With the feature on, row r is COUNTED when labels[r] != ignore_index and 0 <= labels[r] < C -- every label out of range is ignored
+ * (-1, a raster's 255), none indexes out of its row.  W = sum over the counted rows of w[y_r];
+ *     CE = sum_counted w[y_r] (lse_r - logit_r[y_r]) / W,    dlogits_r = (softmax_r - onehot) w[y_r] / W, an exact zero row if not counted;
+ * the number of correct predictions counts counted rows only; the logits output is unchanged.  loss_accum / loss_last keep their
+ * meaning: accum[2] += CE * B, accum[3] += B (all rows of the batch), accum[4] += counted correct rows.
+ * Deviation from torch: when no row is counted (or every counted row has weight 0) W = 0 and torch returns NaN, which this engine
+ * reads as "diverged"; here CE = 0, the head's gradients and dz_cls are exact zeros, everything is finite and the step still trains
+ * on alpha * MSE.
+ * W is summed inside the head kernel by every workgroup in one fixed order (no atomics, no host synchronisation): results are
+ * bitwise repeatable.  The setting reaches every call that computes CE from labels: eae_ae_forward, eae_ae_grad_step(_begin),
+ * eae_ae_train_step, eae_ae_dp_train_step, eae_fp8_calibrate, eae_group_train_step, eae_group_forward; eae_ae_backward (external
+ * dlogits) is unaffected.  Data parallel: each replica normalises by the W of its OWN batch and the gradients are averaged by 1/world
+ * as before -- what DistributedDataParallel around a weighted criterion computes; W is not summed over the replicas.
+ * A grouped call needs the feature on in every member or in none (each member its own vector and ignore_index): a mixture is
+ * EAE_ERR_ARG.  Changing the setting drops the captured step graphs (eae_set_graph): the next calls capture again (synchronises
+ * the device when there is one to drop). */
+#define EAE_NO_IGNORE (-0x7fffffffffffffffLL - 1)
+int eae_set_class_weights(eae_ctx* ctx, const float* weights, long long ignore_index);
+/* Labelled-sample count: counter = a caller-owned device int64 word (kept until replaced) or NULL.  While the feature above is on,
+ * every call that computes CE from labels AND accumulates its loss (io->loss_accum != NULL) adds the number of counted rows of its
+ * batch to *counter -- inside the head kernel's own pass over the labels (one writer per launch): no extra launch, no host
+ * synchronisation.  With the feature off nothing is written (every row counts: accum[3]).  Drops the captured step graphs like
+ * eae_set_class_weights. */
+int eae_set_valid_counter(eae_ctx* ctx, long long* counter);
 /* The host changed parameter values (load_state_dict, optimizer outside the engine): repack before next use. */
 int eae_params_changed(eae_ctx* ctx);
 int eae_set_adam_step(eae_ctx* ctx, long long step);
@@ -332,6 +360,11 @@ long long eae_op_head_scratch_floats(int B, int L, int C);
 int eae_op_head_ce(void* stream, const float* z, const float* w1, const float* b1, const float* w2, const float* b2,
                    const long long* labels, int B, int L, int C, float* logits, float* dz, float* grads, float* loss2,
                    float* scratch, long long scratch_floats);
+/* eae_op_head_ce with the class weights and ignore_index of eae_set_class_weights (same semantics; loss2[0] = the weighted mean,
+ * loss2[1] = correct among the counted rows).  class_w == NULL and ignore_index == EAE_NO_IGNORE: the kernel and the bits of eae_op_head_ce. */
+int eae_op_head_ce_w(void* stream, const float* z, const float* w1, const float* b1, const float* w2, const float* b2,
+                     const long long* labels, int B, int L, int C, float* logits, float* dz, float* grads, float* loss2,
+                     float* scratch, long long scratch_floats, const float* class_w, long long ignore_index);
 /* Sigmoid backward for an externally supplied dL/dx_hat (autograd path): g4 = bf16 NHWC4 of dx_hat*x_hat*(1-x_hat), plus the
  * deconv4 bias gradient db[3]; x_hat, dx_hat fp32 NCHW [B,3,H,W]; scratch >= ceil(B*H*W/256)*4 floats. */
 int eae_op_sigmoid_bwd(void* stream, const float* x_hat, const float* dx_hat, int B, int H, int W, void* g4, float* db,
@@ -383,6 +416,14 @@ int eae_mlp_train_step(eae_mlp* m, void* stream, const float* x, const long long
 /* forward + CE + accuracy bookkeeping without update (validation / test loops, R.md:2660-2668, 2689-2695) */
 int eae_mlp_eval_step(eae_mlp* m, void* stream, const float* x, const long long* labels, int B, float* logits,
                       float* stats);
+/* eae_set_class_weights for the MLP: reaches eae_mlp_train_step and eae_mlp_eval_step (eae_mlp_backward with external dlogits is
+ * unaffected).  Same semantics and the same W == 0 deviation; BatchNorm statistics stay over all rows of the batch, as in torch.
+ * stats[0] += CE * B, stats[1] += B (all rows), stats[2] += correct among the counted rows; in eval mode every 64-row block sums W
+ * over the whole batch in the same fixed order. */
+int eae_mlp_set_class_weights(eae_mlp* m, const float* weights, long long ignore_index);
+/* eae_set_valid_counter for the MLP: with the feature on, eae_mlp_train_step / eae_mlp_eval_step with stats != NULL add the counted
+ * rows of the batch to *counter (device int64, caller-owned, or NULL). */
+int eae_mlp_set_valid_counter(eae_mlp* m, long long* counter);
 
 /* ------------------------------------------------------------------ scene classification ---------- */
 /* These entry points extend beyond the reference, which has no notebook lines for applying the pipeline to a whole scene.
