@@ -10,16 +10,18 @@ from .augment import augment_batch, stage_bands  # noqa: F401
 from .train import (fit_autoencoder, grid_search_autoencoder, extract_features, fit_mlp, grid_search_mlp,  # noqa: F401
                     evaluate)
 from .report import confusion_matrix, classification_report, loss_heatmap  # noqa: F401
+from .report import confusion_metrics, classification_report_from_confusion  # noqa: F401
 from .probe import ce_mse_ratio_probe  # noqa: F401
 from . import scene  # noqa: F401
 from .scene import scene_windows, encode_scene, classify_scene, window_grid, window_invalid_counts, valid_windows  # noqa: F401
 from .scene import scene_reconstruction_error, reconstruct_scene, owned_span, border_grid, border_source  # noqa: F401
 from .scene import stage_scene_windows, window_labels, SceneLoader, window_schedule, drawable_windows  # noqa: F401
-from .scene import class_weights  # noqa: F401
+from .scene import class_weights, scene_confusion, evaluate_scene, block_split, footprint_mask  # noqa: F401
 
 __all__ = ["Encoder", "Decoder", "SupervisedAutoencoder", "MLP", "fit_autoencoder", "grid_search_autoencoder",
            "extract_features", "fit_mlp", "grid_search_mlp", "evaluate", "augment_batch", "stage_bands",
            "confusion_matrix", "classification_report", "loss_heatmap", "ce_mse_ratio_probe", "scene_windows", "encode_scene",
            "classify_scene", "window_grid", "window_invalid_counts", "valid_windows", "scene_reconstruction_error",
            "reconstruct_scene", "owned_span", "border_grid", "border_source", "stage_scene_windows", "window_labels", "SceneLoader",
-           "window_schedule", "drawable_windows", "class_weights"]
+           "window_schedule", "drawable_windows", "class_weights", "scene_confusion", "evaluate_scene", "block_split", "footprint_mask",
+           "confusion_metrics", "classification_report_from_confusion"]

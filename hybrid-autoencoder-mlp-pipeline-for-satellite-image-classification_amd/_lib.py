@@ -144,6 +144,8 @@ _PROTOS = {
     "eae_scene_stage_windows": (C.c_int, [vp, C.POINTER(EaeScene), vp, C.c_int, vp, C.c_int, C.c_float, C.c_ulonglong, C.c_ulonglong,
                                           vp, vp, C.c_int]),
     "eae_scene_window_labels": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "eae_scene_confusion": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int,
+                                      C.c_int, vp]),
 }
 
 EXPORTS = tuple(_PROTOS.keys())

@@ -1,8 +1,9 @@
 // Scene classification helpers (include/eae.h, "scene classification"): the window gather (the public way to get patches, and the
 // reference the fused conv1 scene source is tested against), the cell blends of window probabilities, and the nodata / mask path:
 // per-window invalid-pixel counts and the compaction of the valid window ids; and training from a scene (include/eae.h, "training from
-// a scene"): augmented window batches and a label for every window from a label raster.  None uses matrix instructions, so all are
-// built with packed FP32 disabled (EAE_NO_PK, tests/test_isa_guard.py).
+// a scene"): augmented window batches and a label for every window from a label raster; and the confusion counts of a class map against
+// a label raster (include/eae.h, "accuracy assessment").  None uses matrix instructions, so all are built with packed FP32 disabled
+// (EAE_NO_PK, tests/test_isa_guard.py).
 #include "eae_internal.h"
 #include "eae_ctx.h"
 #include "eae_common.hip.h"
@@ -370,6 +371,113 @@ __global__ EAE_NO_PK __launch_bounds__(LBL_NT) void scene_window_labels_kernel(c
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- accuracy assessment
+// Confusion counts of a cell map against a label raster (include/eae.h, "accuracy assessment").  The unit of work is a RUN: 16
+// consecutive pixels of one row, starting at a 16-element boundary of the raster's memory (run g of row y covers columns
+// [16 g - m, 16 g - m + 16), m = the element misalignment of the row's first pixel), so a whole run is one 16-byte load of a uint8
+// raster (four of an int32 one) and one of the mask, and the clipped first and last runs of a row load element by element.  Rows
+// have G = ceil((W + 15) / 16) run slots (the last may be empty for a small m); a tile is CONF_NT consecutive slots of the flattened
+// [H][G] list, so narrow rasters fill a workgroup with several rows, and the workgroups take tiles grid-strided.  Divisions: one 64-bit
+// one per tile (uniform), then per run one 32-bit one for the row, one for the cell row and one for the first cell column; the cell
+// column is stepped from there and pred is re-read only when the cell changes.  (r, c) pairs go to a (K+1)^2 int table in LDS, a run
+// of equal pairs as one atomic (the label kernel's scheme); the non-zero bins are flushed with 64-bit integer atomics.  Integers
+// only: exact, and identical from run to run.  The launch keeps a workgroup's share below 2^31 pixels (the table is 32-bit).
+constexpr int CONF_NT = 256, CONF_RUN = 16;
+// the table column of cell x of a map row: its class in [0, K), else K (rowin: the row lies inside the map; prow is read only then)
+__device__ __forceinline__ int conf_cell_class(const long long* __restrict__ prow, bool rowin, unsigned cW, unsigned x, int K) {
+  if (!rowin || x >= cW) return K;
+  const long long v = prow[x];
+  return v >= 0 && v < K ? (int)v : K;
+}
+template <typename T>
+__global__ EAE_NO_PK __launch_bounds__(CONF_NT) void scene_confusion_kernel(const T* __restrict__ truth, int H, int W,
+                                                                         const long long* __restrict__ pred, int cH, int cW,
+                                                                         unsigned cell, unsigned oy, unsigned ox,
+                                                                         const unsigned char* __restrict__ mask, int K, unsigned G,
+                                                                         long long ntiles, unsigned long long* __restrict__ counts) {
+  extern __shared__ int conf_tab[];                         // [(K+1)][(K+1)]
+  constexpr int V = CONF_RUN;
+  const int tid = threadIdx.x, K1 = K + 1, nbin = K1 * K1;
+  for (int i = tid; i < nbin; i += CONF_NT) conf_tab[i] = 0;
+  __syncthreads();
+  const unsigned long long base_el = reinterpret_cast<uintptr_t>(truth) / sizeof(T);      // element address of pixel (0, 0)
+  for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const long long u0 = t * CONF_NT, y0 = u0 / G;
+    const unsigned q = (unsigned)(u0 - y0 * G) + (unsigned)tid, dy = q / G, g = q - dy * G;      // q < G + CONF_NT
+    const long long y = y0 + dy;
+    if (y >= H) continue;                                   // the last tile's tail (no barrier inside the loop)
+    const long long row = y * W;
+    const int m = (int)((base_el + (unsigned long long)row) & (V - 1));
+    const long long gx = (long long)g * V - m;              // first column of the run; < 0 for a clipped first run
+    const int lo = gx > 0 ? (int)gx : 0, hi = gx + V < W ? (int)(gx + V) : W;
+    if (lo >= hi) continue;                                 // the empty last slot of a row
+    const bool full = hi - lo == V;
+    const T* p = truth + row + gx;                          // dereferenced at [lo - gx, hi - gx) only
+    int tv[V], mk[V];                                       // truth values and mask bytes of the run (statically indexed: registers)
+    if (full) {                                             // 16 elements from a 16-element boundary
+      const uint4* p4 = reinterpret_cast<const uint4*>(p);
+      if constexpr (sizeof(T) == 1) {
+        const uint4 w = p4[0];
+        const unsigned ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+        for (int v = 0; v < V; ++v) tv[v] = (int)((ww[v >> 2] >> ((v & 3) * 8)) & 255u);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const uint4 w = p4[i];
+          tv[4 * i] = (int)w.x; tv[4 * i + 1] = (int)w.y; tv[4 * i + 2] = (int)w.z; tv[4 * i + 3] = (int)w.w;
+        }
+      }
+    } else {
+#pragma unroll
+      for (int v = 0; v < V; ++v) tv[v] = (gx + v >= lo && gx + v < hi) ? (int)p[v] : 0;
+    }
+#pragma unroll
+    for (int v = 0; v < V; ++v) mk[v] = 0;
+    if (mask) {
+      const unsigned char* pm = mask + row + gx;
+      if (full && (reinterpret_cast<uintptr_t>(pm) & 15) == 0) {
+        const uint4 w = *reinterpret_cast<const uint4*>(pm);
+        const unsigned ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+        for (int v = 0; v < V; ++v) mk[v] = (int)((ww[v >> 2] >> ((v & 3) * 8)) & 255u);
+      } else {
+#pragma unroll
+        for (int v = 0; v < V; ++v) mk[v] = (gx + v >= lo && gx + v < hi) ? (int)pm[v] : 0;
+      }
+    }
+    // the cell of pixel (y, lo), stepped along the row; pc = its column in the table (K: not classified)
+    const unsigned cy = ((unsigned)y + oy) / cell;
+    unsigned cx = ((unsigned)lo + ox) / cell, rem = ((unsigned)lo + ox) - cx * cell;
+    const bool rowin = cy < (unsigned)cH;
+    const long long* prow = pred + (long long)cy * cW;      // read only when rowin
+    int pc = conf_cell_class(prow, rowin, (unsigned)cW, cx, K);
+    int cur = -1, run = 0;
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      const bool in = gx + v >= lo && gx + v < hi;
+      int bin = -1;
+      if (in) {
+        const int r = tv[v] >= 0 && tv[v] < K ? tv[v] : K;
+        if (mk[v] == 0) bin = r * K1 + pc;
+        if (++rem == cell) { rem = 0; ++cx; pc = conf_cell_class(prow, rowin, (unsigned)cW, cx, K); }
+      }
+      if (bin != cur) {
+        if (cur >= 0) atomicAdd(&conf_tab[cur], run);
+        cur = bin;
+        run = 0;
+      }
+      ++run;
+    }
+    if (cur >= 0) atomicAdd(&conf_tab[cur], run);
+  }
+  __syncthreads();
+  for (int i = tid; i < nbin; i += CONF_NT) {
+    const int n = conf_tab[i];
+    if (n) atomicAdd(&counts[i], (unsigned long long)n);
+  }
+}
+
 }  // namespace
 
 long long eae_scene_extent(long long n, int patch, int stride) { return (n - 1) * stride + patch; }
@@ -566,6 +674,38 @@ extern "C" int eae_scene_window_labels(void* stream, const void* raster, int ele
   else
     hipLaunchKernelGGL(scene_window_labels_kernel<int32_t>, grid, dim3(LBL_NT), 0, st, (const int32_t*)raster, W, patch, stride, (int)nW, K,
                        label, count, labelled);
+  EAE_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int eae_scene_confusion(void* stream, const void* truth, int elem_bytes, int H, int W, const long long* pred, int cH, int cW,
+                                   int cell, int oy, int ox, const unsigned char* mask, int K, int accumulate, long long* counts) {
+  if (!truth || !pred || !counts) return eae_set_error(EAE_ERR_ARG, "scene_confusion: NULL truth, pred or counts");
+  if (elem_bytes != 1 && elem_bytes != 4) return eae_set_error(EAE_ERR_ARG, "scene_confusion: truth must be uint8 or int32 (elem_bytes 1 or 4)");
+  if (K < 1 || K > 64) return eae_set_error(EAE_ERR_ARG, "scene_confusion: the number of classes must be in 1..64");
+  if (cell < 1) return eae_set_error(EAE_ERR_ARG, "scene_confusion: the cell size must be positive");
+  if (oy < 0 || ox < 0) return eae_set_error(EAE_ERR_ARG, "scene_confusion: the origin must not be negative");
+  if (H < 1 || W < 1 || cH < 1 || cW < 1) return eae_set_error(EAE_ERR_ARG, "scene_confusion: empty raster or map");
+  if (accumulate != 0 && accumulate != 1) return eae_set_error(EAE_ERR_ARG, "scene_confusion: accumulate must be 0 or 1");
+  EAE_NO_GROUP("scene_confusion_kernel");
+  const hipStream_t st = (hipStream_t)stream;
+  const int nbin = (K + 1) * (K + 1);
+  if (!accumulate && hipMemsetAsync(counts, 0, (size_t)nbin * sizeof(long long), st) != hipSuccess)
+    return eae_set_error(-3, "scene_confusion: clearing counts failed");
+  // bounded grid (8 workgroups on each of 256 CUs), raised only where a workgroup's share of tiles would reach 2^31 pixels
+  const unsigned G = (unsigned)(((long long)W + 2 * CONF_RUN - 2) / CONF_RUN);          // ceil((W + 15) / 16) run slots per row
+  const long long ntiles = ((long long)H * G + CONF_NT - 1) / CONF_NT;
+  const long long max_share = (0x7fffffffLL / (CONF_NT * CONF_RUN)) - 1;          // tiles per workgroup
+  long long grid = ntiles < 2048 ? ntiles : 2048;
+  if ((ntiles + grid - 1) / grid > max_share) grid = (ntiles + max_share - 1) / max_share;
+  if (grid > 0x7fffffffLL) return eae_set_error(EAE_ERR_ARG, "scene_confusion: raster too large");
+  const size_t lds = (size_t)nbin * sizeof(int);
+  if (elem_bytes == 1)
+    hipLaunchKernelGGL(scene_confusion_kernel<uint8_t>, dim3((unsigned)grid), dim3(CONF_NT), lds, st, (const uint8_t*)truth, H, W, pred, cH,
+                       cW, (unsigned)cell, (unsigned)oy, (unsigned)ox, mask, K, G, ntiles, (unsigned long long*)counts);
+  else
+    hipLaunchKernelGGL(scene_confusion_kernel<int32_t>, dim3((unsigned)grid), dim3(CONF_NT), lds, st, (const int32_t*)truth, H, W, pred, cH,
+                       cW, (unsigned)cell, (unsigned)oy, (unsigned)ox, mask, K, G, ntiles, (unsigned long long*)counts);
   EAE_LAUNCH_CHECK();
   return 0;
 }

@@ -79,9 +79,61 @@ def class_metrics(labels, preds):
     }
 
 
+def confusion_metrics(cm, num_classes=None):
+    """Per-class and overall accuracy figures of a confusion matrix of pixel (or sample) counts, NumPy array or tensor: the [K+1,K+1]
+    matrix of `scene.scene_confusion` (row K: unlabelled truth, column K: not classified; num_classes=None takes K = n - 1), or a
+    plain [K,K] one (``num_classes=K``).  With M = cm[:K,:K], u = cm[:K,K] and a = cm[K,:K]:
+
+    support_c = sum M[c,:] + u_c (a labelled pixel the map left unclassified is an omission); recall (producer's accuracy) =
+    M[c,c] / support_c; precision (user's accuracy) = M[c,c] / sum M[:,c]; f1; iou = M[c,c] / (support_c + sum M[:,c] - M[c,c]);
+    accuracy = trace / sum support; kappa = Cohen's over the labelled rows, "not classified" being a predicted category without a
+    true row; macro / weighted averages as `class_metrics`; unclassified = u; area = cm[:, :K].sum(0), the pixels mapped to each
+    class, unlabelled truth included.  Zero division gives 0."""
+    if hasattr(cm, "detach"):
+        cm = cm.detach().cpu().numpy()
+    cm = np.asarray(cm)
+    if cm.ndim != 2 or cm.shape[0] != cm.shape[1] or cm.shape[0] < 1:
+        raise ValueError("cm must be a square matrix")
+    n = cm.shape[0]
+    k = n - 1 if num_classes is None else int(num_classes)
+    if k < 1 or n not in (k, k + 1):
+        raise ValueError(f"cm must be [K,K] or [K+1,K+1] with K = {k}, got {list(cm.shape)}")
+    cm = cm.astype(np.int64)
+    m = cm[:k, :k]
+    u = cm[:k, k] if n > k else np.zeros(k, dtype=np.int64)
+    tp = np.diag(m).astype(np.float64)
+    pred_n = m.sum(0).astype(np.float64)
+    true_n = (m.sum(1) + u).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        prec = np.where(pred_n > 0, tp / pred_n, 0.0)
+        rec = np.where(true_n > 0, tp / true_n, 0.0)
+        f1 = np.where(prec + rec > 0, 2 * prec * rec / (prec + rec), 0.0)
+        union = true_n + pred_n - tp
+        iou = np.where(union > 0, tp / union, 0.0)
+    total = true_n.sum()
+    w = true_n / max(total, 1.0)
+    po = tp.sum() / max(total, 1.0)
+    pe = float((true_n * pred_n).sum()) / max(total * total, 1.0)          # column K has no true row: its product is 0
+    return {
+        "classes": np.arange(k), "precision": prec, "recall": rec, "f1": f1, "iou": iou, "support": true_n.astype(np.int64),
+        "accuracy": float(po), "kappa": float((po - pe) / (1.0 - pe)) if pe < 1.0 else 0.0,
+        "macro": (float(prec.mean()), float(rec.mean()), float(f1.mean())),
+        "weighted": (float((prec * w).sum()), float((rec * w).sum()), float((f1 * w).sum())),
+        "mean_iou": float(iou.mean()), "unclassified": u.copy(), "area": cm[:, :k].sum(0), "total": int(total),
+    }
+
+
+def classification_report_from_confusion(cm, digits=4, num_classes=None):
+    """`classification_report`'s table from a confusion matrix (`confusion_metrics`: the same matrix forms)."""
+    return _report_text(confusion_metrics(cm, num_classes), digits)
+
+
 def classification_report(labels, preds, digits=4):
     """Text table in the layout sklearn prints for the notebook's call (R.md:3216-3237)."""
-    m = class_metrics(labels, preds)
+    return _report_text(class_metrics(labels, preds), digits)
+
+
+def _report_text(m, digits):
     names = [str(c) for c in m["classes"].tolist()]
     width = max(max(len(n) for n in names), len("weighted avg"), digits)
     head = "{:>{w}s} ".format("", w=width) + "".join(" {:>9}".format(h) for h in ("precision", "recall", "f1-score", "support"))

@@ -55,6 +55,16 @@ per-patch label is made on the host; no model runs, so P is any positive size; t
 - `SceneLoader` is the iterable over (x, y) batches of the labelled windows: epoch e orders the ids by
   ``torch.randperm(n, generator=torch.Generator().manual_seed(seed + e))`` (`window_schedule`) and batch i is
   ``stage_scene_windows(ids, seed=seed, step=e * len(loader) + i)``; nothing inside an epoch synchronises the host.
+
+Accuracy assessment (how good is the map `classify_scene` returned?).  The class map is compared with the label raster pixel by pixel
+on the device: the raster and an optional mask are read once, the map is looked up per cell, and no upsampled copy of the map is made.
+- `scene_confusion` returns the int64 [K+1,K+1] confusion counts of a cell map against a label raster (row K: unlabelled truth,
+  column K: not classified), exact and identical from run to run; `report.confusion_metrics` turns them into user's / producer's
+  accuracy, IoU, kappa and the mapped area per class;
+- `evaluate_scene` is `classify_scene` followed by `scene_confusion` with the map's cell size and origin;
+- `block_split` cuts the window grid into blocks, gives some to validation and drops the training windows that share pixels with a
+  validation window (overlapping windows make a random split of window ids leak); `footprint_mask` is the pixel footprint of a list
+  of windows, the ``region=`` an honest validation figure is assessed over.
 """
 from __future__ import annotations
 
@@ -635,6 +645,34 @@ def _stage_windows(desc, keep, windows, train, noise_std, seed, step, params, no
     return out
 
 
+def _ignore_arg(ignore, k):
+    """The classes of [0, k) that ``ignore`` (None, one integer or a list of them) declares unlabelled, ascending; any other value
+    is unlabelled already."""
+    if ignore is None:
+        ignore = []
+    elif isinstance(ignore, numbers.Integral) and not isinstance(ignore, bool):
+        ignore = [int(ignore)]
+    else:
+        ignore = list(ignore)
+        if any(isinstance(v, bool) or not isinstance(v, numbers.Integral) for v in ignore):
+            raise RuntimeError(f"ignore must be an integer or a list of integers, got {ignore!r}")
+    return sorted({int(v) for v in ignore if 0 <= int(v) < k})
+
+
+def _label_raster(raster, k, ignore):
+    """An integer label raster as the kernels read it: contiguous uint8 or int32 (other dtypes converted to int32, values outside
+    [0, k) becoming -1), the `_ignore_arg` classes replaced by an unlabelled value."""
+    if raster.dtype not in (torch.uint8, torch.int32):
+        wide = raster.to(torch.int64)
+        raster = torch.where((wide >= 0) & (wide < k), wide, -1).to(torch.int32)
+    if ignore:
+        hit = raster == ignore[0]
+        for v in ignore[1:]:
+            hit = hit | (raster == v)
+        raster = raster.masked_fill(hit, 255 if raster.dtype == torch.uint8 else -1)          # K <= 64: 255 is never a class
+    return raster.contiguous()
+
+
 def window_labels(raster, patch, stride, num_classes, ignore=None):
     """(label int64 [nH,nW], purity float32 [nH,nW], labelled float32 [nH,nW]) of every whole P x P window at stride S over a label
     raster [H,W] on the device (any integer dtype; uint8 and int32 are read as they are, the others converted to int32).  A pixel is
@@ -654,25 +692,9 @@ def window_labels(raster, patch, stride, num_classes, ignore=None):
         raise RuntimeError(f"the patch size must be at most {_MAX_LABEL_PATCH}, got {patch}")
     h, w = (int(v) for v in raster.shape)
     n_h, n_w = window_grid(h, w, patch, stride, any_patch=True)
-    if ignore is None:
-        ignore = []
-    elif isinstance(ignore, numbers.Integral) and not isinstance(ignore, bool):
-        ignore = [int(ignore)]
-    else:
-        ignore = list(ignore)
-        if any(isinstance(v, bool) or not isinstance(v, numbers.Integral) for v in ignore):
-            raise RuntimeError(f"ignore must be an integer or a list of integers, got {ignore!r}")
-    ignore = sorted({int(v) for v in ignore if 0 <= int(v) < k})          # any other value is unlabelled already
+    ignore = _ignore_arg(ignore, k)
     _require_gpu(raster.device)
-    if raster.dtype not in (torch.uint8, torch.int32):
-        wide = raster.to(torch.int64)
-        raster = torch.where((wide >= 0) & (wide < k), wide, -1).to(torch.int32)
-    if ignore:
-        hit = raster == ignore[0]
-        for v in ignore[1:]:
-            hit = hit | (raster == v)
-        raster = raster.masked_fill(hit, 255 if raster.dtype == torch.uint8 else -1)          # K <= 64: 255 is never a class
-    raster = raster.contiguous()
+    raster = _label_raster(raster, k, ignore)
     dev = raster.device
     label = torch.empty((n_h, n_w), dtype=torch.int64, device=dev)
     count = torch.empty((n_h, n_w), dtype=torch.int32, device=dev)
@@ -841,3 +863,169 @@ class SceneLoader:
             x = _stage_windows(self._desc, self._keep, w, self.train, self.noise_std, self.seed, base + i, None, None, cid)
             yield x, ys[at:at + b.numel()]
             at += b.numel()
+
+
+# ---------------------------------------------------------------------------------------------------- accuracy assessment
+_INT_MAX = 2 ** 31 - 1
+
+
+def scene_confusion(pred, truth, num_classes, cell=1, origin=(0, 0), mask=None, ignore=None, out=None):
+    """Confusion counts int64 [K+1,K+1] (on the device) of a class map against a label raster, pixel by pixel.  ``truth`` [H,W] is a
+    label raster of any integer dtype (read as `window_labels` reads it; the values of ``ignore`` count as unlabelled), ``pred`` an
+    int64 [cH,cW] map of ``cell`` x ``cell`` cells: pixel (y, x) lies in cell ((y + oy) // cell, (x + ox) // cell), (oy, ox) =
+    ``origin``.  Every pixel with ``mask[y, x] == 0`` (``mask``: bool / uint8 [H,W], or None) adds 1 to counts[r, c]: r = the truth
+    value in [0, K), else K (unlabelled); c = the cell's value in [0, K), else K (not classified: -1, any other value, a pixel the
+    map does not cover).  ``out=``: an earlier result to add to (assessment over several scenes); otherwise the counts start at 0.
+    cell=1 compares two maps of one shape, for example `classify_scene`'s window labels with `window_labels`' majority map.
+    Exact integer counts: identical from run to run.  `report.confusion_metrics` turns the matrix into accuracy figures."""
+    k = int(num_classes)
+    if not 1 <= k <= 64:
+        raise RuntimeError(f"num_classes must be in 1..64, got {num_classes}")
+    if not isinstance(truth, torch.Tensor) or truth.dim() != 2:
+        raise RuntimeError("truth must be a [H, W] tensor of class ids")
+    if truth.dtype.is_floating_point or truth.dtype.is_complex or truth.dtype == torch.bool:
+        raise RuntimeError(f"truth must have an integer dtype, got {truth.dtype}")
+    if not isinstance(pred, torch.Tensor) or pred.dim() != 2 or pred.dtype != torch.int64:
+        raise RuntimeError("pred must be a 2-D int64 map of class ids")
+    cell = int(cell)
+    if not 1 <= cell <= _INT_MAX:
+        raise RuntimeError(f"cell must be positive, got {cell}")
+    try:
+        oy, ox = (int(v) for v in origin)
+    except (TypeError, ValueError):
+        raise RuntimeError(f"origin must be a pair (oy, ox) of integers, got {origin!r}") from None
+    if not (0 <= oy <= _INT_MAX and 0 <= ox <= _INT_MAX):
+        raise RuntimeError(f"origin must not be negative, got {origin!r}")
+    h, w = (int(v) for v in truth.shape)
+    c_h, c_w = (int(v) for v in pred.shape)
+    if min(h, w, c_h, c_w) < 1:
+        raise RuntimeError(f"empty truth {[h, w]} or pred {[c_h, c_w]}")
+    if max(h, w, c_h, c_w) > _INT_MAX:
+        raise RuntimeError("truth or pred is too large")
+    if pred.device != truth.device:
+        raise RuntimeError(f"pred is on {pred.device}, truth on {truth.device}")
+    m = _mask_arg(truth.unsqueeze(0), mask)
+    ignore = _ignore_arg(ignore, k)
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or tuple(out.shape) != (k + 1, k + 1) or not out.is_contiguous():
+            raise RuntimeError(f"out must be a contiguous int64 [{k + 1}, {k + 1}] tensor (an earlier result)")
+        if out.device != truth.device:
+            raise RuntimeError(f"out is on {out.device}, truth on {truth.device}")
+    _require_gpu(truth.device)
+    truth = _label_raster(truth, k, ignore)
+    pred = pred.contiguous()
+    counts = torch.empty((k + 1, k + 1), dtype=torch.int64, device=truth.device) if out is None else out
+    lib = _lib.load()
+    with torch.cuda.device(truth.device):
+        check(lib.eae_scene_confusion(_stream(), _ptr(truth), truth.element_size(), h, w, _ptr(pred), c_h, c_w, cell, oy, ox, _ptr(m),
+                                      k, int(out is not None), _ptr(counts)))
+    return counts
+
+
+def evaluate_scene(scene, encoder, mlp, truth, divisor=1.0, stride=None, batch=512, blend=False, nodata=None, mask=None,
+                   max_invalid=0.0, rule="all", windows=None, border=None, fill=0, anchor="center", ignore=None, region=None):
+    """Classify a scene and assess the map against a label raster ``truth`` [H,W] of the scene's size: `classify_scene` with the
+    same arguments, then `scene_confusion` with the map's geometry -- blend=True: the cells of S x S pixels; blend=False: the
+    windows themselves, which must not overlap (stride == patch: overlapping windows without blending give a pixel no single class);
+    origin = the leading pads of the border grid (cell (ci, cj) starts at pixel (ci*S - pt, cj*S - pl)).  ``ignore``: truth values
+    to count as unlabelled.  ``region``: a [H,W] tensor, non-zero where a pixel is to be assessed (`footprint_mask` of the
+    validation windows of a `block_split`); None assesses every pixel.  ``mask`` / ``nodata`` decide which windows are classified,
+    as in `classify_scene`; their pixels stay in the counts, under "not classified" where the window was left out.
+
+    Returns {"confusion": int64 [K+1,K+1] on the device, "metrics": `report.confusion_metrics` of it, "probs", "labels": what
+    `classify_scene` returned}."""
+    from .modules import MLP
+    from .report import confusion_metrics
+    enc = _encoder_of(encoder)
+    if not isinstance(mlp, MLP):
+        raise RuntimeError(f"mlp must be an MLP, got {type(mlp).__name__}")
+    patch = int(enc.image_size)
+    stride = patch if stride is None else int(stride)
+    if not blend and stride != patch:
+        raise RuntimeError(f"blend=False needs stride == patch ({patch}): overlapping windows give a pixel no single class without "
+                           f"blending, got stride {stride}")
+    if blend:
+        cell_grid(1, 1, patch, stride)                   # the stride must divide the patch size
+    _check_scene(scene)
+    h, w = int(scene.shape[1]), int(scene.shape[2])
+    if not isinstance(truth, torch.Tensor) or tuple(truth.shape) != (h, w):
+        got = tuple(truth.shape) if isinstance(truth, torch.Tensor) else type(truth).__name__
+        raise RuntimeError(f"truth must be a [H, W] = {[h, w]} label raster of the scene's size, got {got}")
+    if truth.device != scene.device:
+        raise RuntimeError(f"truth is on {truth.device}, the scene on {scene.device}")
+    exclude = None
+    if region is not None:
+        if not isinstance(region, torch.Tensor) or tuple(region.shape) != (h, w) or region.dtype.is_floating_point:
+            raise RuntimeError(f"region must be a bool or integer [H, W] = {[h, w]} tensor")
+        if region.device != scene.device:
+            raise RuntimeError(f"region is on {region.device}, the scene on {scene.device}")
+        exclude = region == 0
+    pads = _border_arg(scene, patch, stride, border, fill, anchor)[4]
+    k = int(mlp.num_classes)
+    # the remaining host checks of scene_confusion, before a kernel runs (truth's dtype, K, ignore)
+    if truth.dtype.is_floating_point or truth.dtype.is_complex or truth.dtype == torch.bool:
+        raise RuntimeError(f"truth must have an integer dtype, got {truth.dtype}")
+    if not 1 <= k <= 64:
+        raise RuntimeError(f"the MLP's num_classes must be in 1..64, got {k}")
+    _ignore_arg(ignore, k)
+    probs, labels = classify_scene(scene, encoder, mlp, divisor, stride, batch, blend, nodata, mask, max_invalid, rule, windows, border,
+                                   fill, anchor)
+    cm = scene_confusion(labels, truth, k, cell=stride, origin=(pads[0], pads[2]), mask=exclude, ignore=ignore)
+    return {"confusion": cm, "metrics": confusion_metrics(cm), "probs": probs, "labels": labels}
+
+
+def block_split(n_h, n_w, patch, stride, block, val_fraction=0.2, seed=0):
+    """A spatially blocked train / validation split of an n_h x n_w window grid (pure host arithmetic): `SceneLoader` windows
+    overlap when S < P, so a random split of window ids shares pixels between the two sides and inflates validation accuracy.  The
+    grid is cut into blocks of ``block`` x ``block`` windows (row-major block ids, the last row / column of blocks may be smaller);
+    the blocks are ordered by ``torch.randperm(n_blocks, generator=torch.Generator().manual_seed(seed))`` and the first
+    max(1, round(val_fraction * n_blocks)) of them are validation.  A training-side window whose pixel footprint intersects a
+    validation window's is dropped: the guard band, ceil(P/S) - 1 windows wide.  Returns (train_ids, val_ids, dropped_ids), ascending
+    int64 CPU tensors that partition the grid; they feed ``SceneLoader(windows=...)`` and `footprint_mask`."""
+    n_h, n_w, patch, stride, block = int(n_h), int(n_w), int(patch), int(stride), int(block)
+    if n_h < 1 or n_w < 1:
+        raise RuntimeError(f"the grid {n_h} x {n_w} is empty")
+    if patch < 1 or not 1 <= stride <= patch:
+        raise RuntimeError(f"stride must be in 1..{patch} (the patch size), got {stride}")
+    if block < 1:
+        raise RuntimeError(f"block must be positive, got {block}")
+    f = float(val_fraction)
+    if not 0.0 < f < 1.0:
+        raise RuntimeError(f"val_fraction must be in (0, 1), got {val_fraction}")
+    b_h, b_w = -(-n_h // block), -(-n_w // block)
+    n_blocks = b_h * b_w
+    order = torch.randperm(n_blocks, generator=torch.Generator().manual_seed(int(seed)))
+    is_val_block = torch.zeros(n_blocks, dtype=torch.bool)
+    is_val_block[order[:max(1, round(f * n_blocks))]] = True
+    bi = torch.arange(n_h) // block
+    bj = torch.arange(n_w) // block
+    val = is_val_block[bi[:, None] * b_w + bj[None, :]]                       # [n_h, n_w]
+    g = -(-patch // stride) - 1                 # windows i and i' share pixels on an axis exactly when |i - i'| * S < P: |i - i'| <= g
+    near = torch.nn.functional.max_pool2d(val[None, None].to(torch.float32), 2 * g + 1, stride=1, padding=g)[0, 0] > 0
+    dropped = near & ~val
+    flat = lambda m: torch.nonzero(m.reshape(-1)).reshape(-1)           # noqa: E731  ascending int64 ids
+    return flat(~near), flat(val), flat(dropped)
+
+
+def footprint_mask(ids, n_w, patch, stride, height, width, device=None):
+    """bool [height, width]: true where one of the windows ``ids`` (1-D int64 ids of a grid of whole windows with n_w per row, window
+    n at pixel (n // n_w * S, n % n_w * S)) covers the pixel, clipped to the raster.  Torch only (a 2-D difference array and two
+    cumulative sums, any S), on ``device`` (default: where ``ids`` is), CPU included.  What `evaluate_scene` takes as ``region=``."""
+    if not isinstance(ids, torch.Tensor) or ids.dim() != 1 or ids.dtype != torch.int64:
+        raise RuntimeError("ids must be a 1-D int64 tensor of window ids")
+    n_w, patch, stride, height, width = int(n_w), int(patch), int(stride), int(height), int(width)
+    if n_w < 1 or patch < 1 or stride < 1 or height < 1 or width < 1:
+        raise RuntimeError("n_w, patch, stride, height and width must be positive")
+    dev = ids.device if device is None else torch.device(device)
+    ids = ids.to(dev)
+    if ids.numel() and int(ids.min()) < 0:
+        raise RuntimeError("window ids must not be negative")
+    y0 = torch.clamp(torch.div(ids, n_w, rounding_mode="floor") * stride, max=height)
+    x0 = torch.clamp(ids % n_w * stride, max=width)
+    y1, x1 = torch.clamp(y0 + patch, max=height), torch.clamp(x0 + patch, max=width)
+    diff = torch.zeros((height + 1) * (width + 1), dtype=torch.int32, device=dev)
+    one = torch.ones(ids.numel(), dtype=torch.int32, device=dev)
+    for yy, xx, s in ((y0, x0, one), (y0, x1, -one), (y1, x0, -one), (y1, x1, one)):
+        diff.index_add_(0, yy * (width + 1) + xx, s)
+    cover = diff.reshape(height + 1, width + 1).cumsum(0, dtype=torch.int32).cumsum(1, dtype=torch.int32)
+    return cover[:height, :width] > 0

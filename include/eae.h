@@ -570,6 +570,24 @@ int eae_scene_stage_windows(void* stream, const eae_scene* scene, const long lon
 int eae_scene_window_labels(void* stream, const void* raster, int elem_bytes, int H, int W, int patch, int stride, int K,
                             long long* label, int* count, int* labelled);
 
+/* ------------------------------------------------------------------ accuracy assessment ------------ */
+/* Confusion counts of a class map against a label raster, pixel by pixel, both on the device.  truth [H][W] is uint8 (elem_bytes 1)
+ * or int32 (4), as in eae_scene_window_labels; pred is an int64 [cH][cW] map of cell x cell cells (the labels of
+ * eae_scene_classify: cell = the patch size; the cell labels of eae_scene_blend: cell = the stride; cell = 1: a map of the raster's
+ * own resolution); mask is NULL or uint8 [H][W]; counts is int64 [(K+1)][(K+1)], K in 1..64.
+ *   Pixel (y, x) lies in cell ((y + oy) / cell, (x + ox) / cell): (oy, ox) = the leading pads of a border grid, 0 without one.
+ *   A pixel with mask[y][x] != 0 is skipped.  Every other pixel adds 1 to counts[r][c]:
+ *     r = truth[y][x] when that is in [0, K), else K (unlabelled);
+ *     c = the cell's pred value when the cell lies inside the map and the value is in [0, K), else K (not classified: the -1 of an
+ *         invalid or unlisted window, any value outside [0, K), a pixel the map does not cover).
+ *   So the entries sum to the number of unmasked pixels.  accumulate = 0: counts is cleared first, on the stream; accumulate = 1:
+ *   the call adds to what counts holds (assessment over several scenes).
+ * Integer counting throughout (LDS tables per workgroup, 64-bit global adds): exact, and identical from run to run.  The raster
+ * and the mask are read once; no per-pixel copy of the map is made.  Rejected (EAE_ERR_ARG): a NULL truth, pred or counts, any
+ * other elem_bytes, K outside 1..64, cell < 1, a negative oy or ox, an empty raster or map, accumulate outside 0..1. */
+int eae_scene_confusion(void* stream, const void* truth, int elem_bytes, int H, int W, const long long* pred, int cH, int cW, int cell,
+                        int oy, int ox, const unsigned char* mask, int K, int accumulate, long long* counts);
+
 #ifdef __cplusplus
 }
 #endif
