@@ -53,6 +53,7 @@ _PROTOS = {
     "eae_set_graph": (C.c_int, [vp, C.c_int]),
     "eae_set_class_weights": (C.c_int, [vp, vp, C.c_longlong]),
     "eae_set_valid_counter": (C.c_int, [vp, vp]),
+    "eae_set_grad_clip": (C.c_int, [vp, C.c_float, vp]),
     "eae_set_adam_step": (C.c_int, [vp, C.c_longlong]),
     "eae_get_adam_step": (C.c_longlong, [vp]),
     "eae_ae_forward": (C.c_int, [vp, vp, C.POINTER(EaeStepIO)]),

@@ -152,6 +152,12 @@ struct eae_ctx {
   long long ignore_index = EAE_NO_IGNORE;
   bool wce() const { return class_w != nullptr || ignore_index != EAE_NO_IGNORE; }
   long long* valid_acc = nullptr;  // eae_set_valid_counter: caller-owned device word, += counted rows of every step that accumulates its loss
+  // global gradient-norm clipping (eae_set_grad_clip): every optimizer launch of the context is preceded by the sum-of-squares kernel
+  float clip_max = 0.f;            // 0 = off; > 0 or +inf = on
+  float* clip_out = nullptr;       // caller-owned device float[2] (total, coef), or nullptr
+  double* clip_part = nullptr;     // workspace: EAE_CLIP_MAX_PARTS fp64 partials
+  long long psize[38];             // elements of the 38 tensors without the layout's rounding
+  bool clip_on() const { return clip_max != 0.f; }
   float* dyn = nullptr;            // device: lr/bc1, sqrt(bc2), weight decay of the current Adam step
   // optional in-situ timing of ONE launch site (eae_profile_enable(ctx, site); sites: include/eae.h) with HIP events on the
   // stream that launch goes to
@@ -201,6 +207,8 @@ int train_step_eager(eae_ctx* c, hipStream_t st, const eae_step_io* io, float lr
 // the engine's Adam over the first n arena elements; bad / bad2 = the words that make it refuse the update (default: the context's own)
 int launch_adam(eae_ctx* c, hipStream_t st, long long n, float lr, float wd, float grad_scale, const unsigned* bad = nullptr,
                 const unsigned* bad2 = nullptr);
+// with eae_set_grad_clip on: the sum-of-squares launch that goes in front of an optimizer launch, and that launch's clip block
+int clip_prepare(eae_ctx* c, hipStream_t st, EaeClip* clip);
 // optimizer.step(): launch_adam over the whole arena and the host-side state behind it
 int optimizer_step(eae_ctx* c, hipStream_t st, float lr, float wd, float grad_scale, const unsigned* bad = nullptr, const unsigned* bad2 = nullptr);
 // dL/d(pre-sigmoid) from (x_hat, dx_hat) into g (bf16 NHWC-CP), then deconv4's bias gradient db from the per-block partials in `part`

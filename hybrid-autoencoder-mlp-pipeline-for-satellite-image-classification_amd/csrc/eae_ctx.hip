@@ -67,6 +67,7 @@ extern "C" int eae_create(const eae_config* cfg, eae_ctx** out) {
   c->Lp = (c->L + 63) / 64 * 64; c->lpad = c->Lp != c->L;
   c->Pn = (long long)(c->H / 16) * (c->W / 16); c->K = 256 * c->Pn;
   eae_ae_layout(cfg, c->poff, c->bnoff);
+  param_sizes(*cfg, c->psize);
   const long long Bm = c->Bm;
   // ---- carve one allocation
   size_t off = 0;
@@ -134,6 +135,7 @@ extern "C" int eae_create(const eae_config* cfg, eae_ctx** out) {
     o_gsh = carve((size_t)c->head_stride * 4); o_zst = carve(Bm * c->Lp * 4);
   }
   size_t o_ce = carve(hb * 2 * 4), o_head = carve(hb * c->head_stride * 4), o_loss = carve(64 * 4), o_dyn = carve(64), o_sig = carve(64);
+  size_t o_clip = carve(EAE_CLIP_MAX_PARTS * sizeof(double));
   // ---- pack arena
   size_t poffb = 0;
   auto pcarve = [&](size_t bytes) { size_t o = poffb; poffb += (bytes + 255) & ~(size_t)255; return o; };
@@ -198,6 +200,7 @@ extern "C" int eae_create(const eae_config* cfg, eae_ctx** out) {
   c->msepart = (float*)(b + o_mse); c->cepart = (float*)(b + o_ce); c->headpart = (float*)(b + o_head); c->lossbuf = (float*)(b + o_loss);
   c->pack = b + o_pack; c->descs_dev = (PackDesc*)(b + o_desc); c->blkmap = (unsigned short*)(b + o_bmap);
   c->dyn = (float*)(b + o_dyn);
+  c->clip_part = (double*)(b + o_clip);
   c->sigwords = (unsigned*)(b + o_sig);
   c->q = (Fp8State*)(b + o_q);
   c->bn_save = (float*)(b + o_bns);
@@ -395,6 +398,15 @@ extern "C" int eae_set_class_weights(eae_ctx* c, const float* weights, long long
   if (c->capturing) return eae_set_error(EAE_ERR_STATE, "set_class_weights: a step is being captured");
   RC(drop_graphs(c, true));
   c->class_w = weights; c->ignore_index = ignore_index;
+  return 0;
+}
+// Global gradient-norm clipping in front of every optimizer launch (include/eae.h).
+extern "C" int eae_set_grad_clip(eae_ctx* c, float max_norm, float* norm_out) {
+  if (!c) return eae_set_error(EAE_ERR_ARG, "ctx is NULL");
+  if (!(max_norm >= 0.f)) return eae_set_error(EAE_ERR_ARG, "set_grad_clip: max_norm must be 0 (off), positive or +inf");
+  if (c->capturing) return eae_set_error(EAE_ERR_STATE, "set_grad_clip: a step is being captured");
+  RC(drop_graphs(c, true));
+  c->clip_max = max_norm; c->clip_out = max_norm != 0.f ? norm_out : nullptr;
   return 0;
 }
 extern "C" int eae_set_valid_counter(eae_ctx* c, long long* counter) {

@@ -53,6 +53,8 @@ int group_run(int what, eae_ctx* const* ctxs, int n, int mult, void* stream, con
     if (c->Cin != c0->Cin) return eae_set_error(EAE_ERR_ARG, "group call: members must share in_channels");
     if (c->wce() != c0->wce())       // one head kernel serves the whole group (each member with its own vector and ignore_index)
       return eae_set_error(EAE_ERR_ARG, "group call: class weights / ignore_index must be set on every member or on none");
+    if (what == 0 && c->clip_on() != c0->clip_on())      // one optimizer kernel serves the whole group (each member with its own max_norm and norm_out)
+      return eae_set_error(EAE_ERR_ARG, "group call: gradient clipping must be on in every member or in none (+inf measures without clipping)");
     for (int j = 0; j < k; ++j) if (ctxs[j] == c) return eae_set_error(EAE_ERR_ARG, "group call: a context appears twice");
   }
   RC(streams_distinct(c0, user));

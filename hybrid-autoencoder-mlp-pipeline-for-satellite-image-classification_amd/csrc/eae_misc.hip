@@ -574,7 +574,40 @@ struct AdamArgs {
   float* p; const float* g; float* m; float* v; long n4; float b1, b2, step_size, bc2_sqrt, eps, wd, gscale; uint4* zbuf; long zn16;
   const unsigned* bad; const unsigned* bad2; float* nan_out; int nan_fill;
 };
-__device__ __forceinline__ EAE_NO_PK void adam_body(const AdamArgs& aa) {
+
+// ---- global gradient-norm clipping (eae_set_grad_clip)
+// grad_sumsq_kernel leaves GradNormArgs-many fp64 partial sums of g^2 in a workspace; EVERY workgroup of the optimizer kernel behind it
+// adds them in one fixed order (the idiom of the weighted head kernel's W), so all of them hold the same bits of
+//   total = s * sqrt(sum g^2)      coef = min(1, max_norm / (total + 1e-6))      (torch.nn.utils.clip_grad_norm_, norm_type 2)
+// and Adam consumes fma(g, fl32(s * coef), wd * p): with coef == 1 the unclipped arithmetic.  No atomics, nothing depends on the
+// optimizer's grid (eae_launch_adam_scaled shrinks it for a member of a grouped step).
+struct ClipArgs { const double* part; int nparts; float max_norm; float* norm_out; };
+struct AdamClipArgs { AdamArgs a; ClipArgs c; };
+struct ClipCoef { float coef; bool finite; };
+
+// sum of 256 per-thread fp64 values in a fixed order, the same value in every thread: lanes by xor-butterfly (each level adds the
+// same pairs in every lane, and fp64 addition commutes), then the four waves 0 + 1 + 2 + 3
+__device__ __forceinline__ double block_sum_fixed(double v, double* lds4) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((lds4[0] + lds4[1]) + lds4[2]) + lds4[3];
+}
+__device__ __forceinline__ EAE_NO_PK ClipCoef clip_coef(const ClipArgs& ca, float gscale) {
+#pragma clang fp contract(off)
+  __shared__ double lds4[4];
+  double v = 0.0;
+  for (int i = threadIdx.x; i < ca.nparts; i += 256) v += ca.part[i];
+  const double ss = block_sum_fixed(v, lds4);
+  const float total = (float)((double)gscale * sqrt(ss));
+  const float coef = fminf(1.0f, ca.max_norm / (total + 1e-6f));
+  if (ca.norm_out != nullptr && blockIdx.x == 0 && threadIdx.x == 0) { ca.norm_out[0] = total; ca.norm_out[1] = coef; }
+  ClipCoef r; r.coef = coef; r.finite = total - total == 0.0f;      // (inf - inf and NaN - NaN are NaN)
+  return r;
+}
+
+template <bool CLIP> __device__ __forceinline__ EAE_NO_PK void adam_body(const AdamArgs& aa, const ClipArgs* ca = nullptr) {
   float* __restrict__ p = aa.p; const float* __restrict__ g = aa.g; float* __restrict__ m = aa.m; float* __restrict__ v = aa.v;
   const long n4 = aa.n4; const float b1 = aa.b1, b2 = aa.b2, step_size = aa.step_size, bc2_sqrt = aa.bc2_sqrt, eps = aa.eps, wd = aa.wd, gscale = aa.gscale;
   uint4* __restrict__ zbuf = aa.zbuf; const long zn16 = aa.zn16;
@@ -585,7 +618,13 @@ __device__ __forceinline__ EAE_NO_PK void adam_body(const AdamArgs& aa) {
   // a side-stream gate of this context has timed out at some point (sticky word): gradients may have been computed from stale
   // activations -- no update, and the step's loss scalars become NaN so that the run cannot go on unnoticed
   const bool stale = bad != nullptr && __hip_atomic_load(bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
-  const bool diverged = bad2 != nullptr && __hip_atomic_load(bad2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
+  bool diverged = bad2 != nullptr && __hip_atomic_load(bad2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
+  float geff = gscale;
+  if constexpr (CLIP) {      // norm_out is written also when the update is refused; a non-finite norm refuses it (diverged)
+    const ClipCoef cc = clip_coef(*ca, gscale);
+    diverged = diverged || !cc.finite;
+    geff = gscale * cc.coef;
+  }
   if (stale || diverged) {
     if (nan_out != nullptr && blockIdx.x == 0 && threadIdx.x < 3) nan_out[threadIdx.x] = __builtin_nanf("");
     // nan_fill (eae_config.nan_exact / EAE_NAN_EXACT=1): a DIVERGED step does to the replica what it does to the reference's model --
@@ -608,24 +647,76 @@ __device__ __forceinline__ EAE_NO_PK void adam_body(const AdamArgs& aa) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const float wp = wd * P[j];
-      adam_update(P[j], __builtin_fmaf(G[j], gscale, wp), M[j], V[j], b1, b2, step_size, bc2_sqrt, eps);
+      adam_update(P[j], __builtin_fmaf(G[j], CLIP ? geff : gscale, wp), M[j], V[j], b1, b2, step_size, bc2_sqrt, eps);
     }
     reinterpret_cast<float4*>(p)[i] = pp;
     reinterpret_cast<float4*>(m)[i] = mm;
     reinterpret_cast<float4*>(v)[i] = vv;
   }
 }
-__global__ EAE_NO_PK __launch_bounds__(256) void adam_kernel(AdamArgs a) { adam_body(a); }
-__global__ EAE_NO_PK __launch_bounds__(256) void adam_kernel_g(GroupPack<AdamArgs> p, int gz) { adam_body(group_args<AdamArgs>(gz)); }
+__global__ EAE_NO_PK __launch_bounds__(256) void adam_kernel(AdamArgs a) { adam_body<false>(a); }
+__global__ EAE_NO_PK __launch_bounds__(256) void adam_kernel_g(GroupPack<AdamArgs> p, int gz) { adam_body<false>(group_args<AdamArgs>(gz)); }
+__global__ EAE_NO_PK __launch_bounds__(256) void adam_clip_kernel(AdamClipArgs a) { adam_body<true>(a.a, &a.c); }
+__global__ EAE_NO_PK __launch_bounds__(256) void adam_clip_kernel_g(GroupPack<AdamClipArgs> p, int gz) {
+  const AdamClipArgs a = group_args<AdamClipArgs>(gz);
+  adam_body<true>(a.a, &a.c);
+}
+
+// Sum of squares of the 38 gradient tensors, fp64, one partial per workgroup.  The arena is caller-owned and every tensor is rounded
+// up to 4 elements: the 1..3 padding floats behind a tensor must not count.  They sit in the tensor's LAST 16-byte piece only, so the
+// segment table shrinks to the few pieces that hold padding (tail[k] = piece index * 4 + valid elements; ntail <= 38, 3 at most for
+// this model: enc.fc.bias [L], deconv4.bias [bands], classifier.2.bias [C]) and every other piece is summed whole.  Thread t of the
+// grid takes pieces t, t + T, ...: four independent 16-byte loads in flight per round; the grid is a function of the arena length
+// alone, so which elements a partial covers is too.
+struct GradNormArgs { const float* g; double* part; unsigned n4; int ntail; unsigned tail[38]; };
+__device__ __forceinline__ EAE_NO_PK void grad_sumsq_body(const GradNormArgs& a) {
+#pragma clang fp contract(off)
+  __shared__ double lds4[4];
+  const unsigned T = gridDim.x * 256u, t = blockIdx.x * 256u + threadIdx.x, n4 = a.n4;
+  const float4* __restrict__ g4 = reinterpret_cast<const float4*>(a.g);
+  double acc = 0.0;
+  for (unsigned i0 = t; i0 < n4; i0 += 4u * T) {      // (n4 < 2^30 and T <= 2^17: no wrap)
+    float4 q[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {      // (past the end: piece n4 - 1 again, counted with 0 valid elements below)
+      const unsigned i = i0 + (unsigned)u * T;
+      q[u] = g4[i < n4 ? i : n4 - 1];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const unsigned i = i0 + (unsigned)u * T;
+      unsigned valid = i < n4 ? 4u : 0u;
+      for (int k = 0; k < a.ntail; ++k) if ((a.tail[k] >> 2) == i) valid = a.tail[k] & 3u;
+      const double x = valid > 0 ? q[u].x : 0.f, y = valid > 1 ? q[u].y : 0.f, z = valid > 2 ? q[u].z : 0.f, w = valid > 3 ? q[u].w : 0.f;
+      acc += x * x; acc += y * y; acc += z * z; acc += w * w;
+    }
+  }
+  const double tot = block_sum_fixed(acc, lds4);
+  if (threadIdx.x == 0) a.part[blockIdx.x] = tot;
+}
+__global__ EAE_NO_PK __launch_bounds__(256) void grad_sumsq_kernel(GradNormArgs a) { grad_sumsq_body(a); }
+// (the member's block is read in place: a copy indexed with the run-time k of the tail loop would live in scratch)
+__global__ EAE_NO_PK __launch_bounds__(256) void grad_sumsq_kernel_g(GroupPack<GradNormArgs> p, int gz) {
+  const char* base = (const char*)__builtin_amdgcn_kernarg_segment_ptr();
+  grad_sumsq_body(*reinterpret_cast<const GradNormArgs*>(base + (size_t)(blockIdx.z / (unsigned)gz) * sizeof(GradNormArgs)));
+}
 
 // Same update with the per-step scalars (lr/bias_correction1, sqrt(bias_correction2), weight decay) read from device memory,
 // so that a captured hipGraph of the whole train step can be replayed while the step count advances.
-__global__ EAE_NO_PK __launch_bounds__(256) void adam_dyn_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+template <bool CLIP>
+__device__ __forceinline__ EAE_NO_PK void adam_dyn_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                         float* __restrict__ v, long n4, float b1, float b2, float eps,
                                                         const float* __restrict__ dyn, const unsigned* __restrict__ bad,
-                                                        const unsigned* __restrict__ bad2, float* __restrict__ nan_out) {
-  if ((bad != nullptr && __hip_atomic_load(bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) ||
-      (bad2 != nullptr && __hip_atomic_load(bad2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {     // see adam_kernel
+                                                        const unsigned* __restrict__ bad2, float* __restrict__ nan_out, const ClipArgs* ca = nullptr) {
+  bool refuse = (bad != nullptr && __hip_atomic_load(bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) ||
+                (bad2 != nullptr && __hip_atomic_load(bad2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u);     // see adam_kernel
+  float coef = 1.0f;
+  if constexpr (CLIP) {
+    const ClipCoef cc = clip_coef(*ca, 1.0f);
+    refuse = refuse || !cc.finite;
+    coef = 1.0f * cc.coef;
+  }
+  if (refuse) {
     if (nan_out != nullptr && blockIdx.x == 0 && threadIdx.x < 3) nan_out[threadIdx.x] = __builtin_nanf("");
     return;
   }
@@ -638,22 +729,43 @@ __global__ EAE_NO_PK __launch_bounds__(256) void adam_dyn_kernel(float* __restri
     float* P = &pp.x; float* G = &gg.x; float* M = &mm.x; float* V = &vv.x;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      adam_update(P[j], __builtin_fmaf(wd, P[j], G[j]), M[j], V[j], b1, b2, step_size, bc2_sqrt, eps);
+      if constexpr (CLIP) {      // adam_clip_kernel's form, so that replay and eager agree bit for bit
+        const float wp = wd * P[j];
+        adam_update(P[j], __builtin_fmaf(G[j], coef, wp), M[j], V[j], b1, b2, step_size, bc2_sqrt, eps);
+      } else {
+        adam_update(P[j], __builtin_fmaf(wd, P[j], G[j]), M[j], V[j], b1, b2, step_size, bc2_sqrt, eps);
+      }
     }
     reinterpret_cast<float4*>(p)[i] = pp;
     reinterpret_cast<float4*>(m)[i] = mm;
     reinterpret_cast<float4*>(v)[i] = vv;
   }
 }
+__global__ EAE_NO_PK __launch_bounds__(256) void adam_dyn_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                        float* __restrict__ v, long n4, float b1, float b2, float eps,
+                                                        const float* __restrict__ dyn, const unsigned* __restrict__ bad,
+                                                        const unsigned* __restrict__ bad2, float* __restrict__ nan_out) {
+  adam_dyn_body<false>(p, g, m, v, n4, b1, b2, eps, dyn, bad, bad2, nan_out);
+}
+__global__ EAE_NO_PK __launch_bounds__(256) void adam_dyn_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                        float* __restrict__ v, long n4, float b1, float b2, float eps,
+                                                        const float* __restrict__ dyn, const unsigned* __restrict__ bad,
+                                                        const unsigned* __restrict__ bad2, float* __restrict__ nan_out, ClipArgs ca) {
+  adam_dyn_body<true>(p, g, m, v, n4, b1, b2, eps, dyn, bad, bad2, nan_out, &ca);
+}
 __global__ EAE_NO_PK void set_dyn_kernel(float* dyn, float a, float b, float c) { dyn[0] = a; dyn[1] = b; dyn[2] = c; }
 
 int eae_launch_adam_dyn(hipStream_t st, float* p, const float* g, float* m, float* v, long long n, double b1, double b2, double eps,
-                        const float* dyn, const unsigned* bad, const unsigned* bad2, float* nan_out) {
+                        const float* dyn, const unsigned* bad, const unsigned* bad2, float* nan_out, const EaeClip* clip) {
   if (n % 4) return eae_set_error(-2, "adam: arena length must be a multiple of 4");
   long n4 = n / 4;
   int blocks = (int)((n4 + 255) / 256);
   if (blocks > 2048) blocks = 2048;
   EAE_NO_GROUP("adam_dyn_kernel");
+  if (clip) {
+    const ClipArgs ca = {clip->part, clip->nparts, clip->max_norm, clip->norm_out};
+    hipLaunchKernelGGL(adam_dyn_clip_kernel, dim3(blocks), dim3(256), 0, st, p, g, m, v, n4, (float)b1, (float)b2, (float)eps, dyn, bad, bad2, nan_out, ca);
+  } else
   hipLaunchKernelGGL(adam_dyn_kernel, dim3(blocks), dim3(256), 0, st, p, g, m, v, n4, (float)b1, (float)b2, (float)eps, dyn, bad, bad2, nan_out);
   EAE_LAUNCH_CHECK();
   return 0;
@@ -673,7 +785,7 @@ int eae_launch_adam(hipStream_t st, float* p, const float* g, float* m, float* v
 
 int eae_launch_adam_scaled(hipStream_t st, float* p, const float* g, float* m, float* v, long long n, double lr, double b1, double b2,
                            double eps, double wd, long long step, float gscale, void* zero_buf, long long zero_bytes,
-                           const unsigned* bad, const unsigned* bad2, float* nan_out, int nan_fill, int max_blocks) {
+                           const unsigned* bad, const unsigned* bad2, float* nan_out, int nan_fill, int max_blocks, const EaeClip* clip) {
   if (n % 4) return eae_set_error(-2, "adam: arena length must be a multiple of 4");
   double bc1 = 1.0 - pow(b1, (double)step), bc2 = 1.0 - pow(b2, (double)step);
   long n4 = n / 4;
@@ -683,7 +795,31 @@ int eae_launch_adam_scaled(hipStream_t st, float* p, const float* g, float* m, f
   if (eae_geo_mult > 1) blocks = blocks / eae_geo_mult > 64 ? blocks / eae_geo_mult : (blocks < 64 ? blocks : 64);      // member of a grouped step
   const AdamArgs aa = {p, g, m, v, n4, (float)b1, (float)b2, (float)(lr / bc1), (float)sqrt(bc2), (float)eps, (float)wd, gscale,
                        (uint4*)zero_buf, (long)(zero_bytes / 16), bad, bad2, nan_out, nan_fill};
+  if (clip) {
+    const AdamClipArgs ac = {aa, {clip->part, clip->nparts, clip->max_norm, clip->norm_out}};
+    eae_launch(adam_clip_kernel, adam_clip_kernel_g, dim3(blocks), dim3(256), 0, st, ac);
+  } else
   eae_launch(adam_kernel, adam_kernel_g, dim3(blocks), dim3(256), 0, st, aa);
+  EAE_LAUNCH_CHECK();
+  return 0;
+}
+
+// number of fp64 partials grad_sumsq_kernel writes for an arena of n elements: one workgroup per 4096 elements, 512 at the most
+int eae_grad_sumsq_parts(long long n) {
+  const long long b = (n + 4095) / 4096;
+  return (int)(b < 1 ? 1 : b > EAE_CLIP_MAX_PARTS ? EAE_CLIP_MAX_PARTS : b);
+}
+int eae_launch_grad_sumsq(hipStream_t st, const float* g, const long long* poff39, const long long* sizes38, double* part) {
+  GradNormArgs a = GradNormArgs();
+  a.g = g; a.part = part;
+  if (poff39[0] != 0 || poff39[38] <= 0 || poff39[38] >= (1LL << 32)) return eae_set_error(-2, "grad norm: arena of 1 .. 2^32 - 1 elements");
+  for (int s = 0; s < 38; ++s) {
+    if (sizes38[s] <= 0 || poff39[s + 1] != poff39[s] + ((sizes38[s] + 3) & ~3LL))
+      return eae_set_error(-2, "grad norm: every tensor must be followed by its padding to 4 elements and the next tensor");
+    if (sizes38[s] % 4) a.tail[a.ntail++] = (unsigned)((poff39[s] + sizes38[s]) / 4 * 4 + sizes38[s] % 4);
+  }
+  a.n4 = (unsigned)(poff39[38] / 4);
+  eae_launch(grad_sumsq_kernel, grad_sumsq_kernel_g, dim3(eae_grad_sumsq_parts(poff39[38])), dim3(256), 0, st, a);
   EAE_LAUNCH_CHECK();
   return 0;
 }

@@ -695,9 +695,18 @@ extern "C" int eae_fp8_scales(eae_ctx* c, float* out18) {
   return 0;
 }
 
+// eae_set_grad_clip: the partial sums of g^2 over the 38 tensors, on the stream of the optimizer launch and right in front of it
+int clip_prepare(eae_ctx* c, hipStream_t st, EaeClip* clip) {
+  RC(eae_launch_grad_sumsq(st, c->G, c->poff, c->psize, c->clip_part));
+  clip->part = c->clip_part; clip->nparts = eae_grad_sumsq_parts(c->poff[38]); clip->max_norm = c->clip_max; clip->norm_out = c->clip_out;
+  return 0;
+}
 int launch_adam(eae_ctx* c, hipStream_t st, long long n, float lr, float wd, float grad_scale, const unsigned* bad, const unsigned* bad2) {
+  EaeClip clip;
+  if (c->clip_on()) RC(clip_prepare(c, st, &clip));
   return eae_launch_adam_scaled(st, c->P, c->G, c->M, c->V, n, lr, 0.9, 0.999, 1e-8, wd, c->adam_step, grad_scale, c->acc_base,
-                                (long long)c->poison_off, bad ? bad : c->sigwords + 8, bad2 ? bad2 : poison_word(c), c->last_loss, c->nan_exact);
+                                (long long)c->poison_off, bad ? bad : c->sigwords + 8, bad2 ? bad2 : poison_word(c), c->last_loss, c->nan_exact,
+                                0, c->clip_on() ? &clip : nullptr);
 }
 int optimizer_step(eae_ctx* c, hipStream_t st, float lr, float wd, float grad_scale, const unsigned* bad, const unsigned* bad2) {
   if (!c || !c->P || !c->G || !c->M || !c->V) return eae_set_error(EAE_ERR_STATE, "adam: parameter, gradient and moment arenas must be bound");
@@ -782,7 +791,10 @@ extern "C" int eae_ae_train_step(eae_ctx* c, void* stream, const eae_step_io* io
   c->capturing = capture;
   int rc = forward_impl(c, st, io, true);
   if (!rc) rc = backward_impl(c, st, io);
-  if (!rc) rc = eae_launch_adam_dyn(st, c->P, c->G, c->M, c->V, c->poff[38], 0.9, 0.999, 1e-8, c->dyn, c->sigwords + 8, poison_word(c), c->last_loss);
+  EaeClip clip;
+  if (!rc && c->clip_on()) rc = clip_prepare(c, st, &clip);
+  if (!rc) rc = eae_launch_adam_dyn(st, c->P, c->G, c->M, c->V, c->poff[38], 0.9, 0.999, 1e-8, c->dyn, c->sigwords + 8, poison_word(c), c->last_loss,
+                                    c->clip_on() ? &clip : nullptr);
   c->capturing = false;
   c->packed = false;
   if (capture) {

@@ -302,11 +302,14 @@ class DPAEStepper:
     epoch phase, so every rank sees the reference's global epoch means (R.md:656-660, 679-683) and takes the same
     early-stopping decisions."""
 
-    def __init__(self, model, alpha, lr, head=True, max_batch=None, process_group=None, sync_bn=False):
+    def __init__(self, model, alpha, lr, head=True, max_batch=None, process_group=None, sync_bn=False, max_grad_norm=None):
         from .engine import engine_for
+        from .train import _apply_grad_clip
         self.model, self.alpha, self.lr, self.head = model, float(alpha), float(lr), head
         self.eng = engine_for(model, max_batch=max_batch)
         self.eng.reset_optimizer()
+        # the norm of the AVERAGED gradient, taken after the all-reduce: the replicas hold the same sums and derive the same coefficient
+        _apply_grad_clip(self.eng, max_grad_norm)
         self.device = self.eng.device
         self.pg = process_group
         self.trainer = DataParallelTrainer(self.eng, process_group, sync_bn=sync_bn)
@@ -342,11 +345,13 @@ class DPAEStepper:
 
 def fit_autoencoder_dp(train_loader, val_loader, alpha, lr, process_group=None, sync_bn=False, model=None, latent_dim=64,
                        num_classes=10, device="cuda", **kw):
-    """train.fit_autoencoder (R.md:619-697) with one process per GPU: `train_loader` / `val_loader` yield THIS rank's shard."""
+    """train.fit_autoencoder (R.md:619-697) with one process per GPU: `train_loader` / `val_loader` yield THIS rank's shard.
+    max_grad_norm= clips the norm of the averaged gradient on every replica; lr_schedule= goes to fit_autoencoder (every rank sees the
+    same all-reduced validation loss, so the replicas' schedules agree)."""
     from .modules import SupervisedAutoencoder
     from .train import fit_autoencoder, _first_batch_size
     if model is None:
         model = SupervisedAutoencoder(latent_dim=latent_dim, num_classes=num_classes).to(device)
-    st = DPAEStepper(model, alpha, lr, head=kw.pop("head", True), process_group=process_group, sync_bn=sync_bn,
+    st = DPAEStepper(model, alpha, lr, head=kw.pop("head", True), process_group=process_group, sync_bn=sync_bn, max_grad_norm=kw.pop("max_grad_norm", None),
                      max_batch=max(_first_batch_size(train_loader), _first_batch_size(val_loader)))
     return fit_autoencoder(train_loader, val_loader, alpha, lr, model=model, stepper=st, **kw)

@@ -109,6 +109,7 @@ class AEEngine:
             self.loss_last = torch.zeros(4, dtype=torch.float32, device=self.device)
             self.valid = torch.zeros((), dtype=torch.int64, device=self.device)
         self.class_weights, self.ignore_index = None, None
+        self.max_grad_norm, self.grad_norm = None, None
         # slots: (module attribute path) in named_parameters() order of SupervisedAutoencoder
         self._slots = []      # (param tensor holder, index)
         self._bn_slots = []   # (bn module, l)
@@ -205,6 +206,27 @@ class AEEngine:
         check(self.lib.eae_set_class_weights(self.ctx, _ptr(w), ign))
         self.class_weights, self.ignore_index = w, (None if ignore_index is None else int(ignore_index))
         self.valid.zero_()          # the count starts with the setting (a reset while the feature is off leaves the word alone)
+
+    @_on_device
+    def set_grad_clip(self, max_norm=None):
+        """Clip the global gradient norm (torch's clip_grad_norm_, norm_type 2) on the device in front of every optimizer launch of
+        this engine (include/eae.h eae_set_grad_clip): max_norm > 0, or float("inf") to measure the norm without ever clipping; None
+        or 0 switch the feature off.  The (total, coef) pair of the last launch stays on the device: `read_grad_norm`."""
+        m = 0.0 if max_norm is None else float(max_norm)
+        if not m >= 0.0:
+            raise ValueError(f"max_norm must be positive, inf, or None / 0 (off); got {max_norm!r}")
+        if m != 0.0 and self.grad_norm is None:
+            self.grad_norm = torch.zeros(2, dtype=torch.float32, device=self.device)
+        check(self.lib.eae_set_grad_clip(self.ctx, m, _ptr(self.grad_norm) if m != 0.0 else None))
+        self.max_grad_norm = m if m != 0.0 else None
+
+    def read_grad_norm(self):
+        """(total, coef) of the last optimizer launch with clipping on: the global L2 norm of the gradient that launch saw (after
+        grad_scale) and the factor it applied (1.0 = not clipped).  One D2H sync."""
+        if self.max_grad_norm is None:
+            raise RuntimeError("read_grad_norm: gradient clipping is off (set_grad_clip)")
+        t, c = self.grad_norm.tolist()
+        return t, c
 
     @property
     def weighted(self):
@@ -470,6 +492,10 @@ def _engine_for_locked(module, max_batch, quant):
                 eng.loss_accum.copy_(old.loss_accum)
             if old.weighted:
                 eng.set_class_weights(old.class_weights, old.ignore_index)
+            if old.max_grad_norm is not None:
+                eng.set_grad_clip(old.max_grad_norm)
+                with torch.no_grad():
+                    eng.grad_norm.copy_(old.grad_norm)
             with torch.no_grad():
                 eng.valid.copy_(old.valid)
             check(eng.lib.eae_set_adam_step(eng.ctx, old.lib.eae_get_adam_step(old.ctx)))

@@ -37,6 +37,40 @@ def _apply_class_weight(eng, class_weight, ignore_index):
         eng.set_class_weights(class_weight, ignore_index)
 
 
+def _apply_grad_clip(eng, max_grad_norm):
+    # (as for the class weights: a stepper without the argument switches off what an earlier one set on the cached engine)
+    if max_grad_norm is not None or getattr(eng, "max_grad_norm", None) is not None:
+        eng.set_grad_clip(max_grad_norm)
+
+
+def _group_grad_norms(max_grad_norm, n):
+    """GroupAEStepper's max_grad_norm as one value per member: a scalar for all, or a sequence; a group clips in every member or in
+    none, so None / 0 entries become inf (measured, never clipped) when any member clips."""
+    vals = list(max_grad_norm) if isinstance(max_grad_norm, (list, tuple)) else [max_grad_norm] * n
+    if len(vals) != n:
+        raise ValueError(f"max_grad_norm: {len(vals)} values for {n} members")
+    vals = [None if (v is None or float(v) == 0.0) else float(v) for v in vals]
+    if any(v is not None for v in vals):
+        vals = [float("inf") if v is None else v for v in vals]
+    return vals
+
+
+def _training_kw(max_grad_norm, lr_schedule):
+    """Clipping and schedule as keywords for a fit function, only when set (a custom fit_fn without them keeps working)."""
+    kw = {}
+    if max_grad_norm is not None:
+        kw["max_grad_norm"] = max_grad_norm
+    if lr_schedule is not None:
+        kw["lr_schedule"] = lr_schedule
+    return kw
+
+
+def _scheduled_lr(stepper, attr):
+    if not hasattr(stepper, attr):
+        raise RuntimeError(f"lr_schedule needs a stepper with a settable `.{attr}` (the learning rate{'s' if attr == 'lrs' else ''} its "
+                           f"train_step uses); {type(stepper).__name__} has none")
+
+
 def _criterion_kw(class_weight, ignore_index):
     """The two arguments as keywords for a fit function, only when set (a custom fit_fn without them keeps working)."""
     kw = {}
@@ -50,12 +84,13 @@ def _criterion_kw(class_weight, ignore_index):
 class AEStepper:
     """HIP-engine stepper for SupervisedAutoencoder: train_step / eval_step / read_loss."""
 
-    def __init__(self, model, alpha, lr, head=True, max_batch=None, graph=None, class_weight=None, ignore_index=None):
+    def __init__(self, model, alpha, lr, head=True, max_batch=None, graph=None, class_weight=None, ignore_index=None, max_grad_norm=None):
         from .engine import engine_for
         self.model, self.alpha, self.lr, self.head = model, float(alpha), float(lr), head
         self.eng = engine_for(model, max_batch=max_batch)
         self.eng.reset_optimizer()
         _apply_class_weight(self.eng, class_weight, ignore_index)     # CrossEntropyLoss(weight=, ignore_index=) of train and eval steps
+        _apply_grad_clip(self.eng, max_grad_norm)                     # clip_grad_norm_(max_grad_norm) in front of every optimizer launch
         if graph is not None:
             self.eng.set_graph(graph)
         self.graph = bool(graph)
@@ -90,13 +125,15 @@ class GroupAEStepper:
     include/eae.h eae_group_train_step).  `active` = indices of the members that have not stopped early; the tile geometries stay
     those of the full group, so a member's arithmetic does not depend on which other members are still training."""
 
-    def __init__(self, models, alphas, lrs, head=True, max_batch=None, class_weight=None, ignore_index=None):
+    def __init__(self, models, alphas, lrs, head=True, max_batch=None, class_weight=None, ignore_index=None, max_grad_norm=None):
         from .engine import engine_for
         self.models, self.alphas, self.lrs, self.head = list(models), [float(a) for a in alphas], [float(v) for v in lrs], head
         self.engs = [engine_for(m, max_batch=max_batch) for m in self.models]
-        for e in self.engs:
+        norms = _group_grad_norms(max_grad_norm, len(self.engs))      # a scalar or one value per member (None: inf when any member clips)
+        for e, mn in zip(self.engs, norms):
             e.reset_optimizer()
             _apply_class_weight(e, class_weight, ignore_index)        # the same criterion for every member (a group is all on or all off)
+            _apply_grad_clip(e, mn)
         self.mult = len(self.engs)
         self.device = self.engs[0].device
 
@@ -160,7 +197,7 @@ def _first_batch_size(loader, default=64):
 # ------------------------------------------------------------------------------------------------ autoencoder
 def fit_autoencoder(train_loader, val_loader, alpha, lr, latent_dim=64, num_classes=10, num_epochs=80, patience=15,
                     device="cuda", model=None, stepper=None, head=True, verbose=True, log=print, graph=None, side_streams=None,
-                    in_channels=3, class_weight=None, ignore_index=None):
+                    in_channels=3, class_weight=None, ignore_index=None, max_grad_norm=None, lr_schedule=None):
     """One (alpha, lr) configuration of the reference's AE loop (R.md:619-697).
 
     Returns dict(model, train_curve, val_curve, best_val_loss, epochs).  As in the reference, `model` holds the weights of
@@ -171,7 +208,13 @@ def fit_autoencoder(train_loader, val_loader, alpha, lr, latent_dim=64, num_clas
     (engine.AEEngine.set_class_weights) -- for an imbalanced or partly labelled scene.  class_weight = a [num_classes] vector, or
     "balanced" / "inverse_sqrt" (`scene.class_weights` over ``train_loader.labels``); with ignore_index=-1 and a
     ``SceneLoader(unlabelled=True)`` every window trains the reconstruction and the labelled ones the classifier.  They configure the
-    stepper built here (a custom `stepper` brings its own criterion)."""
+    stepper built here (a custom `stepper` brings its own criterion).
+
+    max_grad_norm: clip the global gradient norm to it in front of every optimizer launch, on the device (engine.AEEngine.set_grad_clip;
+    float("inf") only measures: `stepper.eng.read_grad_norm()`); configures the stepper built here.  lr_schedule: None, or a
+    zero-argument factory of a `schedule` object (``lambda: schedule.cosine(num_epochs)``): its lr(epoch, lr) is written to
+    ``stepper.lr`` before each epoch's train phase, its observe(val_loss) called after each validation phase, and the epoch's log
+    line carries the learning rate."""
     if model is None and stepper is None:
         model = SupervisedAutoencoder(latent_dim=latent_dim, num_classes=num_classes, in_channels=in_channels).to(device)
         if side_streams is not None:
@@ -179,11 +222,17 @@ def fit_autoencoder(train_loader, val_loader, alpha, lr, latent_dim=64, num_clas
     if stepper is None:
         stepper = AEStepper(model, alpha, lr, head=head, graph=graph,
                             max_batch=max(_first_batch_size(train_loader), _first_batch_size(val_loader)),
-                            class_weight=resolve_class_weight(class_weight, train_loader, num_classes), ignore_index=ignore_index)
+                            class_weight=resolve_class_weight(class_weight, train_loader, num_classes), ignore_index=ignore_index,
+                            max_grad_norm=max_grad_norm)
     dev = getattr(stepper, "device", None)
+    sched = lr_schedule() if lr_schedule is not None else None
+    if sched is not None:
+        _scheduled_lr(stepper, "lr")
     counter, best_val_loss = 0, float("inf")
     train_curve, val_curve = [], []
     for epoch in range(num_epochs):
+        if sched is not None:
+            stepper.lr = float(sched.lr(epoch, lr))
         if model is not None:
             model.train()
         stepper.begin()
@@ -203,8 +252,11 @@ def fit_autoencoder(train_loader, val_loader, alpha, lr, latent_dim=64, num_clas
                 stepper.eval_step(imgs, labels)
         val_loss, _ = stepper.end()
         val_curve.append(val_loss)
+        if sched is not None:
+            sched.observe(val_loss)
         if verbose:
-            log(f"[AE α={alpha} LR={lr}] Epoch {epoch + 1} | TrainLoss={train_loss:.4f} | ValLoss={val_loss:.4f}")
+            log(f"[AE α={alpha} LR={lr}] Epoch {epoch + 1} | TrainLoss={train_loss:.4f} | ValLoss={val_loss:.4f}"
+                + (f" | lr={stepper.lr:.3e}" if sched is not None else ""))
         if val_loss < best_val_loss:          # strict improvement, R.md:690
             best_val_loss = val_loss
             counter = 0
@@ -220,13 +272,15 @@ def fit_autoencoder(train_loader, val_loader, alpha, lr, latent_dim=64, num_clas
 
 def fit_autoencoder_group(train_loader, val_loader, configs, latent_dim=64, num_classes=10, num_epochs=80, patience=15,
                           device="cuda", models=None, stepper=None, head=True, verbose=True, logs=None, in_channels=3,
-                          class_weight=None, ignore_index=None):
+                          class_weight=None, ignore_index=None, max_grad_norm=None, lr_schedule=None):
     """fit_autoencoder for SEVERAL (alpha, lr) configurations at once: the members share every batch of the two loaders (one pass of
     the loader per epoch for the whole group) and each keeps its own curves, best loss and early-stopping counter exactly as the
     reference's loop does for it alone (R.md:619-697); a member that stops early drops out, the others go on.
 
     Returns one fit_autoencoder-style dict per configuration.  logs: optional list of per-configuration line lists.  in_channels: image
-    bands of the models built here (1..16).  class_weight / ignore_index: as for `fit_autoencoder`, the same criterion for every member."""
+    bands of the models built here (1..16).  class_weight / ignore_index: as for `fit_autoencoder`, the same criterion for every member.
+    max_grad_norm: a scalar or one value per configuration (GroupAEStepper).  lr_schedule: a factory as for `fit_autoencoder`; every
+    configuration gets its own instance (its own plateau state, its own learning rate in ``stepper.lrs[k]``)."""
     n = len(configs)
     if models is None and stepper is None:
         models = [SupervisedAutoencoder(latent_dim=latent_dim, num_classes=num_classes, in_channels=in_channels).to(device)
@@ -236,8 +290,12 @@ def fit_autoencoder_group(train_loader, val_loader, configs, latent_dim=64, num_
     if stepper is None:
         stepper = GroupAEStepper(models, [a for a, _ in configs], [l for _, l in configs], head=head,
                                  max_batch=max(_first_batch_size(train_loader), _first_batch_size(val_loader)),
-                                 class_weight=resolve_class_weight(class_weight, train_loader, num_classes), ignore_index=ignore_index)
+                                 class_weight=resolve_class_weight(class_weight, train_loader, num_classes), ignore_index=ignore_index,
+                                 max_grad_norm=max_grad_norm)
     dev = getattr(stepper, "device", None)
+    scheds = [lr_schedule() for _ in range(n)] if lr_schedule is not None else None
+    if scheds is not None:
+        _scheduled_lr(stepper, "lrs")
     lines = logs if logs is not None else [[] for _ in range(n)]
     counter, best = [0] * n, [float("inf")] * n
     train_curve, val_curve = [[] for _ in range(n)], [[] for _ in range(n)]
@@ -245,6 +303,9 @@ def fit_autoencoder_group(train_loader, val_loader, configs, latent_dim=64, num_
     for epoch in range(num_epochs):
         if not active:
             break
+        if scheds is not None:
+            for k in active:
+                stepper.lrs[k] = float(scheds[k].lr(epoch, configs[k][1]))
         if models is not None:
             for k in active:
                 models[k].train()
@@ -268,8 +329,11 @@ def fit_autoencoder_group(train_loader, val_loader, configs, latent_dim=64, num_
         for j, k in enumerate(active):
             alpha, lr = configs[k]
             train_curve[k].append(tr[j][0]); val_curve[k].append(va[j][0])
+            if scheds is not None:
+                scheds[k].observe(va[j][0])
             if verbose:
-                lines[k].append(f"[AE α={alpha} LR={lr}] Epoch {epoch + 1} | TrainLoss={tr[j][0]:.4f} | ValLoss={va[j][0]:.4f}")
+                lines[k].append(f"[AE α={alpha} LR={lr}] Epoch {epoch + 1} | TrainLoss={tr[j][0]:.4f} | ValLoss={va[j][0]:.4f}"
+                                + (f" | lr={stepper.lrs[k]:.3e}" if scheds is not None else ""))
             if va[j][0] < best[k]:            # strict improvement, R.md:690
                 best[k] = va[j][0]; counter[k] = 0
                 still.append(k)
@@ -385,7 +449,7 @@ def grid_search_autoencoder(train_loader, val_loader, alpha_values=(20, 25, 30, 
                             lr_values=(1e-4, 2e-4, 5e-4, 1e-3, 2e-3, 5e-3, 1e-2, 5e-2, 1e-1), latent_dim=64, num_epochs=80,
                             patience=15, out_dir="models_best", device="cuda", verbose=True, log=print, fit_fn=None, concurrent=1,
                             grouped=0, group_fit_fn=None, concurrent_groups=1, in_channels=3, class_weight=None, ignore_index=None,
-                            num_classes=10):
+                            num_classes=10, max_grad_norm=None, lr_schedule=None):
     """The reference's alpha x lr grid (R.md:599-729): trains every configuration, keeps the global best, writes
     `out_dir/AE_GLOBAL_BEST.pt` (plain state_dict) and `out_dir/validation_losses.json` (keys "alpha={a}, lr={lr}").
 
@@ -416,10 +480,14 @@ def grid_search_autoencoder(train_loader, val_loader, alpha_values=(20, 25, 30, 
 
     class_weight / ignore_index: the criterion of every configuration, as for `fit_autoencoder` (sequential, `concurrent` and `grouped`
     drivers alike); a scheme name is resolved once, from ``train_loader.labels``, for `num_classes` classes.  A custom fit_fn / group_fit_fn sees
-    them only when set.  num_classes: classes of the models built here and of the weight vector (passed on when it is not 10)."""
+    them only when set.  num_classes: classes of the models built here and of the weight vector (passed on when it is not 10).
+
+    max_grad_norm / lr_schedule: gradient clipping and the per-epoch learning-rate schedule of every configuration, as for
+    `fit_autoencoder` (lr_schedule is a factory: every configuration gets its own instance); passed on only when set."""
     os.makedirs(out_dir, exist_ok=True)
     fit_fn = fit_fn or fit_autoencoder
     crit = _criterion_kw(resolve_class_weight(class_weight, train_loader, num_classes), ignore_index)
+    crit.update(_training_kw(max_grad_norm, lr_schedule))
     if int(num_classes) != 10:
         crit["num_classes"] = int(num_classes)          # like in_channels: a custom fit function sees it only when it is not the default
     results, best = {}, {"loss": float("inf"), "info": None, "state": None, "train": None, "val": None}
@@ -534,7 +602,7 @@ def extract_features(loader, encoder):
 
 # ------------------------------------------------------------------------------------------------ MLP
 def fit_mlp(train_dl, val_dl, test_dl, lr, input_dim=64, num_classes=10, num_epochs=30, weight_decay=1e-4, device="cuda",
-            clf=None, stepper=None, alias_best=True, verbose=True, log=print, class_weight=None, ignore_index=None):
+            clf=None, stepper=None, alias_best=True, verbose=True, log=print, class_weight=None, ignore_index=None, lr_schedule=None):
     """One learning rate of the reference's MLP loop (R.md:2619-2697): Adam(lr, weight_decay), CE, accuracy tracking,
     best-validation snapshot, test accuracy.
 
@@ -544,13 +612,19 @@ def fit_mlp(train_dl, val_dl, test_dl, lr, input_dim=64, num_classes=10, num_epo
 
     class_weight / ignore_index: CrossEntropyLoss(weight=, ignore_index=) in the train, validation and test steps
     (mlp_engine.MLPEngine.set_class_weights); class_weight = a vector or a `scene.class_weights` scheme name over ``train_dl.labels``.
-    The accuracies stay correct / all samples; `stepper.eng.read_valid()` gives the labelled count of the last phase."""
+    The accuracies stay correct / all samples; `stepper.eng.read_valid()` gives the labelled count of the last phase.
+
+    lr_schedule: None or a factory of a `schedule` object, as for `fit_autoencoder` (observe() sees the validation LOSS).  The MLP's
+    one-kernel step has no gradient clipping; weight decay and dropout stay its regularisers."""
     if clf is None and stepper is None:
         clf = MLP(input_dim=input_dim, num_classes=num_classes).to(device)
     if stepper is None:
         stepper = MLPStepper(clf, lr, weight_decay, max_batch=max(256, _first_batch_size(train_dl)),
                              class_weight=resolve_class_weight(class_weight, train_dl, num_classes), ignore_index=ignore_index)
     dev = getattr(stepper, "device", None)
+    sched = lr_schedule() if lr_schedule is not None else None
+    if sched is not None:
+        _scheduled_lr(stepper, "lr")
     curves = {"train_acc": [], "val_acc": [], "train_loss": [], "val_loss": []}
     best_val_acc, best_state = 0, None
 
@@ -563,6 +637,8 @@ def fit_mlp(train_dl, val_dl, test_dl, lr, input_dim=64, num_classes=10, num_epo
         return stepper.end()
 
     for e in range(num_epochs):
+        if sched is not None:
+            stepper.lr = float(sched.lr(e, lr))
         if clf is not None:
             clf.train()
         tr_loss, tr_acc, _ = run(train_dl, True)
@@ -572,8 +648,10 @@ def fit_mlp(train_dl, val_dl, test_dl, lr, input_dim=64, num_classes=10, num_epo
             va_loss, va_acc, _ = run(val_dl, False)
         curves["train_acc"].append(tr_acc); curves["val_acc"].append(va_acc)
         curves["train_loss"].append(tr_loss); curves["val_loss"].append(va_loss)
+        if sched is not None:
+            sched.observe(va_loss)
         if verbose:
-            log(f"Epoch {e + 1}/{num_epochs} | TrainAcc={tr_acc:.3f} ValAcc={va_acc:.3f}")
+            log(f"Epoch {e + 1}/{num_epochs} | TrainAcc={tr_acc:.3f} ValAcc={va_acc:.3f}" + (f" | lr={stepper.lr:.3e}" if sched is not None else ""))
         if va_acc > best_val_acc:
             best_val_acc = va_acc
             if clf is not None:
@@ -589,15 +667,17 @@ def fit_mlp(train_dl, val_dl, test_dl, lr, input_dim=64, num_classes=10, num_epo
 
 def grid_search_mlp(train_dl, val_dl, test_dl, lr_values=(1e-6, 5e-6, 1e-5, 5e-5, 1e-4, 5e-4, 1e-3, 5e-3, 1e-2, 5e-2, 1e-1),
                     input_dim=64, num_epochs=30, out_dir="mlp_best", device="cuda", verbose=True, log=print, fit_fn=None,
-                    class_weight=None, ignore_index=None, num_classes=10):
+                    class_weight=None, ignore_index=None, num_classes=10, lr_schedule=None):
     """The reference's MLP learning-rate grid (R.md:2611-2732); saves `out_dir/MLP_GLOBAL_BEST.pt`.  class_weight / ignore_index: the
     criterion of every learning rate, as for `fit_mlp` (a custom fit_fn sees them only when set); num_classes: classes of the classifier and
-    of the weight vector (passed on when it is not 10)."""
+    of the weight vector (passed on when it is not 10).  lr_schedule: a schedule factory as for `fit_mlp`, a fresh instance per
+    learning rate (passed on only when set)."""
     os.makedirs(out_dir, exist_ok=True)
     fit_fn = fit_fn or fit_mlp
     crit = _criterion_kw(resolve_class_weight(class_weight, train_dl, num_classes), ignore_index)
     if int(num_classes) != 10:
         crit["num_classes"] = int(num_classes)          # a custom fit function sees it only when it is not the default
+    crit.update(_training_kw(None, lr_schedule))
     best = {"val": 0, "test": 0, "lr": None, "state": None, "curves": None}
     for lr in lr_values:
         if verbose:

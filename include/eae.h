@@ -124,6 +124,26 @@ int eae_set_class_weights(eae_ctx* ctx, const float* weights, long long ignore_i
  * synchronisation.  With the feature off nothing is written (every row counts: accum[3]).  Drops the captured step graphs like
  * eae_set_class_weights. */
 int eae_set_valid_counter(eae_ctx* ctx, long long* counter);
+/* Clip the global gradient norm on the device (torch.nn.utils.clip_grad_norm_ with norm_type = 2) in front of EVERY optimizer launch
+ * of the context.  max_norm == 0: off (the default: the launches and the bits of before).  max_norm > 0 or +inf: on; +inf measures the
+ * norm and never clips.  Negative or NaN: EAE_ERR_ARG.  norm_out: a caller-owned device float[2], kept until replaced, or NULL.
+ * While on, with s = the call's grad_scale (1, or 1/world in data parallel):
+ *     total = s * sqrt(sum g_i^2)   over the elements of the 38 gradient tensors -- the padding eae_ae_layout leaves between tensors
+ *                                   does not contribute (the arenas are the caller's: it need not be zero)
+ *     coef  = min(1, max_norm / (total + 1e-6))       in fp32
+ * and Adam consumes fma(g, fl32(s * coef), weight_decay * p): weight decay is added after the clip, as in torch, and with coef == 1
+ * the update is the unclipped one bit for bit.  norm_out[0] = total and norm_out[1] = coef are written by that optimizer launch, also
+ * when the update is refused.  A non-finite total makes the step DIVERGED: no update, loss_last reads NaN, and with EAE_NAN_EXACT=1 the
+ * NaN fill applies as for non-finite BatchNorm statistics (torch would write NaN gradients; this engine keeps the last finite state).
+ * The sum is taken in fp64 by one extra launch in front of the optimizer kernel: per-workgroup partials in a fixed order, added by
+ * every workgroup of the optimizer kernel in a fixed order -- no atomics, no host synchronisation, bitwise repeatable, and independent
+ * of the launch geometry (a member of a grouped step computes what it computes alone).
+ * Reached: eae_adam_step, eae_adam_step_scaled, eae_adam_step_dp, eae_ae_train_step (eager and graph replay, bitwise equal),
+ * eae_ae_dp_train_step (the norm of the all-reduced gradient: the replicas hold the same sums and derive the same coefficient, no
+ * extra collective), eae_group_train_step (each member its own max_norm and norm_out; on in every member or in none -- a mixture is
+ * EAE_ERR_ARG, a member that should not clip passes +inf), fp8 contexts.  Not reached: eae_mlp_train_step (its iteration is one
+ * kernel) and eae_op_adam.  Changing the setting drops the captured step graphs like eae_set_class_weights. */
+int eae_set_grad_clip(eae_ctx* ctx, float max_norm, float* norm_out);
 /* The host changed parameter values (load_state_dict, optimizer outside the engine): repack before next use. */
 int eae_params_changed(eae_ctx* ctx);
 int eae_set_adam_step(eae_ctx* ctx, long long step);
