@@ -57,6 +57,7 @@ struct eae_ctx {
   float *z, *dz, *dzc, *coef_f[7], *coef_b[7], *stat, *wscratch, *fcpart, *msepart, *cepart, *headpart, *lossbuf;
   long long wscratch_floats, head_stride;
   uint8_t* pack = nullptr;
+  size_t pack_bytes = 0;           // length of the pack arena (eae_debug_fill_packs)
   PackDesc* descs_dev = nullptr;
   int ndesc = 0;
   unsigned short* blkmap = nullptr;   // flattened pack launch (eae_pack_assign_blocks): workgroup -> descriptor; blk_tot workgroups

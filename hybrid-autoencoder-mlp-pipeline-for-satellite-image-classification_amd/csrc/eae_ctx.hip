@@ -173,6 +173,7 @@ extern "C" int eae_create(const eae_config* cfg, eae_ctx** out) {
   c->ndesc = (int)descs.size();
   std::vector<unsigned short> blkmap(descs.size() * 1024);
   c->blk_tot = eae_pack_assign_blocks(descs.data(), (int)descs.size(), blkmap.data(), (int)blkmap.size());
+  c->pack_bytes = poffb;
   size_t o_pack = carve(poffb), o_desc = carve(descs.size() * sizeof(PackDesc)), o_q = carve(sizeof(Fp8State)), o_bns = carve(2048 * 4 + 64);
   size_t o_bmap = carve((size_t)(c->blk_tot > 0 ? c->blk_tot : 1) * sizeof(unsigned short));
   hipError_t e = hipMalloc(&c->ws, off);
@@ -422,7 +423,44 @@ extern "C" long long eae_get_adam_step(eae_ctx* c) { return c ? c->adam_step : -
 // Test / diagnostic access to the engine's workspace tensors of the most recent step (device synchronised first; bf16 NHWC, sized
 // for the context's max_batch): kind 0 = y[idx] (idx 0..3), 1 = gy[idx], 2 = u[idx] (0..2), 3 = gu[idx], 4 = dyy[idx] (1..3), 5 = dyu[idx].
 // Copies up to `bytes` to `host_dst`, returns the number of bytes copied or a negative status.
+// kind 6 (EAE_DEBUG_PACK) = one pack of the pack arena, idx in the enumeration of include/eae.h: returns the pack's full length.
+namespace {
+// offset and length in bytes of pack `idx` inside the pack arena; 0 = found, else the status to return
+int pack_entry(eae_ctx* c, int idx, size_t* off, long long* len) {
+  const long long KP = (9 * c->CP + 31) / 32 * 32, LK = (long long)c->Lp * c->K;
+  if (idx == EAE_PACK_CONV1) { *off = c->pk_c1; *len = 32 * KP * 2; return 0; }
+  if (idx >= EAE_PACK_P1 && idx < EAE_PACK_P1 + 12) {
+    const int i = (idx - EAE_PACK_P1) % 6;
+    *off = idx < EAE_PACK_P2 ? c->pk_p1[i] : c->pk_p2[i]; *len = (long long)W3_A[i] * W3_B[i] * 9 * 2; return 0;
+  }
+  if (idx == EAE_PACK_DECONV4_JOINT) { *off = c->pk_d4j; *len = 4LL * c->CP * 128 * 2; return 0; }
+  if (idx == EAE_PACK_DECONV4_KCP) { *off = c->pk_d4k; *len = 32 * KP * 2; return 0; }
+  if (idx >= EAE_PACK_WE1 && idx <= EAE_PACK_WD2) {
+    *off = idx == EAE_PACK_WE1 ? c->pk_we1 : idx == EAE_PACK_WE2 ? c->pk_we2 : idx == EAE_PACK_WD1 ? c->pk_wd1 : c->pk_wd2; *len = LK * 2; return 0;
+  }
+  if (idx == EAE_PACK_W1P || idx == EAE_PACK_BEP) {
+    if (!c->lpad) return eae_set_error(EAE_ERR_STATE, "debug_read: w1p / bep exist only with latent padding (latent_dim % 64 != 0)");
+    *off = idx == EAE_PACK_W1P ? c->pk_w1p : c->pk_bep; *len = (idx == EAE_PACK_W1P ? 128LL : 1LL) * c->Lp * 4; return 0;
+  }
+  if (idx == EAE_PACK_BD) { *off = c->pk_bd; *len = c->K * 4; return 0; }
+  if (idx >= EAE_PACK_FP8_P1 && idx < EAE_PACK_FP8_P1 + 12) {
+    if (!c->fp8) return eae_set_error(EAE_ERR_STATE, "debug_read: the fp8 packs exist only with quant = 1");
+    const int i = (idx - EAE_PACK_FP8_P1) % 6;
+    *off = idx < EAE_PACK_FP8_P2 ? c->pk8_p1[i] : c->pk8_p2[i]; *len = (long long)W3_A[i] * W3_B[i] * 9; return 0;
+  }
+  return eae_set_error(EAE_ERR_ARG, "debug_read: no such pack");
+}
+}  // namespace
 extern "C" long long eae_debug_read(eae_ctx* c, int kind, int idx, void* host_dst, long long bytes) {
+  if (c && kind == EAE_DEBUG_PACK) {
+    size_t off = 0; long long have = 0;
+    if (int rc = pack_entry(c, idx, &off, &have)) return rc;
+    if (bytes > have) bytes = have;
+    if (bytes > 0 && !host_dst) return eae_set_error(EAE_ERR_ARG, "debug_read: null argument");
+    EAE_HIP(hipDeviceSynchronize());
+    if (bytes > 0) EAE_HIP(hipMemcpy(host_dst, c->pack + off, (size_t)bytes, hipMemcpyDeviceToHost));
+    return have;
+  }
   if (!c || !host_dst) return eae_set_error(EAE_ERR_ARG, "debug_read: null argument");
   const bool enc = kind == 0 || kind == 1 || kind == 4;
   if (kind < 0 || kind > 5 || idx < 0 || idx > (enc ? 3 : 2) || (kind == 4 && idx == 0)) return eae_set_error(EAE_ERR_ARG, "debug_read: no such tensor");
@@ -433,6 +471,15 @@ extern "C" long long eae_debug_read(eae_ctx* c, int kind, int idx, void* host_ds
   EAE_HIP(hipDeviceSynchronize());
   EAE_HIP(hipMemcpy(host_dst, p, (size_t)bytes, hipMemcpyDeviceToHost));
   return bytes;
+}
+// Test / diagnostic: set every byte of the pack arena and mark the packs stale, so that the next forward packs again (synchronises)
+extern "C" int eae_debug_fill_packs(eae_ctx* c, int byte) {
+  if (!c) return eae_set_error(EAE_ERR_ARG, "ctx is NULL");
+  EAE_HIP(hipDeviceSynchronize());
+  EAE_HIP(hipMemset(c->pack, byte & 0xff, c->pack_bytes));
+  EAE_HIP(hipDeviceSynchronize());
+  c->packed = false; invalidate_forward(c);
+  return 0;
 }
 extern "C" int eae_set_halves(eae_ctx* c, int encoder, int decoder) {
   if (!c) return eae_set_error(EAE_ERR_ARG, "set_halves: NULL context");

@@ -194,6 +194,39 @@ void* eae_side_stream(eae_ctx* ctx);
  * (idx 1..3 / 0..2).  Copies up to `bytes` into host memory; returns the bytes copied (negative: error).  No reference counterpart:
  * torch keeps these as autograd-internal buffers of loss.backward() (R.md:653). */
 long long eae_debug_read(eae_ctx* ctx, int kind, int idx, void* host_dst, long long bytes);
+/* kind EAE_DEBUG_PACK: read-only access to the pack arena, the kernel layouts of the weights (bf16 unless noted) that the pack kernel
+ * derives from the parameter arena in front of the first forward after eae_bind, eae_params_changed or an optimizer step.  idx selects
+ * one pack (CP = the padded band count 4 / 8 / 16, KP = 9 * CP rounded up to 32, P = image_h / 16 * image_w / 16, K = 256 * P,
+ * Lp = latent_dim rounded up to 64):
+ *    0       conv1 [32][KP], k = tap * CP + c
+ *    1..6    p1 of conv2, conv3, conv4, deconv1, deconv2, deconv3: [A][9][B] of the weight [A][B][3][3]
+ *    7..12   p2 of the same layers: [B][9][A]
+ *    13      deconv4 joint pack [4 * CP][128]              14  deconv4 [32][KP] (its weight [32][C][3][3] as conv1's)
+ *    15, 16  enc.fc [Lp][K'] and its transpose [K'][Lp], k' = p * 256 + c
+ *    17, 18  dec.fc [K'][Lp] and its transpose [Lp][K']
+ *    19, 20  classifier.0.weight [128][Lp] and enc.fc.bias [Lp], fp32: only with latent padding (Lp != latent_dim), else EAE_ERR_STATE
+ *    21      dec.fc bias [K'], fp32
+ *    22..27  e4m3 bytes of p1 for the six layers, 28..33 of p2: only with quant = 1, else EAE_ERR_STATE
+ * Synchronises the device, copies min(bytes, length) bytes (host_dst may be NULL when bytes is 0) and returns the pack's full length,
+ * so that a first call with bytes = 0 sizes the buffer.  The read never packs: it shows what the arena holds.
+ * eae_debug_fill_packs: set every byte of the pack arena to `byte` and mark the packs stale (synchronises); with 0xFF every bf16, fp32
+ * and e4m3 element reads as NaN until the pack kernel has written it. */
+#define EAE_DEBUG_PACK 6
+#define EAE_PACK_CONV1 0
+#define EAE_PACK_P1 1
+#define EAE_PACK_P2 7
+#define EAE_PACK_DECONV4_JOINT 13
+#define EAE_PACK_DECONV4_KCP 14
+#define EAE_PACK_WE1 15
+#define EAE_PACK_WE2 16
+#define EAE_PACK_WD1 17
+#define EAE_PACK_WD2 18
+#define EAE_PACK_W1P 19
+#define EAE_PACK_BEP 20
+#define EAE_PACK_BD 21
+#define EAE_PACK_FP8_P1 22
+#define EAE_PACK_FP8_P2 28
+int eae_debug_fill_packs(eae_ctx* ctx, int byte);
 /* The same hand-off without splitting the call (no host gap between the halves): once requested, engine-owned stream `which`
  * is, after every eae_ae_grad_step, ordered after the completion of gradient tensors 18..37 (which = 0: classifier, decoder,
  * dec.fc) or 8..17 (which = 1: enc.fc, conv4, conv3); a collective enqueued behind it overlaps the rest of that step's

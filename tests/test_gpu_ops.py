@@ -21,7 +21,7 @@ def _pack(lib, w):
     import gpu_util as G
     a, b = w.shape[0], w.shape[1]
     wd = G.f32(w)
-    buf = torch.empty(2 * a * b * 9, dtype=torch.bfloat16, device=G.dev())
+    buf = torch.full((2 * a * b * 9,), float("nan"), dtype=torch.bfloat16, device=G.dev())      # an element no workgroup writes stays NaN
     p1, p2 = buf[: a * b * 9], buf[a * b * 9:]
     from eae_amd._lib import check
     check(lib.eae_op_pack3x3(G.stream(), G.ptr(wd), a, b, G.ptr(p1), G.ptr(p2)))
@@ -29,15 +29,16 @@ def _pack(lib, w):
     return buf, p1, p2
 
 
-def test_pack3x3(lib):
+@pytest.mark.parametrize("a,b", [(64, 32), (128, 64), (256, 128), (5, 3)])       # (5, 3): A * B is no multiple of the 256-thread workgroup
+def test_pack3x3(lib, a, b):
     rng = np.random.default_rng(0)
-    w = rng.standard_normal((64, 32, 3, 3)).astype(np.float32)
+    w = rng.standard_normal((a, b, 3, 3)).astype(np.float32)
     buf, p1, p2 = _pack(lib, w)
     wq = O.bf16_round(w)
-    e1 = wq.reshape(64, 32, 9).transpose(0, 2, 1)        # [A][9][B]
-    e2 = wq.reshape(64, 32, 9).transpose(1, 2, 0)        # [B][9][A]
-    assert np.array_equal(p1.float().cpu().numpy().reshape(64, 9, 32), e1)
-    assert np.array_equal(p2.float().cpu().numpy().reshape(32, 9, 64), e2)
+    e1 = wq.reshape(a, b, 9).transpose(0, 2, 1)        # [A][9][B]
+    e2 = wq.reshape(a, b, 9).transpose(1, 2, 0)        # [B][9][A]
+    assert np.array_equal(p1.float().cpu().numpy().reshape(a, 9, b), e1)
+    assert np.array_equal(p2.float().cpu().numpy().reshape(b, 9, a), e2)
 
 
 @pytest.mark.parametrize("B,H", [(3, 32), (5, 64)])
@@ -139,11 +140,11 @@ def test_edge_conv_and_wgrad(lib):
     assert G.relmax(dw.cpu().numpy(), refw) < 1e-4
 
 
-def test_adam_kernel(lib):
+@pytest.mark.parametrize("n", [4, 4096, 2 * 1024 * 1024 + 4 * 257])      # one vector; four workgroups; past the 2048-workgroup grid: a second pass of the grid-stride loop
+def test_adam_kernel(lib, n):
     import gpu_util as G
     from eae_amd._lib import check
     rng = np.random.default_rng(5)
-    n = 4096
     p = {"w": rng.standard_normal(n).astype(np.float32)}
     st = O.new_adam_state()
     pd = G.f32(p["w"])
@@ -154,6 +155,8 @@ def test_adam_kernel(lib):
         check(lib.eae_op_adam(G.stream(), G.ptr(pd), G.ptr(G.f32(g)), G.ptr(md), G.ptr(vd), n, 1e-3, 0.9, 0.999, 1e-8, 1e-4, step))
     torch.cuda.synchronize()
     np.testing.assert_allclose(pd.cpu().numpy(), p["w"], rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(md.cpu().numpy(), st["m"]["w"], rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(vd.cpu().numpy(), st["v"]["w"], rtol=1e-5, atol=1e-6)
 
 
 def test_augment_matches_oracle(lib):
