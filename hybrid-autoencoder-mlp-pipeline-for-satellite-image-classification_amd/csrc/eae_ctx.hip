@@ -86,10 +86,10 @@ extern "C" int eae_create(const eae_config* cfg, eae_ctx** out) {
   long long stat_floats = 0;
   {
     long long t1 = (long long)eae_edge_tiles((int)Bm, c->H, c->W) * 2 * 32;
-    long long t2 = (long long)eae_conv_s2_ntiles(0, (int)Bm, c->H / 2, c->W / 2) * 2 * 64;
+    long long t2 = (long long)eae_conv_s2_ntiles(0, 32, 64, (int)Bm, c->H / 2, c->W / 2) * 2 * 64;
     long long t3 = ((Bm + 127) / 128) * c->Pn * 2 * 256;
-    long long t4 = (long long)eae_conv_s2_ntiles(1, (int)Bm, c->H / 4, c->W / 4, 64) * 2 * 32;
-    long long t5 = (long long)eae_conv_s2_ntiles(1, (int)Bm, c->H / 8, c->W / 8) * 2 * 64 + (long long)Bm * 2 * 256;
+    long long t4 = (long long)eae_conv_s2_ntiles(1, 64, 32, (int)Bm, c->H / 4, c->W / 4) * 2 * 32;
+    long long t5 = (long long)eae_conv_s2_ntiles(1, 128, 64, (int)Bm, c->H / 8, c->W / 8) * 2 * 64 + (long long)Bm * 2 * 256;
     stat_floats = std::max(std::max(t1, t2), std::max(t3, std::max(t4, t5))) + 1024;
   }
   size_t o_stat = carve(stat_floats * 4);
@@ -110,9 +110,9 @@ extern "C" int eae_create(const eae_config* cfg, eae_ctx** out) {
   size_t o_acc[7], acc_total = 0;
   {
     const int Bi = (int)Bm;
-    const int nt[7] = {eae_edge_tiles(Bi, c->H, c->W), eae_conv_s2_ntiles(0, Bi, c->H / 2, c->W / 2), eae_conv_s2_ntiles(0, Bi, c->H / 4, c->W / 4, 64),
-                       eae_conv_s2_ntiles(0, Bi, c->H / 8, c->W / 8, 128), eae_conv_s2_ntiles(1, Bi, c->H / 16, c->W / 16),
-                       eae_conv_s2_ntiles(1, Bi, c->H / 8, c->W / 8), eae_conv_s2_ntiles(1, Bi, c->H / 4, c->W / 4, 64)};
+    const int nt[7] = {eae_edge_tiles(Bi, c->H, c->W), eae_conv_s2_ntiles(0, 32, 64, Bi, c->H / 2, c->W / 2), eae_conv_s2_ntiles(0, 64, 128, Bi, c->H / 4, c->W / 4),
+                       eae_conv_s2_ntiles(0, 128, 256, Bi, c->H / 8, c->W / 8), eae_conv_s2_ntiles(1, 256, 128, Bi, c->H / 16, c->W / 16),
+                       eae_conv_s2_ntiles(1, 128, 64, Bi, c->H / 8, c->W / 8), eae_conv_s2_ntiles(1, 64, 32, Bi, c->H / 4, c->W / 4)};
     for (int l = 0; l < 7; ++l) {
       int cp = 8;
       while (cp < 64 && cp * 2 * 16 <= nt[l]) cp *= 2;        // about one accumulator set per 16 producer workgroups ...

@@ -9,7 +9,7 @@ int eae_set_error(int code, const char* msg);   // records the message for eae_l
 struct ConvArgs;
 int eae_launch_conv_s2(const ConvArgs& a, int cin, int cout, int src, int epi, hipStream_t st);
 int eae_launch_deconv_s2(const ConvArgs& a, int cin, int cout, int src, int epi, hipStream_t st);
-int eae_conv_s2_ntiles(int kind, int B, int Hin, int Win, int cin = 0);   // statistics partials per channel = workgroups along grid.x
+int eae_conv_s2_ntiles(int kind, int cin, int cout, int B, int Hin, int Win);   // statistics partials per channel of that launch (-1: no geometry)
 
 #define EAE_HIP(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) return eae_set_error(-3, hipGetErrorString(e__)); } while (0)
 #define EAE_LAUNCH_CHECK() do { hipError_t e__ = hipGetLastError(); if (e__ != hipSuccess) return eae_set_error(-3, hipGetErrorString(e__)); } while (0)

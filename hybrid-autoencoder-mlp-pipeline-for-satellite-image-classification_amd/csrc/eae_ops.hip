@@ -27,7 +27,9 @@ extern "C" int eae_op_conv_s2(void* stream, int kind, eae_src src, int cin, int 
                               const float* bias, void* out, float* stat_part, int epilogue, const void* yprev, const float* prev_coef) {
   return op_conv_s2(stream, kind, src, cin, cout, B, Hin, Win, wpack, bias, out, stat_part, epilogue, yprev, prev_coef, nullptr, nullptr);
 }
-extern "C" int eae_op_conv_s2_ntiles(int kind, int cin, int B, int Hin, int Win) { return eae_conv_s2_ntiles(kind, B, Hin, Win, cin); }
+extern "C" int eae_op_conv_s2_ntiles(int kind, int cin, int B, int Hin, int Win) {
+  return eae_conv_s2_ntiles(kind, cin, kind == 0 ? 2 * cin : cin / 2, B, Hin, Win);     // every instantiated conv layer doubles the channels, every transposed one halves them
+}
 // fp8 variant of the same op (16 x 8-tileable maps only): wpack = e4m3 bytes [cout][9][cin] of w * s_w;  qs (device) = {1/s_pixel,
 // 1/(s_pixel * s_w)};  amax (device, may be NULL) receives max |staged pixel operand| as float bits (atomicMax)
 extern "C" int eae_op_conv_s2_fp8(void* stream, int kind, eae_src src, int cin, int cout, int B, int Hin, int Win, const void* wpack_e4m3,

@@ -246,7 +246,7 @@ int run_encoder(eae_ctx* c, hipStream_t st, const float* x, int B, bool train, c
       RC(eae_launch_conv_s2(a, ENC_C[i], ENC_C[i + 1], SRC_BNRELU, EPI_FWD, st));
     }
     RC(sync_fwd(c, st, i, train));
-    RC(bn_fwd_finalize(c, st, i, eae_conv_s2_ntiles(0, B, a.Hin, a.Win, ENC_C[i]), (long long)B * (a.Hin / 2) * (a.Win / 2), train));
+    RC(bn_fwd_finalize(c, st, i, eae_conv_s2_ntiles(0, ENC_C[i], ENC_C[i + 1], B, a.Hin, a.Win), (long long)B * (a.Hin / 2) * (a.Win / 2), train));
   }
   FcNtArgs f = FcNtArgs();
   f.a = src_bnrelu(c->y[3], c->coef_f[3]);
@@ -292,7 +292,7 @@ int run_decoder_trunk(eae_ctx* c, hipStream_t st, const float* z, int B, bool tr
       RC(eae_launch_deconv_s2(a, cin[i], cin[i] / 2, i == 0 ? SRC_RAW : SRC_BNRELU, EPI_FWD, st));
     }
     RC(sync_fwd(c, st, 4 + i, train));
-    RC(bn_fwd_finalize(c, st, 4 + i, eae_conv_s2_ntiles(1, B, a.Hin, a.Win, cin[i]), (long long)B * (a.Hin * 2) * (a.Win * 2), train));
+    RC(bn_fwd_finalize(c, st, 4 + i, eae_conv_s2_ntiles(1, cin[i], cin[i] / 2, B, a.Hin, a.Win), (long long)B * (a.Hin * 2) * (a.Win * 2), train));
   }
   d = Deconv4Args();
   d.src = src_bnrelu(c->u[2], c->coef_f[6]);
@@ -477,7 +477,7 @@ int backward_impl(eae_ctx* c, hipStream_t st, const eae_step_io* io, const float
           RC(eae_launch_conv_s2(a, cb, cs, SRC_BNBWD, EPI_MASK, st));
         }
         if (c->sq_forked) RC(sq_commit(c, st));
-        RC(bn_bwd_fin(c, st, 3 + i, eae_conv_s2_ntiles(0, B, a.Hin, a.Win, cb), (long long)B * Hs * Ws));
+        RC(bn_bwd_fin(c, st, 3 + i, eae_conv_s2_ntiles(0, cb, cs, B, a.Hin, a.Win), (long long)B * Hs * Ws));
       } else {
         a.out = c->gd0;
         {
@@ -583,7 +583,7 @@ int backward_impl(eae_ctx* c, hipStream_t st, const eae_step_io* io, const float
       RC(eae_launch_deconv_s2(a, cs, cb, SRC_BNBWD, EPI_MASK, st));
     }
     if (c->sq_forked) RC(sq_commit(c, st));
-    RC(bn_bwd_fin(c, st, i - 1, eae_conv_s2_ntiles(1, B, Hs, Ws, cs), (long long)B * (Hs * 2) * (Ws * 2)));
+    RC(bn_bwd_fin(c, st, i - 1, eae_conv_s2_ntiles(1, cs, cb, B, Hs, Ws), (long long)B * (Hs * 2) * (Ws * 2)));
     if (dym) push_wgrad();
     if (i == 2 && part == 0 && c->dp_stream[1]) {     // enc.fc, conv4 and conv3 weight gradients: enqueued by the commit below
       RC(sq_commit(c, st));

@@ -108,7 +108,9 @@ def test_igemm_instantiation(lib, kind, cin, cout, hin, smode, epi, B):
     bd = G.f32(bias) if bias is not None else None
     out = torch.zeros((B, hout, hout, cout), dtype=torch.bfloat16, device=G.dev())
     nt = lib.eae_op_conv_s2_ntiles(kind, cin, B, hin, hin)
-    part = torch.zeros((2, cout, nt), dtype=torch.float32, device=G.dev())
+    # the launch and the count it reports must agree: every partial slot written (epilogues 0 and 1), nothing behind them touched
+    flat = torch.full((2 * cout * nt + 64,), float("nan"), dtype=torch.float32, device=G.dev())
+    part, guard = flat[:2 * cout * nt].view(2, cout, nt), flat[2 * cout * nt:]
     yprev_d = pcoef_d = None
     if epi == 1:
         yprev = O.bf16_round(rng.standard_normal((B, cout, hout, hout)).astype(np.float32))
@@ -120,6 +122,9 @@ def test_igemm_instantiation(lib, kind, cin, cout, hin, smode, epi, B):
     check(lib.eae_op_conv_s2(G.stream(), kind, src.src, cin, cout, B, hin, hin, G.ptr(wp), G.ptr(bd), G.ptr(out),
                              G.ptr(part) if epi != 2 else None, epi, G.ptr(yprev_d), G.ptr(pcoef_d)))
     torch.cuda.synchronize()
+    assert torch.isnan(guard).all()
+    if epi != 2:
+        assert not torch.isnan(part).any()
     got = G.from_nhwc(out)
     bc = lambda v: v[None, :, None, None]
     if epi == 0:
