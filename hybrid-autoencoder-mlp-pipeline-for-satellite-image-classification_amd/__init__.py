@@ -17,6 +17,9 @@ from .scene import scene_windows, encode_scene, classify_scene, window_grid, win
 from .scene import scene_reconstruction_error, reconstruct_scene, owned_span, border_grid, border_source  # noqa: F401
 from .scene import stage_scene_windows, window_labels, SceneLoader, window_schedule, drawable_windows  # noqa: F401
 from .scene import class_weights, scene_confusion, evaluate_scene, block_split, footprint_mask  # noqa: F401
+from . import cluster  # noqa: F401
+from .cluster import kmeans_fit, kmeans_predict, kmeans_init, cluster_scene, KMeansResult  # noqa: F401
+from .report import cluster_class_table, name_clusters  # noqa: F401
 
 __all__ = ["Encoder", "Decoder", "SupervisedAutoencoder", "MLP", "fit_autoencoder", "grid_search_autoencoder",
            "extract_features", "fit_mlp", "grid_search_mlp", "evaluate", "augment_batch", "stage_bands",
@@ -24,4 +27,5 @@ __all__ = ["Encoder", "Decoder", "SupervisedAutoencoder", "MLP", "fit_autoencode
            "classify_scene", "window_grid", "window_invalid_counts", "valid_windows", "scene_reconstruction_error",
            "reconstruct_scene", "owned_span", "border_grid", "border_source", "stage_scene_windows", "window_labels", "SceneLoader",
            "window_schedule", "drawable_windows", "class_weights", "scene_confusion", "evaluate_scene", "block_split", "footprint_mask",
-           "confusion_metrics", "classification_report_from_confusion"]
+           "confusion_metrics", "classification_report_from_confusion", "kmeans_fit", "kmeans_predict", "kmeans_init", "cluster_scene",
+           "KMeansResult", "cluster_class_table", "name_clusters"]

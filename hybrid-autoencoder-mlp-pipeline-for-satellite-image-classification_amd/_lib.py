@@ -148,6 +148,9 @@ _PROTOS = {
     "eae_scene_window_labels": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "eae_scene_confusion": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int,
                                       C.c_int, vp]),
+    "eae_kmeans_workspace_bytes": (C.c_longlong, [C.c_longlong, C.c_int, C.c_int]),
+    "eae_kmeans_assign": (C.c_int, [vp, vp, C.c_longlong, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp]),
+    "eae_kmeans_update": (C.c_int, [vp, vp, C.c_longlong, C.c_int, vp, C.c_int, vp, vp, vp, C.c_longlong]),
 }
 
 EXPORTS = tuple(_PROTOS.keys())

@@ -123,6 +123,34 @@ def confusion_metrics(cm, num_classes=None):
     }
 
 
+def cluster_class_table(cluster_labels, class_labels, k, num_classes):
+    """Contingency counts of clusters against classes: int64 [k, num_classes], entry (q, c) = the number of positions with cluster q
+    and class c.  Both arguments are integer tensors of one shape (CPU or GPU: plain torch), e.g. the cluster map of
+    `cluster.cluster_scene` and the labels of `scene.window_labels`; a pair with either label outside its range (-1: window not run,
+    unlabelled) is skipped."""
+    import torch
+    if cluster_labels.shape != class_labels.shape:
+        raise ValueError("cluster_labels and class_labels must have the same shape")
+    k, num_classes = int(k), int(num_classes)
+    if k < 1 or num_classes < 1:
+        raise ValueError("k and num_classes must be positive")
+    q = cluster_labels.reshape(-1).to(torch.int64)
+    c = class_labels.reshape(-1).to(torch.int64).to(q.device)
+    ok = (q >= 0) & (q < k) & (c >= 0) & (c < num_classes)
+    # a skipped pair goes to the extra bin k * num_classes, dropped below (no boolean indexing: nothing is read back on a GPU)
+    flat = torch.where(ok, q * num_classes + c, k * num_classes)
+    return torch.zeros(k * num_classes + 1, dtype=torch.int64, device=q.device).scatter_add_(0, flat, torch.ones_like(flat))[:-1].reshape(
+        k, num_classes)
+
+
+def name_clusters(table):
+    """The majority class of every cluster of a `cluster_class_table`: int64 [k], the lowest class on a tie, -1 for a cluster whose row
+    is empty."""
+    import torch
+    best = torch.argmax((table == table.max(dim=1, keepdim=True).values).to(torch.int64), dim=1)      # the first maximum
+    return torch.where(table.sum(dim=1) > 0, best, -1)
+
+
 def classification_report_from_confusion(cm, digits=4, num_classes=None):
     """`classification_report`'s table from a confusion matrix (`confusion_metrics`: the same matrix forms)."""
     return _report_text(confusion_metrics(cm, num_classes), digits)

@@ -65,6 +65,10 @@ on the device: the raster and an optional mask are read once, the map is looked 
 - `block_split` cuts the window grid into blocks, gives some to validation and drops the training windows that share pixels with a
   validation window (overlapping windows make a random split of window ids leak); `footprint_mask` is the pixel footprint of a list
   of windows, the ``region=`` an honest validation figure is assessed over.
+
+Clustering (no labels yet: the unsupervised map).  `cluster.cluster_scene` takes the window set as `classify_scene` does, encodes it
+with `encode_scene` and runs k-means over the latents on the device (`cluster.kmeans_fit`), or applies given centroids to another
+scene; windows that are not run hold -1 in the cluster map.
 """
 from __future__ import annotations
 

@@ -641,6 +641,31 @@ int eae_scene_window_labels(void* stream, const void* raster, int elem_bytes, in
 int eae_scene_confusion(void* stream, const void* truth, int elem_bytes, int H, int W, const long long* pred, int cH, int cW, int cell,
                         int oy, int ox, const unsigned char* mask, int K, int accumulate, long long* counts);
 
+/* ------------------------------------------------------------------ latent clustering -------------- */
+/* k-means over the latents eae_scene_encode returns (no reference counterpart: the notebook classifies with a trained MLP only).  The
+ * two halves of a Lloyd iteration, stateless: z [N][L] fp32 row-major, centroids [K][L] fp32, labels int64; 1 <= L <= 256,
+ * 1 <= K <= 256, 1 <= N < 2^31, anything else or a NULL required pointer is EAE_ERR_ARG.  Nothing synchronises the host.
+ *
+ * eae_kmeans_assign: labels[n] = argmin_k ||z_n - c_k||^2, compared as score_k = ||c_k||^2 - 2 z_n . c_k in fp32 (fp32 operands and
+ * accumulation, the f32-input MFMA: a k-ordered fma chain); the lowest k wins a tie, exactly (equal centroids give equal scores).
+ * dist (or NULL): dist[n] = max(0, score + ||z_n||^2), the fp32 squared distance to the chosen centroid.  A row that holds a NaN or an
+ * Inf gets label -1 and dist NaN.  have_prev != 0: labels is read first as the previous labelling and *changed (device, or NULL)
+ * receives the exact number of rows whose label differs; have_prev == 0: labels is written only and changed is not touched.  No N x K
+ * matrix is written, and a row's result does not depend on the launch geometry or on the other rows.
+ *
+ * eae_kmeans_update: counts[k] = the exact number of rows with label k; centroids[k] = the fp32 mean of those rows, unchanged when
+ * there are none.  Labels outside [0, K) (-1 included) are skipped, values and all.  Bitwise identical from run to run: the sums are a
+ * one-hot product on the same MFMA, per-workgroup partial sums go to `workspace` and a second kernel adds them in one fixed order and
+ * divides; no float atomics (the counts are integer adds).  workspace: device memory of at least
+ * eae_kmeans_workspace_bytes(N, L, K) bytes (host only; < 0 on bad arguments), contents irrelevant on entry; NULL or too small is
+ * EAE_ERR_ARG and nothing is launched.  A row with a non-finite value must not carry a label in [0, K): 0 x Inf is NaN, and it would
+ * reach every cluster of its workgroup's partial, not only its own (eae_kmeans_assign labels such rows -1). */
+long long eae_kmeans_workspace_bytes(long long N, int L, int K);
+int eae_kmeans_assign(void* stream, const float* z, long long N, int L, const float* centroids, int K, long long* labels, int have_prev,
+                      float* dist, long long* changed);
+int eae_kmeans_update(void* stream, const float* z, long long N, int L, const long long* labels, int K, float* centroids,
+                      long long* counts, void* workspace, long long workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif
