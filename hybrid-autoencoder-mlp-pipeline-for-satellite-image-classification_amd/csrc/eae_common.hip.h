@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include "eae_args.h"      // bf16_t, SRC_* / EPI_*, SrcDesc, BnAcc / BnFold / BnBwdFold
 #include "eae_group.h"
+#include "eae_store_policy.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;   // one MFMA A/B fragment (4 VGPRs)
 typedef __attribute__((ext_vector_type(4))) float f32x4;     // one 16x16 accumulator fragment
@@ -73,6 +74,32 @@ struct SrcRsrc {
     r0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(s.p0), 0, 0x7fffff00, 0x00020000);
     if (MODE == SRC_BNBWD) r1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(s.p1), 0, 0x7fffff00, 0x00020000);
   }
+};
+
+// Buffer resource of an OUTPUT window: stores through it take a 32-bit byte offset and a compile-time cache policy AUX
+// (eae_store_policy.h: 0 = plain, 16 = write-through), and the hardware drops a store whose offset lies outside the window, so an
+// invalid row stores at OOB_OFF instead of branching around the store.
+// The window is NOT the whole tensor (outputs may be larger than the 2 GiB a descriptor spans): the caller bases it, per workgroup and
+// with wave-uniform 64-bit arithmetic, at the first element the workgroup may write (its tile's first image / row block / slice) and
+// sizes it to what the workgroup owns, so the vector offset never exceeds one tile's extent.  `bytes` must stay below OOB_OFF.
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+struct OutRsrc {
+  __amdgpu_buffer_rsrc_t r;
+  __device__ __forceinline__ void init(void* base, long bytes) {
+    r = __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)(bytes < (long)OOB_OFF ? (bytes > 0 ? bytes : 0) : (long)OOB_OFF), 0x00020000);
+  }
+  // (the offset is always the VECTOR offset, soffset stays the constant 0: build.scan_wide_stores_sgpr_soffset)
+  template <int AUX> __device__ __forceinline__ void st16(uint32_t off, const u32x4& v) const { __builtin_amdgcn_raw_buffer_store_b128(v, r, off, 0, AUX); }
+  template <int AUX> __device__ __forceinline__ void st16(uint32_t off, const uint4& v) const { st16<AUX>(off, (u32x4){v.x, v.y, v.z, v.w}); }
+  template <int AUX> __device__ __forceinline__ void st16(uint32_t off, const float4& v) const {
+    st16<AUX>(off, (u32x4){__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)});
+  }
+  template <int AUX> __device__ __forceinline__ void st8(uint32_t off, const u32x2& v) const { __builtin_amdgcn_raw_buffer_store_b64(v, r, off, 0, AUX); }
+  template <int AUX> __device__ __forceinline__ void st4(uint32_t off, uint32_t v) const { __builtin_amdgcn_raw_buffer_store_b32(v, r, off, 0, AUX); }
+  template <int AUX> __device__ __forceinline__ void st4(uint32_t off, float v) const { st4<AUX>(off, __float_as_uint(v)); }
+  // (element-wise layouts of the weight packs only: a wave's 64 two-byte stores still cover one 128-byte line)
+  template <int AUX> __device__ __forceinline__ void st2(uint32_t off, uint16_t v) const { __builtin_amdgcn_raw_buffer_store_b16(v, r, off, 0, AUX); }
+  template <int AUX> __device__ __forceinline__ void st1(uint32_t off, uint8_t v) const { __builtin_amdgcn_raw_buffer_store_b8(v, r, off, 0, AUX); }
 };
 
 // Raw 16-byte loads of one 8-channel piece (second tensor only for BNBWD).

@@ -405,11 +405,12 @@ __device__ __forceinline__ void edge_conv_body(const EdgeArgs& a, const SceneSrc
   }
   EDGE_STAMP(18);
   __syncthreads();
+  // output window: the tile's E_TH output rows of image n
   auto rowmap = [=](int row) -> long {
     int ty = row / E_TW, tx = row % E_TW;
-    return (((long)n * Hout + (tyb * E_TH + ty)) * Wout + (txb * E_TW + tx)) * 32;
+    return (ty * Wout + (txb * E_TW + tx)) * 32;
   };
-  tile_epilogue<32, 32, EPI>(a.c, at, red, 0, blockIdx.x, 128, rowmap);
+  tile_epilogue<32, 32, EPI>(a.c, at, red, 0, blockIdx.x, 128, ((long)n * Hout + tyb * E_TH) * Wout * 32, (long)E_TH * Wout * 32, rowmap);
   EDGE_STAMP(19);
 }
 template <int SRC3, int EPI, int CP>
@@ -546,6 +547,8 @@ __device__ __forceinline__ void edge_wgrad_body(const EdgeWgradArgs& a) {
     }
   }
   // cross-wave reduction (fixed order) and store in reference layout, one 32-wide k chunk at a time
+  OutRsrc po;      // window: this block's partial
+  po.init(a.part + (size_t)blockIdx.x * (32 * 9 * C), (long)(32 * 9 * C) * 4);
 #pragma unroll
   for (int kc = 0; kc < KC; ++kc) {
     if (kc >= nkc) break;
@@ -569,7 +572,7 @@ __device__ __forceinline__ void edge_wgrad_body(const EdgeWgradArgs& a) {
       int c = jt * 16 + (l & 15);                        // D col  = side channel
       if (k < 9 * C) {
         int tap = k / C, cx = k % C;
-        a.part[(size_t)blockIdx.x * (32 * 9 * C) + c * 9 * C + cx * 9 + tap] = v;
+        po.st4<EAE_WT_EDGE>((uint32_t)(c * 9 * C + cx * 9 + tap) * 4u, v);
       }
     }
   }
@@ -681,6 +684,10 @@ __device__ __forceinline__ void deconv4_loss_body(const Deconv4Args& a) {
   for (int co = 0; co < CMAX; ++co) { gsum[co] = 0.f; bb[co] = co < C ? a.bias[co] : 0.f; }
   const size_t plane = (size_t)Hout * Wout;
   const int ox = tid & 63;
+  // output windows: the tile's 2 * E_TH output rows of image n -- of the gradient tensor [n][oy][ox][CP], and (x_hat, per band) of a plane
+  const size_t row0 = (size_t)(2 * iy0) * Wout;
+  OutRsrc og;
+  og.init(a.g4 ? a.g4 + ((size_t)n * plane + row0) * CP : (bf16_t*)nullptr, a.g4 ? (long)(2 * E_TH) * Wout * CP * 2 : 0);
   float xt[2][CMAX];                 // the target values of this thread, requested together (the stores below may not be reordered against loads)
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -692,8 +699,6 @@ __device__ __forceinline__ void deconv4_loss_body(const Deconv4Args& a) {
     const int oy = (tid >> 6) + 4 * i;
     const int pos = (oy >> 1) * E_TW + (ox >> 1), ph = (oy & 1) * 2 + (ox & 1);
     const float* sp = sl + pos * SLW + ph * C;
-    const size_t pix = (size_t)(2 * iy0 + oy) * Wout + 2 * ix0 + ox;
-    const size_t gi = (size_t)n * C * plane + pix;
     uint32_t gb[CP];
 #pragma unroll
     for (int co = 0; co < CP; ++co) gb[co] = 0u;
@@ -702,7 +707,11 @@ __device__ __forceinline__ void deconv4_loss_body(const Deconv4Args& a) {
       if (co < C) {
         const float s = sp[co] + bb[co];
         const float xh = 1.0f / (1.0f + __expf(-s));
-        if (a.x_hat) a.x_hat[gi + co * plane] = xh;
+        if (a.x_hat) {
+          OutRsrc oh;
+          oh.init(a.x_hat + ((size_t)n * C + co) * plane + row0, (long)(2 * E_TH) * Wout * 4);
+          oh.st4<EAE_WT_EDGE>((uint32_t)(oy * Wout + 2 * ix0 + ox) * 4u, xh);
+        }
         if (a.x) {
           const float d = xh - xt[i][co];
           lsum = fmaf(d, d, lsum);
@@ -714,14 +723,14 @@ __device__ __forceinline__ void deconv4_loss_body(const Deconv4Args& a) {
       }
     }
     if (a.g4) {
-      bf16_t* gp = a.g4 + ((size_t)n * plane + pix) * CP;
+      const uint32_t go = (uint32_t)((oy * Wout + 2 * ix0 + ox) * CP) * 2u;
       if constexpr (CP == 4) {
-        *reinterpret_cast<uint2*>(gp) = make_uint2(gb[0] | (gb[1] << 16), gb[2] | (gb[3] << 16));
+        og.st8<EAE_WT_EDGE>(go, (u32x2){gb[0] | (gb[1] << 16), gb[2] | (gb[3] << 16)});
       } else {
 #pragma unroll
         for (int q = 0; q < CP / 8; ++q)
-          reinterpret_cast<uint4*>(gp)[q] = make_uint4(gb[8 * q] | (gb[8 * q + 1] << 16), gb[8 * q + 2] | (gb[8 * q + 3] << 16),
-                                                       gb[8 * q + 4] | (gb[8 * q + 5] << 16), gb[8 * q + 6] | (gb[8 * q + 7] << 16));
+          og.st16<EAE_WT_EDGE>(go + 16u * q, make_uint4(gb[8 * q] | (gb[8 * q + 1] << 16), gb[8 * q + 2] | (gb[8 * q + 3] << 16),
+                                                       gb[8 * q + 4] | (gb[8 * q + 5] << 16), gb[8 * q + 6] | (gb[8 * q + 7] << 16)));
       }
     }
   }
@@ -740,7 +749,9 @@ __device__ __forceinline__ void deconv4_loss_body(const Deconv4Args& a) {
       }
     }
     __syncthreads();
-    if (tid < LPS) a.loss_part[(size_t)blockIdx.x * LPS + tid] = tid <= C ? redl[0][tid] + redl[1][tid] + redl[2][tid] + redl[3][tid] : 0.f;
+    OutRsrc ol;      // window: this block's row of the loss partials
+    ol.init(a.loss_part + (size_t)blockIdx.x * LPS, (long)LPS * 4);
+    if (tid < LPS) ol.st4<EAE_WT_EDGE>((uint32_t)tid * 4u, tid <= C ? redl[0][tid] + redl[1][tid] + redl[2][tid] + redl[3][tid] : 0.f);
   }
   EDGE_STAMP(7);
 }

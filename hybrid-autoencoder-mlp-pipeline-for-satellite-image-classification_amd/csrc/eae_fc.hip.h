@@ -172,16 +172,18 @@ __device__ __forceinline__ void fc_nt_body(const FcNtArgs& a, const int bz) {
     }
   }
   if (EPI == FCE_PARTIAL) {
-    float* out = a.part + (size_t)bz * a.M * a.N;
+    // output window: the valid rows of this M-block in the K-slice's image; a row past M lies behind the window's end (dropped)
+    OutRsrc po;
+    po.init(a.part + ((size_t)bz * a.M + m0) * a.N, (long)((a.M - m0) < 128 ? (a.M - m0) : 128) * a.N * 4);
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          int row = m0 + (wm * 4 + mi) * 16 + (lane >> 4) * 4 + r;
+          int row = (wm * 4 + mi) * 16 + (lane >> 4) * 4 + r;
           int col = n0 + wn * 32 + ni * 16 + (lane & 15);
-          if (row < a.M) out[(size_t)row * a.N + col] = acc[mi][ni][r];
+          po.st4<EAE_WT_PART>((uint32_t)(row * a.N + col) * 4u, acc[mi][ni][r]);
         }
     return;
   }
@@ -201,10 +203,12 @@ __device__ __forceinline__ void fc_nt_body(const FcNtArgs& a, const int bz) {
   __syncthreads();
   const int M = a.M, N = a.N;
   const int pcol = n0 & ~255, c0 = n0 & 255;       // pixel base column / channel offset inside the 256-channel pixel
-  auto rowmap = [=](int row) -> long { return (m0 + row) < M ? (long)(m0 + row) * N + pcol : -1; };
+  // output window: this M-block's valid rows (offsets relative to row m0)
+  auto rowmap = [=](int row) -> long { return (m0 + row) < M ? row * N + pcol : -1; };
   const int tile_id = blockIdx.x * (N / 256) + (n0 >> 8);
-  if (EPI == FCE_MASK) tile_epilogue<256, 64, EPI_MASK>(a.c, al, red, c0, tile_id, 128, rowmap);
-  else tile_epilogue<256, 64, EPI_PLAIN>(a.c, al, red, c0, tile_id, 128, rowmap);
+  const long base = (long)m0 * N, win = (long)((M - m0) < 128 ? (M - m0) : 128) * N;
+  if (EPI == FCE_MASK) tile_epilogue<256, 64, EPI_MASK>(a.c, al, red, c0, tile_id, 128, base, win, rowmap);
+  else tile_epilogue<256, 64, EPI_PLAIN>(a.c, al, red, c0, tile_id, 128, base, win, rowmap);
 }
 template <int AMODE, int EPI>
 __global__ __launch_bounds__(256) void fc_nt_kernel(FcNtArgs a) { fc_nt_body<AMODE, EPI>(a, (int)blockIdx.z); }
@@ -243,7 +247,10 @@ static __device__ __forceinline__ EAE_NO_PK void fc_splitk_reduce_body(const FcR
     if (bias) { float4 b = *reinterpret_cast<const float4*>(bias + (i * 4) % N); r.x += b.x; r.y += b.y; r.z += b.z; r.w += b.w; }
     if (addend) { float4 b = reinterpret_cast<const float4*>(addend)[i]; r.x += b.x; r.y += b.y; r.z += b.z; r.w += b.w; }
     if (addend2) { float4 b = reinterpret_cast<const float4*>(addend2)[i]; r.x += b.x; r.y += b.y; r.z += b.z; r.w += b.w; }
-    reinterpret_cast<float4*>(out)[i] = r;
+    OutRsrc oo;      // window: this block's 16 float4
+    const long b0 = (long)blockIdx.x * 16;
+    oo.init(out + b0 * 4, ((n4 - b0) < 16 ? (n4 - b0) : 16) * 16);
+    oo.st16<EAE_WT_PART>((uint32_t)lx * 16u, r);
   }
 }
 static __global__ EAE_NO_PK __launch_bounds__(256) void fc_splitk_reduce_kernel(FcReduceArgs a) { fc_splitk_reduce_body(a); }

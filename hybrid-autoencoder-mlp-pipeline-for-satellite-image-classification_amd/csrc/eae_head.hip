@@ -124,7 +124,11 @@ __device__ __forceinline__ EAE_NO_PK void head_body(const HeadArgs& a, const flo
       float se = 0.f;
       for (int c = 0; c < C; ++c) se += expf(lg[tid * HC + c] - mx);
       float lse = logf(se) + mx;
-      if (a.logits) for (int c = 0; c < C; ++c) a.logits[(size_t)r * C + c] = lg[tid * HC + c];
+      if (a.logits) {
+        OutRsrc ol;      // window: this block's valid rows
+        ol.init(a.logits + (size_t)r0 * C, (long)((a.B - r0) < HR_ ? (a.B - r0) : HR_) * C * 4);
+        for (int c = 0; c < C; ++c) ol.st4<EAE_WT_PART>((uint32_t)(tid * C + c) * 4u, lg[tid * HC + c]);
+      }
       if (a.dlogits_in) {
         for (int c = 0; c < C; ++c) lg[tid * HC + c] = a.dlogits_in[(size_t)r * C + c];
       } else if (WCE) {
@@ -162,7 +166,9 @@ __device__ __forceinline__ EAE_NO_PK void head_body(const HeadArgs& a, const flo
   if (tid == 0 && a.loss_part) {
     float s = 0.f, cr = 0.f;
     for (int r = 0; r < HR_; ++r) { s += rl[r]; cr += rl[HR_ + r]; }
-    a.loss_part[blockIdx.x * 2] = s; a.loss_part[blockIdx.x * 2 + 1] = cr;
+    OutRsrc ol;
+    ol.init(a.loss_part + (size_t)blockIdx.x * 2, 8);
+    ol.st8<EAE_WT_PART>(0u, (u32x2){__float_as_uint(s), __float_as_uint(cr)});
   }
   if (WCE && tid == 0 && blockIdx.x == 0 && valid) {      // one writer per launch; launches of a context are ordered by its streams
     const int* wn = reinterpret_cast<const int*>(wsum) + 4;
@@ -179,6 +185,8 @@ __device__ __forceinline__ EAE_NO_PK void head_body(const HeadArgs& a, const flo
   }
   __syncthreads();
   // dz_cls[r][k..k+3] = sum_j dh[r][j] * W1[j][k..k+3]
+  OutRsrc odz;      // window: this block's valid rows of dz
+  odz.init(a.dz + (size_t)r0 * L, (long)((a.B - r0) < HR_ ? (a.B - r0) : HR_) * L * 4);
   for (int i = tid; i < HR_ * L4; i += 256) {
     const int r = i / L4, k4 = i - r * L4;
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -193,10 +201,11 @@ __device__ __forceinline__ EAE_NO_PK void head_body(const HeadArgs& a, const flo
         s.x = fmaf(d[q], w[q].x, s.x); s.y = fmaf(d[q], w[q].y, s.y); s.z = fmaf(d[q], w[q].z, s.z); s.w = fmaf(d[q], w[q].w, s.w);
       }
     }
-    if (r0 + r < a.B) *reinterpret_cast<float4*>(a.dz + (size_t)(r0 + r) * L + k4 * 4) = s;
+    odz.st16<EAE_WT_PART>((uint32_t)(r * L + k4 * 4) * 4u, s);      // (a row past the batch lies behind the window's end: dropped)
   }
   // partial weight gradients of this block, arena order: W1 [128][L], b1 [128], W2 [C][128], b2 [C] (+pad)
-  float* gp = a.grad_part + (size_t)blockIdx.x * a.grad_stride;
+  OutRsrc og;      // window: this block's partial
+  og.init(a.grad_part + (size_t)blockIdx.x * a.grad_stride, (long)a.grad_stride * 4);
   for (int i = tid; i < 32 * L4; i += 256) {            // dW1: tiles of 4 j x 4 k
     const int jt = i / L4, k4 = i - jt * L4;
     float4 s[4];
@@ -213,24 +222,24 @@ __device__ __forceinline__ EAE_NO_PK void head_body(const HeadArgs& a, const flo
       }
     }
 #pragma unroll
-    for (int q = 0; q < 4; ++q) *reinterpret_cast<float4*>(gp + (size_t)(jt * 4 + q) * L + k4 * 4) = s[q];
+    for (int q = 0; q < 4; ++q) og.st16<EAE_WT_PART>((uint32_t)((jt * 4 + q) * L + k4 * 4) * 4u, s[q]);
   }
   if (tid < 128) {
     float s = 0.f;
     for (int r = 0; r < HR_; ++r) s += dh[r * HS + tid];
-    gp[128 * L + tid] = s;
+    og.st4<EAE_WT_PART>((uint32_t)(128 * L + tid) * 4u, s);
   }
   for (int i = tid; i < C * 128; i += 256) {
     int c = i >> 7, j = i & 127;
     float s = 0.f;
 #pragma unroll
     for (int r = 0; r < HR_; ++r) s = fmaf(lg[r * HC + c], relu_nan(hp[r * HS + j]), s);
-    gp[128 * L + 128 + i] = s;
+    og.st4<EAE_WT_PART>((uint32_t)(128 * L + 128 + i) * 4u, s);
   }
   if (tid < ((C + 3) & ~3)) {
     float s = 0.f;
     if (tid < C) for (int r = 0; r < HR_; ++r) s += lg[r * HC + tid];
-    gp[128 * L + 128 + C * 128 + tid] = s;
+    og.st4<EAE_WT_PART>((uint32_t)(128 * L + 128 + C * 128 + tid) * 4u, s);
   }
 }
 template <int HR_>
@@ -355,9 +364,15 @@ __device__ __forceinline__ EAE_NO_PK void loss_finalize_body(const LossFinArgs& 
     float loss = alpha * mse + cem;
     // a BatchNorm layer of this step saw non-finite statistics (bn_fold_fwd_finish): the losses read NaN like the reference's
     if (poison != nullptr && __hip_atomic_load(poison, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) loss = mse = cem = __builtin_nanf("");
-    if (db4) for (int k = 0; k < a.nch; ++k) db4[k] = (float)r[1 + k];
-    if (accum) { accum[0] += loss * B; accum[1] += mse * B; accum[2] += cem * B; accum[3] += B; accum[4] += (float)r[NS - 1]; }
-    if (last) { last[0] = loss; last[1] = mse; last[2] = cem; }
+    OutRsrc od, oa, ol;      // windows: the three small outputs (an absent one gets an empty window)
+    od.init(db4, db4 ? (long)a.nch * 4 : 0); oa.init(accum, accum ? 20 : 0); ol.init(last, last ? 12 : 0);
+    if (db4) for (int k = 0; k < a.nch; ++k) od.st4<EAE_WT_PART>((uint32_t)k * 4u, (float)r[1 + k]);
+    if (accum) {
+      const float na[5] = {accum[0] + loss * B, accum[1] + mse * B, accum[2] + cem * B, accum[3] + B, accum[4] + (float)r[NS - 1]};
+#pragma unroll
+      for (int k = 0; k < 5; ++k) oa.st4<EAE_WT_PART>((uint32_t)k * 4u, na[k]);
+    }
+    if (last) { ol.st4<EAE_WT_PART>(0u, loss); ol.st4<EAE_WT_PART>(4u, mse); ol.st4<EAE_WT_PART>(8u, cem); }
   }
 }
 template <int NQ>

@@ -75,8 +75,13 @@ struct TileEpilogue {
   static constexpr int TS = BN + 8, CPR = BN / 8, RPP = 256 / CPR;
   f32x2 s1[4], s2[4], ps[4], pt[4], pmi[4], pi[4];
   int c, r0;
-  __device__ __forceinline__ void begin(const ConvArgs& a, int n0) {
+  OutRsrc orr;            // the workgroup's window of a.out
+  const bf16_t* yprev0;   // a.yprev at the window's first element
+  // base / win: first element (wave-uniform) and number of elements of a.out this workgroup may write; rowmap offsets are relative to base
+  __device__ __forceinline__ void begin(const ConvArgs& a, int n0, long base, long win) {
     c = threadIdx.x % CPR; r0 = threadIdx.x / CPR;
+    orr.init(a.out + base, win * 2);
+    yprev0 = a.yprev + base;
 #pragma unroll
     for (int j = 0; j < 4; ++j) { s1[j] = (f32x2){0.f, 0.f}; s2[j] = (f32x2){0.f, 0.f}; }
     if (EPI == EPI_MASK) {
@@ -91,11 +96,11 @@ struct TileEpilogue {
       }
     }
   }
-  // rowmap(row) -> element offset of that output pixel (channel 0) in the NHWC tensor, or -1 if the row is invalid
+  // rowmap(row) -> element offset of that output pixel (channel 0) inside the workgroup's window, or -1 if the row is invalid
   template <class RowMap>
   __device__ __forceinline__ void rows(const ConvArgs& a, const bf16_t* tile, int n0, int nrows, RowMap rowmap) {
     for (int row = r0; row < nrows; row += RPP) {
-      long off = rowmap(row);
+      const int off = (int)rowmap(row);
       if (off < 0) continue;
       uint4 v = *reinterpret_cast<const uint4*>(tile + row * TS + c * 8);
       size_t g = (size_t)off + n0 + c * 8;
@@ -104,7 +109,7 @@ struct TileEpilogue {
 #pragma unroll
         for (int j = 0; j < 4; ++j) { f32x2 f = up2(w[j]); s1[j] += f; s2[j] += f * f; }
       } else if (EPI == EPI_MASK) {
-        uint4 yv = *reinterpret_cast<const uint4*>(a.yprev + g);
+        uint4 yv = *reinterpret_cast<const uint4*>(yprev0 + g);
         uint32_t w[4] = {v.x, v.y, v.z, v.w}, yw[4] = {yv.x, yv.y, yv.z, yv.w};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -118,7 +123,7 @@ struct TileEpilogue {
         }
         v = make_uint4(w[0], w[1], w[2], w[3]);
       }
-      *reinterpret_cast<uint4*>(a.out + g) = v;
+      orr.st16<EAE_WT_EPI>((uint32_t)g * 2u, v);
     }
   }
   // EPI_MASK: the previous layer's raw tensor at this thread's rows of one pass, requested ahead of the pass (one exposed memory
@@ -130,7 +135,7 @@ struct TileEpilogue {
     for (int it = 0; it < NIT; ++it) {
       const int row = r0 + it * RPP;
       const long off = row < nrows ? rowmap(row) : -1;
-      yv[it] = off >= 0 ? *reinterpret_cast<const uint4*>(a.yprev + (size_t)off + n0 + c * 8) : make_uint4(0, 0, 0, 0);
+      yv[it] = off >= 0 ? *reinterpret_cast<const uint4*>(yprev0 + (size_t)off + n0 + c * 8) : make_uint4(0, 0, 0, 0);
     }
   }
   template <int NIT, class RowMap>
@@ -138,10 +143,12 @@ struct TileEpilogue {
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
       const int row = r0 + it * RPP;
-      const long off = row < nrows ? rowmap(row) : -1;
+      const int off = row < nrows ? (int)rowmap(row) : -1;
+      // (the branch stays: the form without it -- an invalid row masked to zero, its store at OOB_OFF -- lets hipcc interleave all NIT
+      //  row groups and cost the mask instances 9-59 VGPRs and igemm2's 16-24 bytes of scratch)
       if (off < 0) continue;
       uint4 v = *reinterpret_cast<const uint4*>(tile + row * TS + c * 8);
-      const size_t g = (size_t)off + n0 + c * 8;
+      const uint32_t g = (uint32_t)(off + n0 + c * 8) * 2u;
       uint32_t w[4] = {v.x, v.y, v.z, v.w}, yw[4] = {yv[it].x, yv[it].y, yv[it].z, yv[it].w};
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -153,7 +160,7 @@ struct TileEpilogue {
         s1[j] += f;
         s2[j] += f * (y * pi[j] + pmi[j]);
       }
-      *reinterpret_cast<uint4*>(a.out + g) = make_uint4(w[0], w[1], w[2], w[3]);
+      orr.st16<EAE_WT_EPI>(g, make_uint4(w[0], w[1], w[2], w[3]));
     }
   }
   // deterministic reduction over the RPP row-groups that share a channel chunk; red = [2][RPP][BN] floats of LDS
@@ -180,9 +187,9 @@ struct TileEpilogue {
 // backwards-compatible free function used by the edge and FC kernels (single-pass tiles)
 template <int COUT, int BN, int EPI, class RowMap>
 __device__ __forceinline__ void tile_epilogue(const ConvArgs& a, bf16_t* tile, float* red, int n0, int tile_id, int nrows,
-                                              RowMap rowmap) {
+                                              long base, long win, RowMap rowmap) {
   TileEpilogue<COUT, BN, EPI> e;
-  e.begin(a, n0);
+  e.begin(a, n0, base, win);
   if constexpr (EPI == EPI_MASK) {      // (every caller has 128-row tiles) all rows of the previous layer's tensor requested at once
     constexpr int RPP = 256 / (BN / 8), NIT = (128 + RPP - 1) / RPP;
     uint4 yv[NIT];
@@ -368,7 +375,9 @@ __device__ __forceinline__ void igemm_body(const ConvArgs& a, const int li_given
   // (a workgroup that does not store dy -- no dy_out, or not channel block 0 -- gets a descriptor of ZERO bytes: its stores are all
   //  out of range and dropped by the hardware, so the staging loop needs no branch around them; a branch per piece cut the loop into
   //  basic blocks and cost the 128-register instances scratch)
-  __amdgpu_buffer_rsrc_t rs_dy = __builtin_amdgcn_make_buffer_rsrc(DY ? a.dy_out : (bf16_t*)nullptr, 0, wr_dy ? 0x7fffff00 : 0, 0x00020000);
+  //  (the store reuses the LOAD's offsets, so this window is the source's: the whole tensor, below 2 GiB like the loads' range)
+  OutRsrc rs_dy;
+  rs_dy.init(DY ? a.dy_out : (bf16_t*)nullptr, wr_dy ? (long)OOB_OFF : 0);
 
   // ---- patch pieces of this thread: piece q = tid + 256*i covers patch pixel q/4, channels kgs*8.. of the current
   //      K-chunk; consecutive i advance the pixel by 64 -> (img, row, col) are updated incrementally.  Byte offsets are
@@ -469,7 +478,7 @@ __device__ __forceinline__ void igemm_body(const ConvArgs& a, const int li_given
           //  192 are no inline constants -- hipcc (ROCm 7.2) omits the wait state between the store and a following VALU write of its
           //  data registers, and on gfx950 the third dword of sporadic pieces of chunks 2 and 3 then came out as the NEXT piece's
           //  intermediate: tools/debug_det.py found the stored dy differing from run to run in exactly those dwords)
-          __builtin_amdgcn_raw_buffer_store_b128((u32x4){o.x, o.y, o.z, o.w}, rs_dy, boff[i] + chunk * 64, 0, 0);
+          rs_dy.st16<0>(boff[i] + chunk * 64, o);      // plain policy: the path is off by default
       }
     }
     EAE_STAMP(8 + chunk * 4 + 1);
@@ -556,16 +565,20 @@ __device__ __forceinline__ void igemm_body(const ConvArgs& a, const int li_given
   bf16_t* tile = smem;
   float* red = reinterpret_cast<float*>(smem);     // aliases the tile: TileEpilogue::end() starts with a barrier after the last rows() pass
   TileEpilogue<COUT, BN, EPI, false> epi;
-  epi.begin(a, n0);
+  // the workgroup's output window: from the first output row of the tile in its first image to the last one in its last valid image
+  // (wave-uniform 64-bit base, 32-bit offsets inside: one tile's images, whatever the size of the tensor)
+  constexpr int OTH = (KIND == KIND_CONV) ? TH : 2 * TH;       // output rows of the tile
+  const int oyb = tyb * OTH;
+  const int nimg = (a.B - img0) < NI ? (a.B - img0) : NI;
+  epi.begin(a, n0, ((long)img0 * Hout + oyb) * Wout * COUT, ((long)(nimg - 1) * Hout + OTH) * Wout * COUT);
   auto rowmap_of = [=](int pass) {
     return [=](int row2) -> long {
       const int row = row2 / PHG, px = row2 % PHG;
       int img = row / (TH * TW), ty = (row / TW) % TH, tx = row % TW;
-      int n = img0 + img;
-      if (n >= a.B) return -1;
-      int oy = (KIND == KIND_CONV) ? tyb * TH + ty : 2 * (tyb * TH + ty) + pass;
+      if (img0 + img >= a.B) return -1;
+      int oy = (KIND == KIND_CONV) ? ty : 2 * ty + pass;       // relative to the window's first row
       int ox = (KIND == KIND_CONV) ? txb * TW + tx : 2 * (txb * TW + tx) + px;
-      return (((long)n * Hout + oy) * Wout + ox) * COUT;
+      return ((img * Hout + oy) * Wout + ox) * COUT;      // (32-bit: inside the window)
     };
   };
   constexpr int NIT = (R2 + 256 / (BN / 8) - 1) / (256 / (BN / 8));

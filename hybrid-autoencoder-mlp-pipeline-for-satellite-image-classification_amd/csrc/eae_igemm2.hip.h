@@ -250,7 +250,9 @@ __device__ __forceinline__ void igemm2_body(const ConvArgs& a, const int li_give
     constexpr int PHG = (KIND == KIND_CONV) ? 1 : 2, R2 = P * PHG;
     if (NBL > 1 && nbi > 0) __syncthreads();               // the previous block's tile / reduction scratch has been consumed
     TileEpilogue<COUT, BN, EPI, false> epi;
-    epi.begin(a, n0);
+    constexpr int OTH = (KIND == KIND_CONV) ? TH : 2 * TH;       // output rows of the tile; the window: igemm_body's
+    const int nimg = (B - img0) < NI ? (B - img0) : NI;
+    epi.begin(a, n0, ((long)img0 * Hout + tyb * OTH) * Wout * COUT, ((long)(nimg - 1) * Hout + OTH) * Wout * COUT);
     float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
     if (EPI == EPI_FWD) bv = *reinterpret_cast<const float4*>(a.bias + n0 + wn * 16 + kgl * 4);
     const bool do_stats = (EPI == EPI_FWD) && (a.stat_part != nullptr || a.bacc.acc != nullptr) && wave < BN / 16;
@@ -284,11 +286,10 @@ __device__ __forceinline__ void igemm2_body(const ConvArgs& a, const int li_give
       auto rowmap = [=](int row2) -> long {
         const int row = row2 / PHG, px = row2 % PHG;
         int img = row / (TH * TW), ty = (row / TW) % TH, tx = row % TW;
-        int n = img0 + img;
-        if (n >= B) return -1;
-        int oy = (KIND == KIND_CONV) ? tyb * TH + ty : 2 * (tyb * TH + ty) + pass;
+        if (img0 + img >= B) return -1;
+        int oy = (KIND == KIND_CONV) ? ty : 2 * ty + pass;       // relative to the window's first row
         int ox = (KIND == KIND_CONV) ? txb * TW + tx : 2 * (txb * TW + tx) + px;
-        return (((long)n * Hout + oy) * Wout + ox) * COUT;
+        return ((img * Hout + oy) * Wout + ox) * COUT;      // (32-bit: inside the window)
       };
       epi.rows(a, tile, n0, R2, rowmap);
     }

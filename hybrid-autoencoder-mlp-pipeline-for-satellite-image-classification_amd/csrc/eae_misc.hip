@@ -277,6 +277,17 @@ __device__ __forceinline__ float pack_fetch(const PackDesc& d, const float* __re
   }
 }
 
+// Destination of one pack descriptor: a window over its bytes (the stores of a workgroup are spread over the whole layout, so the
+// window is the descriptor's, not a tile's).  A destination of 2 GiB or more -- element counts go up to 2^32 -- keeps plain pointer
+// stores: `big` is uniform over the launch's workgroups of that descriptor.
+struct PackOut {
+  OutRsrc o; uint8_t* base; bool big;
+  __device__ __forceinline__ void init(uint8_t* b, size_t bytes) { base = b; big = bytes >= (size_t)OOB_OFF; o.init(b, big ? 0 : (long)bytes); }
+  __device__ __forceinline__ void put16(size_t off, const uint4& v) const { if (big) *reinterpret_cast<uint4*>(base + off) = v; else o.st16<EAE_WT_OPT>((uint32_t)off, v); }
+  __device__ __forceinline__ void put4(size_t off, float v) const { if (big) *reinterpret_cast<float*>(base + off) = v; else o.st4<EAE_WT_OPT>((uint32_t)off, v); }
+  __device__ __forceinline__ void put2(size_t off, uint16_t v) const { if (big) *reinterpret_cast<uint16_t*>(base + off) = v; else o.st2<EAE_WT_OPT>((uint32_t)off, v); }
+  __device__ __forceinline__ void put1(size_t off, uint8_t v) const { if (big) base[off] = v; else o.st1<EAE_WT_OPT>((uint32_t)off, v); }
+};
 struct PackAllArgs { const PackDesc* descs; const float* params; uint8_t* pack_base; Fp8State* q; unsigned* clear_word; const unsigned short* blkmap; int blk_begin; };
 __device__ __forceinline__ EAE_NO_PK void pack_all_body(const PackAllArgs& pa) {
   const PackDesc* __restrict__ descs = pa.descs; const float* __restrict__ params = pa.params; uint8_t* __restrict__ pack_base = pa.pack_base;
@@ -291,6 +302,8 @@ __device__ __forceinline__ EAE_NO_PK void pack_all_body(const PackAllArgs& pa) {
   if (clear_word != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *clear_word = 0u;
   const float* src = params + d.src_off;
   const unsigned count = (unsigned)d.count;
+  PackOut po;
+  po.init(pack_base + d.dst_off, (size_t)count * (d.q_layer >= 0 ? 1u : d.out_f32 ? 4u : 2u));
   if (d.q_layer >= 0) {        // e4m3 bytes = sat(w * s_w); also reports max |w| for the next step's scale (delayed scaling)
     const float sw = q->s_w[d.q_layer];
     float mx = 0.f;
@@ -298,7 +311,7 @@ __device__ __forceinline__ EAE_NO_PK void pack_all_body(const PackAllArgs& pa) {
       const float v = pack_fetch(d, src, i);
       mx = fmaxf(mx, fabsf(v));
       const float sv = fminf(fmaxf(v * sw, -448.f), 448.f);
-      pack_base[d.dst_off + i] = (uint8_t)(__builtin_amdgcn_cvt_pk_fp8_f32(sv, 0.f, 0, false) & 0xff);
+      po.put1(i, (uint8_t)(__builtin_amdgcn_cvt_pk_fp8_f32(sv, 0.f, 0, false) & 0xff));
     }
 #pragma unroll
     for (int sh = 32; sh >= 1; sh >>= 1) mx = fmaxf(mx, __shfl_xor(mx, sh));
@@ -311,7 +324,6 @@ __device__ __forceinline__ EAE_NO_PK void pack_all_body(const PackAllArgs& pa) {
     // every source line is read once (the element-per-thread mapping gathered one float per line and lane for P2)
     const unsigned A = (unsigned)d.d0, Bq = (unsigned)d.d1;
     const bool p1 = d.mode == PACK_3x3_P1;
-    bf16_t* dst = reinterpret_cast<bf16_t*>(pack_base + d.dst_off);
     for (unsigned t = bx * 256u + threadIdx.x; t < A * Bq; t += nbx * 256u) {
       const unsigned a = p1 ? t / Bq : t % A, b = p1 ? t % Bq : t / A;
       const float* sp = src + ((size_t)a * Bq + b) * 9;
@@ -320,7 +332,7 @@ __device__ __forceinline__ EAE_NO_PK void pack_all_body(const PackAllArgs& pa) {
       for (int tap = 0; tap < 9; ++tap) w[tap] = sp[tap];
 #pragma unroll
       for (int tap = 0; tap < 9; ++tap)
-        dst[p1 ? ((size_t)a * 9 + tap) * Bq + b : ((size_t)b * 9 + tap) * A + a] = (bf16_t)f2bf(w[tap]);
+        po.put2((p1 ? ((size_t)a * 9 + tap) * Bq + b : ((size_t)b * 9 + tap) * A + a) * 2, (uint16_t)f2bf(w[tap]));
     }
     return;
   }
@@ -334,7 +346,6 @@ __device__ __forceinline__ EAE_NO_PK void pack_all_body(const PackAllArgs& pa) {
     const unsigned Lp = (unsigned)d.d0, Cc = (unsigned)d.d1, P = (unsigned)d.d2, lv = (unsigned)d.lv, J = Cc * P;
     const unsigned ncc = Cc / 64, nlc = Lp / 64, ntiles = P * ncc * nlc;
     const bool vec = (lv & 3u) == 0;
-    bf16_t* dst = reinterpret_cast<bf16_t*>(pack_base + d.dst_off);
     for (unsigned tl = bx; tl < ntiles; tl += nbx) {
       const unsigned lc = tl % nlc, cch = (tl / nlc) % ncc, p = tl / (nlc * ncc);
       const unsigned c0 = cch * 64, l0 = lc * 64;
@@ -355,7 +366,7 @@ __device__ __forceinline__ EAE_NO_PK void pack_all_body(const PackAllArgs& pa) {
         uint4 o;
         o.x = pack2(tile[c8][l], tile[c8 + 1][l]); o.y = pack2(tile[c8 + 2][l], tile[c8 + 3][l]);
         o.z = pack2(tile[c8 + 4][l], tile[c8 + 5][l]); o.w = pack2(tile[c8 + 6][l], tile[c8 + 7][l]);
-        *reinterpret_cast<uint4*>(dst + (size_t)(l0 + l) * J + (size_t)p * Cc + c0 + c8) = o;
+        po.put16(((size_t)(l0 + l) * J + (size_t)p * Cc + c0 + c8) * 2, o);
       }
     }
     return;
@@ -371,7 +382,6 @@ __device__ __forceinline__ EAE_NO_PK void pack_all_body(const PackAllArgs& pa) {
     const unsigned R = (unsigned)d.d0, Cc = (unsigned)d.d1, P = (unsigned)d.d2, K = Cc * P, lv = (unsigned)d.lv;
     const bool rowmajor = d.mode == PACK_FC_ROWMAJOR_KPERM;
     const unsigned npc = P / 64, nA = rowmajor ? Cc / 64 : R / 64, nfix = rowmajor ? R : Cc, ntiles = nfix * nA * npc;
-    bf16_t* dst = reinterpret_cast<bf16_t*>(pack_base + d.dst_off);
     for (unsigned tl = bx; tl < ntiles; tl += nbx) {
       const unsigned pc = tl % npc, ac = (tl / npc) % nA, fix = tl / (npc * nA);
       const unsigned p0 = pc * 64, a0 = ac * 64;                 // a = channel (row-major form) or row (transposed form)
@@ -392,7 +402,7 @@ __device__ __forceinline__ EAE_NO_PK void pack_all_body(const PackAllArgs& pa) {
         o.z = pack2(tile[a8 + 4][pp], tile[a8 + 5][pp]); o.w = pack2(tile[a8 + 6][pp], tile[a8 + 7][pp]);
         const size_t oo = rowmajor ? (size_t)fix * K + (size_t)(p0 + pp) * Cc + a0 + a8
                                    : ((size_t)(p0 + pp) * Cc + fix) * R + a0 + a8;
-        *reinterpret_cast<uint4*>(dst + oo) = o;
+        po.put16(oo * 2, o);
       }
     }
     return;
@@ -404,7 +414,6 @@ __device__ __forceinline__ EAE_NO_PK void pack_all_body(const PackAllArgs& pa) {
     // pack_fetch reads one float per 64-byte line and lane: 16x the L2 traffic for these two packs.
     const unsigned R = (unsigned)d.d0, Cc = (unsigned)d.d1, P = (unsigned)d.d2, K = Cc * P, lv = (unsigned)d.lv;
     const bool rowmajor = d.mode == PACK_FC_ROWMAJOR_KPERM;
-    bf16_t* dst = reinterpret_cast<bf16_t*>(pack_base + d.dst_off);
     for (unsigned t = bx * 256u + threadIdx.x; t < R * Cc; t += nbx * 256u) {
       const unsigned r = rowmajor ? t / Cc : t % R, c = rowmajor ? t % Cc : t / R;
       const float* sp = src + (size_t)r * K + (size_t)c * P;
@@ -414,7 +423,7 @@ __device__ __forceinline__ EAE_NO_PK void pack_all_body(const PackAllArgs& pa) {
 #pragma unroll
         for (unsigned q = 0; q < 4; ++q) {
           const size_t o = rowmajor ? (size_t)r * K + (size_t)(p + q) * Cc + c : ((size_t)(p + q) * Cc + c) * R + r;
-          dst[o] = (bf16_t)f2bf(e[q]);
+          po.put2(o * 2, (uint16_t)f2bf(e[q]));
         }
       }
     }
@@ -424,7 +433,6 @@ __device__ __forceinline__ EAE_NO_PK void pack_all_body(const PackAllArgs& pa) {
     // dec.fc's row-permuted layout dst[p*Cc + c][l] <- src[c*P + p][l]: whole rows move, so a thread takes 8 consecutive l (two 16-byte
     // loads, one 16-byte store) instead of one float in and one bf16 out (16.7 M elements at 256x256 inputs)
     const unsigned Lp = (unsigned)d.d0, Cc = (unsigned)d.d1, P = (unsigned)d.d2, lv = (unsigned)d.lv, n8 = count / 8u, l8n = Lp / 8u;
-    bf16_t* dst = reinterpret_cast<bf16_t*>(pack_base + d.dst_off);
     for (unsigned i = bx * 256u + threadIdx.x; i < n8; i += nbx * 256u) {
       const unsigned l = (i % l8n) * 8u, j2 = i / l8n, cc = j2 % Cc, pp = j2 / Cc;
       uint4 o = make_uint4(0, 0, 0, 0);
@@ -433,14 +441,14 @@ __device__ __forceinline__ EAE_NO_PK void pack_all_body(const PackAllArgs& pa) {
         const float4 a = sp[0], b = sp[1];
         o.x = pack2(a.x, a.y); o.y = pack2(a.z, a.w); o.z = pack2(b.x, b.y); o.w = pack2(b.z, b.w);
       }
-      *reinterpret_cast<uint4*>(dst + (size_t)i * 8u) = o;
+      po.put16((size_t)i * 16u, o);
     }
     return;
   }
   for (unsigned i = bx * 256u + threadIdx.x; i < count; i += nbx * 256u) {
     float v = pack_fetch(d, src, i);
-    if (d.out_f32) reinterpret_cast<float*>(pack_base + d.dst_off)[i] = v;
-    else reinterpret_cast<bf16_t*>(pack_base + d.dst_off)[i] = (bf16_t)f2bf(v);
+    if (d.out_f32) po.put4((size_t)i * 4u, v);
+    else po.put2((size_t)i * 2u, (uint16_t)f2bf(v));
   }
 }
 __global__ EAE_NO_PK __launch_bounds__(256) void pack_all_kernel(PackAllArgs a) { pack_all_body(a); }
@@ -614,7 +622,13 @@ template <bool CLIP> __device__ __forceinline__ EAE_NO_PK void adam_body(const A
   const unsigned* __restrict__ bad = aa.bad; const unsigned* __restrict__ bad2 = aa.bad2; float* __restrict__ nan_out = aa.nan_out;
   const int nan_fill = aa.nan_fill;
   // side job: clear the BatchNorm statistics accumulators for the next step (every consumer of this step has finished)
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < zn16; i += (long)gridDim.x * 256) zbuf[i] = make_uint4(0, 0, 0, 0);
+  // (the stores of this kernel go through per-round windows of 256 pieces: the round's first piece is wave-uniform, a piece past the
+  //  end of the arena lies behind the window's end and is dropped by the hardware)
+  for (long i0 = (long)blockIdx.x * 256; i0 < zn16; i0 += (long)gridDim.x * 256) {
+    OutRsrc oz;
+    oz.init(zbuf + i0, ((zn16 - i0) < 256 ? (zn16 - i0) : 256) * 16);
+    oz.st16<EAE_WT_OPT>(threadIdx.x * 16u, make_uint4(0, 0, 0, 0));
+  }
   // a side-stream gate of this context has timed out at some point (sticky word): gradients may have been computed from stale
   // activations -- no update, and the step's loss scalars become NaN so that the run cannot go on unnoticed
   const bool stale = bad != nullptr && __hip_atomic_load(bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
@@ -638,7 +652,12 @@ template <bool CLIP> __device__ __forceinline__ EAE_NO_PK void adam_body(const A
     }
     return;
   }
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+  for (long i0 = (long)blockIdx.x * 256; i0 < n4; i0 += (long)gridDim.x * 256) {      // one window of 256 pieces per round and arena
+    const long i = i0 + threadIdx.x;
+    if (i >= n4) break;
+    const long wb = ((n4 - i0) < 256 ? (n4 - i0) : 256) * 16;
+    OutRsrc op, om, ov;
+    op.init(p + i0 * 4, wb); om.init(m + i0 * 4, wb); ov.init(v + i0 * 4, wb);
     float4 pp = reinterpret_cast<float4*>(p)[i];
     float4 gg = reinterpret_cast<const float4*>(g)[i];
     float4 mm = reinterpret_cast<float4*>(m)[i];
@@ -649,9 +668,9 @@ template <bool CLIP> __device__ __forceinline__ EAE_NO_PK void adam_body(const A
       const float wp = wd * P[j];
       adam_update(P[j], __builtin_fmaf(G[j], CLIP ? geff : gscale, wp), M[j], V[j], b1, b2, step_size, bc2_sqrt, eps);
     }
-    reinterpret_cast<float4*>(p)[i] = pp;
-    reinterpret_cast<float4*>(m)[i] = mm;
-    reinterpret_cast<float4*>(v)[i] = vv;
+    op.st16<EAE_WT_OPT>(threadIdx.x * 16u, pp);
+    om.st16<EAE_WT_OPT>(threadIdx.x * 16u, mm);
+    ov.st16<EAE_WT_OPT>(threadIdx.x * 16u, vv);
   }
 }
 __global__ EAE_NO_PK __launch_bounds__(256) void adam_kernel(AdamArgs a) { adam_body<false>(a); }
@@ -721,7 +740,12 @@ __device__ __forceinline__ EAE_NO_PK void adam_dyn_body(float* __restrict__ p, c
     return;
   }
   const float step_size = dyn[0], bc2_sqrt = dyn[1], wd = dyn[2];
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+  for (long i0 = (long)blockIdx.x * 256; i0 < n4; i0 += (long)gridDim.x * 256) {      // one window of 256 pieces per round and arena
+    const long i = i0 + threadIdx.x;
+    if (i >= n4) break;
+    const long wb = ((n4 - i0) < 256 ? (n4 - i0) : 256) * 16;
+    OutRsrc op, om, ov;
+    op.init(p + i0 * 4, wb); om.init(m + i0 * 4, wb); ov.init(v + i0 * 4, wb);
     float4 pp = reinterpret_cast<float4*>(p)[i];
     float4 gg = reinterpret_cast<const float4*>(g)[i];
     float4 mm = reinterpret_cast<float4*>(m)[i];
@@ -736,9 +760,9 @@ __device__ __forceinline__ EAE_NO_PK void adam_dyn_body(float* __restrict__ p, c
         adam_update(P[j], __builtin_fmaf(wd, P[j], G[j]), M[j], V[j], b1, b2, step_size, bc2_sqrt, eps);
       }
     }
-    reinterpret_cast<float4*>(p)[i] = pp;
-    reinterpret_cast<float4*>(m)[i] = mm;
-    reinterpret_cast<float4*>(v)[i] = vv;
+    op.st16<EAE_WT_OPT>(threadIdx.x * 16u, pp);
+    om.st16<EAE_WT_OPT>(threadIdx.x * 16u, mm);
+    ov.st16<EAE_WT_OPT>(threadIdx.x * 16u, vv);
   }
 }
 __global__ EAE_NO_PK __launch_bounds__(256) void adam_dyn_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,

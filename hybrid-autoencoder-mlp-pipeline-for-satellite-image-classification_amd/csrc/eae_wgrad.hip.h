@@ -297,11 +297,13 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& a, const int li_give
   }
   // ---- whole 1152-byte rows of the partial go out with 16-byte stores, already in the reference layout
   float* out = a.part + (size_t)slice * ((size_t)CS * CB * 9) + (size_t)cs0 * (CB * 9) + cb0 * 9;
+  OutRsrc po;      // window: the workgroup's 64 rows of the slice's image, from its first to its last float
+  po.init(out, (long)(63 * (CB * 9) + 288) * 4);
 #pragma unroll
   for (int i = 0; i < 6; ++i) {          // 64 rows x 72 float4 = 4608 = 6 x 768
     const int e = (int)threadIdx.x + i * WG_THREADS;
     const int row = e / 72, c4 = e % 72;
-    *reinterpret_cast<float4*>(out + (size_t)row * (CB * 9) + c4 * 4) = *reinterpret_cast<const float4*>(ep + row * WG_EP_STRIDE + c4 * 4);
+    po.st16<EAE_WT_PART>((uint32_t)(row * (CB * 9) + c4 * 4) * 4u, *reinterpret_cast<const float4*>(ep + row * WG_EP_STRIDE + c4 * 4));
   }
 }
 
@@ -354,9 +356,13 @@ struct ReduceArgs { const float* part; int nslices; long n4; float* out; float s
 static __device__ __forceinline__ EAE_NO_PK void reduce_slices_run(const ReduceArgs& a) {
   float* __restrict__ out = a.out;
   const float scale = a.scale;
+  const long n4 = a.n4;
   reduce_slices_body(a.part, a.nslices, a.n4, [=](long i, float4 r) {
     r.x *= scale; r.y *= scale; r.z *= scale; r.w *= scale;
-    reinterpret_cast<float4*>(out)[i] = r;
+    OutRsrc oo;      // window: this block's 16 float4
+    const long b0 = (long)blockIdx.x * 16;
+    oo.init(out + b0 * 4, ((n4 - b0) < 16 ? (n4 - b0) : 16) * 16);
+    oo.st16<EAE_WT_PART>((uint32_t)(i - b0) * 16u, r);
   });
 }
 static __global__ EAE_NO_PK __launch_bounds__(256) void reduce_slices_kernel(ReduceArgs a) { reduce_slices_run(a); }
@@ -395,7 +401,10 @@ static __device__ __forceinline__ EAE_NO_PK void reduce_slices_tall_body(const R
   if (ly == 0 && i < n4) {
     float4 r = red[0][lx];
     for (int k = 1; k < 64; ++k) { r.x += red[k][lx].x; r.y += red[k][lx].y; r.z += red[k][lx].z; r.w += red[k][lx].w; }
-    reinterpret_cast<float4*>(out)[i] = r;
+    OutRsrc oo;      // window: this block's 4 float4 (the conv1 / deconv4 weight gradients on the main stream: the EDGE family)
+    const long b0 = (long)blockIdx.x * 4;
+    oo.init(out + b0 * 4, ((n4 - b0) < 4 ? (n4 - b0) : 4) * 16);
+    oo.st16<EAE_WT_EDGE>((uint32_t)lx * 16u, r);
   }
   if (blockIdx.x == 0 && threadIdx.x == 0 && a.tail.n) gate_wait(a.tail);
 }
