@@ -2,6 +2,7 @@
 #pragma once
 #include "eae_internal.h"
 #include "eae_args.h"
+#include "eae_layers.h"
 #include <atomic>
 #include <functional>
 #include <vector>
@@ -9,13 +10,6 @@
 #define RC(x) do { int rc__ = (x); if (rc__) return rc__; } while (0)
 
 constexpr float BN_EPS = 1e-5f, BN_MOM = 0.1f;
-const int ENC_C[5] = {3, 32, 64, 128, 256};
-const int BN_C[7] = {32, 64, 128, 256, 128, 64, 32};
-const int BN_GAMMA_IDX[7] = {2, 6, 10, 14, 22, 26, 30};
-const int W3_PARAM[6] = {4, 8, 12, 20, 24, 28};      // conv2, conv3, conv4, deconv1, deconv2, deconv3
-const int W3_A[6] = {64, 128, 256, 256, 128, 64};
-const int W3_B[6] = {32, 64, 128, 128, 64, 32};
-const int PREBN_BIAS[7] = {1, 5, 9, 13, 21, 25, 29};  // biases in front of a BatchNorm: gradient is identically zero
 
 struct eae_ctx {
   eae_config cfg;
@@ -34,7 +28,7 @@ struct eae_ctx {
   Fp8State* q = nullptr;
   float* bn_save = nullptr;          // eae_fp8_calibrate: copy of the running statistics + num_batches_tracked
   long long Pn, K;                 // pixels of the 256-channel map, flattened features
-  long long poff[39], bnoff[15];
+  long long poff[T_COUNT + 1], bnoff[2 * N_BN + 1];
   float *P = nullptr, *G = nullptr, *M = nullptr, *V = nullptr, *bnrun = nullptr;
   long long* nbt = nullptr;
   long long adam_step = 0;
@@ -157,7 +151,7 @@ struct eae_ctx {
   float clip_max = 0.f;            // 0 = off; > 0 or +inf = on
   float* clip_out = nullptr;       // caller-owned device float[2] (total, coef), or nullptr
   double* clip_part = nullptr;     // workspace: EAE_CLIP_MAX_PARTS fp64 partials
-  long long psize[38];             // elements of the 38 tensors without the layout's rounding
+  long long psize[T_COUNT];        // elements of the 38 tensors without the layout's rounding
   bool clip_on() const { return clip_max != 0.f; }
   float* dyn = nullptr;            // device: lr/bc1, sqrt(bc2), weight decay of the current Adam step
   // optional in-situ timing of ONE launch site (eae_profile_enable(ctx, site); sites: include/eae.h) with HIP events on the
@@ -169,12 +163,35 @@ struct eae_ctx {
   hipEvent_t prof_ev[3 * PROF_RING] = {};     // per sample: before, after, after an EMPTY bracket (calibration)
   EaeProfHook prof_hook = {};
   long long act_elems(int lvl) const {   // per-image elements of the map after `lvl` stride-2 stages (1..4)
-    return (long long)(H >> lvl) * (W >> lvl) * ENC_C[lvl];
+    return (long long)(H >> lvl) * (W >> lvl) * enc_channels(lvl);
   }
+  // the arenas by tensor (eae_layers.h: EaeTensor); numel = the tensor's length in the arena (rounded up to 4)
+  float* param(int t) const { return P + poff[t]; }
+  float* grad(int t) const { return G + poff[t]; }
+  long long numel(int t) const { return poff[t + 1] - poff[t]; }
+  long long arena_len() const { return poff[T_COUNT]; }
+  // ... and by BatchNorm layer l (0..6)
+  float* bn_gamma(int l) const { return param(BN_LAYERS[l].gamma); }
+  float* bn_beta(int l) const { return param(BN_LAYERS[l].gamma + 1); }
+  float* bn_dgamma(int l) const { return grad(BN_LAYERS[l].gamma); }
+  float* bn_dbeta(int l) const { return grad(BN_LAYERS[l].gamma + 1); }
+  float* bn_rmean(int l) const { return bnrun + bnoff[2 * l]; }
+  float* bn_rvar(int l) const { return bnrun + bnoff[2 * l + 1]; }
+  float* prebn_dbias(int l) const { return grad(BN_LAYERS[l].bias); }
+  // the raw output of BatchNorm layer l (y[0..3], u[0..2]), its gradient and the dy tensor of its 3x3 layer
+  bf16_t* act(int l) const { return l < 4 ? y[l] : u[l - 4]; }
+  bf16_t* gact(int l) const { return l < 4 ? gy[l] : gu[l - 4]; }
+  bf16_t*& dyact(int l) { return l < 4 ? dyy[l] : dyu[l - 4]; }
 };
 
 // a forward (full, or one half alone) is no longer resident: no backward may differentiate it
 inline void invalidate_forward(eae_ctx* c) { c->fwd_ready = false; c->fwd_eval_ready = false; c->enc_ready = 0; c->dec_ready = 0; }
+// host-side state behind an optimizer launch (rc = its status).  The step's loss_last buffer is the caller's: it is written (NaN, when
+// the update is refused) by THAT launch only.  The packs are stale, and the optimizer kernel has cleared the accumulators when it ran.
+inline void after_optimizer(eae_ctx* c, int rc) {
+  c->last_loss = nullptr;
+  c->packed = false; c->acc_clean = (rc == 0); c->bwd_dirty = !c->acc_clean;
+}
 inline long long r4(long long n) { return (n + 3) & ~3LL; }
 inline unsigned* poison_word(const eae_ctx* c) { return reinterpret_cast<unsigned*>(c->acc_base + c->poison_off); }
 inline SrcDesc src_raw(const bf16_t* p) { SrcDesc s; s.p0 = p; s.p1 = nullptr; s.coef = nullptr; return s; }

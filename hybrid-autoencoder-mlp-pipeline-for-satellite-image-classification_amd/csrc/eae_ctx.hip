@@ -15,16 +15,9 @@ const unsigned EV_FLAGS = hipEventDisableTiming | (getenv("EAE_EVENT_SYSTEM_FENC
 
 namespace {
 
-int bands_of(const eae_config& c) { return c.in_channels == 0 ? 3 : c.in_channels; }     // in_channels 0 = RGB
+int bands_of(const eae_config& c) { return c.in_channels == 0 ? DEFAULT_BANDS : c.in_channels; }
 
-void param_sizes(const eae_config& c, long long* sz) {
-  const long long P = (long long)(c.image_h / 16) * (c.image_w / 16), K = 256 * P, L = c.latent_dim, C = c.num_classes;
-  const long long N = bands_of(c);      // conv1 weight [32,N,3,3], deconv4 weight [32,N,3,3] ([Cin,Cout,kh,kw]) and bias [N]
-  const long long s[38] = {32 * 9 * N, 32, 32, 32, 64 * 32 * 9, 64, 64, 64, 128 * 64 * 9, 128, 128, 128, 256 * 128 * 9, 256, 256, 256,
-                           L * K, L, K * L, K, 256 * 128 * 9, 128, 128, 128, 128 * 64 * 9, 64, 64, 64, 64 * 32 * 9, 32, 32, 32,
-                           32 * 9 * N, N, 128 * L, 128, C * 128, C};
-  for (int i = 0; i < 38; ++i) sz[i] = s[i];
-}
+void param_sizes(const eae_config& c, long long* sz) { eae_param_sizes(c.image_h, c.image_w, c.latent_dim, c.num_classes, bands_of(c), sz); }
 
 int check_cfg(const eae_config* c) {
   if (!c) return eae_set_error(EAE_ERR_ARG, "config is NULL");
@@ -44,17 +37,17 @@ int check_cfg(const eae_config* c) {
 
 extern "C" int eae_ae_layout(const eae_config* cfg, long long* param_off, long long* bn_off) {
   if (int rc = check_cfg(cfg)) return rc;
-  long long sz[38];
+  long long sz[T_COUNT];
   param_sizes(*cfg, sz);
   long long o = 0;
-  for (int i = 0; i < 38; ++i) { if (param_off) param_off[i] = o; o += r4(sz[i]); }
-  if (param_off) param_off[38] = o;
+  for (int i = 0; i < T_COUNT; ++i) { if (param_off) param_off[i] = o; o += r4(sz[i]); }
+  if (param_off) param_off[T_COUNT] = o;
   o = 0;
-  for (int l = 0; l < 7; ++l) {
-    if (bn_off) { bn_off[2 * l] = o; bn_off[2 * l + 1] = o + BN_C[l]; }
-    o += 2 * BN_C[l];
+  for (int l = 0; l < N_BN; ++l) {
+    if (bn_off) { bn_off[2 * l] = o; bn_off[2 * l + 1] = o + BN_LAYERS[l].c; }
+    o += 2 * BN_LAYERS[l].c;
   }
-  if (bn_off) bn_off[14] = o;
+  if (bn_off) bn_off[2 * N_BN] = o;
   return 0;
 }
 
@@ -65,23 +58,22 @@ extern "C" int eae_create(const eae_config* cfg, eae_ctx** out) {
   c->cfg = *cfg; c->H = cfg->image_h; c->W = cfg->image_w; c->L = cfg->latent_dim; c->C = cfg->num_classes; c->Bm = cfg->max_batch;
   c->Cin = bands_of(*cfg); c->CP = edge_cp(c->Cin);
   c->Lp = (c->L + 63) / 64 * 64; c->lpad = c->Lp != c->L;
-  c->Pn = (long long)(c->H / 16) * (c->W / 16); c->K = 256 * c->Pn;
+  c->Pn = (long long)(c->H / 16) * (c->W / 16); c->K = FC_CHANNELS * c->Pn;
   eae_ae_layout(cfg, c->poff, c->bnoff);
   param_sizes(*cfg, c->psize);
   const long long Bm = c->Bm;
   // ---- carve one allocation
   size_t off = 0;
   auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-  size_t o_y[4], o_u[3], o_gy[4], o_gu[3], o_dyy[4] = {0, 0, 0, 0}, o_dyu[3];
+  size_t o_y[4], o_u[3], o_gy[4], o_gu[3], o_dy[N_L3];
   for (int i = 0; i < 4; ++i) { o_y[i] = carve(Bm * c->act_elems(i + 1) * 2); o_gy[i] = carve(Bm * c->act_elems(i + 1) * 2); }
   for (int i = 0; i < 3; ++i) { o_u[i] = carve(Bm * c->act_elems(3 - i) * 2); o_gu[i] = carve(Bm * c->act_elems(3 - i) * 2); }
   const unsigned dy_mask_env = (getenv("EAE_DY_MASK") ? (unsigned)strtoul(getenv("EAE_DY_MASK"), nullptr, 0) : 0u) & 0x3cu;
-  for (int i = 1; i < 4; ++i) o_dyy[i] = ((dy_mask_env >> i) & 1u) ? carve(Bm * c->act_elems(i + 1) * 2) : 0;
-  for (int i = 0; i < 3; ++i) o_dyu[i] = ((dy_mask_env >> (4 + i)) & 1u) ? carve(Bm * c->act_elems(3 - i) * 2) : 0;
+  for (int j = 0; j < N_L3; ++j) o_dy[j] = ((dy_mask_env >> L3[j].dy_bit) & 1u) ? carve(Bm * c->act_elems(L3[j].out_lvl()) * 2) : 0;
   size_t o_d0 = carve(Bm * c->K * 2), o_gd0 = carve(Bm * c->K * 2), o_g4 = carve(Bm * (size_t)c->H * c->W * c->CP * 2);
   size_t o_z = carve(Bm * c->Lp * 4), o_dz = carve(Bm * c->Lp * 4), o_dzc = carve(Bm * c->Lp * 4);
   size_t o_cf[7], o_cb[7];
-  for (int l = 0; l < 7; ++l) { o_cf[l] = carve(4 * BN_C[l] * 4); o_cb[l] = carve(3 * BN_C[l] * 4); }
+  for (int l = 0; l < 7; ++l) { o_cf[l] = carve(4 * BN_LAYERS[l].c * 4); o_cb[l] = carve(3 * BN_LAYERS[l].c * 4); }
   // statistics partials: the largest producer is conv1 / deconv4-backward (tiles x 2 x 32) or enc.fc backward (mtiles*P x 2 x 256)
   long long stat_floats = 0;
   {
@@ -110,17 +102,16 @@ extern "C" int eae_create(const eae_config* cfg, eae_ctx** out) {
   size_t o_acc[7], acc_total = 0;
   {
     const int Bi = (int)Bm;
-    const int nt[7] = {eae_edge_tiles(Bi, c->H, c->W), eae_conv_s2_ntiles(0, 32, 64, Bi, c->H / 2, c->W / 2), eae_conv_s2_ntiles(0, 64, 128, Bi, c->H / 4, c->W / 4),
-                       eae_conv_s2_ntiles(0, 128, 256, Bi, c->H / 8, c->W / 8), eae_conv_s2_ntiles(1, 256, 128, Bi, c->H / 16, c->W / 16),
-                       eae_conv_s2_ntiles(1, 128, 64, Bi, c->H / 8, c->W / 8), eae_conv_s2_ntiles(1, 64, 32, Bi, c->H / 4, c->W / 4)};
+    int nt[N_BN] = {eae_edge_tiles(Bi, c->H, c->W)};      // workgroups of the layer's forward producer: conv1, then the six 3x3 layers
+    for (const Layer3& r : L3) nt[r.bn_out] = eae_conv_s2_ntiles(r.kind, r.cin, r.cout, Bi, c->H >> r.in_lvl(), c->W >> r.in_lvl());
     for (int l = 0; l < 7; ++l) {
       int cp = 8;
       while (cp < 64 && cp * 2 * 16 <= nt[l]) cp *= 2;        // about one accumulator set per 16 producer workgroups ...
-      while (cp > BN_FOLD_K * (256 / BN_C[l])) cp /= 2;       // ... but at most BN_FOLD_K sets per consumer thread
+      while (cp > BN_FOLD_K * (256 / BN_LAYERS[l].c)) cp /= 2;       // ... but at most BN_FOLD_K sets per consumer thread
       if (const char* e = getenv("EAE_ACC_COPIES_MAX")) { int mx = atoi(e); while (mx >= 1 && cp > mx) cp /= 2; }
       c->acc_copies[l] = cp;
       o_acc[l] = acc_total;
-      acc_total += (size_t)cp * 2 * BN_C[l] * 8 + (size_t)BN_C[l] * 8;        // + the layer's [C] sticky non-finite flag words (BnAcc::flag)
+      acc_total += (size_t)cp * 2 * BN_LAYERS[l].c * 8 + (size_t)BN_LAYERS[l].c * 8;        // + the layer's [C] sticky non-finite flag words (BnAcc::flag)
     }
   }
   size_t o_accb = carve(2 * acc_total + 32);  // forward accumulators, then the backward ones (cleared together)   // conv1 weight gradient (last kernel of the backward, runs on the main stream)
@@ -146,30 +137,31 @@ extern "C" int eae_create(const eae_config* cfg, eae_ctx** out) {
     descs.push_back(d);
   };
   const int KP = (9 * c->CP + 31) / 32 * 32;      // conv1 / deconv4-backward pack [32][KP] (edge_conv_kernel)
-  c->pk_c1 = pcarve(32 * KP * 2); add(c->poff[0], c->pk_c1, 32 * KP, PACK_KCP, 32, c->Cin, c->CP, 0);
-  for (int i = 0; i < 6; ++i) {
-    long long n = (long long)W3_A[i] * W3_B[i] * 9;
-    c->pk_p1[i] = pcarve(n * 2); add(c->poff[W3_PARAM[i]], c->pk_p1[i], n, PACK_3x3_P1, W3_A[i], W3_B[i], 0, 0);
-    c->pk_p2[i] = pcarve(n * 2); add(c->poff[W3_PARAM[i]], c->pk_p2[i], n, PACK_3x3_P2, W3_A[i], W3_B[i], 0, 0);
+  c->pk_c1 = pcarve(32 * KP * 2); add(c->poff[T_CONV1_W], c->pk_c1, 32 * KP, PACK_KCP, 32, c->Cin, c->CP, 0);
+  for (int i = 0; i < N_L3; ++i) {
+    const int cs = L3[i].cs(), cb = L3[i].cb();      // the weight is [cs][cb][3][3]
+    const long long n = (long long)cs * cb * 9, src = c->poff[L3[i].w];
+    c->pk_p1[i] = pcarve(n * 2); add(src, c->pk_p1[i], n, PACK_3x3_P1, cs, cb, 0, 0);
+    c->pk_p2[i] = pcarve(n * 2); add(src, c->pk_p2[i], n, PACK_3x3_P2, cs, cb, 0, 0);
     if (cfg->quant == 1) {
-      c->pk8_p1[i] = pcarve(n); add(c->poff[W3_PARAM[i]], c->pk8_p1[i], n, PACK_3x3_P1, W3_A[i], W3_B[i], 0, 0); descs.back().q_layer = i;
-      c->pk8_p2[i] = pcarve(n); add(c->poff[W3_PARAM[i]], c->pk8_p2[i], n, PACK_3x3_P2, W3_A[i], W3_B[i], 0, 0); descs.back().q_layer = i;
+      c->pk8_p1[i] = pcarve(n); add(src, c->pk8_p1[i], n, PACK_3x3_P1, cs, cb, 0, 0); descs.back().q_layer = i;
+      c->pk8_p2[i] = pcarve(n); add(src, c->pk8_p2[i], n, PACK_3x3_P2, cs, cb, 0, 0); descs.back().q_layer = i;
     }
   }
   c->fp8 = cfg->quant == 1;
-  c->pk_d4j = pcarve(4 * c->CP * 128 * 2); add(c->poff[32], c->pk_d4j, 4 * c->CP * 128, PACK_DECONV4_JOINT, 0, c->Cin, 0, 0);
-  c->pk_d4k = pcarve(32 * KP * 2); add(c->poff[32], c->pk_d4k, 32 * KP, PACK_KCP, 32, c->Cin, c->CP, 0);
+  c->pk_d4j = pcarve(4 * c->CP * 128 * 2); add(c->poff[T_DECONV4_W], c->pk_d4j, 4 * c->CP * 128, PACK_DECONV4_JOINT, 0, c->Cin, 0, 0);
+  c->pk_d4k = pcarve(32 * KP * 2); add(c->poff[T_DECONV4_W], c->pk_d4k, 32 * KP, PACK_KCP, 32, c->Cin, c->CP, 0);
   const long long LK = c->Lp * c->K;      // d0 = padded latent width, lv = the real one (rows / columns beyond it are zero)
-  c->pk_we1 = pcarve(LK * 2); add(c->poff[16], c->pk_we1, LK, PACK_FC_ROWMAJOR_KPERM, c->Lp, 256, (int)c->Pn, 0);
-  c->pk_we2 = pcarve(LK * 2); add(c->poff[16], c->pk_we2, LK, PACK_FC_TRANS_KPERM, c->Lp, 256, (int)c->Pn, 0);
-  c->pk_wd1 = pcarve(LK * 2); add(c->poff[18], c->pk_wd1, LK, PACK_FC_ROWPERM, c->Lp, 256, (int)c->Pn, 0);
-  c->pk_wd2 = pcarve(LK * 2); add(c->poff[18], c->pk_wd2, LK, PACK_FC_ROWPERM_TRANS, c->Lp, 256, (int)c->Pn, 0);
+  c->pk_we1 = pcarve(LK * 2); add(c->poff[T_ENCFC_W], c->pk_we1, LK, PACK_FC_ROWMAJOR_KPERM, c->Lp, 256, (int)c->Pn, 0);
+  c->pk_we2 = pcarve(LK * 2); add(c->poff[T_ENCFC_W], c->pk_we2, LK, PACK_FC_TRANS_KPERM, c->Lp, 256, (int)c->Pn, 0);
+  c->pk_wd1 = pcarve(LK * 2); add(c->poff[T_DECFC_W], c->pk_wd1, LK, PACK_FC_ROWPERM, c->Lp, 256, (int)c->Pn, 0);
+  c->pk_wd2 = pcarve(LK * 2); add(c->poff[T_DECFC_W], c->pk_wd2, LK, PACK_FC_ROWPERM_TRANS, c->Lp, 256, (int)c->Pn, 0);
   for (int k = 0; k < 4; ++k) descs[descs.size() - 1 - k].lv = c->L;
   if (c->lpad) {
-    c->pk_w1p = pcarve(128LL * c->Lp * 4); add(c->poff[34], c->pk_w1p, 128LL * c->Lp, PACK_PAD_COLS, c->Lp, 0, 0, 1); descs.back().lv = c->L;
-    c->pk_bep = pcarve(c->Lp * 4); add(c->poff[17], c->pk_bep, c->Lp, PACK_PAD_COLS, c->Lp, 0, 0, 1); descs.back().lv = c->L;
+    c->pk_w1p = pcarve(128LL * c->Lp * 4); add(c->poff[T_CLS0_W], c->pk_w1p, 128LL * c->Lp, PACK_PAD_COLS, c->Lp, 0, 0, 1); descs.back().lv = c->L;
+    c->pk_bep = pcarve(c->Lp * 4); add(c->poff[T_ENCFC_B], c->pk_bep, c->Lp, PACK_PAD_COLS, c->Lp, 0, 0, 1); descs.back().lv = c->L;
   }
-  c->pk_bd = pcarve(c->K * 4); add(c->poff[19], c->pk_bd, c->K, PACK_FC_ROWPERM, 1, 256, (int)c->Pn, 1);
+  c->pk_bd = pcarve(c->K * 4); add(c->poff[T_DECFC_B], c->pk_bd, c->K, PACK_FC_ROWPERM, 1, 256, (int)c->Pn, 1);
   c->ndesc = (int)descs.size();
   std::vector<unsigned short> blkmap(descs.size() * 1024);
   c->blk_tot = eae_pack_assign_blocks(descs.data(), (int)descs.size(), blkmap.data(), (int)blkmap.size());
@@ -180,12 +172,9 @@ extern "C" int eae_create(const eae_config* cfg, eae_ctx** out) {
   if (e != hipSuccess) { delete c; return eae_set_error(EAE_ERR_HIP, hipGetErrorString(e)); }
   uint8_t* b = static_cast<uint8_t*>(c->ws);
   for (int i = 0; i < 4; ++i) { c->y[i] = (bf16_t*)(b + o_y[i]); c->gy[i] = (bf16_t*)(b + o_gy[i]); }
-  for (int i = 0; i < 3; ++i) {
-    c->u[i] = (bf16_t*)(b + o_u[i]); c->gu[i] = (bf16_t*)(b + o_gu[i]);
-    c->dyu[i] = ((dy_mask_env >> (4 + i)) & 1u) ? (bf16_t*)(b + o_dyu[i]) : nullptr;
-  }
+  for (int i = 0; i < 3; ++i) { c->u[i] = (bf16_t*)(b + o_u[i]); c->gu[i] = (bf16_t*)(b + o_gu[i]); }
   c->dyy[0] = nullptr;
-  for (int i = 1; i < 4; ++i) c->dyy[i] = ((dy_mask_env >> i) & 1u) ? (bf16_t*)(b + o_dyy[i]) : nullptr;
+  for (int j = 0; j < N_L3; ++j) c->dyact(L3[j].bn_out) = ((dy_mask_env >> L3[j].dy_bit) & 1u) ? (bf16_t*)(b + o_dy[j]) : nullptr;
   c->d0 = (bf16_t*)(b + o_d0); c->gd0 = (bf16_t*)(b + o_gd0); c->g4 = (bf16_t*)(b + o_g4);
   c->z = (float*)(b + o_z); c->dz = (float*)(b + o_dz); c->dzc = (float*)(b + o_dzc);
   if (c->lpad) {
@@ -325,8 +314,7 @@ extern "C" int eae_bind(eae_ctx* c, float* params, float* grads, float* adam_m, 
   c->P = params; c->G = grads; c->M = adam_m; c->V = adam_v; c->bnrun = bn_running; c->nbt = bn_nbt;
   c->packed = false; invalidate_forward(c);
   if (grads)
-    for (int k = 0; k < 7; ++k)
-      EAE_HIP(hipMemset(grads + c->poff[PREBN_BIAS[k]], 0, (size_t)(c->poff[PREBN_BIAS[k] + 1] - c->poff[PREBN_BIAS[k]]) * 4));
+    for (int l = 0; l < N_BN; ++l) EAE_HIP(hipMemset(c->prebn_dbias(l), 0, (size_t)c->numel(BN_LAYERS[l].bias) * 4));
   return 0;
 }
 // Synchronized BatchNorm (new work, SURVEY.md 8e "Equivalence to test": R ranks x B/R with SyncBN == 1 rank x B).
@@ -431,7 +419,7 @@ int pack_entry(eae_ctx* c, int idx, size_t* off, long long* len) {
   if (idx == EAE_PACK_CONV1) { *off = c->pk_c1; *len = 32 * KP * 2; return 0; }
   if (idx >= EAE_PACK_P1 && idx < EAE_PACK_P1 + 12) {
     const int i = (idx - EAE_PACK_P1) % 6;
-    *off = idx < EAE_PACK_P2 ? c->pk_p1[i] : c->pk_p2[i]; *len = (long long)W3_A[i] * W3_B[i] * 9 * 2; return 0;
+    *off = idx < EAE_PACK_P2 ? c->pk_p1[i] : c->pk_p2[i]; *len = (long long)L3[i].cin * L3[i].cout * 9 * 2; return 0;
   }
   if (idx == EAE_PACK_DECONV4_JOINT) { *off = c->pk_d4j; *len = 4LL * c->CP * 128 * 2; return 0; }
   if (idx == EAE_PACK_DECONV4_KCP) { *off = c->pk_d4k; *len = 32 * KP * 2; return 0; }
@@ -446,7 +434,7 @@ int pack_entry(eae_ctx* c, int idx, size_t* off, long long* len) {
   if (idx >= EAE_PACK_FP8_P1 && idx < EAE_PACK_FP8_P1 + 12) {
     if (!c->fp8) return eae_set_error(EAE_ERR_STATE, "debug_read: the fp8 packs exist only with quant = 1");
     const int i = (idx - EAE_PACK_FP8_P1) % 6;
-    *off = idx < EAE_PACK_FP8_P2 ? c->pk8_p1[i] : c->pk8_p2[i]; *len = (long long)W3_A[i] * W3_B[i] * 9; return 0;
+    *off = idx < EAE_PACK_FP8_P2 ? c->pk8_p1[i] : c->pk8_p2[i]; *len = (long long)L3[i].cin * L3[i].cout * 9; return 0;
   }
   return eae_set_error(EAE_ERR_ARG, "debug_read: no such pack");
 }

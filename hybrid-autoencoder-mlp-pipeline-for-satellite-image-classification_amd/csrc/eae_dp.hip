@@ -124,7 +124,7 @@ extern "C" int eae_dp_destroy(eae_ctx* c) {
 }
 extern "C" int eae_dp_allreduce_bucket(eae_ctx* c, void* stream, long long elem_off, long long count) {
   if (!c || !c->dp_comm) return eae_set_error(EAE_ERR_STATE, "dp_allreduce_bucket: eae_dp_init has not been called");
-  if (!c->G || elem_off < 0 || count <= 0 || elem_off + count > c->poff[38]) return eae_set_error(EAE_ERR_ARG, "dp_allreduce_bucket: range outside the gradient arena");
+  if (!c->G || elem_off < 0 || count <= 0 || elem_off + count > c->arena_len()) return eae_set_error(EAE_ERR_ARG, "dp_allreduce_bucket: range outside the gradient arena");
   RcclApi* r = rccl_api();
   RCCL(r->allReduce(c->G + elem_off, c->G + elem_off, (size_t)count, ncclFloat, ncclSum, static_cast<ncclComm_t>(c->dp_comm), (hipStream_t)stream),
        "ncclAllReduce");
@@ -174,7 +174,7 @@ extern "C" int eae_ae_dp_train_step(eae_ctx* c, void* stream, const eae_step_io*
   RC(forward_impl(c, st, io, true));
   RC(backward_impl(c, st, io));             // with a hand-off stream: dp_stream[0] is now ordered after gradient tensors 18..37
   c->adam_step += 1;                        // (behind the launches that can fail: a failed step must not advance the bias correction)
-  const long long cut = c->poff[18], total = c->poff[38];
+  const long long cut = c->poff[CUT_ENC_DEC], total = c->arena_len();
   RcclApi* r = rccl_api();
   unsigned* flag = dp_flag_word(c);
   hipLaunchKernelGGL(dp_flag_kernel, dim3(1), dim3(64), 0, st, c->sigwords + 8, poison_word(c), flag);
@@ -195,8 +195,7 @@ extern "C" int eae_ae_dp_train_step(eae_ctx* c, void* stream, const eae_step_io*
     RC(rc);
   }
   if (ov) EAE_HIP(hipStreamWaitEvent(st, c->ev_dp_done, 0));
-  RC(launch_adam(c, st, c->poff[38], lr, 0.f, 1.0f / (float)c->dp_world, flag, flag + 1));
-  c->last_loss = nullptr;
-  c->packed = false; c->acc_clean = true; c->bwd_dirty = false;
+  RC(launch_adam(c, st, c->arena_len(), lr, 0.f, 1.0f / (float)c->dp_world, flag, flag + 1));
+  after_optimizer(c, 0);
   return 0;
 }

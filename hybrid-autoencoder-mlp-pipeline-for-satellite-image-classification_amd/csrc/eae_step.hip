@@ -26,16 +26,10 @@ static const EaeProfHook* prof_hook_for(eae_ctx* c, int site) {
 }
 struct ProfBracket {
   eae_ctx* c; hipStream_t st; bool on;
-  ProfBracket(eae_ctx* c_, int site, hipStream_t st_) : c(c_), st(st_) {
-    on = c->prof_on && c->prof_site == site && c->prof_n < eae_ctx::PROF_RING && !c->capturing;
-    if (on) hipEventRecord(c->prof_ev[3 * c->prof_n], st);
+  ProfBracket(eae_ctx* c_, int site, hipStream_t st_) : c(c_), st(st_), on(prof_hook_for(c_, site) != nullptr) {
+    if (on) prof_hook_begin(c, st);
   }
-  ~ProfBracket() {
-    if (!on) return;
-    hipEventRecord(c->prof_ev[3 * c->prof_n + 1], st);
-    hipEventRecord(c->prof_ev[3 * c->prof_n + 2], st);
-    c->prof_n++;
-  }
+  ~ProfBracket() { if (on) prof_hook_end(c, st); }
 };
 
 // split-K of the latent projections: K-range per slice.  128 (32 slices) at the reference's 64x64 inputs; wider inputs keep the number
@@ -49,7 +43,7 @@ int fc_klen(const eae_ctx* c) {
 }
 
 // the [C] sticky non-finite flag words of BN layer l sit behind the layer's [acc_copies][2][C] accumulators (forward or backward half)
-unsigned long long* acc_flag(const eae_ctx* c, unsigned long long* acc, int l) { return acc + (size_t)c->acc_copies[l] * 2 * BN_C[l]; }
+unsigned long long* acc_flag(const eae_ctx* c, unsigned long long* acc, int l) { return acc + (size_t)c->acc_copies[l] * 2 * BN_LAYERS[l].c; }
 constexpr float ACC_SCALE_FWD = 16777216.f;      // 2^24: sums of y and y^2 over <= 2^21 elements of |y| <~ 1e3 stay far below 2^63
 
 // fp8 variant: weight pack, scales and the amax word of 3x3 layer j (W3 order) for a forward / backward-data launch
@@ -74,7 +68,7 @@ int sync_fwd(eae_ctx* c, hipStream_t st, int l, bool train) {
   if (!train || c->sync_world <= 1) return 0;
   if (!c->fold_fwd) return eae_set_error(EAE_ERR_STATE, "SyncBN needs the folded forward finalize (unset EAE_NO_FOLD_FWD)");
   const long long off = (long long)(c->accf[l] - reinterpret_cast<unsigned long long*>(c->acc_base));
-  if (c->sync_fn(c->sync_user, 0, off, (long long)c->acc_copies[l] * 2 * BN_C[l] + BN_C[l], (void*)st) != 0)      // (+C: the non-finite flag words)
+  if (c->sync_fn(c->sync_user, 0, off, (long long)c->acc_copies[l] * 2 * BN_LAYERS[l].c + BN_LAYERS[l].c, (void*)st) != 0)      // (+C: the non-finite flag words)
     return eae_set_error(EAE_ERR_STATE, "SyncBN: the exchange hook failed (forward statistics)");
   return 0;
 }
@@ -85,8 +79,8 @@ void fold_consumer(eae_ctx* c, BnFold& f, int l, long long count, bool train) {
   f.acc = c->accf[l]; f.copies = c->acc_copies[l]; f.inv_scale = 1.0f / ACC_SCALE_FWD; f.count = (float)count; f.flag = acc_flag(c, c->accf[l], l);
   f.poison = poison_word(c);
   f.momentum = BN_MOM; f.eps = BN_EPS;
-  f.gamma = c->P + c->poff[BN_GAMMA_IDX[l]]; f.beta = c->P + c->poff[BN_GAMMA_IDX[l] + 1];
-  f.rm = c->bnrun + c->bnoff[2 * l]; f.rv = c->bnrun + c->bnoff[2 * l + 1]; f.nbt = c->nbt ? c->nbt + l : nullptr;
+  f.gamma = c->bn_gamma(l); f.beta = c->bn_beta(l);
+  f.rm = c->bn_rmean(l); f.rv = c->bn_rvar(l); f.nbt = c->nbt ? c->nbt + l : nullptr;
   f.coef_out = c->coef_f[l];
 }
 
@@ -103,17 +97,14 @@ int prep_bwd_accumulators(eae_ctx* c, hipStream_t st) {
 
 int bn_fwd_finalize(eae_ctx* c, hipStream_t st, int l, int ntiles, long long count, bool train) {
   if (train && c->fold_fwd) return 0;       // folded into the producer (accumulators) and the next kernel (prologue)
-  const float* gamma = c->P + c->poff[BN_GAMMA_IDX[l]];
-  const float* beta = c->P + c->poff[BN_GAMMA_IDX[l] + 1];
-  float* rm = c->bnrun + c->bnoff[2 * l];
-  float* rv = c->bnrun + c->bnoff[2 * l + 1];
-  if (train) return eae_launch_bn_finalize(st, c->stat, ntiles, BN_C[l], count, gamma, beta, rm, rv, c->nbt ? c->nbt + l : nullptr, BN_MOM, BN_EPS, c->coef_f[l]);
-  return eae_launch_bn_eval_coef(st, BN_C[l], gamma, beta, rm, rv, BN_EPS, c->coef_f[l]);
+  if (train) return eae_launch_bn_finalize(st, c->stat, ntiles, BN_LAYERS[l].c, count, c->bn_gamma(l), c->bn_beta(l), c->bn_rmean(l), c->bn_rvar(l),
+                                           c->nbt ? c->nbt + l : nullptr, BN_MOM, BN_EPS, c->coef_f[l]);
+  return eae_launch_bn_eval_coef(st, BN_LAYERS[l].c, c->bn_gamma(l), c->bn_beta(l), c->bn_rmean(l), c->bn_rvar(l), BN_EPS, c->coef_f[l]);
 }
 
 constexpr float ACC_SCALE_BWD = 4398046511104.f;   // 2^42 (eae_common.hip.h, BnBwdFold)
 bool bwd_folded(const eae_ctx* c, int l) { (void)l; return c->fold_bwd && c->sync_world <= 1; }
-int bwd_copies(const eae_ctx* c, int l) { return std::min(c->acc_copies[l], BN_FOLD_KB * (256 / BN_C[l])); }
+int bwd_copies(const eae_ctx* c, int l) { return std::min(c->acc_copies[l], BN_FOLD_KB * (256 / BN_LAYERS[l].c)); }
 // producer side of the folded BatchNorm-backward finalize of layer l: call before launching the kernel whose epilogue takes the sums
 void fold_bwd_producer(eae_ctx* c, ConvArgs& a, int l) {
   if (!bwd_folded(c, l)) return;
@@ -128,10 +119,10 @@ void fold_bwd_consumer(eae_ctx* c, BnBwdFold& f, int l, long long count, bool wr
   f.acc = c->accb[l]; f.copies = bwd_copies(c, l); f.inv_scale = 1.0f / ACC_SCALE_BWD; f.flag = acc_flag(c, c->accb[l], l);
   f.poison = poison_word(c);
   f.count = c->bwd_eval ? __builtin_inff() : (float)count;
-  f.gamma = c->P + c->poff[BN_GAMMA_IDX[l]]; f.coef_fwd = c->coef_f[l];
+  f.gamma = c->bn_gamma(l); f.coef_fwd = c->coef_f[l];
   if (writer) {
-    f.dgamma = c->G + c->poff[BN_GAMMA_IDX[l]]; f.dbeta = c->G + c->poff[BN_GAMMA_IDX[l] + 1]; f.coef_out = c->coef_b[l];
-    if (c->bwd_eval) f.dbias = c->G + c->poff[PREBN_BIAS[l]];
+    f.dgamma = c->bn_dgamma(l); f.dbeta = c->bn_dbeta(l); f.coef_out = c->coef_b[l];
+    if (c->bwd_eval) f.dbias = c->prebn_dbias(l);
   }
 }
 
@@ -140,13 +131,12 @@ int bn_bwd_fin(eae_ctx* c, hipStream_t st, int l, int ntiles, long long count) {
   if (c->bwd_eval) count = 1LL << 40;       // eval-mode BatchNorm: no batch-size terms (see eae_ae_backward)
   if (c->sync_world > 1) {
     double* sums = c->sync_sums + (size_t)l * 512;
-    RC(eae_launch_bn_bwd_reduce(st, c->stat, ntiles, BN_C[l], sums, c->G + c->poff[BN_GAMMA_IDX[l]], c->G + c->poff[BN_GAMMA_IDX[l] + 1]));
-    if (c->sync_fn(c->sync_user, 1, (long long)l * 512, 2LL * BN_C[l], (void*)st) != 0)
+    RC(eae_launch_bn_bwd_reduce(st, c->stat, ntiles, BN_LAYERS[l].c, sums, c->bn_dgamma(l), c->bn_dbeta(l)));
+    if (c->sync_fn(c->sync_user, 1, (long long)l * 512, 2LL * BN_LAYERS[l].c, (void*)st) != 0)
       return eae_set_error(EAE_ERR_STATE, "SyncBN: the exchange hook failed (backward sums)");
-    return eae_launch_bn_bwd_coef(st, sums, BN_C[l], count * c->sync_world, c->P + c->poff[BN_GAMMA_IDX[l]], c->coef_f[l], c->coef_b[l]);
+    return eae_launch_bn_bwd_coef(st, sums, BN_LAYERS[l].c, count * c->sync_world, c->bn_gamma(l), c->coef_f[l], c->coef_b[l]);
   }
-  return eae_launch_bn_bwd_finalize(st, c->stat, ntiles, BN_C[l], count, c->P + c->poff[BN_GAMMA_IDX[l]], c->coef_f[l],
-                                    c->G + c->poff[BN_GAMMA_IDX[l]], c->G + c->poff[BN_GAMMA_IDX[l] + 1], c->coef_b[l]);
+  return eae_launch_bn_bwd_finalize(st, c->stat, ntiles, BN_LAYERS[l].c, count, c->bn_gamma(l), c->coef_f[l], c->bn_dgamma(l), c->bn_dbeta(l), c->coef_b[l]);
 }
 
 int copy_latent_in(eae_ctx* c, hipStream_t st, float* dst_padded, const float* src, int B) {      // padding columns of dst stay as they are (zero)
@@ -179,12 +169,95 @@ int run_head(eae_ctx* c, hipStream_t st, int B, const long long* labels, float* 
              bool count_valid = false) {
   HeadArgs h = HeadArgs();
   h.dlogits_in = dlogits_in;
-  h.z = c->z; h.w1 = c->lpad ? (const float*)(c->pack + c->pk_w1p) : c->P + c->poff[34]; h.b1 = c->P + c->poff[35]; h.w2 = c->P + c->poff[36]; h.b2 = c->P + c->poff[37];
+  h.z = c->z; h.w1 = c->lpad ? (const float*)(c->pack + c->pk_w1p) : c->param(T_CLS0_W); h.b1 = c->param(T_CLS0_B); h.w2 = c->param(T_CLS2_W); h.b2 = c->param(T_CLS2_B);
   h.labels = labels; h.B = B; h.L = c->Lp; h.C = c->C; h.inv_batch = 1.0f / (float)B;
   h.logits = logits; h.dz = c->dzc; h.grad_part = want_grad ? c->headpart : nullptr; h.grad_stride = c->head_stride;
   h.loss_part = c->cepart;
   if (c->wce()) return eae_launch_head_w(st, h, c->class_w, c->ignore_index, count_valid ? c->valid_acc : nullptr);     // (labels NULL or external dlogits: the plain kernels)
   return eae_launch_head(st, h);
+}
+
+// ---- the six 3x3 stride-2 layers (eae_layers.h: L3[j]).  What differs between them comes from the table row: conv layers use the
+//      p1 packs forward and the transposed launcher with the p2 packs backward, transposed layers the other way round; deconv1's
+//      input d0 is raw (no BatchNorm in front of it).
+
+// the layer's input as a source: BatchNorm + ReLU of the layer in front applied on load, or d0 as it is
+SrcDesc l3_input(const eae_ctx* c, const Layer3& r) { return r.bn_in < 0 ? src_raw(c->d0) : src_bnrelu(c->act(r.bn_in), c->coef_f[r.bn_in]); }
+
+// forward: raw output (bf16) + the statistics of its BatchNorm
+int l3_forward(eae_ctx* c, hipStream_t st, int j, int B, bool train) {
+  const Layer3& r = L3[j];
+  const bool conv = r.kind == L3_CONV;
+  ConvArgs a = ConvArgs();
+  a.src = l3_input(c, r);
+  a.wpack = (const bf16_t*)(c->pack + (conv ? c->pk_p1[j] : c->pk_p2[j])); a.bias = c->param(r.b); a.out = c->act(r.bn_out);
+  a.stat_part = train ? c->stat : nullptr;
+  a.B = B; a.Hin = c->H >> r.in_lvl(); a.Win = c->W >> r.in_lvl();
+  fold_producer(c, a, r.bn_out, train);
+  if (r.bn_in >= 0) fold_consumer(c, a.fold, r.bn_in, (long long)B * a.Hin * a.Win, train);
+  fp8_conv_args(c, a, j, true, conv);
+  {
+    ProfBracket pb(c, EAE_PROF_SITE(r.site, 0), st);
+    RC((conv ? eae_launch_conv_s2 : eae_launch_deconv_s2)(a, r.cin, r.cout, r.bn_in < 0 ? SRC_RAW : SRC_BNRELU, EPI_FWD, st));
+  }
+  RC(sync_fwd(c, st, r.bn_out, train));
+  return bn_fwd_finalize(c, st, r.bn_out, eae_conv_s2_ntiles(r.kind, r.cin, r.cout, B, a.Hin, a.Win),
+                         (long long)B * (c->H >> r.out_lvl()) * (c->W >> r.out_lvl()), train);
+}
+
+// backward: the weight gradient (queued for a side stream) and backward-data into the BatchNorm + ReLU of the layer in front (deconv1:
+// plainly into gd0).  dy mode: backward-data first -- while it stages dy = BatchNorm-backward(g, y) of this layer's output it also
+// stores it (dy_out); the weight gradient queued behind it reads that one tensor and is released when the NEXT kernel of the chain
+// starts.  Otherwise the weight gradient transforms g and y itself and is released together with the backward-data kernel.
+int l3_backward(eae_ctx* c, hipStream_t st, int j, int B) {
+  const Layer3& r = L3[j];
+  const bool conv = r.kind == L3_CONV;
+  const int cs = r.cs(), cb = r.cb(), lo = r.bn_out;
+  const int Hs = c->H >> r.lvl, Ws = c->W >> r.lvl;                                  // the small map
+  const int Ho = c->H >> r.out_lvl(), Wo = c->W >> r.out_lvl();                      // the map of the output and its gradient
+  const bool dym = (c->dy_mask >> r.dy_bit) & 1u;
+  auto push_wgrad = [&]() {
+    if (c->skip_wgrad) return;
+    sq_push(c, [=](hipStream_t s2, float* scr) {
+      const Layer3& lr = L3[j];
+      const SrcDesc g = dym ? src_raw(c->dyact(lo)) : src_bnbwd(c->gact(lo), c->act(lo), c->coef_b[lo]), x = l3_input(c, lr);
+      const int gk = dym ? SRC_RAWG : SRC_BNBWD, xk = lr.bn_in < 0 ? SRC_RAW : SRC_BNRELU;
+      WgradArgs w = WgradArgs();
+      w.small = conv ? g : x; w.big = conv ? x : g;         // a conv's small side is its output, a transposed conv's its input
+      w.B = B; w.Hs = Hs; w.Ws = Ws;
+      if (!dym) fold_bwd_consumer(c, w.bfold, lo, (long long)B * Ho * Wo, false);
+      if (c->fp8) w.qs = c->q->qs_wg[j];
+      return eae_launch_wgrad_s2(s2, w, cs, cb, conv ? gk : xk, conv ? xk : gk, scr, c->wscratch_floats, c->grad(lr.w),
+                                 prof_hook_for(c, EAE_PROF_SITE(lr.site, 2)));
+    });
+    sq_fork(c);              // released by the next kernel of the chain (dy mode, conv2: by conv1's weight gradient)
+  };
+  if (!dym) push_wgrad();
+  ConvArgs a = ConvArgs();
+  a.src = src_bnbwd(c->gact(lo), c->act(lo), c->coef_b[lo]);
+  a.dy_out = dym ? c->dyact(lo) : nullptr;
+  a.wpack = (const bf16_t*)(c->pack + (conv ? c->pk_p2[j] : c->pk_p1[j]));
+  a.B = B; a.Hin = Ho; a.Win = Wo;
+  fold_bwd_consumer(c, a.bfold, lo, (long long)B * Ho * Wo, true);
+  fp8_conv_args(c, a, j, false, !conv);
+  const int li = r.bn_in;
+  if (li >= 0) {
+    a.out = c->gact(li); a.stat_part = c->stat; a.yprev = c->act(li); a.prev_coef = c->coef_f[li];
+    fold_bwd_producer(c, a, li);
+  } else {
+    a.out = c->gd0;
+  }
+  take_sig(c, a);
+  {                          // backward-data of a conv is a transposed conv cout -> cin, and the other way round
+    ProfBracket pb(c, EAE_PROF_SITE(r.site, 1), st);
+    RC((conv ? eae_launch_deconv_s2 : eae_launch_conv_s2)(a, r.cout, r.cin, SRC_BNBWD, li >= 0 ? EPI_MASK : EPI_PLAIN, st));
+  }
+  if (c->sq_forked) RC(sq_commit(c, st));
+  if (li >= 0)
+    RC(bn_bwd_fin(c, st, li, eae_conv_s2_ntiles(conv ? L3_DECONV : L3_CONV, r.cout, r.cin, B, Ho, Wo),
+                  (long long)B * (c->H >> r.in_lvl()) * (c->W >> r.in_lvl())));
+  if (dym) push_wgrad();
+  return 0;
 }
 
 }  // namespace
@@ -221,7 +294,7 @@ int run_encoder(eae_ctx* c, hipStream_t st, const float* x, int B, bool train, c
     EdgeArgs a;
     a.src3 = x; a.B = B; a.H = H; a.W = W; a.C = c->Cin;
     a.c = ConvArgs();
-    a.c.wpack = (const bf16_t*)(c->pack + c->pk_c1); a.c.bias = c->P + c->poff[1]; a.c.out = c->y[0];
+    a.c.wpack = (const bf16_t*)(c->pack + c->pk_c1); a.c.bias = c->param(T_CONV1_B); a.c.out = c->y[0];
     a.c.stat_part = train ? c->stat : nullptr; a.c.B = B;
     fold_producer(c, a.c, 0, train);
     {
@@ -232,22 +305,7 @@ int run_encoder(eae_ctx* c, hipStream_t st, const float* x, int B, bool train, c
     RC(sync_fwd(c, st, 0, train));
     RC(bn_fwd_finalize(c, st, 0, eae_edge_tiles(B, H, W), (long long)B * (H / 2) * (W / 2), train));
   }
-  for (int i = 1; i < 4; ++i) {
-    ConvArgs a = ConvArgs();
-    a.src = src_bnrelu(c->y[i - 1], c->coef_f[i - 1]);
-    a.wpack = (const bf16_t*)(c->pack + c->pk_p1[i - 1]); a.bias = c->P + c->poff[4 * i + 1]; a.out = c->y[i];
-    a.stat_part = train ? c->stat : nullptr;
-    a.B = B; a.Hin = H >> i; a.Win = W >> i;
-    fold_producer(c, a, i, train);
-    fold_consumer(c, a.fold, i - 1, (long long)B * a.Hin * a.Win, train);
-    fp8_conv_args(c, a, i - 1, true, true);
-    {
-      ProfBracket pb(c, EAE_PROF_SITE(i, 0), st);
-      RC(eae_launch_conv_s2(a, ENC_C[i], ENC_C[i + 1], SRC_BNRELU, EPI_FWD, st));
-    }
-    RC(sync_fwd(c, st, i, train));
-    RC(bn_fwd_finalize(c, st, i, eae_conv_s2_ntiles(0, ENC_C[i], ENC_C[i + 1], B, a.Hin, a.Win), (long long)B * (a.Hin / 2) * (a.Win / 2), train));
-  }
+  for (int j = 0; j < L3_FIRST_DECONV; ++j) RC(l3_forward(c, st, j, B, train));      // conv2, conv3, conv4
   FcNtArgs f = FcNtArgs();
   f.a = src_bnrelu(c->y[3], c->coef_f[3]);
   f.w = (const bf16_t*)(c->pack + c->pk_we1);
@@ -255,7 +313,7 @@ int run_encoder(eae_ctx* c, hipStream_t st, const float* x, int B, bool train, c
   fold_consumer(c, f.c.fold, 3, (long long)B * c->Pn, train);
   const int ksplit = (int)(c->K / f.klen);
   RC(eae_launch_fc_nt(st, f, SRC_BNRELU, FCE_PARTIAL, ksplit));
-  RC(eae_launch_fc_reduce(st, c->fcpart, ksplit, B, c->Lp, c->lpad ? (const float*)(c->pack + c->pk_bep) : c->P + c->poff[17], nullptr,
+  RC(eae_launch_fc_reduce(st, c->fcpart, ksplit, B, c->Lp, c->lpad ? (const float*)(c->pack + c->pk_bep) : c->param(T_ENCFC_B), nullptr,
                           nullptr, c->z));
   return 0;
 }
@@ -277,30 +335,22 @@ int run_decoder_trunk(eae_ctx* c, hipStream_t st, const float* z, int B, bool tr
     RC(eae_launch_fc_nt(st, f, SRC_F32, FCE_BIAS_BF16, 1));
     RC(sq_commit(c, st));          // the classification head (queued by forward_impl) starts beside the decoder
   }
-  const int cin[3] = {256, 128, 64};
-  for (int i = 0; i < 3; ++i) {
-    ConvArgs a = ConvArgs();
-    a.src = (i == 0) ? src_raw(c->d0) : src_bnrelu(c->u[i - 1], c->coef_f[3 + i]);
-    a.wpack = (const bf16_t*)(c->pack + c->pk_p2[3 + i]); a.bias = c->P + c->poff[21 + 4 * i]; a.out = c->u[i];
-    a.stat_part = train ? c->stat : nullptr;
-    a.B = B; a.Hin = H >> (4 - i); a.Win = W >> (4 - i);
-    fold_producer(c, a, 4 + i, train);
-    if (i > 0) fold_consumer(c, a.fold, 3 + i, (long long)B * a.Hin * a.Win, train);
-    fp8_conv_args(c, a, 3 + i, true, false);
-    {
-      ProfBracket pb(c, EAE_PROF_SITE(4 + i, 0), st);
-      RC(eae_launch_deconv_s2(a, cin[i], cin[i] / 2, i == 0 ? SRC_RAW : SRC_BNRELU, EPI_FWD, st));
-    }
-    RC(sync_fwd(c, st, 4 + i, train));
-    RC(bn_fwd_finalize(c, st, 4 + i, eae_conv_s2_ntiles(1, cin[i], cin[i] / 2, B, a.Hin, a.Win), (long long)B * (a.Hin * 2) * (a.Win * 2), train));
-  }
+  for (int j = L3_FIRST_DECONV; j < N_L3; ++j) RC(l3_forward(c, st, j, B, train));    // deconv1, deconv2, deconv3
   d = Deconv4Args();
   d.src = src_bnrelu(c->u[2], c->coef_f[6]);
-  d.wjoint = (const bf16_t*)(c->pack + c->pk_d4j); d.bias = c->P + c->poff[33];
+  d.wjoint = (const bf16_t*)(c->pack + c->pk_d4j); d.bias = c->param(T_DECONV4_B);
   d.B = B; d.Hin = H / 2; d.Win = W / 2; d.C = c->Cin;
   fold_consumer(c, d.fold, 6, (long long)B * (H / 2) * (W / 2), train);
   return 0;
 }
+
+// A backward that differentiates an eval-mode forward (eae_ctx::bwd_eval), for as long as it is being enqueued; it writes the
+// gradients of the biases in front of the BatchNorms, which a later train-mode backward has to clear again (prebn_dirty)
+struct EvalBackward {
+  eae_ctx* c;
+  EvalBackward(eae_ctx* c_, bool eval) : c(c_) { c->bwd_eval = eval; if (eval) c->prebn_dirty = true; }
+  ~EvalBackward() { c->bwd_eval = false; }
+};
 
 // the arenas are bound and the batch fits the workspace
 static int check_bound_batch(const eae_ctx* c, int B) {
@@ -367,13 +417,13 @@ int forward_impl(eae_ctx* c, hipStream_t st, const eae_step_io* io, bool want_gr
       float *accum = io->loss_accum, *last = io->loss_last;
       const int ntile = eae_edge_tiles(B, c->H, c->W);
       sq_push(c, [=](hipStream_t ls, float*) {
-        return eae_launch_loss_finalize(ls, c->msepart, ntile, c->cepart, n_ce, alpha, numel, B, c->G + c->poff[33], accum, last, poison_word(c),
+        return eae_launch_loss_finalize(ls, c->msepart, ntile, c->cepart, n_ce, alpha, numel, B, c->grad(T_DECONV4_B), accum, last, poison_word(c),
                                         c->Cin);
       }, 0);
       sq_fork(c);                  // released by the first kernel of the backward-data chain (backward_impl commits behind it)
     } else {
       RC(eae_launch_loss_finalize(st, c->msepart, eae_edge_tiles(B, c->H, c->W), c->cepart, n_ce, io->alpha, numel, B,
-                                  want_grad ? c->G + c->poff[33] : nullptr, io->loss_accum, io->loss_last, poison_word(c), c->Cin));
+                                  want_grad ? c->grad(T_DECONV4_B) : nullptr, io->loss_accum, io->loss_last, poison_word(c), c->Cin));
     }
   }
   return 0;
@@ -386,8 +436,7 @@ int backward_impl(eae_ctx* c, hipStream_t st, const eae_step_io* io, const float
   //  layers' sums -- nothing is cleared; the stand-alone encoder backward clears before it calls)
   if (part != 2) RC(prep_bwd_accumulators(c, st));
   if (c->prebn_dirty && !c->bwd_eval) {      // train mode again: those biases have an identically zero gradient, never written
-    for (int k = 0; k < 7; ++k)
-      EAE_HIP(eae_memset_async(c->G + c->poff[PREBN_BIAS[k]], 0, (size_t)(c->poff[PREBN_BIAS[k] + 1] - c->poff[PREBN_BIAS[k]]) * 4, st));
+    for (int l = 0; l < N_BN; ++l) EAE_HIP(eae_memset_async(c->prebn_dbias(l), 0, (size_t)c->numel(BN_LAYERS[l].bias) * 4, st));
     c->prebn_dirty = false;
   }
   const bool head = io->head != 0;
@@ -399,25 +448,25 @@ int backward_impl(eae_ctx* c, hipStream_t st, const eae_step_io* io, const float
     if (head) {
       sq_push(c, [=](hipStream_t ss, float*) {
         const int nb = eae_head_blocks(B, c->Lp);
-        RC(eae_launch_reduce_slices(ss, c->headpart, nb, (long)(c->head_stride / 4), c->lpad ? c->gs_head : c->G + c->poff[34], 1.0f));
-        if (c->lpad) {     // padded shadow -> arena: classifier.0.weight [128][L], then bias / classifier.2 (contiguous)
+        RC(eae_launch_reduce_slices(ss, c->headpart, nb, (long)(c->head_stride / 4), c->lpad ? c->gs_head : c->grad(T_CLS0_W), 1.0f));
+        if (c->lpad) {     // padded shadow -> arena: classifier.0.weight [128][L], then bias / classifier.2 (contiguous, the arena's last)
           EAE_NO_GROUP("a latent width that needs the padded classifier shadow");
-          EAE_HIP(hipMemcpy2DAsync(c->G + c->poff[34], (size_t)c->L * 4, c->gs_head, (size_t)c->Lp * 4, (size_t)c->L * 4, 128,
+          EAE_HIP(hipMemcpy2DAsync(c->grad(T_CLS0_W), (size_t)c->L * 4, c->gs_head, (size_t)c->Lp * 4, (size_t)c->L * 4, CLS_HIDDEN,
                                    hipMemcpyDeviceToDevice, ss));
-          EAE_HIP(hipMemcpyAsync(c->G + c->poff[35], c->gs_head + 128LL * c->Lp, (size_t)(c->poff[38] - c->poff[35]) * 4,
+          EAE_HIP(hipMemcpyAsync(c->grad(T_CLS0_B), c->gs_head + (long long)CLS_HIDDEN * c->Lp, (size_t)(c->grad(T_COUNT) - c->grad(T_CLS0_B)) * 4,
                                  hipMemcpyDeviceToDevice, ss));
         }
         return 0;
       }, 0);
     } else {
       sq_push(c, [=](hipStream_t ss, float*) {
-        EAE_HIP(eae_memset_async(c->G + c->poff[34], 0, (size_t)(c->poff[38] - c->poff[34]) * 4, ss));
+        EAE_HIP(eae_memset_async(c->grad(T_CLS0_W), 0, (size_t)(c->grad(T_COUNT) - c->grad(T_CLS0_W)) * 4, ss));
         return 0;
       }, 0);
     }
     sq_push(c, [=](hipStream_t ss, float* scr) {
       return eae_launch_edge_wgrad(ss, SRC3_NHWCP_BF16, c->g4, B, H, W, src_bnrelu(c->u[2], c->coef_f[6]), SRC_BNRELU, scr,
-                                   c->wscratch_floats, c->G + c->poff[32], prof_hook_for(c, EAE_PROF_SITE(7, 2)), nullptr, nullptr, 0,
+                                   c->wscratch_floats, c->grad(T_DECONV4_W), prof_hook_for(c, EAE_PROF_SITE(7, 2)), nullptr, nullptr, 0,
                                    nullptr, nullptr, c->Cin);
     }, 0);
     sq_fork(c);
@@ -437,64 +486,15 @@ int backward_impl(eae_ctx* c, hipStream_t st, const eae_step_io* io, const float
       RC(sq_commit(c, st));
       RC(bn_bwd_fin(c, st, 6, eae_edge_tiles(B, H, W), (long long)B * (H / 2) * (W / 2)));
     }
-    // ---- deconv3, deconv2, deconv1 (i = 2, 1, 0): weight gradients queued, handed over together before the last dgrad
-    const int dcin[3] = {256, 128, 64};
-    for (int i = 2; i >= 0; --i) {
-      const int cs = dcin[i], cb = dcin[i] / 2;         // deconv weight [cs][cb][3][3]
-      const int Hs = H >> (4 - i), Ws = W >> (4 - i);   // input (small) map of the deconv
-      // dy mode: backward-data first -- while it stages dy = BatchNorm-backward(g, y) of this layer's output it also stores it
-      // (dy_out); the weight gradient queued behind it reads that one tensor and is released when the NEXT kernel of the chain
-      // starts.  Otherwise the weight gradient transforms g and y itself and is released together with the backward-data kernel.
-      const bool dym = (c->dy_mask >> (4 + i)) & 1u;
-      auto push_wgrad = [&]() {
-        if (c->skip_wgrad) return;
-        sq_push(c, [=](hipStream_t s2, float* scr) {
-          WgradArgs w = WgradArgs();
-          w.small = (i == 0) ? src_raw(c->d0) : src_bnrelu(c->u[i - 1], c->coef_f[3 + i]);
-          w.big = dym ? src_raw(c->dyu[i]) : src_bnbwd(c->gu[i], c->u[i], c->coef_b[4 + i]);
-          w.B = B; w.Hs = Hs; w.Ws = Ws;
-          if (!dym) fold_bwd_consumer(c, w.bfold, 4 + i, (long long)B * (Hs * 2) * (Ws * 2), false);
-          if (c->fp8) w.qs = c->q->qs_wg[3 + i];
-          return eae_launch_wgrad_s2(s2, w, cs, cb, i == 0 ? SRC_RAW : SRC_BNRELU, dym ? SRC_RAWG : SRC_BNBWD, scr, c->wscratch_floats,
-                                     c->G + c->poff[20 + 4 * i], prof_hook_for(c, EAE_PROF_SITE(4 + i, 2)));
-        });
-        sq_fork(c);
-      };
-      if (!dym) push_wgrad();
-      ConvArgs a = ConvArgs();
-      a.src = src_bnbwd(c->gu[i], c->u[i], c->coef_b[4 + i]);
-      a.dy_out = dym ? c->dyu[i] : nullptr;
-      a.wpack = (const bf16_t*)(c->pack + c->pk_p1[3 + i]);
-      a.B = B; a.Hin = Hs * 2; a.Win = Ws * 2;
-      fold_bwd_consumer(c, a.bfold, 4 + i, (long long)B * a.Hin * a.Win, true);
-      fp8_conv_args(c, a, 3 + i, false, true);
-      take_sig(c, a);
-      if (i > 0) {
-        a.out = c->gu[i - 1]; a.stat_part = c->stat; a.yprev = c->u[i - 1]; a.prev_coef = c->coef_f[3 + i];
-        fold_bwd_producer(c, a, 3 + i);
-        {
-          ProfBracket pb(c, EAE_PROF_SITE(4 + i, 1), st);
-          RC(eae_launch_conv_s2(a, cb, cs, SRC_BNBWD, EPI_MASK, st));
-        }
-        if (c->sq_forked) RC(sq_commit(c, st));
-        RC(bn_bwd_fin(c, st, 3 + i, eae_conv_s2_ntiles(0, cb, cs, B, a.Hin, a.Win), (long long)B * Hs * Ws));
-      } else {
-        a.out = c->gd0;
-        {
-          ProfBracket pb(c, EAE_PROF_SITE(4, 1), st);
-          RC(eae_launch_conv_s2(a, cb, cs, SRC_BNBWD, EPI_PLAIN, st));
-        }
-        if (c->sq_forked) RC(sq_commit(c, st));
-      }
-      if (dym) push_wgrad();
-    }
+    // ---- deconv3, deconv2, deconv1: weight gradients queued, handed over together before the last dgrad
+    for (int j = N_L3 - 1; j >= L3_FIRST_DECONV; --j) RC(l3_backward(c, st, j, B));
     // ---- dec.fc: weight/bias gradient (queued: needs gd0) and dz
     sq_push(c, [=](hipStream_t s2, float*) {
       FcTnArgs t = FcTnArgs();
       t.p = src_raw(c->gd0); t.q = src_f32(c->z); t.Bt = B; t.I = (int)c->K; t.J = c->Lp;
-      t.out = c->lpad ? c->gs_decw : c->G + c->poff[18]; t.colsum = c->G + c->poff[19]; t.out_mode = 0; t.Pn = (int)c->Pn;
+      t.out = c->lpad ? c->gs_decw : c->grad(T_DECFC_W); t.colsum = c->grad(T_DECFC_B); t.out_mode = 0; t.Pn = (int)c->Pn;
       RC(eae_launch_fc_tn(s2, t, SRC_RAW, SRC_F32));
-      if (c->lpad) EAE_HIP(hipMemcpy2DAsync(c->G + c->poff[18], (size_t)c->L * 4, c->gs_decw, (size_t)c->Lp * 4, (size_t)c->L * 4,
+      if (c->lpad) EAE_HIP(hipMemcpy2DAsync(c->grad(T_DECFC_W), (size_t)c->L * 4, c->gs_decw, (size_t)c->Lp * 4, (size_t)c->L * 4,
                                             (size_t)c->K, hipMemcpyDeviceToDevice, s2));
       return 0;
     });
@@ -526,11 +526,11 @@ int backward_impl(eae_ctx* c, hipStream_t st, const eae_step_io* io, const float
   sq_push(c, [=](hipStream_t s2, float*) {
     FcTnArgs t = FcTnArgs();
     t.p = src_f32(c->dz); t.q = src_bnrelu(c->y[3], c->coef_f[3]); t.Bt = B; t.I = c->Lp; t.J = (int)c->K;
-    t.out = c->lpad ? c->gs_encw : c->G + c->poff[16]; t.colsum = c->lpad ? c->gs_encb : c->G + c->poff[17]; t.out_mode = 1; t.Pn = (int)c->Pn;
+    t.out = c->lpad ? c->gs_encw : c->grad(T_ENCFC_W); t.colsum = c->lpad ? c->gs_encb : c->grad(T_ENCFC_B); t.out_mode = 1; t.Pn = (int)c->Pn;
     RC(eae_launch_fc_tn(s2, t, SRC_F32, SRC_BNRELU));
     if (c->lpad) {       // the first L rows of the padded shadows are the arena tensors
-      EAE_HIP(eae_memcpy_d2d_async(c->G + c->poff[16], c->gs_encw, (size_t)c->L * c->K * 4, s2));
-      EAE_HIP(eae_memcpy_d2d_async(c->G + c->poff[17], c->gs_encb, (size_t)c->L * 4, s2));
+      EAE_HIP(eae_memcpy_d2d_async(c->grad(T_ENCFC_W), c->gs_encw, (size_t)c->L * c->K * 4, s2));
+      EAE_HIP(eae_memcpy_d2d_async(c->grad(T_ENCFC_B), c->gs_encb, (size_t)c->L * 4, s2));
     }
     return 0;
   });
@@ -547,45 +547,11 @@ int backward_impl(eae_ctx* c, hipStream_t st, const eae_step_io* io, const float
     RC(sq_commit(c, st));
     RC(bn_bwd_fin(c, st, 3, ((B + 127) / 128) * (int)c->Pn, (long long)B * c->Pn));
   }
-  // ---- conv4, conv3, conv2 (i = 3, 2, 1): weight gradient (queued; conv4 + conv3 go together, conv2 before the last dgrad so
+  // ---- conv4, conv3, conv2: weight gradient (queued; conv4 + conv3 go together, conv2 before the last dgrad so
   //      that it runs beside it and beside conv1's weight gradient) + backward-data
-  for (int i = 3; i >= 1; --i) {
-    const int cs = ENC_C[i + 1], cb = ENC_C[i];       // conv weight [cs][cb][3][3]
-    const int Hs = H >> (i + 1), Ws = W >> (i + 1);   // output (small) map of the conv
-    const bool dym = (c->dy_mask >> i) & 1u;         // (see the transposed layers above)
-    auto push_wgrad = [&]() {
-      if (c->skip_wgrad) return;
-      sq_push(c, [=](hipStream_t s2, float* scr) {
-        WgradArgs w = WgradArgs();
-        w.small = dym ? src_raw(c->dyy[i]) : src_bnbwd(c->gy[i], c->y[i], c->coef_b[i]);
-        w.big = src_bnrelu(c->y[i - 1], c->coef_f[i - 1]);
-        w.B = B; w.Hs = Hs; w.Ws = Ws;
-        if (!dym) fold_bwd_consumer(c, w.bfold, i, (long long)B * Hs * Ws, false);
-        if (c->fp8) w.qs = c->q->qs_wg[i - 1];
-        return eae_launch_wgrad_s2(s2, w, cs, cb, dym ? SRC_RAWG : SRC_BNBWD, SRC_BNRELU, scr, c->wscratch_floats, c->G + c->poff[4 * i],
-                                   prof_hook_for(c, EAE_PROF_SITE(i, 2)));
-      });
-      sq_fork(c);              // released by the next kernel of the chain (dy mode, conv2: by conv1's weight gradient)
-    };
-    if (!dym) push_wgrad();
-    ConvArgs a = ConvArgs();
-    a.src = src_bnbwd(c->gy[i], c->y[i], c->coef_b[i]);
-    a.dy_out = dym ? c->dyy[i] : nullptr;
-    a.wpack = (const bf16_t*)(c->pack + c->pk_p2[i - 1]);
-    a.out = c->gy[i - 1]; a.stat_part = c->stat; a.yprev = c->y[i - 1]; a.prev_coef = c->coef_f[i - 1];
-    a.B = B; a.Hin = Hs; a.Win = Ws;
-    fold_bwd_producer(c, a, i - 1);
-    fold_bwd_consumer(c, a.bfold, i, (long long)B * Hs * Ws, true);
-    fp8_conv_args(c, a, i - 1, false, false);
-    take_sig(c, a);
-    {
-      ProfBracket pb(c, EAE_PROF_SITE(i, 1), st);
-      RC(eae_launch_deconv_s2(a, cs, cb, SRC_BNBWD, EPI_MASK, st));
-    }
-    if (c->sq_forked) RC(sq_commit(c, st));
-    RC(bn_bwd_fin(c, st, i - 1, eae_conv_s2_ntiles(1, cs, cb, B, Hs, Ws), (long long)B * (Hs * 2) * (Ws * 2)));
-    if (dym) push_wgrad();
-    if (i == 2 && part == 0 && c->dp_stream[1]) {     // enc.fc, conv4 and conv3 weight gradients: enqueued by the commit below
+  for (int j = L3_FIRST_DECONV - 1; j >= 0; --j) {
+    RC(l3_backward(c, st, j, B));
+    if (L3[j].w == T_CONV3_W && part == 0 && c->dp_stream[1]) {     // enc.fc, conv4 and conv3 weight gradients: enqueued by the commit below
       RC(sq_commit(c, st));
       RC(fold_side2(c));
       EAE_HIP(hipEventRecord(c->ev_part[1], c->side));
@@ -604,7 +570,7 @@ int backward_impl(eae_ctx* c, hipStream_t st, const eae_step_io* io, const float
     struct Mid { eae_ctx* c; hipStream_t st; } mid = {c, st};
     auto mid_fn = [](void* u, GateArgs* g) { Mid* m = static_cast<Mid*>(u); return join_side_begin(m->c, m->st, g); };
     RC(eae_launch_edge_wgrad(st, SRC3_NCHW_F32, io->x, B, H, W, src_bnbwd(c->gy[0], c->y[0], c->coef_b[0]), SRC_BNBWD, c->wscratch_main,
-                             2048LL * 288 * c->Cin, c->G + c->poff[0], prof_hook_for(c, EAE_PROF_CONV1_WGRAD), &bf0, sg.sig, sg.sig_val,
+                             2048LL * 288 * c->Cin, c->grad(T_CONV1_W), prof_hook_for(c, EAE_PROF_CONV1_WGRAD), &bf0, sg.sig, sg.sig_val,
                              +mid_fn, &mid, c->Cin));
   }
   RC(join_side(c, st));                                 // (nothing left to wait for when the gate went with the reduction)
@@ -637,17 +603,15 @@ extern "C" int eae_ae_backward(eae_ctx* c, void* stream, long long generation, c
   const int B = c->fwd_B;
   eae_step_io io = eae_step_io();
   io.x = x; io.B = B; io.train = 1; io.head = (dlogits != nullptr) ? 1 : 0;
-  RC(sigmoid_bwd_bias(st, x_hat, dx_hat, c->Cin, B, c->H, c->W, c->g4, c->G + c->poff[33], c->msepart));
+  RC(sigmoid_bwd_bias(st, x_hat, dx_hat, c->Cin, B, c->H, c->W, c->g4, c->grad(T_DECONV4_B), c->msepart));
   if (dlogits) RC(run_head(c, st, B, nullptr, nullptr, true, dlogits));
   // An eval-mode forward normalises with the running statistics: y -> gamma*(y - rm)*invstd_r + beta is affine per channel, so its
   // backward is dy = gamma*invstd_r * g with dgamma = sum g*xhat_r, dbeta = sum g -- the same kernels with the batch-size terms
   // (B and C of the BatchNorm-backward transform, both ~ 1/count) switched off by an infinite count.
-  c->bwd_eval = c->fwd_eval_ready;
-  if (c->bwd_eval && !(c->fold_bwd && c->sync_world <= 1))
+  if (c->fwd_eval_ready && !(c->fold_bwd && c->sync_world <= 1))
     return eae_set_error(EAE_ERR_STATE, "backward of an eval-mode forward needs the folded BatchNorm-backward finalize (no EAE_NO_FOLD_BWD, no SyncBN)");
-  if (c->bwd_eval) c->prebn_dirty = true;
+  EvalBackward eb(c, c->fwd_eval_ready);
   const int rc = backward_impl(c, st, &io, dz);
-  c->bwd_eval = false;
   invalidate_forward(c);
   return rc;
 }
@@ -698,7 +662,7 @@ extern "C" int eae_fp8_scales(eae_ctx* c, float* out18) {
 // eae_set_grad_clip: the partial sums of g^2 over the 38 tensors, on the stream of the optimizer launch and right in front of it
 int clip_prepare(eae_ctx* c, hipStream_t st, EaeClip* clip) {
   RC(eae_launch_grad_sumsq(st, c->G, c->poff, c->psize, c->clip_part));
-  clip->part = c->clip_part; clip->nparts = eae_grad_sumsq_parts(c->poff[38]); clip->max_norm = c->clip_max; clip->norm_out = c->clip_out;
+  clip->part = c->clip_part; clip->nparts = eae_grad_sumsq_parts(c->arena_len()); clip->max_norm = c->clip_max; clip->norm_out = c->clip_out;
   return 0;
 }
 int launch_adam(eae_ctx* c, hipStream_t st, long long n, float lr, float wd, float grad_scale, const unsigned* bad, const unsigned* bad2) {
@@ -711,9 +675,8 @@ int launch_adam(eae_ctx* c, hipStream_t st, long long n, float lr, float wd, flo
 int optimizer_step(eae_ctx* c, hipStream_t st, float lr, float wd, float grad_scale, const unsigned* bad, const unsigned* bad2) {
   if (!c || !c->P || !c->G || !c->M || !c->V) return eae_set_error(EAE_ERR_STATE, "adam: parameter, gradient and moment arenas must be bound");
   c->adam_step += 1;
-  const int rc = launch_adam(c, st, c->poff[38], lr, wd, grad_scale, bad, bad2);
-  c->last_loss = nullptr;            // the step's loss_last buffer is the caller's: it is written (NaN, when the update is refused) by THIS launch only
-  c->packed = false; c->acc_clean = (rc == 0); c->bwd_dirty = !c->acc_clean;
+  const int rc = launch_adam(c, st, c->arena_len(), lr, wd, grad_scale, bad, bad2);
+  after_optimizer(c, rc);
   return rc;
 }
 extern "C" int eae_adam_step(eae_ctx* c, void* stream, float lr, float weight_decay) { return eae_adam_step_scaled(c, stream, lr, weight_decay, 1.0f); }
@@ -746,11 +709,10 @@ int train_step_eager(eae_ctx* c, hipStream_t st, const eae_step_io* io, float lr
   if (!rc) rc = backward_impl(c, st, io);
   if (!rc) {
     c->adam_step += 1;               // (taken back when the launch fails: a failed step must not advance the bias correction)
-    rc = launch_adam(c, st, c->poff[38], lr, 0.f, 1.0f);
+    rc = launch_adam(c, st, c->arena_len(), lr, 0.f, 1.0f);
     if (rc) c->adam_step -= 1;
   }
-  c->last_loss = nullptr;
-  c->packed = false; c->acc_clean = (rc == 0); c->bwd_dirty = !c->acc_clean;
+  after_optimizer(c, rc);
   return rc;
 }
 
@@ -793,7 +755,7 @@ extern "C" int eae_ae_train_step(eae_ctx* c, void* stream, const eae_step_io* io
   if (!rc) rc = backward_impl(c, st, io);
   EaeClip clip;
   if (!rc && c->clip_on()) rc = clip_prepare(c, st, &clip);
-  if (!rc) rc = eae_launch_adam_dyn(st, c->P, c->G, c->M, c->V, c->poff[38], 0.9, 0.999, 1e-8, c->dyn, c->sigwords + 8, poison_word(c), c->last_loss,
+  if (!rc) rc = eae_launch_adam_dyn(st, c->P, c->G, c->M, c->V, c->arena_len(), 0.9, 0.999, 1e-8, c->dyn, c->sigwords + 8, poison_word(c), c->last_loss,
                                     c->clip_on() ? &clip : nullptr);
   c->capturing = false;
   c->packed = false;
@@ -843,11 +805,9 @@ extern "C" int eae_encoder_backward(eae_ctx* c, void* stream, long long generati
   RC(copy_latent_in(c, st, c->dz, dz, c->fwd_B));
   eae_step_io io = eae_step_io();
   io.x = x; io.B = c->fwd_B; io.train = 1; io.head = 0;
-  c->bwd_eval = c->enc_ready == 2;
-  if (c->bwd_eval) c->prebn_dirty = true;
+  EvalBackward eb(c, c->enc_ready == 2);
   RC(prep_bwd_accumulators(c, st));            // (a stand-alone backward: backward_impl leaves part 2 alone)
   const int rc = backward_impl(c, st, &io, nullptr, 2);
-  c->bwd_eval = false;
   c->enc_ready = 0;
   return rc;
 }
@@ -860,11 +820,9 @@ extern "C" int eae_decoder_backward(eae_ctx* c, void* stream, long long generati
   const int B = c->fwd_B;
   eae_step_io io = eae_step_io();
   io.B = B; io.train = 1; io.head = 0;
-  RC(sigmoid_bwd_bias(st, x_hat, dx_hat, c->Cin, B, c->H, c->W, c->g4, c->G + c->poff[33], c->msepart));
-  c->bwd_eval = c->dec_ready == 2;
-  if (c->bwd_eval) c->prebn_dirty = true;
+  RC(sigmoid_bwd_bias(st, x_hat, dx_hat, c->Cin, B, c->H, c->W, c->g4, c->grad(T_DECONV4_B), c->msepart));
+  EvalBackward eb(c, c->dec_ready == 2);
   int rc = backward_impl(c, st, &io, nullptr, 1);
-  c->bwd_eval = false;
   c->dec_ready = 0;
   if (!rc) rc = join_side(c, st);
   if (!rc && dz_out) rc = copy_latent_out(c, st, dz_out, c->dz, B);

@@ -29,17 +29,24 @@ import sys
 import torch
 import torch.distributed as dist
 
+# Tensors of the parameter arena (csrc/eae_layers.h carries the same names): the 38 tensors lie in forward order, conv1..4 [0, 16),
+# enc.fc 16-17, dec.fc 18-19, deconv1..4 20-33, classifier 34-37; the backward completes them from the end
+T_COUNT = 38            # offsets[T_COUNT] = length of the arena
+T_CONV3_W = 8
+CUT_CONVS_FC = 16       # encoder convolutions | the two latent projections
+CUT_ENC_DEC = 18        # encoder half (conv1..4, enc.fc) | decoder half (dec.fc, decoder, classifier)
+CUT_FC_DECONVS = 20     # the two latent projections | transposed convolutions and classifier
+
 
 def bucket_bounds(offsets, total, n_buckets=3):
     """Split the flat arena [0,total) into `n_buckets` contiguous buckets on tensor boundaries, in BACKWARD order of
     completion: classifier + decoder first, then the two latent projections, then the encoder
     (backward runs classifier -> deconv4..1 -> dec.fc -> enc.fc -> conv4..1)."""
-    # arena order is forward order: enc convs [0,16), enc.fc 16-17, dec.fc 18-19, deconvs 20-33, classifier 34-37
-    cuts = [offsets[16], offsets[20]]
+    cuts = [offsets[CUT_CONVS_FC], offsets[CUT_FC_DECONVS]]
     if n_buckets <= 1:
         return [(0, total)]
     if n_buckets == 2:
-        return [(offsets[16], total), (0, offsets[16])]
+        return [(cuts[0], total), (0, cuts[0])]
     return [(cuts[1], total), (cuts[0], cuts[1]), (0, cuts[0])]
 
 
@@ -94,7 +101,7 @@ class DataParallelTrainer:
         self.pg = process_group
         self.world = dist.get_world_size(process_group)
         self.rank = dist.get_rank(process_group)
-        self.buckets = bucket_bounds(engine.poff, engine.poff[38], n_buckets)
+        self.buckets = bucket_bounds(engine.poff, engine.poff[T_COUNT], n_buckets)
         self._comm = None                      # high-priority stream the collectives are enqueued from (GPU engines only)
         self.sync_bn = SyncBatchNorm(engine, process_group) if (sync_bn and self.world > 1 and hasattr(engine, "ctx")) else None
         self.native = False
@@ -242,8 +249,8 @@ class DataParallelTrainer:
             dist.all_reduce(eng.grads, op=dist.ReduceOp.SUM, group=self.pg)
             self._adam_together(lr)
             return
-        cut = eng.poff[18]
-        total = eng.poff[38]
+        cut = eng.poff[CUT_ENC_DEC]
+        total = eng.poff[T_COUNT]
         if self._comm is None:
             three = os.environ.get("EAE_DP_BUCKETS", "2") == "3"
             self._comm = [eng.dp_stream(0), eng.dp_stream(1) if three else None] if hasattr(eng, "dp_stream") else None
@@ -255,7 +262,7 @@ class DataParallelTrainer:
             # point and overlaps the encoder half of the backward; the encoder-side bucket (2.0 MB) follows after the join.
             # EAE_DP_BUCKETS=3 also hands off tensors 8..17 early, leaving conv1 + conv2 (80 KB) for the end: measured
             # +20 us per extra collective at world size 1, so two buckets are the default.
-            c2 = eng.poff[8] if self._comm[1] is not None else 0
+            c2 = eng.poff[T_CONV3_W] if self._comm[1] is not None else 0
             eng.grad_step(x, labels, alpha, head=head)
             with torch.cuda.stream(self._comm[0]):
                 h1 = dist.all_reduce(eng.grads[cut:total], op=dist.ReduceOp.SUM, group=self.pg, async_op=True)
