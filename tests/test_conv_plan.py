@@ -4,34 +4,17 @@ import os
 
 import pytest
 
+import conv_ref as R
+from conv_ref import GRIDS, IGEMM_EXACT_CASES
 from eae_amd import _lib
 from test_gpu_ops_path import IGEMM_CASES
 
-# (TW, TH, NI): tile width x height in positions (conv: of the output map, transposed: of the input map), images per tile
-WIDE = (16, 8, 1)                                                 # position grids that are multiples of 8 rows x 16 columns
-NARROW = {(0, 8): ((8, 8, 2), (8, 8, 1)), (0, 4): ((4, 4, 8), (4, 4, 4)),      # (kind, side): (large tiles, small tiles)
-          (1, 8): ((8, 8, 1), (8, 8, 1)), (1, 4): ((4, 4, 4), (4, 4, 4))}     # (transposed kind: small = narrower channel blocks)
 
-
-def _cdiv(a, b):
-    return -(-a // b)
-
-
-def _tiles(geo, B, pos):
-    tw, th, ni = geo
-    return _cdiv(B, ni) * (pos // th) * (pos // tw)
-
-
-def _expected(kind, cin, cout, B, hin):
-    pos = hin // 2 if kind == 0 else hin
-    if pos % 16 == 0:
-        return _tiles(WIDE, B, pos)
-    if (kind, pos) not in NARROW:
-        return -1
-    large, small = NARROW[kind, pos]
-    takes_small = kind == 1 or cin >= 64                           # the conv kind has small tiles from 64 input channels on
-    is_small = _tiles(large, B, pos) * (cout // 64) < 256          # the large-tile grid leaves CUs empty (EAE_IG_SMALL unset)
-    return _tiles(small if takes_small and is_small else large, B, pos)
+def _expected(kind, cin, cout, B, hin, win=None):
+    """the closed form for the geometry of conv_ref's literal table (the one copy the tests hold), under this process's settings"""
+    win = hin if win is None else win
+    hp, wp = (hin // 2, win // 2) if kind == 0 else (hin, win)
+    return R.expected_ntiles(kind, cin, cout, hp, wp, B, R.ig_small_setting())
 
 
 @pytest.fixture(scope="module")
@@ -49,6 +32,28 @@ def test_ntiles_is_the_closed_form(lib):
             for B in range(1, 601):
                 got = lib.eae_op_conv_s2_ntiles(kind, cin, B, hin * scale, hin * scale)
                 assert got == _expected(kind, cin, cout, B, hin * scale), (kind, cin, B, hin * scale)
+
+
+def test_ntiles_on_rectangular_and_multi_tile_grids(lib):
+    """The position grids of the bit-exact kernel tests (conv_ref.GRIDS: 4x4, 8x8, one tile, 2x2 tiles, two across, three down)."""
+    assert [g[:2] for g in GRIDS] == [(4, 4), (8, 8), (8, 16), (16, 32), (8, 32), (24, 16)]
+    for kind, cin, cout, _, _, _, _ in IGEMM_CASES:
+        for hp, wp, _ in GRIDS:
+            hin, win = (2 * hp, 2 * wp) if kind == 0 else (hp, wp)
+            for B in range(1, 601):
+                got = lib.eae_op_conv_s2_ntiles(kind, cin, B, hin, win)
+                assert got == _expected(kind, cin, cout, B, hin, win), (kind, cin, B, hin, win)
+    # rows and columns are not interchangeable: 16 rows x 8 columns has no geometry, 8 rows x 16 columns is one tile per image
+    assert _expected(1, 64, 32, 3, 16, 8) == -1 and lib.eae_op_conv_s2_ntiles(1, 64, 3, 16, 8) == -1
+    assert _expected(1, 64, 32, 3, 8, 16) == 3 and lib.eae_op_conv_s2_ntiles(1, 64, 3, 8, 16) == 3
+    assert lib.eae_op_conv_s2_ntiles(0, 32, 1, 48, 32) == 3 and lib.eae_op_conv_s2_ntiles(0, 32, 1, 16, 64) == 2
+
+
+def test_every_bit_exact_case_hits_the_geometry_it_names(lib):
+    """What test_gpu_conv_geometry.py asserts per case on the GPU, here for the whole table at once."""
+    for kind, cin, cout, smode, epi, hp, wp, B in IGEMM_EXACT_CASES:
+        hin, win = (2 * hp, 2 * wp) if kind == 0 else (hp, wp)
+        assert lib.eae_op_conv_s2_ntiles(kind, cin, B, hin, win) == _expected(kind, cin, cout, B, hin, win), (kind, cin, hp, wp, B)
 
 
 def test_conv_kind_boundary_at_4x4(lib):

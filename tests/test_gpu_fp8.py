@@ -34,16 +34,29 @@ IGEMM8_CASES = [
     (1, 256, 128, 16, 0, 0, 1), (1, 128, 64, 16, 1, 0, 2), (1, 64, 32, 16, 1, 0, 3),          # deconv1/2/3 forward
     (1, 256, 128, 16, 2, 1, 1), (1, 128, 64, 16, 2, 1, 2), (1, 64, 32, 16, 2, 1, 3),          # backward-data of conv4/3/2
 ]
+# ... and each of them on two tiles across (position grid 8 x 32: the halo column of the second tile is a real pixel) and on a
+# rectangular map three tiles down (24 x 16); the input size is (rows, columns) there
+IGEMM8_CASES += [(k, ci, co, ((2 * hp, 2 * wp) if k == 0 else (hp, wp)), sm, ep, 2 if b == 2 else 1)
+                 for (k, ci, co, _, sm, ep, b) in IGEMM8_CASES[:12] for (hp, wp) in ((8, 32), (24, 16))]
 
 
-@pytest.mark.parametrize("kind,cin,cout,hin,smode,epi,B", IGEMM8_CASES)
+def _size_id(v):
+    return "x".join(map(str, v)) if isinstance(v, tuple) else None
+
+
+def _hw(size):
+    return size if isinstance(size, tuple) else (size, size)
+
+
+@pytest.mark.parametrize("kind,cin,cout,hin,smode,epi,B", IGEMM8_CASES, ids=_size_id)
 def test_igemm8_instantiation(lib, kind, cin, cout, hin, smode, epi, B):
     import gpu_util as G
     from eae_amd._lib import check
     from test_gpu_ops_path import Src
+    hin, win = _hw(hin)
     rng = np.random.default_rng(5000 + 37 * cin + 11 * kind + smode + 3 * epi)
     gscale = 2.0 ** -12 if smode == 2 else 1.0                # gradient-like magnitudes for the e5m2 operand
-    src = Src(smode, (B, cin, hin, hin), rng, scale=gscale)
+    src = Src(smode, (B, cin, hin, win), rng, scale=gscale)
     if smode == 2:
         # Src's B*y + C part is O(0.1): keep the operand gradient-sized by scaling the coefficient rows too
         coef = src.keep[2].cpu().numpy()
@@ -56,7 +69,7 @@ def test_igemm8_instantiation(lib, kind, cin, cout, hin, smode, epi, B):
     fmt = "e5m2" if smode == 2 else "e4m3"
     maxv = 57344.0 if smode == 2 else 448.0
     s_pix = 2.0 ** np.floor(np.log2(maxv / (2 * np.abs(src.value).max())))
-    hout = hin // 2 if kind == 0 else hin * 2
+    hout, wout = (hin // 2, win // 2) if kind == 0 else (hin * 2, win * 2)
     if kind == 0:
         w = O.bf16_round((rng.standard_normal((cout, cin, 3, 3)) / np.sqrt(9 * cin)).astype(np.float32))
     else:
@@ -70,18 +83,18 @@ def test_igemm8_instantiation(lib, kind, cin, cout, hin, smode, epi, B):
     ref = O.conv_s2_fwd(a8, wq, None) if kind == 0 else O.deconv_s2_fwd(a8, wq, None)
     bias = rng.standard_normal(cout).astype(np.float32) * (1.0 if epi == 0 else 0.0)
     bd = G.f32(bias) if epi == 0 else None
-    out = torch.zeros((B, hout, hout, cout), dtype=torch.bfloat16, device=G.dev())
-    nt = lib.eae_op_conv_s2_ntiles(kind, cin, B, hin, hin)
+    out = torch.zeros((B, hout, wout, cout), dtype=torch.bfloat16, device=G.dev())
+    nt = lib.eae_op_conv_s2_ntiles(kind, cin, B, hin, win)
     part = torch.zeros((2, cout, nt), dtype=torch.float32, device=G.dev())
     yprev_d = pcoef_d = None
     if epi == 1:
-        yprev = O.bf16_round(rng.standard_normal((B, cout, hout, hout)).astype(np.float32))
+        yprev = O.bf16_round(rng.standard_normal((B, cout, hout, wout)).astype(np.float32))
         pc = np.stack([(1.0 + 0.2 * rng.standard_normal(cout)), 0.3 * rng.standard_normal(cout), 0.1 * rng.standard_normal(cout),
                        1.0 + 0.2 * rng.random(cout)]).astype(np.float32)
         yprev_d, pcoef_d = G.to_nhwc_bf16(yprev), G.f32(pc)
     qs = G.f32(np.array([1.0 / s_pix, 1.0 / (s_pix * s_w)], np.float32))
     amax = torch.zeros(1, dtype=torch.int32, device=G.dev())
-    check(lib.eae_op_conv_s2_fp8(G.stream(), kind, src.src, cin, cout, B, hin, hin, G.ptr(wp), G.ptr(bd), G.ptr(out),
+    check(lib.eae_op_conv_s2_fp8(G.stream(), kind, src.src, cin, cout, B, hin, win, G.ptr(wp), G.ptr(bd), G.ptr(out),
                                  G.ptr(part) if epi != 2 else None, epi, G.ptr(yprev_d), G.ptr(pcoef_d), G.ptr(qs), G.ptr(amax)))
     torch.cuda.synchronize()
     got = G.from_nhwc(out)
@@ -106,16 +119,19 @@ def test_igemm8_instantiation(lib, kind, cin, cout, hin, smode, epi, B):
 
 WGRAD8_CASES = [(64, 32, 16, 2, 1, 3), (128, 64, 16, 2, 1, 2), (256, 128, 16, 2, 1, 1),      # conv2/3/4: small = gradient (e5m2)
                 (64, 32, 16, 1, 2, 2), (128, 64, 16, 1, 2, 2), (256, 128, 16, 0, 2, 1)]     # deconv3/2/1: big = gradient (e5m2)
+# ... and each of them with a small map of 8 x 32 (two tiles across) and of 24 x 16 (rectangular, three tiles down)
+WGRAD8_CASES += [(cs, cb, hw, sm, bm, 2 if b == 2 else 1) for (cs, cb, _, sm, bm, b) in WGRAD8_CASES[:6] for hw in ((8, 32), (24, 16))]
 
 
-@pytest.mark.parametrize("cs,cb,hs,smode,bmode,B", WGRAD8_CASES)
+@pytest.mark.parametrize("cs,cb,hs,smode,bmode,B", WGRAD8_CASES, ids=_size_id)
 def test_wgrad8_instantiation(lib, cs, cb, hs, smode, bmode, B):
     import gpu_util as G
     from eae_amd._lib import check
     from test_gpu_ops_path import Src
+    hs, ws = _hw(hs)
     rng = np.random.default_rng(7000 + cs + 7 * smode + bmode)
-    small = Src(smode, (B, cs, hs, hs), rng)
-    big = Src(bmode, (B, cb, 2 * hs, 2 * hs), rng)
+    small = Src(smode, (B, cs, hs, ws), rng)
+    big = Src(bmode, (B, cb, 2 * hs, 2 * ws), rng)
 
     def scale_of(v, grad):
         return 2.0 ** np.floor(np.log2((57344.0 if grad else 448.0) / (2 * np.abs(v).max())))
@@ -123,7 +139,7 @@ def test_wgrad8_instantiation(lib, cs, cb, hs, smode, bmode, B):
     qs = G.f32(np.array([1.0 / s_s, 1.0 / s_b, 1.0 / (s_s * s_b)], np.float32))
     scratch = torch.empty(6 * 1024 * 1024, dtype=torch.float32, device=G.dev())
     dw = torch.full((cs, cb, 3, 3), float("nan"), dtype=torch.float32, device=G.dev())
-    check(lib.eae_op_wgrad_s2_fp8(G.stream(), small.src, big.src, cs, cb, B, hs, hs, G.ptr(scratch), scratch.numel(), G.ptr(dw), G.ptr(qs)))
+    check(lib.eae_op_wgrad_s2_fp8(G.stream(), small.src, big.src, cs, cb, B, hs, ws, G.ptr(scratch), scratch.numel(), G.ptr(dw), G.ptr(qs)))
     torch.cuda.synchronize()
     s8 = O._q8(small.value, s_s, "e5m2" if smode == 2 else "e4m3")
     b8 = O._q8(big.value, s_b, "e5m2" if bmode == 2 else "e4m3")
