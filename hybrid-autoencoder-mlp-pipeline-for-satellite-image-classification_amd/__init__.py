@@ -20,6 +20,8 @@ from .scene import class_weights, scene_confusion, evaluate_scene, block_split, 
 from . import cluster  # noqa: F401
 from .cluster import kmeans_fit, kmeans_predict, kmeans_init, cluster_scene, KMeansResult  # noqa: F401
 from .report import cluster_class_table, name_clusters  # noqa: F401
+from . import neighbors  # noqa: F401
+from .neighbors import knn_search, knn_classify, similar_windows, knn_classify_scene, KNNResult  # noqa: F401
 
 __all__ = ["Encoder", "Decoder", "SupervisedAutoencoder", "MLP", "fit_autoencoder", "grid_search_autoencoder",
            "extract_features", "fit_mlp", "grid_search_mlp", "evaluate", "augment_batch", "stage_bands",
@@ -28,4 +30,5 @@ __all__ = ["Encoder", "Decoder", "SupervisedAutoencoder", "MLP", "fit_autoencode
            "reconstruct_scene", "owned_span", "border_grid", "border_source", "stage_scene_windows", "window_labels", "SceneLoader",
            "window_schedule", "drawable_windows", "class_weights", "scene_confusion", "evaluate_scene", "block_split", "footprint_mask",
            "confusion_metrics", "classification_report_from_confusion", "kmeans_fit", "kmeans_predict", "kmeans_init", "cluster_scene",
-           "KMeansResult", "cluster_class_table", "name_clusters"]
+           "KMeansResult", "cluster_class_table", "name_clusters", "knn_search", "knn_classify", "similar_windows", "knn_classify_scene",
+           "KNNResult"]

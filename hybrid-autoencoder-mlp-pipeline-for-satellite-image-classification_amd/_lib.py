@@ -151,6 +151,9 @@ _PROTOS = {
     "eae_kmeans_workspace_bytes": (C.c_longlong, [C.c_longlong, C.c_int, C.c_int]),
     "eae_kmeans_assign": (C.c_int, [vp, vp, C.c_longlong, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp]),
     "eae_kmeans_update": (C.c_int, [vp, vp, C.c_longlong, C.c_int, vp, C.c_int, vp, vp, vp, C.c_longlong]),
+    "eae_knn_workspace_bytes": (C.c_longlong, [C.c_longlong, C.c_longlong, C.c_int, C.c_int]),
+    "eae_knn_slices": (C.c_int, [C.c_longlong, C.c_longlong, C.c_int, C.c_int]),
+    "eae_knn_search": (C.c_int, [vp, vp, C.c_longlong, vp, C.c_longlong, C.c_int, C.c_int, C.c_longlong, vp, vp, vp, C.c_longlong]),
 }
 
 EXPORTS = tuple(_PROTOS.keys())

@@ -666,6 +666,34 @@ int eae_kmeans_assign(void* stream, const float* z, long long N, int L, const fl
 int eae_kmeans_update(void* stream, const float* z, long long N, int L, const long long* labels, int K, float* centroids,
                       long long* counts, void* workspace, long long workspace_bytes);
 
+/* ------------------------------------------------------------------ latent neighbours -------------- */
+/* Nearest-neighbour search over latents (no reference counterpart): the k nearest rows of bank [M][L] for every row of q [Nq][L],
+ * both fp32 row-major; idx int64 [Nq][k]; dist fp32 [Nq][k] or NULL.  1 <= L <= 256, 1 <= k <= 32, 1 <= Nq, M < 2^31, self_offset
+ * >= -1.  Stateless; nothing synchronises the host.  Anything outside these limits, a NULL q, bank or idx, or a workspace that is
+ * NULL or too small where a non-zero size is required is EAE_ERR_ARG, and nothing is launched.
+ *
+ * Scores: s(n, m) = ||b_m||^2 - 2 q_n . b_m in fp32, eae_kmeans_assign's expression: the dot product on the f32-input MFMA (a k-ordered
+ * fma chain over L), the norm a sequential fma chain, s = fma(-2, dot, norm).  A pair's score depends on the two rows alone, not on
+ * where they sit in a tile, on the grid or on the bank split.
+ * Selection: row n of idx holds the k bank rows with the smallest (s, m) in lexicographic order, ascending: equal scores are ordered
+ * by ascending bank index, exactly (duplicate bank rows give bitwise equal scores).  dist[n][j] = max(0, s + ||q_n||^2), the fp32
+ * squared distance (||q_n||^2: the same sequential chain).
+ * A bank row that holds a NaN or an Inf is never returned.  A query row that holds one gets idx -1 and dist NaN in all k slots.  When
+ * fewer than k bank rows are eligible the tail slots hold -1 and NaN.  UNDEFINED: finite rows whose squared norm overflows fp32 (as
+ * built they are treated like non-finite rows; do not rely on it).
+ * self_offset >= 0 makes query n ineligible to match bank row n + self_offset (leave-one-out with q == bank: 0; queries that are the
+ * contiguous slice bank[o : o + Nq]: o); -1 disables it.
+ * Geometry: a function of (Nq, M, L, k) alone, no device query.  No Nq x M array is written anywhere.  When the query tiles alone
+ * cannot fill the device the bank is cut into eae_knn_slices(...) = S > 1 slices: every (query tile, slice) workgroup writes its
+ * partial top-k to `workspace` (eae_knn_workspace_bytes(...) bytes of device memory, contents irrelevant on entry) and a second
+ * kernel merges the S lists of each row by the same (s, m) order.  That order is total, so the result is bitwise independent of S.
+ * With S == 1 the search kernel writes idx / dist directly, eae_knn_workspace_bytes is 0 and workspace may be NULL.
+ * eae_knn_workspace_bytes / eae_knn_slices are host only and return < 0 on bad arguments. */
+long long eae_knn_workspace_bytes(long long Nq, long long M, int L, int k);
+int eae_knn_slices(long long Nq, long long M, int L, int k);
+int eae_knn_search(void* stream, const float* q, long long Nq, const float* bank, long long M, int L, int k, long long self_offset,
+                   long long* idx, float* dist, void* workspace, long long workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif
