@@ -41,36 +41,46 @@ class KMeansResult(NamedTuple):
 
 
 # ---------------------------------------------------------------------------------------------------- host-side validation
-def _latents_arg(z):
-    if not isinstance(z, torch.Tensor) or z.dim() != 2 or z.dtype != torch.float32:
-        raise RuntimeError("z must be a float32 tensor [N, L]")
-    n, width = int(z.shape[0]), int(z.shape[1])
+def _rows_arg(t, what, shape="[rows, L]", most=2 ** 31 - 1):
+    """(rows, width) of a float32 [rows, L] tensor, 1 <= L <= MAX_L and 1 <= rows <= most: the one check of latents, centroids, queries
+    and banks (neighbors.py shares it)."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32:
+        raise RuntimeError(f"{what} must be a float32 tensor {shape}")
+    n, width = int(t.shape[0]), int(t.shape[1])
     if not 1 <= width <= MAX_L:
-        raise RuntimeError(f"the latent width must be in 1..{MAX_L}, got {width}")
-    if not 1 <= n < 2 ** 31:
-        raise RuntimeError(f"the number of rows must be in 1..2^31-1, got {n}")
+        raise RuntimeError(f"the latent width of {what} must be in 1..{MAX_L}, got {width}")
+    if not 1 <= n <= most:
+        raise RuntimeError(f"the number of rows of {what} must be in 1..{'2^31-1' if most == 2 ** 31 - 1 else most}, got {n}")
     return n, width
 
 
+def _int_arg(v, name, lo, hi):
+    """An integer argument in lo..hi (bool is no integer here)."""
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not lo <= int(v) <= hi:
+        raise RuntimeError(f"{name} must be an integer in {lo}..{hi}, got {v!r}")
+    return int(v)
+
+
 def _k_arg(k, n=None):
-    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not 1 <= int(k) <= MAX_K:
-        raise RuntimeError(f"k must be an integer in 1..{MAX_K}, got {k!r}")
-    if n is not None and int(k) > n:
+    k = _int_arg(k, "k", 1, MAX_K)
+    if n is not None and k > n:
         raise RuntimeError(f"k = {k} is greater than the number of rows to cluster ({n})")
-    return int(k)
+    return k
 
 
 def _centroids_arg(centroids, width, device=None):
     """Centroids [K, L]: float32, K in 1..256, the latent width, and (when known) the data's device."""
-    if not isinstance(centroids, torch.Tensor) or centroids.dim() != 2 or centroids.dtype != torch.float32:
-        raise RuntimeError("centroids must be a float32 tensor [K, L]")
-    if not 1 <= int(centroids.shape[0]) <= MAX_K:
-        raise RuntimeError(f"the number of centroids must be in 1..{MAX_K}, got {centroids.shape[0]}")
-    if int(centroids.shape[1]) != int(width):
-        raise RuntimeError(f"centroids have width {centroids.shape[1]}, the latents {width}")
+    k, cwidth = _rows_arg(centroids, "centroids", "[K, L]", MAX_K)
+    if cwidth != int(width):
+        raise RuntimeError(f"centroids have width {cwidth}, the latents {width}")
     if device is not None and centroids.device != device:
         raise RuntimeError(f"centroids are on {centroids.device}, the latents on {device}")
-    return int(centroids.shape[0])
+    return k
+
+
+def _label_counts(labels, k):
+    """Rows per label in [0, k), int64 [k] (integer adds: exact; -1 lands in the dropped slot 0)."""
+    return torch.zeros(k + 1, dtype=torch.int64, device=labels.device).scatter_add_(0, labels + 1, torch.ones_like(labels))[1:]
 
 
 def _fit_args(n, width, k, max_iter, tol, init, device=None):
@@ -120,7 +130,7 @@ def _predict(z, centroids):
 def kmeans_predict(z, centroids):
     """(labels int64 [N], dist float32 [N]): the nearest centroid of every row and the squared distance to it, compared in fp32; the
     lowest index wins a tie; a row with a NaN or an Inf gets -1 and NaN."""
-    _, width = _latents_arg(z)
+    _, width = _rows_arg(z, "z", "[N, L]")
     _centroids_arg(centroids, width, z.device)
     _require_gpu(z.device)
     return _predict(z.contiguous(), centroids.contiguous())
@@ -143,7 +153,7 @@ def kmeans_init(z, k, seed=0):
     With fewer than k distinct finite rows every remaining distance is 0: the draw then falls back to the uniform weights of the
     first pick and repeats a row.  A repeated centroid never wins a tie against its lower-indexed twin, so its cluster stays empty
     (and `kmeans_fit` leaves an empty cluster's centroid where it is)."""
-    n, width = _latents_arg(z)
+    n, width = _rows_arg(z, "z", "[N, L]")
     k = _k_arg(k, n)
     _require_gpu(z.device)
     z = z.contiguous()
@@ -175,7 +185,7 @@ def kmeans_fit(z, k, max_iter=100, tol=0.0, init="kmeans++", seed=0):
     (an empty cluster keeps its centroid) and the next pass begins.  ``tol=None`` runs exactly `max_iter` updates and reads nothing
     back.  When the loop ends by `max_iter`, one more assign makes the returned labels and distances belong to the returned centroids.
     The whole fit is bitwise repeatable: same data, same init, same result."""
-    n, width = _latents_arg(z)
+    n, width = _rows_arg(z, "z", "[N, L]")
     k, init = _fit_args(n, width, k, max_iter, tol, init, z.device)
     _require_gpu(z.device)
     z = z.contiguous()
@@ -197,16 +207,14 @@ def kmeans_fit(z, k, max_iter=100, tol=0.0, init="kmeans++", seed=0):
             n_iter += 1
         if not settled:
             _assign(z, cent, labels, dist)
-    # rows per cluster of the RETURNED labels (integer adds: exact; -1 lands in the dropped slot 0)
-    counts = torch.zeros(k + 1, dtype=torch.int64, device=dev).scatter_add_(0, labels + 1, torch.ones_like(labels))[1:]
-    return KMeansResult(cent, labels, dist, counts, dist.to(torch.float64).nansum(), n_iter)
+    return KMeansResult(cent, labels, dist, _label_counts(labels, k), dist.to(torch.float64).nansum(), n_iter)     # the RETURNED labels
 
 
 def cluster_scene(scene, encoder, k=None, centroids=None, divisor=1.0, stride=None, batch=512, nodata=None, mask=None, max_invalid=0.0,
                   rule="all", windows=None, border=None, fill=0, anchor="center", max_iter=100, tol=0.0, seed=0):
     """(cluster_map int64 [nH, nW], `KMeansResult`): the unsupervised classification of a scene.  The windows are taken as
     `classify_scene` takes them -- the whole grid, the ids in ``windows=``, or under ``nodata=`` / ``mask=`` the valid windows
-    (`valid_windows`, one host readback) -- encoded by `encode_scene` and clustered by `kmeans_fit(z, k, max_iter, tol, seed=seed)`;
+    (one host readback) -- encoded as `encode_scene` encodes them and clustered by `kmeans_fit(z, k, max_iter, tol, seed=seed)`;
     the result's rows are in the order of that window set.  Windows that are not run hold -1 in the map, as does a window whose
     latent row is not finite.
 
@@ -216,51 +224,26 @@ def cluster_scene(scene, encoder, k=None, centroids=None, divisor=1.0, stride=No
     Rejected before anything runs on the device: neither ``k`` nor ``centroids``; k outside 1..256 or greater than the number of
     windows to run (under nodata / mask that number is known only after the valid windows are counted: then it is checked right
     after, before the encoder runs); centroids of another width, dtype or device; and everything `classify_scene` rejects."""
-    from . import scene as _scene
-    enc = _scene._encoder_of(encoder)
-    patch = int(enc.image_size)
-    stride = patch if stride is None else int(stride)
-    _scene._rule_arg(rule)
-    _scene.invalid_threshold(patch, max_invalid)
-    masked = nodata is not None or mask is not None
-    if windows is not None and masked:
-        raise RuntimeError("windows= cannot be combined with nodata= or mask=")
-    _scene._check_scene(scene)
-    _, _, n_h, n_w, _ = _scene._border_arg(scene, patch, stride, border, fill, anchor)
-    _scene._nodata_arg(scene.dtype, nodata)
-    _scene._mask_arg(scene, mask)
-    if windows is not None and (not isinstance(windows, torch.Tensor) or windows.dim() != 1 or windows.dtype != torch.int64):
-        raise RuntimeError("windows must be a 1-D int64 tensor of window ids")
-    n_run = n_h * n_w if windows is None else int(windows.numel())
+    from .scene import _host_plan, _scene_latents
+    h = _host_plan(scene, encoder, divisor, stride, batch, nodata, mask, max_invalid, rule, windows, allow_empty=False, border=border,
+                   fill=fill, anchor=anchor)
+    width = int(h.enc.latent_dim)
     if centroids is not None:
-        _centroids_arg(centroids, int(enc.latent_dim), scene.device)
+        _centroids_arg(centroids, width, scene.device)
     elif k is None:
         raise RuntimeError("cluster_scene needs k (to fit) or centroids (to predict)")
     else:
-        _fit_args(max(n_run, 1), int(enc.latent_dim), k, max_iter, tol, "kmeans++")
-        if n_run < int(k):
-            raise RuntimeError(f"k = {k} is greater than the number of windows to run ({n_run})")
-    if n_run == 0:
-        raise RuntimeError("windows is empty")
-    if masked:
-        windows = _scene.valid_windows(scene, patch, stride, nodata=nodata, mask=mask, max_invalid=max_invalid, rule=rule, border=border,
-                                       fill=fill, anchor=anchor)
-        if windows.numel() == 0 or (centroids is None and windows.numel() < int(k)):
-            raise RuntimeError(f"only {windows.numel()} valid windows: nothing to cluster into k = {k}" if centroids is None
-                               else "no valid window")
-    z = _scene.encode_scene(scene, encoder, divisor=divisor, stride=stride, batch=batch, windows=windows, border=border, fill=fill,
-                            anchor=anchor)
+        _fit_args(h.n_max, width, k, max_iter, tol, "kmeans++")
+
+    def admit(n):                                       # fewer valid windows than the host could know
+        if n == 0 or (centroids is None and n < int(k)):
+            raise RuntimeError(f"only {n} valid windows: nothing to cluster into k = {k}" if centroids is None else "no valid window")
+
+    ids, z = _scene_latents(h, admit)
     if centroids is not None:
         cent = centroids.contiguous()
         labels, dist = _predict(z, cent)
-        counts = torch.zeros(cent.shape[0] + 1, dtype=torch.int64, device=z.device).scatter_add_(0, labels + 1, torch.ones_like(labels))[1:]
-        res = KMeansResult(cent, labels, dist, counts, dist.to(torch.float64).nansum(), 0)
+        res = KMeansResult(cent, labels, dist, _label_counts(labels, cent.shape[0]), dist.to(torch.float64).nansum(), 0)
     else:
         res = kmeans_fit(z, int(k), max_iter=max_iter, tol=tol, seed=seed)
-    if windows is None:
-        cmap = res.labels.reshape(n_h, n_w).clone()
-    else:
-        cmap = torch.full((n_h * n_w,), -1, dtype=torch.int64, device=z.device)
-        cmap[windows] = res.labels
-        cmap = cmap.reshape(n_h, n_w)
-    return cmap, res
+    return h.scatter(ids, res.labels, -1), res

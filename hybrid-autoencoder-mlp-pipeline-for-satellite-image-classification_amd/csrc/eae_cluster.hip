@@ -7,19 +7,15 @@
 //           sums go to the caller's workspace and a second kernel adds them in one fixed order and divides.  No float atomics.
 #include "eae_internal.h"
 #include "eae_common.hip.h"
+#include "eae_latent.hip.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int KM_NT = 256;        // threads per workgroup: 4 waves
 constexpr int KM_ROWS = 128;      // assign: rows of z per workgroup tile, 32 per wave
 constexpr int KM_LC = 64;         // assign: columns of z and c staged per pass
 constexpr int KM_LDS = KM_LC + 2; // LDS row stride in floats: lane (r, h) reads word r * 66 + kk + h -> bank 2r + h + kk, 64 different banks
-constexpr int KM_MAXK = 256, KM_MAXL = 256;
-
-// row of a 32x32 accumulator tile that register `reg` of a lane in half `h` holds (the column is lane & 31)
-__device__ __forceinline__ int acc_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
+constexpr int KM_MAXK = 256;
 
 // ---------------------------------------------------------------------------------------------------------------
 // assign.  Workgroup tile = 128 rows; wave w owns rows 32 w .. 32 w + 31 of it.  The columns are walked in passes of 64: the z tile's
@@ -46,12 +42,7 @@ __global__ EAE_NO_PK __launch_bounds__(KM_NT) void kmeans_assign_kernel(AssignAr
 
   // ||c_k||^2: thread k, one fixed-order chain
   for (int k = tid; k < KT * 32; k += KM_NT) {
-    float s = 0.f;
-    if (k < K) {
-      const float* ck = a.c + (size_t)k * L;
-      for (int l = 0; l < L; ++l) s = __builtin_fmaf(ck[l], ck[l], s);
-    }
-    cn[k] = s;
+    cn[k] = k < K ? row_sq_chain(a.c + (size_t)k * L, L) : 0.f;
   }
 
   const long long ntiles = (N + KM_ROWS - 1) / KM_ROWS;
@@ -243,7 +234,7 @@ __global__ EAE_NO_PK __launch_bounds__(KM_NT) void kmeans_finalize_kernel(FinalA
 }
 
 int kmeans_dims_ok(long long N, int L, int K) {
-  return N >= 1 && N < 0x80000000LL && L >= 1 && L <= KM_MAXL && K >= 1 && K <= KM_MAXK;
+  return latent_dims_ok(N, L) && K >= 1 && K <= KM_MAXK;
 }
 int kmeans_kt(int K) { return K <= 32 ? 1 : K <= 64 ? 2 : K <= 128 ? 4 : 8; }
 

@@ -11,21 +11,18 @@
 // showed write-through to gain).  No float atomics.
 #include "eae_internal.h"
 #include "eae_common.hip.h"
+#include "eae_latent.hip.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int KN_NT = 256;          // threads per workgroup: 4 waves
 constexpr int KN_QT = 128;          // queries per workgroup tile, 32 per wave
 constexpr int KN_BT = 64;           // bank rows per LDS tile: two 32-row MFMA tiles
 constexpr int KN_LC = 64;           // columns staged per pass
 constexpr int KN_LDS = KN_LC + 4;   // LDS row stride in floats (see lds_col)
-constexpr int KN_MAXL = 256, KN_MAXK = 32;
+constexpr int KN_MAXK = 32;
 constexpr int KN_MAXS = 512;        // most bank slices
 constexpr int KN_EMPTY = 0x7fffffff;    // row of an empty list slot: (+Inf, KN_EMPTY) is the greatest pair
-
-__device__ __forceinline__ int acc_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 
 // (s, m) < (ps, pm), lexicographic; false when s is a NaN.  Without short-circuit branches: it sits in unrolled code.
 __device__ __forceinline__ bool pair_less(float s, int m, float ps, int pm) { return (s < ps) | ((s == ps) & (m < pm)); }
@@ -38,10 +35,9 @@ __device__ __forceinline__ void kn_barrier() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
-// ||row||^2 as one sequential fma chain; NaN unless finite (a row with a NaN or an Inf, or whose squared norm overflows)
+// `row_sq_chain`, NaN unless finite (a row with a NaN or an Inf, or whose squared norm overflows)
 __device__ __forceinline__ float row_norm2(const float* p, int L) {
-  float s = 0.f;
-  for (int l = 0; l < L; ++l) s = __builtin_fmaf(p[l], p[l], s);
+  const float s = row_sq_chain(p, L);
   return s - s == 0.f ? s : __builtin_nanf("");
 }
 
@@ -320,7 +316,7 @@ __global__ EAE_NO_PK __launch_bounds__(64) void knn_merge_kernel(MergeArgs a) {
 }
 
 int knn_dims_ok(long long Nq, long long M, int L, int k) {
-  return Nq >= 1 && Nq < 0x80000000LL && M >= 1 && M < 0x80000000LL && L >= 1 && L <= KN_MAXL && k >= 1 && k <= KN_MAXK;
+  return latent_dims_ok(Nq, L) && latent_dims_ok(M, L) && k >= 1 && k <= KN_MAXK;
 }
 
 // The geometry, a function of (Nq, M) alone.  With 256 query tiles or more (two workgroups' worth of a 256-CU device at k <= 19, one

@@ -21,10 +21,11 @@ import torch
 
 from . import _lib
 from ._lib import check
+from .cluster import MAX_L, _int_arg, _rows_arg          # noqa: F401  one width limit, one check of fp32 rows and of k for both modules
 from .engine import _ptr, _stream, _require_gpu
+from .scene import _host_plan, _scene_latents
 
 MAX_K = 32
-MAX_L = 256
 METRICS = ("l2", "cosine")
 
 
@@ -36,23 +37,6 @@ class KNNResult(NamedTuple):
 
 
 # ---------------------------------------------------------------------------------------------------- host-side validation
-def _rows_arg(t, what):
-    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32:
-        raise RuntimeError(f"{what} must be a float32 tensor [rows, L]")
-    n, width = int(t.shape[0]), int(t.shape[1])
-    if not 1 <= width <= MAX_L:
-        raise RuntimeError(f"the latent width of {what} must be in 1..{MAX_L}, got {width}")
-    if not 1 <= n < 2 ** 31:
-        raise RuntimeError(f"the number of rows of {what} must be in 1..2^31-1, got {n}")
-    return n, width
-
-
-def _k_arg(k, most=MAX_K):
-    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not 1 <= int(k) <= most:
-        raise RuntimeError(f"k must be an integer in 1..{most}, got {k!r}")
-    return int(k)
-
-
 def _search_args(queries, bank, k, exclude_self, metric, most=MAX_K):
     nq, width = _rows_arg(queries, "queries")
     m, bwidth = _rows_arg(bank, "bank")
@@ -60,7 +44,7 @@ def _search_args(queries, bank, k, exclude_self, metric, most=MAX_K):
         raise RuntimeError(f"queries have width {width}, the bank {bwidth}")
     if queries.device != bank.device:
         raise RuntimeError(f"queries are on {queries.device}, the bank on {bank.device}")
-    k = _k_arg(k, most)
+    k = _int_arg(k, "k", 1, most)
     if metric not in METRICS:
         raise RuntimeError(f"metric must be one of {METRICS}, got {metric!r}")
     if exclude_self and queries is not bank and queries.shape != bank.shape:
@@ -163,80 +147,42 @@ def knn_classify(queries, bank, bank_labels, k, num_classes, weights="uniform", 
 
 
 # ---------------------------------------------------------------------------------------------------- scenes
-def _window_set(scene, encoder, stride, nodata, mask, max_invalid, rule, windows, border, fill, anchor):
-    """`cluster_scene`'s host-side checks of a window selection: (encoder, stride, n_h, n_w, masked)."""
-    from . import scene as _scene
-    enc = _scene._encoder_of(encoder)
-    patch = int(enc.image_size)
-    stride = patch if stride is None else int(stride)
-    _scene._rule_arg(rule)
-    _scene.invalid_threshold(patch, max_invalid)
-    masked = nodata is not None or mask is not None
-    if windows is not None and masked:
-        raise RuntimeError("windows= cannot be combined with nodata= or mask=")
-    _scene._check_scene(scene)
-    _, _, n_h, n_w, _ = _scene._border_arg(scene, patch, stride, border, fill, anchor)
-    _scene._nodata_arg(scene.dtype, nodata)
-    _scene._mask_arg(scene, mask)
-    if windows is not None and (not isinstance(windows, torch.Tensor) or windows.dim() != 1 or windows.dtype != torch.int64):
-        raise RuntimeError("windows must be a 1-D int64 tensor of window ids")
-    if windows is not None and windows.numel() == 0:
-        raise RuntimeError("windows is empty")
-    return enc, stride, n_h, n_w, masked
-
-
-def _encode_set(scene, encoder, enc, stride, masked, divisor, batch, nodata, mask, max_invalid, rule, windows, border, fill, anchor):
-    """(window ids of the set or None for the whole grid, latents [n_run, L])"""
-    from . import scene as _scene
-    if masked:
-        windows = _scene.valid_windows(scene, int(enc.image_size), stride, nodata=nodata, mask=mask, max_invalid=max_invalid, rule=rule,
-                                       border=border, fill=fill, anchor=anchor)
-        if windows.numel() == 0:
-            raise RuntimeError("no valid window")
-    z = _scene.encode_scene(scene, encoder, divisor=divisor, stride=stride, batch=batch, windows=windows, border=border, fill=fill,
-                            anchor=anchor)
-    return windows, z
-
-
 def similar_windows(scene, encoder, query, k, divisor=1.0, stride=None, batch=512, nodata=None, mask=None, max_invalid=0.0, rule="all",
                     windows=None, border=None, fill=0, anchor="center", metric="l2"):
     """`KNNResult` of window ids: query by example on a scene.  The window set is taken as `cluster_scene` takes it (the whole grid,
-    the ids in ``windows=``, or under ``nodata=`` / ``mask=`` the valid windows) and encoded once with `encode_scene`; the latents are
-    the bank.  idx [Nq, k] holds window ids of the grid (row-major, as `window_grid` numbers them), -1 in an empty slot.
+    the ids in ``windows=``, or under ``nodata=`` / ``mask=`` the valid windows) and encoded once, as `encode_scene` encodes it; the
+    latents are the bank.  idx [Nq, k] holds window ids of the grid (row-major, as `window_grid` numbers them), -1 in an empty slot.
 
     query: a 1-D int64 tensor of window ids -- each must belong to the window set (checked with one host readback); their latents
     come from the same pass, a query is never its own neighbour, and k is at most 31 (the search asks for k + 1 and drops the query's
     own entry) -- or a float32 [Nq, L] tensor of latents (L = the encoder's latent_dim), searched as they are."""
-    enc, stride, n_h, n_w, masked = _window_set(scene, encoder, stride, nodata, mask, max_invalid, rule, windows, border, fill, anchor)
+    h = _host_plan(scene, encoder, divisor, stride, batch, nodata, mask, max_invalid, rule, windows, allow_empty=False, border=border,
+                   fill=fill, anchor=anchor)
+    n_grid, width = h.n_h * h.n_w, int(h.enc.latent_dim)
     if metric not in METRICS:
         raise RuntimeError(f"metric must be one of {METRICS}, got {metric!r}")
     by_id = isinstance(query, torch.Tensor) and query.dim() == 1 and query.dtype == torch.int64
     if by_id:
-        k = _k_arg(k, MAX_K - 1)
+        k = _int_arg(k, "k", 1, MAX_K - 1)
         if query.numel() == 0:
             raise RuntimeError("query is empty")
         if query.device != scene.device:
             raise RuntimeError(f"query is on {query.device}, the scene on {scene.device}")
-        if bool(((query < 0) | (query >= n_h * n_w)).any()):
-            raise RuntimeError(f"query holds a window id outside the {n_h} x {n_w} grid")
+        if bool(((query < 0) | (query >= n_grid)).any()):
+            raise RuntimeError(f"query holds a window id outside the {h.n_h} x {h.n_w} grid")
     else:
-        k = _k_arg(k)
-        _, width = _rows_arg(query, "query")
-        if width != int(enc.latent_dim):
-            raise RuntimeError(f"query latents have width {width}, the encoder's latent_dim is {int(enc.latent_dim)}")
+        k = _int_arg(k, "k", 1, MAX_K)
+        if _rows_arg(query, "query")[1] != width:
+            raise RuntimeError(f"query latents have width {query.shape[1]}, the encoder's latent_dim is {width}")
         if query.device != scene.device:
             raise RuntimeError(f"query is on {query.device}, the scene on {scene.device}")
-    ids, z = _encode_set(scene, encoder, enc, stride, masked, divisor, batch, nodata, mask, max_invalid, rule, windows, border, fill,
-                         anchor)
+    ids, z = _scene_latents(h)
     if not by_id:
         idx, dist = _knn(query, z, k, -1, metric)
     else:
-        if ids is None:
-            pos = query
-        else:
-            table = torch.full((n_h * n_w,), -1, dtype=torch.int64, device=z.device)
-            table[ids] = torch.arange(ids.numel(), device=z.device)
-            pos = table[query]
+        pos = query
+        if ids is not None:
+            pos = h.scatter(ids, torch.arange(ids.numel(), device=z.device), -1, flat=True)[query]       # window id -> row of z
             if bool((pos < 0).any()):
                 raise RuntimeError("query holds a window id that is not in the window set")
         idx1, dist1 = _knn(z[pos].contiguous(), z, k + 1, -1, metric)
@@ -256,23 +202,16 @@ def knn_classify_scene(scene, encoder, bank, bank_labels, k, num_classes, weight
     """(label_map int64 [nH, nW], votes float32 [num_classes, nH, nW]): the class map of a scene by `knn_classify` of its windows'
     latents (`encode_scene`, with `cluster_scene`'s window selection) against a labelled bank [M, L], L = the encoder's latent_dim.
     Windows that are not run hold -1 and 0 votes, as does a window with no vote."""
-    enc, stride, n_h, n_w, masked = _window_set(scene, encoder, stride, nodata, mask, max_invalid, rule, windows, border, fill, anchor)
-    m, width = _rows_arg(bank, "bank")
-    if width != int(enc.latent_dim):
-        raise RuntimeError(f"the bank has width {width}, the encoder's latent_dim is {int(enc.latent_dim)}")
+    h = _host_plan(scene, encoder, divisor, stride, batch, nodata, mask, max_invalid, rule, windows, allow_empty=False, border=border,
+                   fill=fill, anchor=anchor)
+    if _rows_arg(bank, "bank")[1] != int(h.enc.latent_dim):
+        raise RuntimeError(f"the bank has width {bank.shape[1]}, the encoder's latent_dim is {int(h.enc.latent_dim)}")
     if bank.device != scene.device:
         raise RuntimeError(f"the bank is on {bank.device}, the scene on {scene.device}")
-    k = _k_arg(k)
+    k = _int_arg(k, "k", 1, MAX_K)
     if metric not in METRICS:
         raise RuntimeError(f"metric must be one of {METRICS}, got {metric!r}")
     num_classes = _classify_args(bank, bank_labels, num_classes, weights)
-    ids, z = _encode_set(scene, encoder, enc, stride, masked, divisor, batch, nodata, mask, max_invalid, rule, windows, border, fill,
-                         anchor)
+    ids, z = _scene_latents(h)
     labels, votes = knn_classify(z, bank, bank_labels, k, num_classes, weights=weights, metric=metric)
-    if ids is None:
-        return labels.reshape(n_h, n_w).clone(), votes.t().reshape(num_classes, n_h, n_w).contiguous()
-    lmap = torch.full((n_h * n_w,), -1, dtype=torch.int64, device=z.device)
-    lmap[ids] = labels
-    vmap = torch.zeros((num_classes, n_h * n_w), dtype=torch.float32, device=z.device)
-    vmap[:, ids] = votes.t()
-    return lmap.reshape(n_h, n_w), vmap.reshape(num_classes, n_h, n_w)
+    return h.scatter(ids, labels, -1), h.scatter(ids, votes, 0.0, channels_first=True)

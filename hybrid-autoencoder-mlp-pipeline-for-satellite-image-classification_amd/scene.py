@@ -341,12 +341,53 @@ def _encoder_of(encoder):
     raise RuntimeError(f"encoder must be an Encoder or a SupervisedAutoencoder, got {type(encoder).__name__}")
 
 
-def _scene_desc(scene, divisor, patch, stride, border=None, fill=0, anchor="center", any_patch=False):
-    """(EaeScene, keep-alive tensors, nH, nW) of a scene that has passed `_check_scene`: device, band count, grid (of the virtual
-    scene under a border), border arguments and divisor are validated here, before any kernel."""
-    c, h, w = (int(v) for v in scene.shape)
+class _Host(NamedTuple):
+    """A scene call as the host checks leave it, before anything touches a device.  `_geometry` fills the first nine fields (what
+    `_desc` makes a descriptor from); `_host_plan` adds the rest for the functions that run a model."""
+    scene: torch.Tensor
+    div: torch.Tensor            # fp32 [C], wherever the caller's divisor was
+    patch: int
+    stride: int
+    n_h: int
+    n_w: int
+    border: int                  # mode id
+    fill: float
+    pads: tuple
+    enc: object = None
+    batch: int = 0
+    nodata: tuple = (0, 0.0)     # (mode, value) of the C call
+    rule: int = 0
+    mask: object = None          # uint8 [H, W] or None
+    t: int = 0                   # `invalid_threshold`
+    windows: object = None       # the caller's ids (type, dtype, device and emptiness checked; their range is not: it needs a readback)
+
+    @property
+    def masked(self):
+        return self.nodata[0] != _NODATA_NONE or self.mask is not None
+
+    @property
+    def n_max(self):
+        """Upper bound on the number of windows to run: exact unless `masked`, where the valid windows are counted on the device."""
+        return self.n_h * self.n_w if self.windows is None else int(self.windows.numel())
+
+    def scatter(self, ids, rows, fill, channels_first=False, flat=False):
+        """Per-window rows [n_run] or [n_run, F] of the run windows (ids; None: the whole grid, in order) as a map over the grid:
+        [nH, nW] or [nH, nW, F], `fill` where no window ran.  channels_first: [F, nH, nW]; flat: the grid as one axis of nH * nW."""
+        if ids is None:
+            out = rows.clone()
+        else:
+            out = torch.full((self.n_h * self.n_w,) + rows.shape[1:], fill, dtype=rows.dtype, device=rows.device)
+            out[ids] = rows
+        if not flat:
+            out = out.reshape((self.n_h, self.n_w) + rows.shape[1:])
+        return out.movedim(-1, 0).contiguous() if channels_first else out
+
+
+def _geometry(scene, divisor, patch, stride, border=None, fill=0, anchor="center", any_patch=False):
+    """Every host-side check of a scene that has passed `_check_scene`: the grid (of the virtual scene under a border), the border
+    arguments, the band count and the divisor.  No device is touched."""
+    c = int(scene.shape[0])
     mode, fill, n_h, n_w, pads = _border_arg(scene, patch, stride, border, fill, anchor, any_patch)
-    _require_gpu(scene.device)
     if not 1 <= c <= 16:
         raise RuntimeError(f"scene: in_channels must be in 1..16, got {c}")
     div = torch.as_tensor(divisor, dtype=torch.float32).reshape(-1)
@@ -354,11 +395,24 @@ def _scene_desc(scene, divisor, patch, stride, border=None, fill=0, anchor="cent
         div = div.expand(c)
     if div.numel() != c:
         raise RuntimeError(f"divisor must have one value per band ({c}), got {div.numel()}")
-    div = div.to(scene.device).contiguous()
-    scene = scene.contiguous()
-    desc = _lib.EaeScene(C.c_void_p(scene.data_ptr()), C.c_void_p(div.data_ptr()), _DTYPES[scene.dtype], c, h, w, int(patch),
-                         int(stride), mode, *pads, fill)
-    return desc, (scene, div), n_h, n_w
+    return _Host(scene, div, int(patch), int(stride), n_h, n_w, mode, fill, pads)
+
+
+def _desc(g):
+    """(EaeScene, keep-alive tensors) of a `_Host`: the first step that needs the device."""
+    _require_gpu(g.scene.device)
+    div = g.div.to(g.scene.device).contiguous()
+    scene = g.scene.contiguous()
+    c, h, w = (int(v) for v in scene.shape)
+    desc = _lib.EaeScene(C.c_void_p(scene.data_ptr()), C.c_void_p(div.data_ptr()), _DTYPES[scene.dtype], c, h, w, g.patch, g.stride,
+                         g.border, *g.pads, g.fill)
+    return desc, (scene, div)
+
+
+def _scene_desc(scene, divisor, patch, stride, border=None, fill=0, anchor="center", any_patch=False):
+    """(EaeScene, keep-alive tensors, nH, nW) for the functions that run no model: `_geometry`, then `_desc`."""
+    g = _geometry(scene, divisor, patch, stride, border, fill, anchor, any_patch)
+    return _desc(g) + (g.n_h, g.n_w)
 
 
 def _invalid_counts(desc, keep, n_h, n_w, mode, value, rule, mask):
@@ -394,8 +448,9 @@ def scene_windows(scene, divisor, patch, stride, first=0, count=None, border=Non
     """fp32 NCHW [count,C,P,P] of windows first .. first+count-1 (count=None: to the end of the grid).  border / fill / anchor:
     module docstring, "Borders".  No model runs: without a border P is any positive size."""
     _check_scene(scene)
-    desc, keep, n_h, n_w = _scene_desc(scene, divisor, patch, stride, border, fill, anchor, any_patch=True)
-    first, count = _range(first, count, n_h * n_w)
+    g = _geometry(scene, divisor, patch, stride, border, fill, anchor, any_patch=True)
+    first, count = _range(first, count, g.n_h * g.n_w)
+    desc, keep = _desc(g)
     lib = _lib.load()
     out = torch.empty((count, keep[0].shape[0], int(patch), int(patch)), dtype=torch.float32, device=keep[0].device)
     with torch.cuda.device(keep[0].device):
@@ -421,15 +476,9 @@ def valid_windows(scene, patch, stride, nodata=None, mask=None, max_invalid=0.0,
     return _select(counts, t)
 
 
-def _prepare(enc, desc, keep, batch):
-    """The engine of the encoder for this scene: band count, device, bf16 only, parameters re-read."""
-    if desc.C != int(enc.in_channels):
-        raise RuntimeError(f"scene has {desc.C} bands, the encoder takes in_channels={enc.in_channels}")
-    if int(batch) < 1:
-        raise RuntimeError(f"batch must be positive, got {batch}")
-    if next(enc.parameters()).device != keep[0].device:
-        raise RuntimeError("the scene and the model must be on the same device")
-    eng = engine_for(enc, max_batch=int(batch))
+def _prepare(enc, batch):
+    """The engine of the encoder: bf16 only, parameters re-read."""
+    eng = engine_for(enc, max_batch=batch)
     if eng.quant != 0:
         raise RuntimeError("scene classification supports bf16 engines only (quant=1 / fp8 is not supported)")
     eng.params_changed()
@@ -437,8 +486,8 @@ def _prepare(enc, desc, keep, batch):
 
 
 class _Plan(NamedTuple):
-    """What a model-running scene function works from (`_plan`).  windows: None = every window of the grid (the range entry points of
-    the C library, no id list), else the int64 ids of the windows to run (the index-driven entry points; may be empty)."""
+    """What a model-running scene function works from on the device (`_device_plan`).  windows: None = every window of the grid (the
+    range entry points of the C library, no id list), else the int64 ids of the windows to run (the index-driven ones; may be empty)."""
     eng: object
     desc: object
     keep: tuple
@@ -465,32 +514,69 @@ class _Plan(NamedTuple):
                 check(index_fn(eng.ctx, *head, _stream(), C.byref(self.desc), _ptr(w), w.numel(), *map(_ptr, outs)))
 
 
-def _plan(scene, encoder, divisor, stride, batch, nodata=None, mask=None, max_invalid=0.0, rule="all", windows=None, allow_empty=True,
-          blend=False, stitched=False, border=None, fill=0, anchor="center"):
-    """Every model-running function starts here: (1) all host-side validation, before an engine exists or a kernel runs; (2) `_prepare`;
-    (3) the window set -- None for the whole grid, the given ids, or under nodata / mask the valid ids (`_select`: the one ``.item()``)."""
+def _host_plan(scene, encoder, divisor, stride, batch, nodata=None, mask=None, max_invalid=0.0, rule="all", windows=None,
+               allow_empty=True, blend=False, stitched=False, border=None, fill=0, anchor="center", mlp=...):
+    """Every model-running scene function starts here: all the validation that needs no device, as a `_Host`.  Neither the library nor
+    an engine is loaded, so a bad argument is reported by its own message on any machine.  mlp: the classifier that reads the
+    latents, where there is one."""
+    if mlp is not ...:
+        from .modules import MLP
+        if not isinstance(mlp, MLP):
+            raise RuntimeError(f"mlp must be an MLP, got {type(mlp).__name__}")
+        if int(mlp.input_dim) != int(_encoder_of(encoder).latent_dim):
+            raise RuntimeError(f"the MLP takes input_dim={mlp.input_dim}, the encoder's latent_dim is {_encoder_of(encoder).latent_dim}")
     rid = _rule_arg(rule)
     enc = _encoder_of(encoder)
     patch = int(enc.image_size)
-    stride = patch if stride is None else int(stride)
     t = invalid_threshold(patch, max_invalid)
-    masked = nodata is not None or mask is not None
-    if windows is not None and masked:
+    if windows is not None and (nodata is not None or mask is not None):
         raise RuntimeError("windows= cannot be combined with nodata= or mask=")
     _check_scene(scene)
-    desc, keep, n_h, n_w = _scene_desc(scene, divisor, patch, stride, border, fill, anchor)
+    g = _geometry(scene, divisor, patch, patch if stride is None else int(stride), border, fill, anchor)
     if blend:
-        cell_grid(n_h, n_w, patch, stride)               # the stride must divide the patch size
+        cell_grid(g.n_h, g.n_w, patch, g.stride)         # the stride must divide the patch size
     if stitched:
-        owned_span(0, n_h, patch, stride)                # patch - stride must be even
-    mode, value = _nodata_arg(scene.dtype, nodata)
+        owned_span(0, g.n_h, patch, g.stride)            # patch - stride must be even
+    nd = _nodata_arg(scene.dtype, nodata)
     m = _mask_arg(scene, mask)
     if windows is not None:
-        windows = _windows_arg(windows, scene.device, n_h * n_w, allow_empty)
-    eng = _prepare(enc, desc, keep, batch)
-    if masked:
-        windows = _select(_invalid_counts(desc, keep + (m,), n_h, n_w, mode, value, rid, m), t)
-    return _Plan(eng, desc, keep, n_h, n_w, patch, stride, windows)
+        windows = _windows_arg(windows, scene.device, g.n_h * g.n_w, allow_empty, check_range=False)
+    if scene.shape[0] != int(enc.in_channels):
+        raise RuntimeError(f"scene has {scene.shape[0]} bands, the encoder takes in_channels={enc.in_channels}")
+    if int(batch) < 1:
+        raise RuntimeError(f"batch must be positive, got {batch}")
+    if next(enc.parameters()).device != scene.device:
+        raise RuntimeError("the scene and the model must be on the same device")
+    return g._replace(enc=enc, batch=int(batch), nodata=nd, rule=rid, mask=m, t=t, windows=windows)
+
+
+def _device_plan(h):
+    """The device half of a model-running function, from its `_Host`: `_require_gpu` and the descriptor (`_desc`), the range of the
+    caller's window ids (one aminmax readback), the engine (`_prepare`), and under nodata / mask the valid ids (`_select`: the one
+    ``.item()``; ids it produced are not read back again)."""
+    desc, keep = _desc(h)
+    windows = h.windows
+    if windows is not None:
+        windows = _windows_arg(windows, h.scene.device, h.n_h * h.n_w, allow_empty=True, check_range=True)
+    eng = _prepare(h.enc, h.batch)
+    if h.masked:
+        windows = _select(_invalid_counts(desc, keep + (h.mask,), h.n_h, h.n_w, *h.nodata, h.rule, h.mask), h.t)
+    return _Plan(eng, desc, keep, h.n_h, h.n_w, h.patch, h.stride, windows)
+
+
+def _scene_latents(h, admit=None):
+    """(ids, z): the window set of a `_Host` -- None for the whole grid, else the int64 ids run, the caller's or under nodata / mask
+    the valid ones -- and its latents z [n_run, L], row by row in that order.  One descriptor, one select, one index-driven encode.
+    admit(n_run) is called once the number is known and before the encoder runs (default: at least one window)."""
+    p = _device_plan(h)
+    n = p.n_h * p.n_w if p.windows is None else p.windows.numel()
+    if admit is not None:
+        admit(n)
+    elif n == 0:
+        raise RuntimeError("no valid window")
+    z = torch.empty((n, p.eng.latent), dtype=torch.float32, device=p.eng.device)
+    p.run(p.eng.lib.eae_scene_encode, p.eng.lib.eae_scene_encode_windows, z)
+    return p.windows, z
 
 
 def encode_scene(scene, encoder, divisor=1.0, stride=None, batch=512, windows=None, border=None, fill=0, anchor="center"):
@@ -498,12 +584,8 @@ def encode_scene(scene, encoder, divisor=1.0, stride=None, batch=512, windows=No
     engine's max_batch, at least this).  stride=None: the patch size (non-overlapping windows).
     windows: a non-empty 1-D int64 device tensor of window ids (any order, duplicates allowed): z [len(windows), L] in that order.
     border / fill / anchor: module docstring, "Borders" (the grid is then `border_grid`'s)."""
-    p = _plan(scene, encoder, divisor, stride, batch, windows=windows, allow_empty=False, border=border, fill=fill, anchor=anchor)
-    eng = p.eng
-    n = p.n_h * p.n_w if p.windows is None else p.windows.numel()
-    z = torch.empty((n, eng.latent), dtype=torch.float32, device=eng.device)
-    p.run(eng.lib.eae_scene_encode, eng.lib.eae_scene_encode_windows, z)
-    return z
+    return _scene_latents(_host_plan(scene, encoder, divisor, stride, batch, windows=windows, allow_empty=False, border=border,
+                                     fill=fill, anchor=anchor))[1]
 
 
 def classify_scene(scene, encoder, mlp, divisor=1.0, stride=None, batch=512, blend=False, nodata=None, mask=None, max_invalid=0.0,
@@ -519,15 +601,14 @@ def classify_scene(scene, encoder, mlp, divisor=1.0, stride=None, batch=512, ble
 
     border / fill / anchor (module docstring, "Borders"): the grid covers the whole scene (`border_grid`), so every pixel lies in a
     window and, with blend=True, in a cell of the virtual grid's cell map."""
+    return _classify(_host_plan(scene, encoder, divisor, stride, batch, nodata, mask, max_invalid, rule, windows, blend=blend,
+                                border=border, fill=fill, anchor=anchor, mlp=mlp), mlp, blend)
+
+
+def _classify(h, mlp, blend):
+    """`classify_scene` from its `_Host`."""
     from .mlp_engine import mlp_engine_for
-    from .modules import MLP
-    if not isinstance(mlp, MLP):
-        raise RuntimeError(f"mlp must be an MLP, got {type(mlp).__name__}")
-    enc = _encoder_of(encoder)
-    if int(mlp.input_dim) != int(enc.latent_dim):
-        raise RuntimeError(f"the MLP takes input_dim={mlp.input_dim}, the encoder's latent_dim is {enc.latent_dim}")
-    p = _plan(scene, encoder, divisor, stride, batch, nodata, mask, max_invalid, rule, windows, blend=blend, border=border, fill=fill,
-              anchor=anchor)
+    p = _device_plan(h)
     eng, n_h, n_w = p.eng, p.n_h, p.n_w
     if next(mlp.parameters()).device != eng.device:
         raise RuntimeError("the MLP and the encoder must be on the same device")
@@ -567,8 +648,8 @@ def scene_reconstruction_error(scene, autoencoder, divisor=1.0, stride=None, bat
     without a window to run nothing is launched.  A valid window that holds some invalid pixels is scored with them as stored.
     border / fill / anchor (module docstring, "Borders"): the mean runs over the window as the model saw it, padded pixels included."""
     _autoencoder_arg(autoencoder)
-    p = _plan(scene, autoencoder, divisor, stride, batch, nodata, mask, max_invalid, rule, windows, border=border, fill=fill,
-              anchor=anchor)
+    p = _device_plan(_host_plan(scene, autoencoder, divisor, stride, batch, nodata, mask, max_invalid, rule, windows, border=border,
+                                fill=fill, anchor=anchor))
     err = p.out((p.n_h, p.n_w), float("nan"))
     band = p.out((p.desc.C, p.n_h, p.n_w), float("nan")) if per_band else None
     p.run(p.eng.lib.eae_scene_recon_error, p.eng.lib.eae_scene_recon_error_windows, err, band)
@@ -587,8 +668,8 @@ def reconstruct_scene(scene, autoencoder, divisor=1.0, stride=None, batch=512, r
     border / fill / anchor (module docstring, "Borders"): recon [C,H,W] and residual [H,W] of the REAL scene.  The owned spans are
     those of the virtual grid, which covers the scene, so every pixel has an owner; a window stores the real pixels of its span."""
     _autoencoder_arg(autoencoder)
-    p = _plan(scene, autoencoder, divisor, stride, batch, nodata, mask, max_invalid, rule, windows, stitched=True, border=border,
-              fill=fill, anchor=anchor)
+    p = _device_plan(_host_plan(scene, autoencoder, divisor, stride, batch, nodata, mask, max_invalid, rule, windows, stitched=True,
+                                border=border, fill=fill, anchor=anchor))
     h_g, w_g = (p.n_h - 1) * p.stride + p.patch, (p.n_w - 1) * p.stride + p.patch
     if border is not None:
         h_g, w_g = p.desc.H, p.desc.W
@@ -938,19 +1019,12 @@ def evaluate_scene(scene, encoder, mlp, truth, divisor=1.0, stride=None, batch=5
 
     Returns {"confusion": int64 [K+1,K+1] on the device, "metrics": `report.confusion_metrics` of it, "probs", "labels": what
     `classify_scene` returned}."""
-    from .modules import MLP
     from .report import confusion_metrics
-    enc = _encoder_of(encoder)
-    if not isinstance(mlp, MLP):
-        raise RuntimeError(f"mlp must be an MLP, got {type(mlp).__name__}")
-    patch = int(enc.image_size)
-    stride = patch if stride is None else int(stride)
-    if not blend and stride != patch:
-        raise RuntimeError(f"blend=False needs stride == patch ({patch}): overlapping windows give a pixel no single class without "
-                           f"blending, got stride {stride}")
-    if blend:
-        cell_grid(1, 1, patch, stride)                   # the stride must divide the patch size
-    _check_scene(scene)
+    plan = _host_plan(scene, encoder, divisor, stride, batch, nodata, mask, max_invalid, rule, windows, blend=blend, border=border,
+                      fill=fill, anchor=anchor, mlp=mlp)
+    if not blend and plan.stride != plan.patch:
+        raise RuntimeError(f"blend=False needs stride == patch ({plan.patch}): overlapping windows give a pixel no single class without "
+                           f"blending, got stride {plan.stride}")
     h, w = int(scene.shape[1]), int(scene.shape[2])
     if not isinstance(truth, torch.Tensor) or tuple(truth.shape) != (h, w):
         got = tuple(truth.shape) if isinstance(truth, torch.Tensor) else type(truth).__name__
@@ -964,7 +1038,6 @@ def evaluate_scene(scene, encoder, mlp, truth, divisor=1.0, stride=None, batch=5
         if region.device != scene.device:
             raise RuntimeError(f"region is on {region.device}, the scene on {scene.device}")
         exclude = region == 0
-    pads = _border_arg(scene, patch, stride, border, fill, anchor)[4]
     k = int(mlp.num_classes)
     # the remaining host checks of scene_confusion, before a kernel runs (truth's dtype, K, ignore)
     if truth.dtype.is_floating_point or truth.dtype.is_complex or truth.dtype == torch.bool:
@@ -972,9 +1045,8 @@ def evaluate_scene(scene, encoder, mlp, truth, divisor=1.0, stride=None, batch=5
     if not 1 <= k <= 64:
         raise RuntimeError(f"the MLP's num_classes must be in 1..64, got {k}")
     _ignore_arg(ignore, k)
-    probs, labels = classify_scene(scene, encoder, mlp, divisor, stride, batch, blend, nodata, mask, max_invalid, rule, windows, border,
-                                   fill, anchor)
-    cm = scene_confusion(labels, truth, k, cell=stride, origin=(pads[0], pads[2]), mask=exclude, ignore=ignore)
+    probs, labels = _classify(plan, mlp, blend)
+    cm = scene_confusion(labels, truth, k, cell=plan.stride, origin=(plan.pads[0], plan.pads[2]), mask=exclude, ignore=ignore)
     return {"confusion": cm, "metrics": confusion_metrics(cm), "probs": probs, "labels": labels}
 
 
