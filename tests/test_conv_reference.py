@@ -1,12 +1,14 @@
 """tests/conv_ref.py pinned (CPU): the three fp64 references against torch in float64, the exactness budget of every row of the
 case tables, and the premise of the bit-exact GPU tests shown on the CPU -- an fp32 accumulation in a shuffled order equals the fp64
-result bit for bit."""
+result bit for bit.  Likewise tests/edge_ref.py for the two C-band edge layers: every row of its tables built and held to its budget,
+its launch prediction, its references against oracle/ae_numpy.py, and the bound on x_hat."""
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import conv_ref as R
+import edge_ref as E
 
 MAPS = [(2, 5, 7, 8, 8), (3, 4, 6, 6, 14), (1, 3, 5, 12, 4)]          # (N, Cin, Cout, H, W) of the conv's input: square and rectangular
 
@@ -164,6 +166,153 @@ def test_fp32_accumulation_in_any_order_is_exact_for_the_largest_wgrad_row():
             b2 = bp[:, :, ky:ky + 2 * hs:2, kx:kx + 2 * ws:2].transpose(1, 0, 2, 3).reshape(cb, -1)[:, perm]
             got[:, :, ky, kx] = np.ascontiguousarray(s2) @ np.ascontiguousarray(b2).T
     assert np.array_equal(got, R.exact_f32(ref))
+
+
+# ---------------------------------------------------------------------------------------------------- the edge layers (edge_ref.py)
+def test_edge_tables_are_the_products_the_kernels_instantiate():
+    assert E.EDGE_BANDS == [1, 3, 5, 8, 9, 13, 16]
+    assert [E.edge_cp(c) for c in E.EDGE_BANDS] == [8, 4, 8, 8, 16, 16, 16]
+    assert [E.edge_nkc(c) for c in E.EDGE_BANDS] == [1, 1, 2, 3, 3, 4, 5]
+    assert all(h % 8 == 0 and w % 64 == 0 for h, w, b in E.EDGE_GRIDS) and len(E.EDGE_GRIDS) == 6
+    assert [(h // 8, w // 64, b) for h, w, b in E.EDGE_GRIDS] == [(1, 1, 1), (1, 1, 3), (2, 2, 1), (1, 3, 2), (3, 1, 2), (3, 3, 1)]
+    assert len(set(E.EDGE_CONV_INSTANCES)) == 4 and len(set(E.EDGE_WGRAD_INSTANCES)) == 3 and len(set(E.DECONV4_INSTANCES)) == 2
+    assert len(set(E.EDGE_CONV_CASES)) == 4 * 7 * 6 and len(set(E.DECONV4_CASES)) == 2 * 7 * 6
+    assert len(set(E.EDGE_WGRAD_CASES)) == 3 * 7 * 6 + len(E.EDGE_WGRAD_MULTI_TILE)
+    assert any(case[2] == 16 for case in E.EDGE_WGRAD_MULTI_TILE)             # five k chunks inside the tile loop
+
+
+def test_edge_budget_of_every_row():
+    """By construction: S <= terms * max |operand| * max |weight| (+ max |bias|); the 520-image rows are the tight ones."""
+    for case in E.EDGE_CONV_CASES:
+        R.assert_budget(*E.edge_conv_budget(*case))
+    for case in E.DECONV4_CASES:
+        R.assert_budget(*E.deconv4_budget(*case))
+    for case in E.EDGE_WGRAD_CASES:
+        R.assert_budget(*E.edge_wgrad_budget(*case))
+    S, q = E.edge_wgrad_budget(0, 2, 3, 8, 64, 520)
+    assert 2.0 ** 22 < S * 2.0 ** q < 2.0 ** 23                                   # 66560 positions x 3.5 x 2^5 = 7.5 M
+    with pytest.raises(AssertionError):
+        R.assert_budget(*E.edge_wgrad_budget(0, 2, 3, 8, 64, 1200))
+
+
+def test_edge_wgrad_launch_prediction(monkeypatch):
+    monkeypatch.delenv("EAE_EDGE_WGRAD_BLOCKS", raising=False)
+    monkeypatch.delenv("EAE_EDGE_WGRAD_SIDE_BLOCKS", raising=False)
+    for case, want in E.EDGE_WGRAD_MULTI_TILE.items():
+        kind, smode, c, h, w, b, slices = case
+        got = E.expected_edge_wgrad_launch(kind, c, h, w, b, E.edge_wgrad_scratch_floats(case))
+        assert got == want and got[2] > 1, (case, got)
+        tiles, blocks, per = got
+        assert (blocks - 1) * per < tiles <= blocks * per
+    # the last workgroup of the rows that are meant to have a short one
+    assert 520 - 173 * 3 == 1 and 9 - 5 == 4
+    # every grid row: one tile per workgroup
+    for case in E.EDGE_WGRAD_GRID_CASES:
+        kind, smode, c, h, w, b, slices = case
+        tiles, blocks, per = E.expected_edge_wgrad_launch(kind, c, h, w, b, E.edge_wgrad_scratch_floats(case))
+        assert tiles == E.edge_tiles(h, w, b) == blocks and per == 1
+    # the benchmark's batch: 4096 tiles, 8 per workgroup on the main launch and 16 on the side launch
+    assert E.expected_edge_wgrad_launch(0, 3, 64, 64, 512, 1 << 30) == (4096, 512, 8)
+    assert E.expected_edge_wgrad_launch(1, 3, 64, 64, 512, 1 << 30) == (4096, 256, 16)
+    # the two variables, each for its own source kind
+    monkeypatch.setenv("EAE_EDGE_WGRAD_BLOCKS", "100")
+    assert E.expected_edge_wgrad_launch(0, 3, 8, 64, 520, 1 << 30) == (520, 87, 6)
+    assert E.expected_edge_wgrad_launch(1, 3, 8, 64, 520, 1 << 30) == (520, 174, 3)
+    monkeypatch.setenv("EAE_EDGE_WGRAD_SIDE_BLOCKS", "1024")
+    assert E.expected_edge_wgrad_launch(1, 3, 8, 64, 520, 1 << 30) == (520, 520, 1)
+
+
+def _exact_within(k, bound, q):
+    """the row's measured sums of magnitudes are under the bound promised by construction, that bound is within the fp32 budget, and
+    the fp64 reference converts to fp32 without loss"""
+    assert k.S.max() <= bound
+    R.assert_budget(bound, q)
+    R.assert_budget(k.S, q)
+    assert np.all(np.abs(k.exact) <= k.S)
+    return R.exact_f32(k.exact)
+
+
+def test_every_edge_conv_row_is_exact_in_fp32():
+    rounded = 0.0
+    for case in E.EDGE_CONV_CASES:
+        k = E.edge_conv_case(*case)
+        y = _exact_within(k, *E.edge_conv_budget(*case))
+        assert np.array_equal(k.x.value * 4, np.round(k.x.value * 4)) and np.abs(k.x.value).max() <= 1.0
+        assert np.array_equal(R.bf16_round(k.x.tensors[0]), k.x.tensors[0])      # the fp32 image survives conv1's rounding on load
+        assert np.array_equal(y * 128, np.round(y * 128))
+        assert (k.bias is not None) == (case[1] == 0) and (k.prev is not None) == (case[1] == 1)
+        if case[2] >= 3:
+            rounded = max(rounded, float((R.bf16_round(y) != y).mean()))
+        # the NHWC-CP form of the operand: bands >= C are zero
+        c = case[2]
+        p = E.to_nhwcp(k.x.tensors[0], c)
+        assert p.shape[3] == E.edge_cp(c) and not p[..., c:].any() and np.array_equal(p[..., :c].transpose(0, 3, 1, 2), k.x.tensors[0])
+    assert rounded > 0.2                                          # the epilogue's rounding is exercised
+
+
+def test_every_edge_wgrad_row_is_exact_in_fp32():
+    """Measured on the operands, not assumed: the 520-image rows sum 66560 positions."""
+    for case in E.EDGE_WGRAD_CASES:
+        k = E.edge_wgrad_case(*case)
+        dw = _exact_within(k, *E.edge_wgrad_budget(*case))
+        assert dw.shape == (32, case[2], 3, 3) and np.array_equal(dw * 32, np.round(dw * 32))
+        assert k.side.mode == case[1]
+
+
+def test_every_deconv4_row_is_exact_in_fp32():
+    lo = hi = 0.0
+    for case in E.DECONV4_CASES:
+        k = E.deconv4_case(*case)
+        s = _exact_within(k, *E.deconv4_budget(*case))
+        assert np.array_equal(s * 128, np.round(s * 128))
+        assert k.target.dtype == np.float32 and 0.0 <= k.target.min() and k.target.max() < 1.0
+        assert np.log2(float(k.gscale)) % 1 == 0
+        assert (np.abs(s) < 0.5).any()
+        lo, hi = min(lo, float(s.min())), max(hi, float(s.max()))
+    assert lo < -4.0 and hi > 4.0                                 # the sigmoid's slope and both of its shoulders
+
+
+def test_edge_references_match_the_oracle():
+    """One random non-dyadic case per kernel against oracle/ae_numpy.py.  Its backward functions accumulate in the dtype of the
+    arrays they are given: fp64 operands give fp64 round-off.  Its forward functions accumulate the nine taps in an fp32 array
+    whatever they are given: they agree to that array's own rounding, ten fp32 roundings of magnitude <= the sum of |terms|."""
+    from oracle import ae_numpy as O
+    rng = np.random.default_rng(77)
+    c, b, h, w = 5, 2, 8, 12
+    x = rng.standard_normal((b, c, h, w)).astype(np.float32).astype(np.float64)           # fp32 values: the oracle pads in fp32
+    dy = rng.standard_normal((b, 32, h // 2, w // 2)).astype(np.float32).astype(np.float64)
+    wc = rng.standard_normal((32, c, 3, 3))
+    bias = rng.standard_normal(32)
+    # conv1's weight gradient: conv_s2_bwd's dw
+    _, dw, _ = O.conv_s2_bwd(x, np.zeros_like(wc), dy)
+    np.testing.assert_allclose(R.wgrad_s2(dy, x), dw, rtol=1e-12, atol=1e-12)
+    # deconv4's weight gradient ([32][C]: the small map is its input) and its backward-data (a conv of the gradient): deconv_s2_bwd
+    dx, dwd, _ = O.deconv_s2_bwd(dy, wc, x)
+    np.testing.assert_allclose(R.wgrad_s2(dy, x), dwd, rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose(R.conv_s2(x, wc), dx, rtol=1e-12, atol=1e-12)
+    # conv1 forward
+    y = O.conv_s2_fwd(x, wc, bias)
+    tol = 10 * 2.0 ** -24 * (R.conv_s2_abs(x, wc) + np.abs(bias)[None, :, None, None])
+    assert y.dtype == np.float32 and np.all(np.abs(R.conv_s2(x, wc) + bias[None, :, None, None] - y) <= tol)
+    # deconv4 forward
+    bc = rng.standard_normal(c)
+    s = O.deconv_s2_fwd(dy, wc, bc)
+    tol = 10 * 2.0 ** -24 * (R.deconv_s2_abs(dy, wc) + np.abs(bc)[None, :, None, None])
+    assert s.dtype == np.float32 and np.all(np.abs(R.deconv_s2(dy, wc) + bc[None, :, None, None] - s) <= tol)
+
+
+def test_sigmoid_bound_is_four_orders_below_the_old_tolerance_and_holds_for_an_fp32_evaluation():
+    s = np.arange(-120 * 128, 120 * 128 + 1) / 128.0
+    sig, bound = E.sigmoid_bound(s)
+    assert 1.5 * 2.0 ** -24 <= bound.min() and bound.max() < 2.2 * 2.0 ** -24 < 2e-7       # the old tolerance was 1e-3 at the least
+    # an fp32 evaluation with correctly rounded exp (numpy) is inside the bound everywhere
+    s32 = s.astype(np.float32)
+    with np.errstate(over="ignore"):
+        xh = np.float32(1.0) / (np.float32(1.0) + np.exp(-s32))
+    assert xh.dtype == np.float32 and np.all(np.abs(xh.astype(np.float64) - sig) <= bound)
+    # and a relative error of exp of 2^-18 (a wrong constant, a half-precision path) is outside it
+    bad = 1.0 / (1.0 + np.exp(-s) * (1 + 2.0 ** -18))
+    assert np.any(np.abs(bad - sig) > bound)
 
 
 def test_structured_errors_change_the_expected_bits():
