@@ -22,6 +22,8 @@ from .cluster import kmeans_fit, kmeans_predict, kmeans_init, cluster_scene, KMe
 from .report import cluster_class_table, name_clusters  # noqa: F401
 from . import neighbors  # noqa: F401
 from .neighbors import knn_search, knn_classify, similar_windows, knn_classify_scene, KNNResult  # noqa: F401
+from . import postprocess  # noqa: F401
+from .postprocess import majority_filter, label_regions, region_table, sieve  # noqa: F401
 
 __all__ = ["Encoder", "Decoder", "SupervisedAutoencoder", "MLP", "fit_autoencoder", "grid_search_autoencoder",
            "extract_features", "fit_mlp", "grid_search_mlp", "evaluate", "augment_batch", "stage_bands",
@@ -31,4 +33,4 @@ __all__ = ["Encoder", "Decoder", "SupervisedAutoencoder", "MLP", "fit_autoencode
            "window_schedule", "drawable_windows", "class_weights", "scene_confusion", "evaluate_scene", "block_split", "footprint_mask",
            "confusion_metrics", "classification_report_from_confusion", "kmeans_fit", "kmeans_predict", "kmeans_init", "cluster_scene",
            "KMeansResult", "cluster_class_table", "name_clusters", "knn_search", "knn_classify", "similar_windows", "knn_classify_scene",
-           "KNNResult"]
+           "KNNResult", "majority_filter", "label_regions", "region_table", "sieve"]

@@ -694,6 +694,44 @@ int eae_knn_slices(long long Nq, long long M, int L, int k);
 int eae_knn_search(void* stream, const float* q, long long Nq, const float* bank, long long M, int L, int k, long long self_offset,
                    long long* idx, float* dist, void* workspace, long long workspace_bytes);
 
+/* ------------------------------------------------------------------ map post-processing ------------ */
+/* Cleaning a class map on the device (no reference counterpart): majority filter, connected regions, their table, and a sieve.  A map
+ * is a contiguous int64 [H][W] device array as eae_scene_classify / eae_scene_blend write it: a value in [0, K) is a class, K in 1..64,
+ * every other value (the -1 of a window that was not run included) is "unclassified".  H, W >= 1 and H * W < 2^31.  Stateless; every
+ * call goes to `stream` and nothing synchronises the host.  Anything outside these limits or a NULL required pointer is EAE_ERR_ARG and
+ * nothing is launched.  Integers throughout (vector stores, integer atomics): every result is exact and identical from run to run.
+ *
+ * eae_map_majority: out[y][x] = the most frequent class among the classified cells of the (2 radius + 1)^2 window centred on (y, x),
+ * clipped at the map's edge; radius in 1..7.  Ties: the centre's own class when it is among the tied ones, else the lowest class id.
+ * An unclassified centre stays as stored, unless fill != 0 and the window holds a classified cell: then it takes the winner.
+ * in != out (a pass reads the whole input: Jacobi).
+ *
+ * eae_map_regions: regions[y][x] = the region of a classified cell, -1 for an unclassified one.  A region is a maximal set of cells of
+ * one class connected through edges (connectivity 4) or edges and corners (8); its id is the smallest linear index y * W + x of its
+ * cells, so the result is unique.  Union-find with union-by-minimum in three launches (label 32 x 32 tiles in LDS, merge the tile
+ * borders with device-scope atomics on the parent array, flatten); no workgroup waits for another.  workspace: device memory of at
+ * least eae_map_workspace_bytes(H, W) bytes (host only; < 0 on bad arguments), contents irrelevant on entry; NULL or too small is
+ * EAE_ERR_ARG.
+ *
+ * eae_map_region_stats: area int32 [H * W]: area[id] = the number of cells of region id, 0 at every index that is no region id.
+ * bbox (or NULL) int32 [H * W][4]: (y0, x0, y1, x1) of region id, inclusive, at row id; rows that are no region id hold -1s.
+ * regions is what eae_map_regions wrote (a value outside [0, H * W) counts nowhere).
+ *
+ * eae_map_sieve_pass: one sieve pass, decided entirely from its input.  With regions and area of `labels` as the two calls above give
+ * them (under either connectivity): a region is small when area < min_size (min_size >= 1).  The candidates of a small region are the
+ * regions that are not small and share a cell EDGE with it (for both connectivities); it takes the class of the candidate with the
+ * largest area, the lowest region id on a tie, whatever the order of arrival (a 64-bit atomic max of (area << 32) | (0xFFFFFFFF - id)
+ * per small root).  A small region without a candidate, and every unclassified cell, is copied as stored.  out != labels.  *changed
+ * (device int64, or NULL) receives the number of cells whose value changed.  workspace: as for eae_map_regions (and may be the same:
+ * the parents are dead once regions is written). */
+long long eae_map_workspace_bytes(int H, int W);
+int eae_map_majority(void* stream, const long long* in, int H, int W, int K, int radius, int fill, long long* out);
+int eae_map_regions(void* stream, const long long* labels, int H, int W, int K, int connectivity, long long* regions, void* workspace,
+                    long long workspace_bytes);
+int eae_map_region_stats(void* stream, const long long* regions, int H, int W, int* area, int* bbox);
+int eae_map_sieve_pass(void* stream, const long long* labels, const long long* regions, const int* area, int H, int W,
+                       long long min_size, long long* out, long long* changed, void* workspace, long long workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif
