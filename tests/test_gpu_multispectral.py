@@ -15,6 +15,7 @@ import torch
 import golden_util as gu
 from helpers import load_state_np
 from oracle import ae_numpy as O
+from stage_ref import stage_ref as _stage_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -450,22 +451,6 @@ def test_sigmoid_bwd_op_vs_numpy(c):
 
 
 # ---------------------------------------------------------------------------------------------------- staging
-def _stage_ref(data, idx, div, params, noise, std):
-    """NumPy restatement: flip -> pad-4 crop (zeros) -> / divisor[c] (fp32 true division) -> + std * noise (one fp32 rounding)."""
-    imgs = data[idx]
-    b, c, h, w = imgs.shape
-    out = np.zeros((b, c, h, w), np.float32)
-    for n in range(b):
-        flip, top, left = params[n]
-        img = imgs[n][:, :, ::-1] if flip else imgs[n]
-        pad = np.zeros((c, h + 8, w + 8), img.dtype)
-        pad[:, 4:4 + h, 4:4 + w] = img
-        out[n] = pad[:, top:top + h, left:left + w].astype(np.float32) / div[:, None, None]
-    if noise is not None:
-        out = (out.astype(np.float64) + np.float64(np.float32(std)) * noise.astype(np.float64)).astype(np.float32)
-    return out
-
-
 @pytest.mark.parametrize("dtype", [np.uint16, np.uint8])
 def test_stage_bands_exact_with_explicit_draws_c13(dtype):
     from eae_amd.augment import stage_bands
