@@ -35,6 +35,11 @@ class EaeScene(C.Structure):
                 ("pad_left", C.c_int), ("pad_right", C.c_int), ("fill", C.c_float)]
 
 
+class EaeAug(C.Structure):
+    _fields_ = [("dihedral", C.c_int), ("rotate", C.c_float), ("scale", C.c_float), ("gain", C.c_float), ("band_gain", C.c_float),
+                ("offset", C.c_float), ("draw_mode", C.c_int)]
+
+
 _PROTOS = {
     "eae_last_error": (C.c_char_p, []),
     "eae_version": (C.c_int, []),
@@ -118,6 +123,10 @@ _PROTOS = {
     "eae_stage_bands": (C.c_int, [vp, vp, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_float,
                                   C.c_ulonglong, C.c_ulonglong, vp, vp]),
     "eae_augment": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_ulonglong, C.c_ulonglong, vp, vp]),
+    "eae_stage_bands_aug": (C.c_int, [vp, vp, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_float,
+                                      C.c_ulonglong, C.c_ulonglong, C.POINTER(EaeAug), vp, vp, vp, vp]),
+    "eae_augment_aug": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_ulonglong, C.c_ulonglong,
+                                  C.POINTER(EaeAug), vp, vp, vp, vp]),
     "eae_op_adam": (C.c_int, [vp, vp, vp, vp, vp, C.c_longlong, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_longlong]),
     "eae_mlp_layout": (C.c_int, [C.c_int, C.c_int, c_ll_p, c_ll_p]),
     "eae_mlp_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
@@ -145,6 +154,8 @@ _PROTOS = {
     "eae_scene_reconstruct": (C.c_int, [vp, vp, C.POINTER(EaeScene), vp, C.c_longlong, vp, vp]),
     "eae_scene_stage_windows": (C.c_int, [vp, C.POINTER(EaeScene), vp, C.c_int, vp, C.c_int, C.c_float, C.c_ulonglong, C.c_ulonglong,
                                           vp, vp, C.c_int]),
+    "eae_scene_stage_windows_aug": (C.c_int, [vp, C.POINTER(EaeScene), vp, C.c_int, vp, C.c_int, C.c_float, C.c_ulonglong, C.c_ulonglong,
+                                              C.POINTER(EaeAug), vp, vp, vp, vp, C.c_int]),
     "eae_scene_window_labels": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "eae_scene_confusion": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int,
                                       C.c_int, vp]),

@@ -115,6 +115,27 @@ __device__ __forceinline__ void stage_draw_params(int b, unsigned long long seed
   philox4((uint32_t)b, 0x5eedu, (uint32_t)step, (uint32_t)(step >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), o);
   flip = o[0] >> 31; top = (int)(((unsigned long long)o[1] * 9) >> 32); left = (int)(((unsigned long long)o[2] * 9) >> 32);
 }
+// The augmentation policy (include/eae.h, eae_aug; the kernels of eae_augment.hip).  Its draws take Philox calls of their own, keyed
+// (~seed lo, seed hi): the geometric call is keyed (seed lo, seed hi) and the noise calls (seed lo, ~seed hi), so no counter of one
+// family can meet one of another.  Counter (b, tag + (c0 << 16), step lo, step hi) with b the batch position:
+//   AUG_TAG_IMAGE (c0 = 0)        w0 -> theta (degrees), w1 -> sigma, w2 -> the image gain g
+//   AUG_TAG_GAIN, band group c0   w_j -> the gain of band c0 + j
+//   AUG_TAG_OFFSET, band group c0 w_j -> the offset of band c0 + j
+// and the quarter turn is word 3 of the geometric call, which (flip, top, left) leave unused: rot = w3 >> 30.
+constexpr uint32_t AUG_TAG_IMAGE = 0xA061u, AUG_TAG_GAIN = 0xA062u, AUG_TAG_OFFSET = 0xA063u;
+__device__ __forceinline__ void stage_draw_geom(int b, unsigned long long seed, unsigned long long step, int& flip, int& top, int& left, int& rot) {
+  uint32_t o[4];
+  philox4((uint32_t)b, 0x5eedu, (uint32_t)step, (uint32_t)(step >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), o);
+  flip = o[0] >> 31; top = (int)(((unsigned long long)o[1] * 9) >> 32); left = (int)(((unsigned long long)o[2] * 9) >> 32);
+  rot = (int)(o[3] >> 30);
+}
+__device__ __forceinline__ void stage_aug_words(int b, uint32_t tag, int c0, unsigned long long seed, unsigned long long step, uint32_t* o) {
+  philox4((uint32_t)b, tag + ((uint32_t)c0 << 16), (uint32_t)step, (uint32_t)(step >> 32), ~(uint32_t)seed, (uint32_t)(seed >> 32), o);
+}
+// uniform in [lo, lo + width): (w >> 8) 2^-24, exact in fp32, mapped with one fma
+__device__ __forceinline__ float stage_uniform(uint32_t w, float lo, float width) {
+  return fmaf((float)(w >> 8) * (1.0f / 16777216.0f), width, lo);
+}
 // z[0..3]: the standard normals of bands c0 .. c0 + 3 of pixel p, the flat index over [B][H][W] (two Box-Muller pairs of one call)
 __device__ __forceinline__ void stage_draw_noise4(long long p, int c0, unsigned long long seed, unsigned long long step, float* z) {
   uint32_t o[4];

@@ -8,6 +8,7 @@
 #include "eae_ctx.h"
 #include "eae_common.hip.h"
 #include "eae_edge.hip.h"
+#include "eae_augment.h"
 
 namespace {
 
@@ -653,6 +654,23 @@ extern "C" int eae_scene_stage_windows(void* stream, const eae_scene* s, const l
   });
   EAE_LAUNCH_CHECK();
   return 0;
+}
+
+// with an augmentation policy (include/eae.h, "augmentation policy"; the kernel is eae_augment.hip's)
+extern "C" int eae_scene_stage_windows_aug(void* stream, const eae_scene* s, const long long* windows, int B, float* out, int train,
+                                           float noise_std, unsigned long long seed, unsigned long long step, const eae_aug* aug,
+                                           const int* geom, const float* affine, const float* radio, const float* noise, int crop) {
+  long long nH = 0, nW = 0;
+  if (int rc = scene_check(s, &nH, &nW, false)) return rc;
+  StageAug a;
+  int active = 0;
+  if (int rc = eae_stage_aug_prepare(aug, geom, affine, radio, s->patch, s->patch, "scene_stage_windows", &a, &active)) return rc;
+  if (!train || !active) return eae_scene_stage_windows(stream, s, windows, B, out, train, noise_std, seed, step, nullptr, noise, crop);
+  if (s->border != EAE_BORDER_NONE) return eae_set_error(EAE_ERR_ARG, "scene_stage_windows: border modes are not supported");
+  if (!windows || !out) return eae_set_error(EAE_ERR_ARG, "scene_stage_windows: NULL windows or output");
+  if (B <= 0) return eae_set_error(EAE_ERR_ARG, "scene_stage_windows: B must be positive");
+  if (crop != EAE_CROP_WINDOW && crop != EAE_CROP_SCENE) return eae_set_error(EAE_ERR_ARG, "scene_stage_windows: unknown crop mode");
+  return eae_launch_scene_stage_aug((hipStream_t)stream, s, nW, nH * nW, windows, B, out, noise_std, seed, step, a, noise, crop);
 }
 
 extern "C" int eae_scene_window_labels(void* stream, const void* raster, int elem_bytes, int H, int W, int patch, int stride, int K,

@@ -82,6 +82,7 @@ import torch
 from . import _lib
 from ._lib import check
 from .engine import _ptr, _stream, _require_gpu, engine_for
+from .augment import Augment, _aug_args
 
 _DTYPES = {torch.uint8: 0, torch.uint16: 1, torch.float32: 2}
 
@@ -692,18 +693,22 @@ def _crop_arg(crop):
 
 
 def stage_scene_windows(scene, divisor, patch, stride, windows, train=True, noise_std=0.03, seed=0, step=0, params=None, noise=None,
-                        crop="window"):
+                        crop="window", augment=None, geom=None, affine=None, radio=None):
     """fp32 NCHW [B,C,P,P]: `stage_bands`' transform of the windows ``windows`` (1-D int64 ids on the scene's device, any order,
     duplicates allowed) of the grid of whole P x P windows at stride S: flip -> pad-4 crop -> / divisor[c] -> + noise_std * N(0,1)
     (train=False: the division only, bitwise `scene_windows`).  Randomness as `stage_bands`: Philox keyed by (seed, step), the same
     stream, or explicit ``params`` int32 [B,3] = (flip, top, left) and ``noise`` [B,C,P,P].
     crop="window": outside the window the crop reads 0 -- bitwise `stage_bands` on the materialised windows; crop="scene": it reads
     the scene's own pixels around the window (0 outside the scene).  The ids are not read on the host (no synchronisation): an id
-    outside the grid gives a NaN image, as an index outside the dataset does in `stage_bands`."""
+    outside the grid gives a NaN image, as an index outside the dataset does in `stage_bands`.
+    ``augment``: an `Augment` policy (quarter turns, a small rotation and scale, per-band gain and offset); with crop="scene" a turned
+    window reads its real neighbours.  ``geom`` int32 [B,4] = (flip, top, left, rot), ``affine`` float32 [B,2] = (a, b), ``radio``
+    float32 [B,C,2] = (gain, offset): explicit draws in place of the policy's (include/eae.h, "augmentation policy")."""
     cid = _crop_arg(crop)
     _check_scene(scene)
     windows = _windows_arg(windows, scene.device, 0, allow_empty=False, check_range=False)
     b, c, p = windows.numel(), int(scene.shape[0]), int(patch)
+    aug = _aug_args(augment, params, geom, affine, radio, b, c, p, p, scene.device)
     if params is not None:
         if not isinstance(params, torch.Tensor) or tuple(params.shape) != (b, 3):
             raise RuntimeError(f"params must be int32 [B,3] = (flip, top, left) with B = {b}")
@@ -711,12 +716,12 @@ def stage_scene_windows(scene, divisor, patch, stride, windows, train=True, nois
         if not isinstance(noise, torch.Tensor) or tuple(noise.shape) != (b, c, p, p):
             raise RuntimeError(f"noise must be [B,C,P,P] = {(b, c, p, p)}")
     desc, keep, _, _ = _scene_desc(scene, divisor, patch, stride, any_patch=True)        # grid, device, bands, divisor
-    return _stage_windows(desc, keep, windows, train, noise_std, seed, step, params, noise, cid)
+    return _stage_windows(desc, keep, windows, train, noise_std, seed, step, params, noise, cid, aug)
 
 
-def _stage_windows(desc, keep, windows, train, noise_std, seed, step, params, noise, cid):
+def _stage_windows(desc, keep, windows, train, noise_std, seed, step, params, noise, cid, aug=None):
     """The C call of `stage_scene_windows` on a validated scene descriptor (`_scene_desc`) and id list: what a `SceneLoader` runs
-    per batch."""
+    per batch.  aug: None (the plain call) or `_aug_args`' (policy, geom, affine, radio)."""
     dev, b = keep[0].device, windows.numel()
     if params is not None:
         params = params.to(device=dev, dtype=torch.int32).contiguous()
@@ -724,9 +729,16 @@ def _stage_windows(desc, keep, windows, train, noise_std, seed, step, params, no
         noise = noise.to(device=dev, dtype=torch.float32).contiguous()
     lib = _lib.load()
     out = torch.empty((b, desc.C, desc.patch, desc.patch), dtype=torch.float32, device=dev)
+    seed, step = int(seed) & (2**64 - 1), int(step) & (2**64 - 1)
     with torch.cuda.device(dev):
-        check(lib.eae_scene_stage_windows(_stream(), C.byref(desc), _ptr(windows), b, _ptr(out), int(bool(train)), float(noise_std),
-                                          int(seed) & (2**64 - 1), int(step) & (2**64 - 1), _ptr(params), _ptr(noise), cid))
+        if aug is None:
+            check(lib.eae_scene_stage_windows(_stream(), C.byref(desc), _ptr(windows), b, _ptr(out), int(bool(train)), float(noise_std),
+                                              seed, step, _ptr(params), _ptr(noise), cid))
+        else:
+            pol, geom, affine, radio = aug
+            check(lib.eae_scene_stage_windows_aug(_stream(), C.byref(desc), _ptr(windows), b, _ptr(out), int(bool(train)),
+                                                  float(noise_std), seed, step, pol, _ptr(geom), _ptr(affine), _ptr(radio),
+                                                  _ptr(noise), cid))
     return out
 
 
@@ -879,8 +891,8 @@ class SceneLoader:
     purity >= min_purity (`drawable_windows`); two loaders over disjoint ``windows`` make a train / validation split.  Epoch e
     (counted per ``__iter__``, or set with `set_epoch`) takes the ids in `window_schedule`'s order -- shuffled when ``shuffle``
     (default: ``train``) -- and batch i is ``stage_scene_windows(ids, train=train, seed=seed, step=e * len(self) + i, noise_std=,
-    crop=)`` with ``y = label.reshape(-1)[ids]``.  The epoch's order is uploaded once when the iterator starts; nothing inside an
-    epoch synchronises the host.
+    crop=, augment=)`` with ``y = label.reshape(-1)[ids]`` (``augment``: an `Augment` policy, None by default).  The epoch's order
+    is uploaded once when the iterator starts; nothing inside an epoch synchronises the host.
 
     unlabelled=True keeps the windows without a label as well (``y = -1``; ``windows`` and ``min_purity`` still apply to the labelled
     ones): fit with ``ignore_index=-1`` and the whole scene trains the reconstruction while only the labelled windows train the
@@ -888,8 +900,11 @@ class SceneLoader:
     `class_weights` and ``class_weight="balanced"`` do not count."""
 
     def __init__(self, scene, label, divisor=1.0, patch=64, stride=None, batch_size=64, windows=None, min_purity=0.0, purity=None,
-                 train=True, shuffle=None, drop_last=False, noise_std=0.03, crop="window", seed=0, unlabelled=False):
+                 train=True, shuffle=None, drop_last=False, noise_std=0.03, crop="window", seed=0, unlabelled=False, augment=None):
         _crop_arg(crop)
+        if augment is not None and not isinstance(augment, Augment):
+            raise RuntimeError(f"augment must be an eae_amd.Augment or None, got {type(augment).__name__}")
+        self.augment = augment
         _check_scene(scene)
         self.patch = int(patch)
         self.stride = self.patch if stride is None else int(stride)
@@ -943,9 +958,10 @@ class SceneLoader:
         order = torch.cat(batches).pin_memory().to(dev, non_blocking=True)             # one upload per epoch
         ids, ys = self.windows[order], self.labels[order]
         base, at, cid = e * len(self), 0, _CROPS[self.crop]
+        aug = None if self.augment is None else (self.augment._struct(), None, None, None)
         for i, b in enumerate(batches):
             w = ids[at:at + b.numel()]
-            x = _stage_windows(self._desc, self._keep, w, self.train, self.noise_std, self.seed, base + i, None, None, cid)
+            x = _stage_windows(self._desc, self._keep, w, self.train, self.noise_std, self.seed, base + i, None, None, cid, aug)
             yield x, ys[at:at + b.numel()]
             at += b.numel()
 

@@ -615,6 +615,61 @@ int eae_scene_reconstruct(eae_ctx* ctx, void* stream, const eae_scene* scene, co
 int eae_scene_stage_windows(void* stream, const eae_scene* scene, const long long* windows, int B, float* out, int train,
                             float noise_std, unsigned long long seed, unsigned long long step, const int* params, const float* noise,
                             int crop);
+/* ------------------------------------------------------------------ augmentation policy ------------ */
+/* A stronger training transform for the three staging calls (eae_augment, eae_stage_bands, eae_scene_stage_windows): the eight
+ * rotations and flips of the square (D4), a small rotation and scale about the centre, and a per-band gain and offset.  In the
+ * image's direction:  flip -> pad-4 crop -> quarter turns -> small rotation and scale -> / divisor[c] -> gain and offset -> noise.
+ *
+ *   dihedral   != 0: rot in {0, 1, 2, 3} quarter turns per image, counter-clockwise as np.rot90; with the flip, all of D4.  H == W.
+ *   rotate     theta_max in degrees, >= 0 (at most 180): theta uniform in [-theta_max, theta_max); positive turns as np.rot90 does.
+ *   scale      s in [0, 1): sigma uniform in [1 - s, 1 + s); sigma > 1 enlarges the content.
+ *   gain       in [0, 1): one g per image, uniform in [1 - gain, 1 + gain).
+ *   band_gain  in [0, 1): one g_c per image and band, uniform in [1 - band_gain, 1 + band_gain).
+ *   offset     >= 0: one o_c per image and band, uniform in [-offset, offset), in output units (after the divisor).
+ *   draw_mode  where the per-image draws are made: 0 = chosen by the image size, 1 = by every thread, 2 = once per workgroup, through
+ *              LDS (needs H * W >= 256).  The values do not depend on it.
+ *
+ * An output pixel (x, y) finds its value as follows, with cx = (W - 1) / 2, cy = (H - 1) / 2 and a = cos(theta) / sigma,
+ * b = sin(theta) / sigma (both ranges 0: this step does not exist, X = x, Y = y):
+ *   u = x - cx, v = y - cy;   X = fl(fma(a, u, -fl(b v)) + cx),   Y = fl(fma(b, u, fl(a v)) + cy)              (fp32, as written)
+ *   the value is the bilinear interpolation, in fp32, of the RAW values I(floor Y + {0, 1}, floor X + {0, 1}) with the fractions of
+ *   X and Y: lerp(p, q, t) = fma(t, fl(q - p), p), along x first, then along y, and ONE division by divisor[c] afterwards.  With
+ *   zero fractions that is bitwise I itself, the integer path.
+ *   I(yo, xo), for integers of any size, is the pixel the integer path reads for output position (xo, yo):
+ *     (U, V) = (xo - cx, yo - cy) turned rot times by (U, V) <- (-V, U)                                          (exact)
+ *     sx = U + cx + left - 4, sy = V + cy + top - 4;  eae_augment / eae_stage_bands / EAE_CROP_WINDOW: 0 unless 0 <= sy < H and
+ *     0 <= sx < W (the unflipped sx);  then sx <- W - 1 - sx when flipped;  EAE_CROP_SCENE: scene pixel (oy + sy, ox + sx), 0 outside
+ *     the scene.  The window's origin is added to these integers, never to X or Y: the result does not depend on where in a scene
+ *     the window lies.  Every tap has its own inside test.
+ *   v = I / divisor[c];   v <- fma(v, fl(g g_c), o_c) (when gain, band_gain or offset is set, or radio is given);
+ *   v <- fma(noise_std, n, v) as in eae_stage_bands.
+ * Random draws: (flip, top, left) are those of eae_stage_bands for the same (b, seed, step), whatever the policy; rot = w3 >> 30 of
+ * that Philox call.  The others use calls of their own, keyed (~seed lo, seed hi), counter (b, tag + (c0 << 16), step lo, step hi):
+ * tag 0xA061 (theta in degrees, sigma, g from words 0, 1, 2), 0xA062 (g_c of bands c0 .. c0 + 3), 0xA063 (o_c likewise), c0 in
+ * {0, 4, 8, 12}; a uniform is fma((w >> 8) 2^-24, hi - lo, lo), and theta in radians is fl(theta * fl(pi / 180)).
+ *
+ * The three calls take the policy (NULL = none) and, for parity tests, explicit draws that replace the policy's (each may be NULL):
+ *   geom   int32 [B][4] = (flip, top, left, rot), rot in 0..3 (H == W)        affine float [B][2] = (a, b)
+ *   radio  float [B][C][2] = (gain, offset): v <- fma(v, gain, offset)         noise, as in the plain calls
+ * With train = 0, or with a NULL or all-zero policy and no explicit geom / affine / radio, a call is the plain one (bitwise).  An id
+ * or index outside its range still gives a NaN image and reads nothing.  Rejected (EAE_ERR_ARG): what the plain call rejects; a
+ * negative or non-finite range; rotate > 180; scale, gain or band_gain >= 1; dihedral or geom with H != W; an unknown draw_mode, or
+ * draw_mode 2 with H * W < 256. */
+typedef struct eae_aug {
+  int dihedral;
+  float rotate, scale, gain, band_gain, offset;
+  int draw_mode;
+} eae_aug;
+int eae_augment_aug(void* stream, const void* in_u8, float* out, int B, int H, int W, int train, float noise_std,
+                    unsigned long long seed, unsigned long long step, const eae_aug* aug, const int* geom, const float* affine,
+                    const float* radio, const float* noise);
+int eae_stage_bands_aug(void* stream, const void* src, int elem_bytes, long long N, int C, int H, int W, const long long* index, int B,
+                        const float* divisor, float* out, int train, float noise_std, unsigned long long seed, unsigned long long step,
+                        const eae_aug* aug, const int* geom, const float* affine, const float* radio, const float* noise);
+int eae_scene_stage_windows_aug(void* stream, const eae_scene* scene, const long long* windows, int B, float* out, int train,
+                                float noise_std, unsigned long long seed, unsigned long long step, const eae_aug* aug, const int* geom,
+                                const float* affine, const float* radio, const float* noise, int crop);
+
 /* A label for every window of the grid of whole P x P windows at stride S over a label raster [H][W] on the device, uint8
  * (elem_bytes 1) or int32 (4).  A pixel is labelled when its value is in [0, K), K in 1..64; every other value (255, negatives,
  * >= K) is unlabelled.  For window n: label[n] (int64) = the class with the most labelled pixels, the lowest class on a tie, -1 when

@@ -5,12 +5,15 @@ crop="scene") against the path the parent had: materialise every window into a u
 Philox noise).  Also reported: the one-off materialisation time and the extra device memory the dataset takes (its bytes, and the
 allocator's own difference).
 
+--augment adds four arms with an `eae_amd.Augment` policy on, for both crops: `aug_d4radio_*` (quarter turns, gain, band gain and
+offset: the integer path) and `aug_full_*` (those plus a rotation of up to 15 degrees and a scale of 0.9 .. 1.1: the bilinear path).
+
 Every arm walks the same number of batches of the same sizes; the arms alternate inside one process, after a warm-up, and a repetition
 times whole epochs (--min-windows per repetition at least) between device events, ending in a synchronise.  Median, min and max of
 --reps.  The epoch time includes the host side of every batch (argument checks, the C call); the kernels alone come from a separate
 `rocprofv3 --kernel-trace --stats -- python tools/scene_stage_bench.py` run (scene_stage_windows_kernel, stage_bands_kernel).
 
-    python tools/scene_stage_bench.py [--reps 7] [--warmup 2] [--strides 16 64]   ->  JSON lines
+    python tools/scene_stage_bench.py [--reps 7] [--warmup 2] [--strides 16 64] [--augment]   ->  JSON lines
 """
 import argparse
 import json
@@ -43,7 +46,11 @@ def _timed(fn, epochs):
     return a.elapsed_time(b) / 1e3 / epochs
 
 
-def bench(stride, reps, warmup, min_windows):
+AUG_ARMS = {"aug_d4radio": dict(dihedral=True, gain=0.2, band_gain=0.1, offset=0.05),
+            "aug_full": dict(dihedral=True, rotate=15.0, scale=0.1, gain=0.2, band_gain=0.1, offset=0.05)}
+
+
+def bench(stride, reps, warmup, min_windows, augment=False, draw_mode=0):
     g = torch.Generator().manual_seed(stride)
     scene = torch.randint(0, 10000, (C, SIZE, SIZE), generator=g, dtype=torch.int32).to(torch.uint16).cuda()
     n_h, n_w = eae_amd.window_grid(SIZE, SIZE, P, stride)
@@ -51,6 +58,11 @@ def bench(stride, reps, warmup, min_windows):
     label = torch.zeros((n_h, n_w), dtype=torch.int64, device="cuda")
     loaders = {crop: eae_amd.SceneLoader(scene, label, divisor=DIV, patch=P, stride=stride, batch_size=B, crop=crop, seed=1)
                for crop in ("window", "scene")}
+    if augment:
+        for name, pol in AUG_ARMS.items():
+            for crop in ("window", "scene"):
+                loaders[f"{name}_{crop}"] = eae_amd.SceneLoader(scene, label, divisor=DIV, patch=P, stride=stride, batch_size=B, crop=crop,
+                                                                seed=1, augment=eae_amd.Augment(_draw_mode=draw_mode, **pol))
     sink = torch.zeros((), device="cuda")
 
     def loader_epoch(crop):
@@ -89,6 +101,9 @@ def bench(stride, reps, warmup, min_windows):
     assert torch.equal(x_l, eae_amd.stage_bands(data, DIV, index=first, train=True, seed=1, step=0))
 
     arms = {"loader_window": loader_epoch("window"), "loader_scene": loader_epoch("scene"), "dataset_stage_bands": dataset_epoch}
+    for key in loaders:
+        if key not in ("window", "scene"):
+            arms[key] = loader_epoch(key)
     epochs = max(1, -(-min_windows // n))
     for _ in range(warmup):
         for fn in arms.values():
@@ -102,6 +117,8 @@ def bench(stride, reps, warmup, min_windows):
            "batches_per_epoch": len(loaders["window"]), "epochs_per_rep": epochs, "reps": reps,
            "scene_bytes": scene.numel() * 2, "dataset_bytes": data.numel() * 2, "dataset_extra_allocated_bytes": extra,
            "materialise_s": round(mat_s, 5)}
+    if augment:
+        res["draw_mode"] = draw_mode
     for k, v in ts.items():
         v.sort()
         med = v[len(v) // 2]
@@ -117,11 +134,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--strides", type=int, nargs="+", default=[16, 64])
     ap.add_argument("--min-windows", type=int, default=16384, help="windows timed per repetition at least (whole epochs)")
+    ap.add_argument("--augment", action="store_true", help="add the arms with an augmentation policy on (both crops)")
+    ap.add_argument("--draw-mode", type=int, default=0, choices=[0, 1, 2],
+                    help="with --augment: where the per-image draws are made (0: the library's choice, 1: every thread, 2: LDS)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("scene_stage_bench needs a GPU: nothing is measured without one")
     for s in a.strides:
-        print(json.dumps(bench(s, a.reps, a.warmup, a.min_windows)), flush=True)
+        print(json.dumps(bench(s, a.reps, a.warmup, a.min_windows, a.augment, a.draw_mode)), flush=True)
 
 
 if __name__ == "__main__":
