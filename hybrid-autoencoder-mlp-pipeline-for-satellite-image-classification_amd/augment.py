@@ -91,6 +91,20 @@ def _aug_args(augment, params, geom, affine, radio, b, c, h, w, dev):
     return (augment._struct() if augment is not None else None), geom, affine, radio
 
 
+def _plain_draws(params, noise, shape, dev):
+    """The explicit draws of a plain staging call for an output of ``shape`` = (b, c, h, w), on ``dev`` as the C call reads them:
+    ``params`` int32 [B,3] = (flip, top, left) and ``noise`` float32 [B,C,H,W], each or None."""
+    if params is not None:
+        if not isinstance(params, torch.Tensor) or tuple(params.shape) != (shape[0], 3):
+            raise RuntimeError(f"params must be int32 [B,3] = (flip, top, left) with B = {shape[0]}")
+        params = params.to(device=dev, dtype=torch.int32).contiguous()
+    if noise is not None:
+        if not isinstance(noise, torch.Tensor) or tuple(noise.shape) != tuple(shape):
+            raise RuntimeError(f"noise must be [B,C,H,W] = {tuple(shape)}")
+        noise = noise.to(device=dev, dtype=torch.float32).contiguous()
+    return params, noise
+
+
 def augment_batch(u8, train=True, noise_std=0.03, seed=0, step=0, params=None, noise=None, augment=None, geom=None, affine=None,
                   radio=None):
     """fp32 NCHW [B,3,H,W] of a uint8 HWC batch on the device (module docstring).  ``augment``: an `Augment` policy; ``geom`` int32
@@ -104,14 +118,7 @@ def augment_batch(u8, train=True, noise_std=0.03, seed=0, step=0, params=None, n
     lib = _lib.load()
     u8 = u8.contiguous()
     out = torch.empty((b, 3, h, w), dtype=torch.float32, device=u8.device)
-    if params is not None:
-        params = params.to(device=u8.device, dtype=torch.int32).contiguous()
-        if params.shape != (b, 3):
-            raise RuntimeError("params must be int32 [B,3] = (flip, top, left)")
-    if noise is not None:
-        noise = noise.to(device=u8.device, dtype=torch.float32).contiguous()
-        if noise.shape != out.shape:
-            raise RuntimeError("noise must be [B,3,H,W]")
+    params, noise = _plain_draws(params, noise, out.shape, u8.device)
     seed, step = int(seed) & (2**64 - 1), int(step) & (2**64 - 1)
     if aug is None:
         check(lib.eae_augment(_stream(), _ptr(u8), _ptr(out), b, h, w, int(train), float(noise_std), seed, step, _ptr(params),
@@ -149,14 +156,7 @@ def stage_bands(data, divisor, index=None, train=True, noise_std=0.03, seed=0, s
     if index is not None:
         index = torch.as_tensor(index).to(device=data.device, dtype=torch.int64).reshape(-1).contiguous()
     out = torch.empty((b, c, h, w), dtype=torch.float32, device=data.device)
-    if params is not None:
-        params = params.to(device=data.device, dtype=torch.int32).contiguous()
-        if params.shape != (b, 3):
-            raise RuntimeError("params must be int32 [B,3] = (flip, top, left)")
-    if noise is not None:
-        noise = noise.to(device=data.device, dtype=torch.float32).contiguous()
-        if noise.shape != out.shape:
-            raise RuntimeError(f"noise must be [B,C,H,W] = {tuple(out.shape)}")
+    params, noise = _plain_draws(params, noise, out.shape, data.device)
     seed, step = int(seed) & (2**64 - 1), int(step) & (2**64 - 1)
     if aug is None:
         check(lib.eae_stage_bands(_stream(), _ptr(data), data.element_size(), n, c, h, w, _ptr(index), b, _ptr(div), _ptr(out), int(train),

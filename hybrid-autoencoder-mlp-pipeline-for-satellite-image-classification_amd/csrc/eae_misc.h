@@ -89,61 +89,3 @@ int eae_launch_adam_scaled(hipStream_t st, float* p, const float* g, float* m, f
                            double eps, double wd, long long step, float gscale, void* zero_buf = nullptr, long long zero_bytes = 0,
                            const unsigned* bad = nullptr, const unsigned* bad2 = nullptr, float* nan_out = nullptr, int nan_fill = 0,
                            int max_blocks = 0 /* 0: 2048; the grid-stride loop covers the rest */, const EaeClip* clip = nullptr);
-int eae_launch_stage_bands(hipStream_t st, const void* src, int elem_bytes, long long N, int C, int H, int W, const long long* index, int B,
-                           const float* divisor, float* out, int train, float std, unsigned long long seed, unsigned long long step,
-                           const int* params, const float* noise);
-int eae_launch_augment(hipStream_t st, const void* in_u8, float* out, int B, int H, int W, int train, float std, unsigned long long seed,
-                       unsigned long long step, const int* params, const float* noise);
-
-// The random stream of the staging kernels (augment_kernel, stage_bands_kernel in eae_misc.hip; scene_stage_windows_kernel in
-// eae_scene.hip): counter-based Philox4x32-10 keyed by (seed, step).  The kernels share these bodies, so the same (b, p, c0, seed,
-// step) draws the same values in each of them.
-__device__ __forceinline__ void philox4(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t* o) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-    uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-    uint32_t n0 = h1 ^ c1 ^ k0, n1 = l1, n2 = h0 ^ c3 ^ k1, n3 = l0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
-// (flip, top, left) of the image at batch position b: flip in {0, 1}, top and left in 0..8
-__device__ __forceinline__ void stage_draw_params(int b, unsigned long long seed, unsigned long long step, int& flip, int& top, int& left) {
-  uint32_t o[4];
-  philox4((uint32_t)b, 0x5eedu, (uint32_t)step, (uint32_t)(step >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), o);
-  flip = o[0] >> 31; top = (int)(((unsigned long long)o[1] * 9) >> 32); left = (int)(((unsigned long long)o[2] * 9) >> 32);
-}
-// The augmentation policy (include/eae.h, eae_aug; the kernels of eae_augment.hip).  Its draws take Philox calls of their own, keyed
-// (~seed lo, seed hi): the geometric call is keyed (seed lo, seed hi) and the noise calls (seed lo, ~seed hi), so no counter of one
-// family can meet one of another.  Counter (b, tag + (c0 << 16), step lo, step hi) with b the batch position:
-//   AUG_TAG_IMAGE (c0 = 0)        w0 -> theta (degrees), w1 -> sigma, w2 -> the image gain g
-//   AUG_TAG_GAIN, band group c0   w_j -> the gain of band c0 + j
-//   AUG_TAG_OFFSET, band group c0 w_j -> the offset of band c0 + j
-// and the quarter turn is word 3 of the geometric call, which (flip, top, left) leave unused: rot = w3 >> 30.
-constexpr uint32_t AUG_TAG_IMAGE = 0xA061u, AUG_TAG_GAIN = 0xA062u, AUG_TAG_OFFSET = 0xA063u;
-__device__ __forceinline__ void stage_draw_geom(int b, unsigned long long seed, unsigned long long step, int& flip, int& top, int& left, int& rot) {
-  uint32_t o[4];
-  philox4((uint32_t)b, 0x5eedu, (uint32_t)step, (uint32_t)(step >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), o);
-  flip = o[0] >> 31; top = (int)(((unsigned long long)o[1] * 9) >> 32); left = (int)(((unsigned long long)o[2] * 9) >> 32);
-  rot = (int)(o[3] >> 30);
-}
-__device__ __forceinline__ void stage_aug_words(int b, uint32_t tag, int c0, unsigned long long seed, unsigned long long step, uint32_t* o) {
-  philox4((uint32_t)b, tag + ((uint32_t)c0 << 16), (uint32_t)step, (uint32_t)(step >> 32), ~(uint32_t)seed, (uint32_t)(seed >> 32), o);
-}
-// uniform in [lo, lo + width): (w >> 8) 2^-24, exact in fp32, mapped with one fma
-__device__ __forceinline__ float stage_uniform(uint32_t w, float lo, float width) {
-  return fmaf((float)(w >> 8) * (1.0f / 16777216.0f), width, lo);
-}
-// z[0..3]: the standard normals of bands c0 .. c0 + 3 of pixel p, the flat index over [B][H][W] (two Box-Muller pairs of one call)
-__device__ __forceinline__ void stage_draw_noise4(long long p, int c0, unsigned long long seed, unsigned long long step, float* z) {
-  uint32_t o[4];
-  philox4((uint32_t)p, ((uint32_t)(p >> 32) ^ 0xA5A5u) + ((uint32_t)c0 << 16), (uint32_t)step, (uint32_t)(step >> 32), (uint32_t)seed,
-          ~(uint32_t)(seed >> 32), o);
-  const float u1 = ((o[0] >> 8) + 1) * (1.0f / 16777216.0f), u2 = (o[1] >> 8) * (1.0f / 16777216.0f);
-  const float u3 = ((o[2] >> 8) + 1) * (1.0f / 16777216.0f), u4 = (o[3] >> 8) * (1.0f / 16777216.0f);
-  const float r1 = sqrtf(-2.0f * __logf(u1)), r2 = sqrtf(-2.0f * __logf(u3));
-  z[0] = r1 * __cosf(6.28318530718f * u2); z[1] = r1 * __sinf(6.28318530718f * u2);
-  z[2] = r2 * __cosf(6.28318530718f * u4); z[3] = r2 * __sinf(6.28318530718f * u4);
-}

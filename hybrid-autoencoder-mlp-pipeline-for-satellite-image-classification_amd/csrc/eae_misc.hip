@@ -847,130 +847,3 @@ int eae_launch_grad_sumsq(hipStream_t st, const float* g, const long long* poff3
   EAE_LAUNCH_CHECK();
   return 0;
 }
-
-// ---------------------------------------------------------------------------------------------------------------
-// On-device input staging: the reference's training transform (R.md:225-230)
-//   RandomHorizontalFlip -> RandomCrop(64, padding=4) -> ToTensor -> AddGaussianNoise(0, 0.03)   (eval: ToTensor only, R.md:232-234)
-// fused into one kernel: uint8 HWC [B,H,W,3] -> fp32 NCHW [B,3,H,W] (what conv1 reads), so a batch crosses PCIe as 12 KB/img.
-//   out[n,c,y,x] = img[n, y+top-4, flip ? W-1-(x+left-4) : x+left-4, c] / 255 (0 outside) + std * N(0,1)
-// Per-image (flip, top, left) and the noise come from a counter-based Philox4x32-10 stream keyed by (seed, step) unless
-// explicit `params` [B][3] / `noise` [B,3,H,W] are supplied (parity tests).
-// ---------------------------------------------------------------------------------------------------------------
-__global__ EAE_NO_PK __launch_bounds__(256) void augment_kernel(const uint8_t* __restrict__ in, float* __restrict__ out, int B, int H, int W,
-                                                       int train, float std, unsigned long long seed, unsigned long long step,
-                                                       const int* __restrict__ params, const float* __restrict__ noise) {
-  const long plane = (long)H * W;
-  const long p = (long)blockIdx.x * 256 + threadIdx.x;
-  if (p >= plane * B) return;
-  const int n = (int)(p / plane), r = (int)(p % plane), y = r / W, x = r % W;
-  int flip = 0, top = 4, left = 4;
-  if (train) {
-    if (params) { flip = params[n * 3]; top = params[n * 3 + 1]; left = params[n * 3 + 2]; }
-    else {
-      uint32_t o[4];
-      philox4((uint32_t)n, 0x5eedu, (uint32_t)step, (uint32_t)(step >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), o);
-      flip = o[0] >> 31; top = (int)(((unsigned long long)o[1] * 9) >> 32); left = (int)(((unsigned long long)o[2] * 9) >> 32);
-    }
-  }
-  const int sy = y + top - 4;
-  int sx = x + left - 4;
-  const bool inside = sy >= 0 && sy < H && sx >= 0 && sx < W;
-  if (flip) sx = W - 1 - sx;
-  float v[3] = {0.f, 0.f, 0.f};
-  if (inside) {
-    const uint8_t* q = in + (((long)n * H + sy) * W + sx) * 3;
-    v[0] = q[0] / 255.0f; v[1] = q[1] / 255.0f; v[2] = q[2] / 255.0f;   // ToTensor: .div(255), exact
-  }
-  if (train && std != 0.f) {
-    if (noise) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) v[c] = fmaf(std, noise[((long)n * 3 + c) * plane + r], v[c]);
-    } else {
-      uint32_t o[4];
-      philox4((uint32_t)p, (uint32_t)(p >> 32) ^ 0xA5A5u, (uint32_t)step, (uint32_t)(step >> 32), (uint32_t)seed, ~(uint32_t)(seed >> 32), o);
-      // Box-Muller: two uniforms -> two normals (three needed: a second pair from o[2], o[3])
-      float u1 = ((o[0] >> 8) + 1) * (1.0f / 16777216.0f), u2 = (o[1] >> 8) * (1.0f / 16777216.0f);
-      float u3 = ((o[2] >> 8) + 1) * (1.0f / 16777216.0f), u4 = (o[3] >> 8) * (1.0f / 16777216.0f);
-      float r1 = sqrtf(-2.0f * __logf(u1)), r2 = sqrtf(-2.0f * __logf(u3));
-      v[0] = fmaf(std, r1 * __cosf(6.28318530718f * u2), v[0]);
-      v[1] = fmaf(std, r1 * __sinf(6.28318530718f * u2), v[1]);
-      v[2] = fmaf(std, r2 * __cosf(6.28318530718f * u4), v[2]);
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < 3; ++c) out[((long)n * 3 + c) * plane + r] = v[c];
-}
-
-// Multispectral staging: the same transform for C bands of a dataset kept in device memory, gathered by index.
-//   out[b,c,y,x] = src[n, c, y+top-4, flip ? W-1-(x+left-4) : x+left-4] / divisor[c] (0 outside) + std * N(0,1),  n = index[b] (or b)
-// src uint8 or uint16 planar [N,C,H,W] (e.g. reflectance x 10000); the division is a true one, as ToTensor's.  (flip, top, left)
-// come from the Philox stream of augment_kernel (keyed by (seed, step) and the batch position b) unless `params` is given; the
-// noise from one Philox call per pixel and group of four bands (Box-Muller pairs) unless `noise` [B,C,H,W] is given.  An index
-// outside 0..N-1 yields NaN for that image instead of a read outside the dataset.
-template <typename T>
-__global__ EAE_NO_PK __launch_bounds__(256) void stage_bands_kernel(const T* __restrict__ src, long long N, int C, int H, int W,
-                                                           const long long* __restrict__ index, int B, const float* __restrict__ divisor,
-                                                           float* __restrict__ out, int train, float std, unsigned long long seed,
-                                                           unsigned long long step, const int* __restrict__ params,
-                                                           const float* __restrict__ noise) {
-  const long plane = (long)H * W;
-  const long p = (long)blockIdx.x * 256 + threadIdx.x;
-  if (p >= plane * B) return;
-  const int b = (int)(p / plane), r = (int)(p % plane), y = r / W, x = r % W;
-  const long long n = index ? index[b] : (long long)b;
-  const bool valid = n >= 0 && n < N;
-  int flip = 0, top = 4, left = 4;
-  if (train) {
-    if (params) { flip = params[b * 3]; top = params[b * 3 + 1]; left = params[b * 3 + 2]; }
-    else stage_draw_params(b, seed, step, flip, top, left);
-  }
-  const int sy = y + top - 4;
-  int sx = x + left - 4;
-  const bool inside = valid && sy >= 0 && sy < H && sx >= 0 && sx < W;
-  if (flip) sx = W - 1 - sx;
-  const T* q = src + (inside ? (((size_t)n * C * H + sy) * W + sx) : (size_t)0);
-  for (int c0 = 0; c0 < C; c0 += 4) {
-    float z[4] = {0.f, 0.f, 0.f, 0.f};
-    if (train && std != 0.f && !noise) stage_draw_noise4(p, c0, seed, step, z);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int c = c0 + j;
-      if (c >= C) break;
-      float v = inside ? (float)q[(size_t)c * plane] / divisor[c] : 0.f;
-      if (!valid) v = __builtin_nanf("");
-      if (train && std != 0.f) v = fmaf(std, noise ? noise[((long)b * C + c) * plane + r] : z[j], v);
-      out[((long)b * C + c) * plane + r] = v;
-    }
-  }
-}
-
-int eae_launch_stage_bands(hipStream_t st, const void* src, int elem_bytes, long long N, int C, int H, int W, const long long* index, int B,
-                           const float* divisor, float* out, int train, float std, unsigned long long seed, unsigned long long step,
-                           const int* params, const float* noise) {
-  if (!src || !divisor || !out || N <= 0 || B <= 0 || H <= 0 || W <= 0) return eae_set_error(-2, "stage_bands: bad argument");
-  if (C < 1 || C > 16) return eae_set_error(-2, "stage_bands: in_channels must be in 1..16");
-  if (elem_bytes != 1 && elem_bytes != 2) return eae_set_error(-2, "stage_bands: source must be uint8 or uint16 (elem_bytes 1 or 2)");
-  if (!index && B > N) return eae_set_error(-2, "stage_bands: without an index the batch is the first B images (B <= N)");
-  const long tot = (long)B * H * W;
-  EAE_NO_GROUP("stage_bands_kernel");
-  const dim3 grid((unsigned)((tot + 255) / 256));
-  if (elem_bytes == 1)
-    hipLaunchKernelGGL(stage_bands_kernel<uint8_t>, grid, dim3(256), 0, st, (const uint8_t*)src, N, C, H, W, index, B, divisor, out, train, std,
-                       seed, step, params, noise);
-  else
-    hipLaunchKernelGGL(stage_bands_kernel<uint16_t>, grid, dim3(256), 0, st, (const uint16_t*)src, N, C, H, W, index, B, divisor, out, train,
-                       std, seed, step, params, noise);
-  EAE_LAUNCH_CHECK();
-  return 0;
-}
-
-int eae_launch_augment(hipStream_t st, const void* in_u8, float* out, int B, int H, int W, int train, float std, unsigned long long seed,
-                       unsigned long long step, const int* params, const float* noise) {
-  if (!in_u8 || !out || B <= 0 || H <= 0 || W <= 0) return eae_set_error(-2, "augment: bad argument");
-  const long tot = (long)B * H * W;
-  EAE_NO_GROUP("augment_kernel");
-  hipLaunchKernelGGL(augment_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (const uint8_t*)in_u8, out, B, H, W, train, std,
-                     seed, step, params, noise);
-  EAE_LAUNCH_CHECK();
-  return 0;
-}

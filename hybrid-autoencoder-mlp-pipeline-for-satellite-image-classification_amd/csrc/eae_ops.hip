@@ -1,5 +1,6 @@
 // Thin per-op wrappers over the launchers, used by the kernel-level parity tests.
 #include "eae_ctx.h"
+#include "eae_stage.h"
 
 namespace {
 SrcDesc to_src(const eae_src& s) {

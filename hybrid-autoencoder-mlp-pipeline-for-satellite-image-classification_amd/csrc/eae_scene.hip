@@ -1,14 +1,14 @@
 // Scene classification helpers (include/eae.h, "scene classification"): the window gather (the public way to get patches, and the
 // reference the fused conv1 scene source is tested against), the cell blends of window probabilities, and the nodata / mask path:
 // per-window invalid-pixel counts and the compaction of the valid window ids; and training from a scene (include/eae.h, "training from
-// a scene"): augmented window batches and a label for every window from a label raster; and the confusion counts of a class map against
-// a label raster (include/eae.h, "accuracy assessment").  None uses matrix instructions, so all are built with packed FP32 disabled
-// (EAE_NO_PK, tests/test_isa_guard.py).
+// a scene"): window batches (the kernel is eae_stage.hip's) and a label for every window from a label raster; and the confusion counts
+// of a class map against a label raster (include/eae.h, "accuracy assessment").  None uses matrix instructions, so all are built with
+// packed FP32 disabled (EAE_NO_PK, tests/test_isa_guard.py).
 #include "eae_internal.h"
 #include "eae_ctx.h"
 #include "eae_common.hip.h"
 #include "eae_edge.hip.h"
-#include "eae_augment.h"
+#include "eae_stage.h"
 
 namespace {
 
@@ -275,56 +275,6 @@ __global__ EAE_NO_PK __launch_bounds__(SEL_NT) void scene_select_kernel(const in
 
 
 // ---------------------------------------------------------------------------------------------------------------- training from a scene
-// stage_bands_kernel (eae_misc.hip) with the image of batch position b gathered from the scene: window windows[b], origin (oy, ox).
-//   out[b,c,y,x] = scene[c, oy + sy, ox + sx] / divisor[c] (or 0) + std * N(0,1),  sy = y + top - 4, sx = x + left - 4, flipped: P-1-sx
-// One thread per output pixel, all bands; p is the flat index over [B][P][P], the index stage_bands_kernel has for [B,C,P,P] images, so
-// stage_draw_params(b) and stage_draw_noise4(p, c0) (eae_misc.h) are the draws that kernel makes.  CROP_SCENE = false: (sy, unflipped
-// sx) outside [0, P) reads 0, which keeps every read inside the window.  CROP_SCENE = true: the read is bounds-checked against the
-// scene instead, so the crop slides the window over its real neighbourhood.  An id outside [0, nwin) gives NaN and reads nothing.
-template <typename T, bool CROP_SCENE>
-__global__ EAE_NO_PK __launch_bounds__(256) void scene_stage_windows_kernel(const T* __restrict__ src, const float* __restrict__ divisor,
-                                                                        int C, long long plane, int Hs, int Ws, int P, int S, int nW,
-                                                                        long long nwin, const long long* __restrict__ windows, int B,
-                                                                        float* __restrict__ out, int train, float std,
-                                                                        unsigned long long seed, unsigned long long step,
-                                                                        const int* __restrict__ params, const float* __restrict__ noise) {
-  const long long pp = (long long)P * P;
-  const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (p >= pp * B) return;
-  const int b = (int)(p / pp);
-  const long long r = p - b * pp;
-  const int y = (int)(r / P), x = (int)(r - (long long)y * P);
-  const long long w = windows[b];
-  const bool valid = w >= 0 && w < nwin;
-  int flip = 0, top = 4, left = 4;
-  if (train) {
-    if (params) { flip = params[b * 3]; top = params[b * 3 + 1]; left = params[b * 3 + 2]; }
-    else stage_draw_params(b, seed, step, flip, top, left);
-  }
-  const long long sy = (long long)y + top - 4;
-  long long sx = (long long)x + left - 4;
-  bool inside = valid;
-  if constexpr (!CROP_SCENE) inside = inside && sy >= 0 && sy < P && sx >= 0 && sx < P;
-  if (flip) sx = P - 1 - sx;
-  const long long wi = valid ? w / nW : 0, wj = valid ? w - wi * nW : 0;
-  const long long gy = wi * S + sy, gx = wj * S + sx;                  // scene pixel
-  if constexpr (CROP_SCENE) inside = inside && gy >= 0 && gy < Hs && gx >= 0 && gx < Ws;
-  const T* q = src + (inside ? gy * Ws + gx : 0);
-  for (int c0 = 0; c0 < C; c0 += 4) {
-    float z[4] = {0.f, 0.f, 0.f, 0.f};
-    if (train && std != 0.f && !noise) stage_draw_noise4(p, c0, seed, step, z);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int c = c0 + j;
-      if (c >= C) break;
-      float v = inside ? scene_val(q[c * plane], divisor[c]) : 0.f;
-      if (!valid) v = __builtin_nanf("");
-      if (train && std != 0.f) v = fmaf(std, noise ? noise[((long long)b * C + c) * pp + r] : z[j], v);
-      out[((long long)b * C + c) * pp + r] = v;
-    }
-  }
-}
-
 // One workgroup per window: every wave counts the labelled pixels (values in [0, K)) it reads into its own K-bin LDS histogram, a
 // thread adding a run of equal classes with one atomic (land-cover windows are mostly one class: a run is usually the thread's whole
 // share); wave 0 then sums the waves' bins in wave order, lane = class, and reduces (count, class) to the largest count, the lowest
@@ -630,47 +580,34 @@ extern "C" int eae_scene_select(void* stream, const int* counts, long long n, in
   return 0;
 }
 
+// the checks of eae_scene_stage_windows[_aug] (the kernel and its launcher are eae_stage.hip's); nH, nW: the grid
+static int scene_stage_check(const eae_scene* s, const long long* windows, int B, const float* out, int crop, long long* nH, long long* nW) {
+  if (int rc = scene_check(s, nH, nW, false)) return rc;
+  if (s->border != EAE_BORDER_NONE) return eae_set_error(EAE_ERR_ARG, "scene_stage_windows: border modes are not supported");
+  if (!windows || !out) return eae_set_error(EAE_ERR_ARG, "scene_stage_windows: NULL windows or output");
+  if (B <= 0) return eae_set_error(EAE_ERR_ARG, "scene_stage_windows: B must be positive");
+  if (crop != EAE_CROP_WINDOW && crop != EAE_CROP_SCENE) return eae_set_error(EAE_ERR_ARG, "scene_stage_windows: unknown crop mode");
+  return 0;
+}
+
 extern "C" int eae_scene_stage_windows(void* stream, const eae_scene* s, const long long* windows, int B, float* out, int train,
                                        float noise_std, unsigned long long seed, unsigned long long step, const int* params,
                                        const float* noise, int crop) {
   long long nH = 0, nW = 0;
-  if (int rc = scene_check(s, &nH, &nW, false)) return rc;
-  if (s->border != EAE_BORDER_NONE) return eae_set_error(EAE_ERR_ARG, "scene_stage_windows: border modes are not supported");
-  if (!windows || !out) return eae_set_error(EAE_ERR_ARG, "scene_stage_windows: NULL windows or output");
-  if (B <= 0) return eae_set_error(EAE_ERR_ARG, "scene_stage_windows: B must be positive");
-  if (crop != EAE_CROP_WINDOW && crop != EAE_CROP_SCENE) return eae_set_error(EAE_ERR_ARG, "scene_stage_windows: unknown crop mode");
-  const long long plane = (long long)s->H * s->W, nblk = ((long long)B * s->patch * s->patch + 255) / 256;
-  if (nblk > 0x7fffffffLL) return eae_set_error(EAE_ERR_ARG, "scene_stage_windows: batch too large");
-  EAE_NO_GROUP("scene_stage_windows_kernel");
-  const hipStream_t st = (hipStream_t)stream;
-  auto launch = [&](auto* t, auto scene_crop) {
-    using T = std::remove_cv_t<std::remove_pointer_t<decltype(t)>>;
-    hipLaunchKernelGGL((scene_stage_windows_kernel<T, decltype(scene_crop)::value>), dim3((unsigned)nblk), dim3(256), 0, st,
-                       (const T*)s->data, s->divisor, s->C, plane, s->H, s->W, s->patch, s->stride, (int)nW, nH * nW, windows, B, out,
-                       train, noise_std, seed, step, params, noise);
-  };
-  scene_dtype_dispatch(s, [&](auto* t, auto) {          // border = NONE: one instance per dtype and crop mode
-    if (crop == EAE_CROP_SCENE) launch(t, std::true_type()); else launch(t, std::false_type());
-  });
-  EAE_LAUNCH_CHECK();
-  return 0;
+  if (int rc = scene_stage_check(s, windows, B, out, crop, &nH, &nW)) return rc;
+  return eae_launch_scene_stage_plain((hipStream_t)stream, s, nW, nH * nW, windows, B, out, train, noise_std, seed, step, params, noise,
+                                      crop);
 }
 
-// with an augmentation policy (include/eae.h, "augmentation policy"; the kernel is eae_augment.hip's)
+// with an augmentation policy (include/eae.h, "augmentation policy")
 extern "C" int eae_scene_stage_windows_aug(void* stream, const eae_scene* s, const long long* windows, int B, float* out, int train,
                                            float noise_std, unsigned long long seed, unsigned long long step, const eae_aug* aug,
                                            const int* geom, const float* affine, const float* radio, const float* noise, int crop) {
   long long nH = 0, nW = 0;
-  if (int rc = scene_check(s, &nH, &nW, false)) return rc;
+  if (int rc = scene_stage_check(s, windows, B, out, crop, &nH, &nW)) return rc;
   StageAug a;
-  int active = 0;
-  if (int rc = eae_stage_aug_prepare(aug, geom, affine, radio, s->patch, s->patch, "scene_stage_windows", &a, &active)) return rc;
-  if (!train || !active) return eae_scene_stage_windows(stream, s, windows, B, out, train, noise_std, seed, step, nullptr, noise, crop);
-  if (s->border != EAE_BORDER_NONE) return eae_set_error(EAE_ERR_ARG, "scene_stage_windows: border modes are not supported");
-  if (!windows || !out) return eae_set_error(EAE_ERR_ARG, "scene_stage_windows: NULL windows or output");
-  if (B <= 0) return eae_set_error(EAE_ERR_ARG, "scene_stage_windows: B must be positive");
-  if (crop != EAE_CROP_WINDOW && crop != EAE_CROP_SCENE) return eae_set_error(EAE_ERR_ARG, "scene_stage_windows: unknown crop mode");
-  return eae_launch_scene_stage_aug((hipStream_t)stream, s, nW, nH * nW, windows, B, out, noise_std, seed, step, a, noise, crop);
+  if (int rc = eae_stage_aug_prepare(aug, geom, affine, radio, s->patch, s->patch, "scene_stage_windows", &a)) return rc;
+  return eae_launch_scene_stage((hipStream_t)stream, s, nW, nH * nW, windows, B, out, train, noise_std, seed, step, a, noise, crop);
 }
 
 extern "C" int eae_scene_window_labels(void* stream, const void* raster, int elem_bytes, int H, int W, int patch, int stride, int K,

@@ -1,12 +1,20 @@
-// The augmentation policy of the staging calls (include/eae.h, "augmentation policy"): augment_kernel, stage_bands_kernel
-// (eae_misc.hip) and scene_stage_windows_kernel (eae_scene.hip) with quarter turns, a small rotation and scale, and a per-band gain
-// and offset.  ONE kernel body; the three calls differ in the source a tap is read from (AugSrcHwc, AugSrcBands, AugSrcScene).  The
-// plain kernels stay as they are: a call without a policy, or with train = 0, never comes here.  No matrix instructions: built with
-// packed FP32 disabled (EAE_NO_PK, tests/test_isa_guard.py).
+// On-device input staging: uint8 / uint16 / fp32 source -> the fp32 NCHW batch conv1 reads, so a batch crosses PCIe
+// as 12 KB/img.  The reference's training transform (R.md:225-230)
+//   RandomHorizontalFlip -> RandomCrop(H, padding=4) -> ToTensor -> AddGaussianNoise(0, 0.03)   (eval: ToTensor only, R.md:232-234)
+// as ONE kernel body for every staging call of include/eae.h, plain or with an augmentation policy (but for the plain scene call, which
+// keeps the kernel it had: scene_stage_windows_kernel below):
+//   out[b,c,y,x] = src_b[c, y+top-4, flip ? W-1-(x+left-4) : x+left-4] / divisor[c] (0 outside) + std * N(0,1)
+// The calls differ in the source src_b that a tap is read from: AugSrcHwc (eae_augment: uint8 HWC, / 255), AugSrcBands (eae_stage_bands:
+// image index[b] of a planar dataset), AugSrcScene (eae_scene_stage_windows: window windows[b] of a scene).  The division is a true
+// one, as ToTensor's; an image or window id out of range gives NaN for that image instead of a read outside the source.  Per image
+// (flip, top, left) and the noise come from the Philox stream of eae_stage.h, keyed by (seed, step), unless explicit draws are given
+// (parity tests); train = 0 is the division alone.  The policy ("augmentation policy", include/eae.h) adds quarter turns, a small
+// rotation and scale, and a per-band gain and offset; a plain call is its integer path at rot = 0 with no radiometric step.  No matrix
+// instructions: built with packed FP32 disabled (EAE_NO_PK, tests/test_isa_guard.py).
 #include "eae_internal.h"
 #include "eae_common.hip.h"
 #include "eae_edge.hip.h"
-#include "eae_augment.h"
+#include "eae_stage.h"
 #include <cmath>
 #include <cstdio>
 #include <type_traits>
@@ -19,6 +27,7 @@ namespace {
 // bilinear path may lie anywhere.
 struct AugSrcHwc {                      // eae_augment: uint8 HWC [B][H][W][3], ToTensor's / 255
   typedef uint8_t T;
+  static constexpr int BANDS = 3;
   const uint8_t* in; int H, W;
   struct Img { long long base; };
   __device__ __forceinline__ bool image(int b, Img& im) const { im.base = (long long)b * H * W * 3; return true; }
@@ -35,6 +44,7 @@ struct AugSrcHwc {                      // eae_augment: uint8 HWC [B][H][W][3], 
 template <typename TT>
 struct AugSrcBands {                    // eae_stage_bands: planar [N][C][H][W], gathered by index
   typedef TT T;
+  static constexpr int BANDS = 0;
   const TT* src; const long long* index; const float* divisor; long long N; int C, H, W;
   struct Img { long long base; };
   __device__ __forceinline__ bool image(int b, Img& im) const {
@@ -55,6 +65,7 @@ struct AugSrcBands {                    // eae_stage_bands: planar [N][C][H][W],
 template <typename TT, bool CROP_SCENE>
 struct AugSrcScene {                    // eae_scene_stage_windows: window windows[b] of a planar scene [C][Hs][Ws]
   typedef TT T;
+  static constexpr int BANDS = 0;
   const TT* src; const long long* windows; const float* divisor; long long plane, nwin; int C, Hs, Ws, H, W, S, nW;      // H = W = P
   struct Img { long long oy, ox; };
   __device__ __forceinline__ bool image(int b, Img& im) const {
@@ -96,9 +107,14 @@ __device__ __forceinline__ void aug_barrier() {
 __device__ __forceinline__ EAE_NO_PK void aug_call(const StageAug& A, int C, int b, int call, unsigned long long seed, unsigned long long step,
                                                    uint32_t* w) {
   if (call == 0) {
-    int flip, top, left, rot;
-    if (A.geom) { flip = A.geom[b * 4]; top = A.geom[b * 4 + 1]; left = A.geom[b * 4 + 2]; rot = A.geom[b * 4 + 3] & 3; }
-    else { stage_draw_geom(b, seed, step, flip, top, left, rot); if (!A.dihedral) rot = 0; }
+    // (a stride-3 table and the fixed state come from plain calls and train = 0, which launch the PLAIN instantiation only: in the
+    //  others these two tests are never taken)
+    int flip = 0, top = 4, left = 4, rot = 0;
+    if (A.geom) {
+      const int* g = A.geom + (long long)b * A.geom_stride;
+      flip = g[0]; top = g[1]; left = g[2];
+      if (A.geom_stride == 4) rot = g[3] & 3;
+    } else if (!A.fixed) { stage_draw_geom(b, seed, step, flip, top, left, rot); if (!A.dihedral) rot = 0; }
     w[0] = (uint32_t)flip; w[1] = (uint32_t)top; w[2] = (uint32_t)left; w[3] = (uint32_t)rot;
   } else if (call == 1) {
     float a = 1.f, bb = 0.f, g = 1.f;
@@ -144,32 +160,39 @@ __device__ __forceinline__ bool aug_locate(const SRC& s, const typename SRC::Img
   return valid && s.locate(im, sy, sx, flip, off);
 }
 
+// a / d for 0 <= a < lim and 0 < d <= lim: in 32 bits when lim allows it (uniform; a 64-bit division is some hundred instructions)
+__device__ __forceinline__ long long aug_div(long long a, long long d, long long lim) {
+  return lim <= 0xffffffffLL ? (long long)((unsigned)a / (unsigned)d) : a / d;
+}
 __device__ __forceinline__ float aug_lerp(float p, float q, float t) { return fmaf(t, __fsub_rn(q, p), p); }
 
 // ---------------------------------------------------------------------------------------------------------------- the kernel
-// One thread per output pixel, all bands; p is the flat index over [B][H][W], the one the plain kernels have, so the noise of
-// stage_draw_noise4(p, c0) is theirs.
+// One thread per output pixel, all bands; p is the flat index over [B][H][W], which stage_draw_noise4(p, c0) draws the noise for.
 // AFFINE: the bilinear path (four taps); else the integer path (one).  Loads are unconditional -- a tap that reads 0 loads element 0 of
-// the source and drops it -- so the bands' loads of a thread are all in flight together, as in the plain kernels.
-template <typename SRC, bool LDS, bool AFFINE>
-__global__ EAE_NO_PK __launch_bounds__(256) void stage_aug_kernel(SRC s, int C, int B, float* __restrict__ out, float std,
-                                                                  unsigned long long seed, unsigned long long step, StageAug A,
-                                                                  const float* __restrict__ noise) {
-  const int H = s.H, W = s.W;
+// the source and drops it -- so the bands' loads of a thread are all in flight together.
+// PLAIN: the launch has no quarter turn, no radiometric step and no bilinear path (a plain call, a policy with nothing on, train = 0):
+// rot = 0 and the radiometric branch are folded away and every thread makes the one geometric draw itself, no prologue
+// (without the flag the plain calls ran 6 % slower than the kernels this body replaced).
+// SRC::BANDS: the band count when the source fixes it (else 0: nbands).
+template <typename SRC, bool LDS, bool AFFINE, bool PLAIN>
+__global__ EAE_NO_PK __launch_bounds__(256) void stage_kernel(SRC s, int nbands, int B, float* __restrict__ out, float std,
+                                                              unsigned long long seed, unsigned long long step, StageAug A,
+                                                              const float* __restrict__ noise) {
+  const int H = s.H, W = s.W, C = SRC::BANDS ? SRC::BANDS : nbands;
   const long long plane = (long long)H * W, tot = plane * B;
   const long long p0 = (long long)blockIdx.x * 256, p = p0 + threadIdx.x;
-  const bool radio = A.radio_on || A.radio != nullptr;
+  const bool radio = !PLAIN && (A.radio_on || A.radio != nullptr);
   __shared__ uint32_t draws[LDS ? AUG_LDS_IMGS : 1][AUG_CALLS][4];
-  const int b_first = (int)(p0 / plane);
+  const int b_first = (int)aug_div(p0, plane, tot);
   if constexpr (LDS) {
     const int t = threadIdx.x, i = t / AUG_CALLS, call = t - i * AUG_CALLS;
     if (i < AUG_LDS_IMGS && b_first + i < B) aug_call(A, C, b_first + i, call, seed, step, draws[i][call]);
     aug_barrier();
   }
   if (p >= tot) return;
-  const int b = (int)(p / plane);
+  const int b = (int)aug_div(p, plane, tot);
   const long long r = p - b * plane;
-  const int y = (int)(r / W), x = (int)(r - (long long)y * W);
+  const int y = (int)aug_div(r, W, plane), x = (int)(r - (long long)y * W);
   uint32_t wg[4], wi[4];
   if constexpr (LDS) {
 #pragma unroll
@@ -178,7 +201,7 @@ __global__ EAE_NO_PK __launch_bounds__(256) void stage_aug_kernel(SRC s, int C, 
     aug_call(A, C, b, 0, seed, step, wg);
     if (AFFINE || radio) aug_call(A, C, b, 1, seed, step, wi); else { wi[0] = aug_bits(1.f); wi[1] = 0u; wi[2] = wi[0]; wi[3] = 0u; }
   }
-  const int flip = (int)wg[0], top = (int)wg[1], left = (int)wg[2], rot = (int)wg[3];
+  const int flip = (int)wg[0], top = (int)wg[1], left = (int)wg[2], rot = PLAIN ? 0 : (int)wg[3];
   const float ca = aug_float(wi[0]), cb = aug_float(wi[1]), g = aug_float(wi[2]);
   typename SRC::Img im;
   const bool valid = s.image(b, im);
@@ -239,19 +262,26 @@ __global__ EAE_NO_PK __launch_bounds__(256) void stage_aug_kernel(SRC s, int C, 
   }
 }
 
+// train = 0: the fixed state in place of `policy` -- nothing is drawn, neither through LDS nor by a thread, and no noise is added
 template <typename SRC>
-int launch_aug(hipStream_t st, const SRC& s, int C, int B, float* out, float std, unsigned long long seed, unsigned long long step,
-               const StageAug& aug, const float* noise, const char* too_large) {
+int launch_aug(hipStream_t st, const SRC& s, int C, int B, float* out, int train, float std, unsigned long long seed,
+               unsigned long long step, const StageAug& policy, const float* noise, const char* too_large) {
   const long long nblk = ((long long)B * s.H * s.W + 255) / 256;
   if (nblk > 0x7fffffffLL) return eae_set_error(EAE_ERR_ARG, too_large);
-  EAE_NO_GROUP("stage_aug_kernel");
+  EAE_NO_GROUP("stage_kernel");
+  StageAug aug = policy;
+  if (!train) { aug = StageAug(); aug.fixed = 1; std = 0.f; }
   const bool affine = aug.affine_on || aug.affine != nullptr;
-  auto launch = [&](auto lds, auto aff) {
-    hipLaunchKernelGGL((stage_aug_kernel<SRC, decltype(lds)::value, decltype(aff)::value>), dim3((unsigned)nblk), dim3(256), 0, st, s, C, B,
-                       out, std, seed, step, aug, noise);
+  const bool plain = !affine && !aug.radio_on && !aug.radio && !aug.dihedral && !(aug.geom && aug.geom_stride == 4);
+  const std::true_type yes;
+  const std::false_type no;
+  auto launch = [&](auto lds, auto aff, auto pl) {
+    hipLaunchKernelGGL((stage_kernel<SRC, decltype(lds)::value, decltype(aff)::value, decltype(pl)::value>), dim3((unsigned)nblk), dim3(256),
+                       0, st, s, C, B, out, std, seed, step, aug, noise);
   };
-  if (aug.lds) { if (affine) launch(std::true_type(), std::true_type()); else launch(std::true_type(), std::false_type()); }
-  else { if (affine) launch(std::false_type(), std::true_type()); else launch(std::false_type(), std::false_type()); }
+  if (plain) launch(no, no, yes);                      // whatever aug.lds says: a PLAIN launch draws per thread
+  else if (aug.lds) { if (affine) launch(yes, yes, no); else launch(yes, no, no); }
+  else { if (affine) launch(no, yes, no); else launch(no, no, no); }
   EAE_LAUNCH_CHECK();
   return 0;
 }
@@ -261,7 +291,7 @@ bool range_ok(float v, float below) { return std::isfinite(v) && v >= 0.f && v <
 }  // namespace
 
 int eae_stage_aug_prepare(const eae_aug* aug, const int* geom, const float* affine, const float* radio, int H, int W, const char* who,
-                          StageAug* out, int* active) {
+                          StageAug* out) {
   StageAug a = StageAug();
   char msg[160];
   auto fail = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", who, what); return eae_set_error(EAE_ERR_ARG, msg); };
@@ -283,71 +313,159 @@ int eae_stage_aug_prepare(const eae_aug* aug, const int* geom, const float* affi
     a.bg_lo = 1.f - aug->band_gain; a.bg_w = 2.f * aug->band_gain;
     a.of_lo = -aug->offset; a.of_w = 2.f * aug->offset;
   }
-  a.geom = geom; a.affine = affine; a.radio = radio;
-  *active = a.dihedral || a.affine_on || a.radio_on || geom || affine || radio;
+  a.geom = geom; a.geom_stride = 4; a.affine = affine; a.radio = radio;
   if ((a.dihedral || geom) && H != W) return fail("augment: quarter turns (dihedral, geom) need square images, H == W");
   const long long plane = (long long)H * W;
   if (mode == 2 && plane < 256) return fail("augment: draw_mode 2 needs images of at least 256 pixels");
-  // the draws of an image: by every thread, or once per workgroup through LDS ("Augmentation policy")
+  // the draws of an image: by every thread, or once per workgroup through LDS ("Augmentation policy").  Read by launches
+  // with something of the policy on; one with nothing on (PLAIN) draws per thread under every draw_mode, 2 included.
   a.lds = mode == 2 || (mode == 0 && plane >= 256);
   *out = a;
   return 0;
 }
 
-int eae_launch_augment_aug(hipStream_t st, const void* in_u8, float* out, int B, int H, int W, float std, unsigned long long seed,
-                           unsigned long long step, const StageAug& aug, const float* noise) {
-  if (!in_u8 || !out || B <= 0 || H <= 0 || W <= 0) return eae_set_error(EAE_ERR_ARG, "augment: bad argument");
-  const AugSrcHwc s = {(const uint8_t*)in_u8, H, W};
-  return launch_aug(st, s, 3, B, out, std, seed, step, aug, noise, "augment: batch too large");
+StageAug eae_stage_plain(const int* params) {
+  StageAug a = StageAug();
+  a.geom = params; a.geom_stride = 3;
+  return a;
 }
 
-int eae_launch_stage_bands_aug(hipStream_t st, const void* src, int elem_bytes, long long N, int C, int H, int W, const long long* index,
-                               int B, const float* divisor, float* out, float std, unsigned long long seed, unsigned long long step,
-                               const StageAug& aug, const float* noise) {
+// the checks and the launch of eae_augment[_aug]
+static int stage_hwc(hipStream_t st, const void* in_u8, float* out, int B, int H, int W, int train, float std, unsigned long long seed,
+                     unsigned long long step, const StageAug& aug, const float* noise) {
+  if (!in_u8 || !out || B <= 0 || H <= 0 || W <= 0) return eae_set_error(EAE_ERR_ARG, "augment: bad argument");
+  const AugSrcHwc s = {(const uint8_t*)in_u8, H, W};
+  return launch_aug(st, s, 3, B, out, train, std, seed, step, aug, noise, "augment: batch too large");
+}
+
+// the checks and the launch of eae_stage_bands[_aug]
+static int stage_bands(hipStream_t st, const void* src, int elem_bytes, long long N, int C, int H, int W, const long long* index, int B,
+                       const float* divisor, float* out, int train, float std, unsigned long long seed, unsigned long long step,
+                       const StageAug& aug, const float* noise) {
   if (!src || !divisor || !out || N <= 0 || B <= 0 || H <= 0 || W <= 0) return eae_set_error(EAE_ERR_ARG, "stage_bands: bad argument");
   if (C < 1 || C > 16) return eae_set_error(EAE_ERR_ARG, "stage_bands: in_channels must be in 1..16");
   if (elem_bytes != 1 && elem_bytes != 2) return eae_set_error(EAE_ERR_ARG, "stage_bands: source must be uint8 or uint16 (elem_bytes 1 or 2)");
   if (!index && B > N) return eae_set_error(EAE_ERR_ARG, "stage_bands: without an index the batch is the first B images (B <= N)");
   if (elem_bytes == 1) {
     const AugSrcBands<uint8_t> s = {(const uint8_t*)src, index, divisor, N, C, H, W};
-    return launch_aug(st, s, C, B, out, std, seed, step, aug, noise, "stage_bands: batch too large");
+    return launch_aug(st, s, C, B, out, train, std, seed, step, aug, noise, "stage_bands: batch too large");
   }
   const AugSrcBands<uint16_t> s = {(const uint16_t*)src, index, divisor, N, C, H, W};
-  return launch_aug(st, s, C, B, out, std, seed, step, aug, noise, "stage_bands: batch too large");
+  return launch_aug(st, s, C, B, out, train, std, seed, step, aug, noise, "stage_bands: batch too large");
+}
+
+int eae_launch_augment(hipStream_t st, const void* in_u8, float* out, int B, int H, int W, int train, float std, unsigned long long seed,
+                       unsigned long long step, const int* params, const float* noise) {
+  return stage_hwc(st, in_u8, out, B, H, W, train, std, seed, step, eae_stage_plain(params), noise);
+}
+
+int eae_launch_stage_bands(hipStream_t st, const void* src, int elem_bytes, long long N, int C, int H, int W, const long long* index, int B,
+                           const float* divisor, float* out, int train, float std, unsigned long long seed, unsigned long long step,
+                           const int* params, const float* noise) {
+  return stage_bands(st, src, elem_bytes, N, C, H, W, index, B, divisor, out, train, std, seed, step, eae_stage_plain(params), noise);
 }
 
 template <typename T, bool CROP_SCENE>
-static int launch_scene_aug(hipStream_t st, const eae_scene* sc, long long nW, long long nwin, const long long* windows, int B, float* out,
-                            float std, unsigned long long seed, unsigned long long step, const StageAug& aug, const float* noise) {
+static int launch_scene(hipStream_t st, const eae_scene* sc, long long nW, long long nwin, const long long* windows, int B, float* out,
+                        int train, float std, unsigned long long seed, unsigned long long step, const StageAug& aug, const float* noise) {
   const AugSrcScene<T, CROP_SCENE> s = {(const T*)sc->data, windows, sc->divisor, (long long)sc->H * sc->W, nwin, sc->C, sc->H, sc->W,
                                         sc->patch, sc->patch, sc->stride, (int)nW};
-  return launch_aug(st, s, sc->C, B, out, std, seed, step, aug, noise, "scene_stage_windows: batch too large");
+  return launch_aug(st, s, sc->C, B, out, train, std, seed, step, aug, noise, "scene_stage_windows: batch too large");
 }
-int eae_launch_scene_stage_aug(hipStream_t st, const eae_scene* s, long long nW, long long nwin, const long long* windows, int B,
-                               float* out, float std, unsigned long long seed, unsigned long long step, const StageAug& aug,
-                               const float* noise, int crop) {
+int eae_launch_scene_stage(hipStream_t st, const eae_scene* s, long long nW, long long nwin, const long long* windows, int B, float* out,
+                           int train, float std, unsigned long long seed, unsigned long long step, const StageAug& aug, const float* noise,
+                           int crop) {
   const bool sc = crop == EAE_CROP_SCENE;
   switch (s->dtype) {
     case EAE_SCENE_U8:
-      return sc ? launch_scene_aug<uint8_t, true>(st, s, nW, nwin, windows, B, out, std, seed, step, aug, noise)
-                : launch_scene_aug<uint8_t, false>(st, s, nW, nwin, windows, B, out, std, seed, step, aug, noise);
+      return sc ? launch_scene<uint8_t, true>(st, s, nW, nwin, windows, B, out, train, std, seed, step, aug, noise)
+                : launch_scene<uint8_t, false>(st, s, nW, nwin, windows, B, out, train, std, seed, step, aug, noise);
     case EAE_SCENE_U16:
-      return sc ? launch_scene_aug<uint16_t, true>(st, s, nW, nwin, windows, B, out, std, seed, step, aug, noise)
-                : launch_scene_aug<uint16_t, false>(st, s, nW, nwin, windows, B, out, std, seed, step, aug, noise);
+      return sc ? launch_scene<uint16_t, true>(st, s, nW, nwin, windows, B, out, train, std, seed, step, aug, noise)
+                : launch_scene<uint16_t, false>(st, s, nW, nwin, windows, B, out, train, std, seed, step, aug, noise);
     default:
-      return sc ? launch_scene_aug<float, true>(st, s, nW, nwin, windows, B, out, std, seed, step, aug, noise)
-                : launch_scene_aug<float, false>(st, s, nW, nwin, windows, B, out, std, seed, step, aug, noise);
+      return sc ? launch_scene<float, true>(st, s, nW, nwin, windows, B, out, train, std, seed, step, aug, noise)
+                : launch_scene<float, false>(st, s, nW, nwin, windows, B, out, train, std, seed, step, aug, noise);
   }
+}
+
+// The plain scene call alone keeps a kernel of its own: stage_kernel's PLAIN instantiation over AugSrcScene computes the same values
+// (tests/test_gpu_augment.py::test_no_policy_is_the_plain_call) but ran the loader epochs 1 - 2 % slower, for a cause that was not
+// found.  The transform is the head comment's with src_b = window windows[b], origin (oy, ox); one thread per
+// output pixel, all bands, p the flat index over [B][P][P]; the draws are stage_kernel's calls (eae_stage.h), so equal (b, p, c0, seed,
+// step) give equal values.  CROP_SCENE = false: (sy, unflipped sx) outside [0, P) reads 0; true: the read is bounds-checked against
+// the scene instead.  An id outside [0, nwin) gives NaN and reads nothing.
+template <typename T, bool CROP_SCENE>
+__global__ EAE_NO_PK __launch_bounds__(256) void scene_stage_windows_kernel(const T* __restrict__ src, const float* __restrict__ divisor,
+                                                                        int C, long long plane, int Hs, int Ws, int P, int S, int nW,
+                                                                        long long nwin, const long long* __restrict__ windows, int B,
+                                                                        float* __restrict__ out, int train, float std,
+                                                                        unsigned long long seed, unsigned long long step,
+                                                                        const int* __restrict__ params, const float* __restrict__ noise) {
+  const long long pp = (long long)P * P;
+  const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= pp * B) return;
+  const int b = (int)(p / pp);
+  const long long r = p - b * pp;
+  const int y = (int)(r / P), x = (int)(r - (long long)y * P);
+  const long long w = windows[b];
+  const bool valid = w >= 0 && w < nwin;
+  int flip = 0, top = 4, left = 4, rot = 0;
+  if (train) {
+    if (params) { flip = params[b * 3]; top = params[b * 3 + 1]; left = params[b * 3 + 2]; }
+    else stage_draw_geom(b, seed, step, flip, top, left, rot);
+  }
+  const long long sy = (long long)y + top - 4;
+  long long sx = (long long)x + left - 4;
+  bool inside = valid;
+  if constexpr (!CROP_SCENE) inside = inside && sy >= 0 && sy < P && sx >= 0 && sx < P;
+  if (flip) sx = P - 1 - sx;
+  const long long wi = valid ? w / nW : 0, wj = valid ? w - wi * nW : 0;
+  const long long gy = wi * S + sy, gx = wj * S + sx;                  // scene pixel
+  if constexpr (CROP_SCENE) inside = inside && gy >= 0 && gy < Hs && gx >= 0 && gx < Ws;
+  const T* q = src + (inside ? gy * Ws + gx : 0);
+  for (int c0 = 0; c0 < C; c0 += 4) {
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+    if (train && std != 0.f && !noise) stage_draw_noise4(p, c0, seed, step, z);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int c = c0 + j;
+      if (c >= C) break;
+      float v = inside ? scene_val(q[c * plane], divisor[c]) : 0.f;
+      if (!valid) v = __builtin_nanf("");
+      if (train && std != 0.f) v = fmaf(std, noise ? noise[((long long)b * C + c) * pp + r] : z[j], v);
+      out[((long long)b * C + c) * pp + r] = v;
+    }
+  }
+}
+int eae_launch_scene_stage_plain(hipStream_t st, const eae_scene* s, long long nW, long long nwin, const long long* windows, int B,
+                                 float* out, int train, float std, unsigned long long seed, unsigned long long step, const int* params,
+                                 const float* noise, int crop) {
+  const long long plane = (long long)s->H * s->W, nblk = ((long long)B * s->patch * s->patch + 255) / 256;
+  if (nblk > 0x7fffffffLL) return eae_set_error(EAE_ERR_ARG, "scene_stage_windows: batch too large");
+  EAE_NO_GROUP("scene_stage_windows_kernel");
+  auto launch = [&](auto* t, auto scene_crop) {
+    using T = std::remove_cv_t<std::remove_pointer_t<decltype(t)>>;
+    hipLaunchKernelGGL((scene_stage_windows_kernel<T, decltype(scene_crop)::value>), dim3((unsigned)nblk), dim3(256), 0, st,
+                       (const T*)s->data, s->divisor, s->C, plane, s->H, s->W, s->patch, s->stride, (int)nW, nwin, windows, B, out, train,
+                       std, seed, step, params, noise);
+  };
+  auto by_crop = [&](auto* t) { if (crop == EAE_CROP_SCENE) launch(t, std::true_type()); else launch(t, std::false_type()); };
+  switch (s->dtype) {
+    case EAE_SCENE_U8: by_crop((const uint8_t*)nullptr); break;
+    case EAE_SCENE_U16: by_crop((const uint16_t*)nullptr); break;
+    default: by_crop((const float*)nullptr);
+  }
+  EAE_LAUNCH_CHECK();
+  return 0;
 }
 
 extern "C" int eae_augment_aug(void* stream, const void* in_u8, float* out, int B, int H, int W, int train, float noise_std,
                                unsigned long long seed, unsigned long long step, const eae_aug* aug, const int* geom,
                                const float* affine, const float* radio, const float* noise) {
   StageAug a;
-  int active = 0;
-  if (int rc = eae_stage_aug_prepare(aug, geom, affine, radio, H, W, "augment", &a, &active)) return rc;
-  if (!train || !active) return eae_launch_augment((hipStream_t)stream, in_u8, out, B, H, W, train, noise_std, seed, step, nullptr, noise);
-  return eae_launch_augment_aug((hipStream_t)stream, in_u8, out, B, H, W, noise_std, seed, step, a, noise);
+  if (int rc = eae_stage_aug_prepare(aug, geom, affine, radio, H, W, "augment", &a)) return rc;
+  return stage_hwc((hipStream_t)stream, in_u8, out, B, H, W, train, noise_std, seed, step, a, noise);
 }
 
 extern "C" int eae_stage_bands_aug(void* stream, const void* src, int elem_bytes, long long N, int C, int H, int W, const long long* index,
@@ -355,10 +473,6 @@ extern "C" int eae_stage_bands_aug(void* stream, const void* src, int elem_bytes
                                    unsigned long long step, const eae_aug* aug, const int* geom, const float* affine,
                                    const float* radio, const float* noise) {
   StageAug a;
-  int active = 0;
-  if (int rc = eae_stage_aug_prepare(aug, geom, affine, radio, H, W, "stage_bands", &a, &active)) return rc;
-  if (!train || !active)
-    return eae_launch_stage_bands((hipStream_t)stream, src, elem_bytes, N, C, H, W, index, B, divisor, out, train, noise_std, seed, step,
-                                  nullptr, noise);
-  return eae_launch_stage_bands_aug((hipStream_t)stream, src, elem_bytes, N, C, H, W, index, B, divisor, out, noise_std, seed, step, a, noise);
+  if (int rc = eae_stage_aug_prepare(aug, geom, affine, radio, H, W, "stage_bands", &a)) return rc;
+  return stage_bands((hipStream_t)stream, src, elem_bytes, N, C, H, W, index, B, divisor, out, train, noise_std, seed, step, a, noise);
 }

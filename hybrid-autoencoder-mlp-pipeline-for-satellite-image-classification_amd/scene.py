@@ -82,7 +82,7 @@ import torch
 from . import _lib
 from ._lib import check
 from .engine import _ptr, _stream, _require_gpu, engine_for
-from .augment import Augment, _aug_args
+from .augment import Augment, _aug_args, _plain_draws
 
 _DTYPES = {torch.uint8: 0, torch.uint16: 1, torch.float32: 2}
 
@@ -709,12 +709,7 @@ def stage_scene_windows(scene, divisor, patch, stride, windows, train=True, nois
     windows = _windows_arg(windows, scene.device, 0, allow_empty=False, check_range=False)
     b, c, p = windows.numel(), int(scene.shape[0]), int(patch)
     aug = _aug_args(augment, params, geom, affine, radio, b, c, p, p, scene.device)
-    if params is not None:
-        if not isinstance(params, torch.Tensor) or tuple(params.shape) != (b, 3):
-            raise RuntimeError(f"params must be int32 [B,3] = (flip, top, left) with B = {b}")
-    if noise is not None:
-        if not isinstance(noise, torch.Tensor) or tuple(noise.shape) != (b, c, p, p):
-            raise RuntimeError(f"noise must be [B,C,P,P] = {(b, c, p, p)}")
+    params, noise = _plain_draws(params, noise, (b, c, p, p), scene.device)
     desc, keep, _, _ = _scene_desc(scene, divisor, patch, stride, any_patch=True)        # grid, device, bands, divisor
     return _stage_windows(desc, keep, windows, train, noise_std, seed, step, params, noise, cid, aug)
 
@@ -723,10 +718,6 @@ def _stage_windows(desc, keep, windows, train, noise_std, seed, step, params, no
     """The C call of `stage_scene_windows` on a validated scene descriptor (`_scene_desc`) and id list: what a `SceneLoader` runs
     per batch.  aug: None (the plain call) or `_aug_args`' (policy, geom, affine, radio)."""
     dev, b = keep[0].device, windows.numel()
-    if params is not None:
-        params = params.to(device=dev, dtype=torch.int32).contiguous()
-    if noise is not None:
-        noise = noise.to(device=dev, dtype=torch.float32).contiguous()
     lib = _lib.load()
     out = torch.empty((b, desc.C, desc.patch, desc.patch), dtype=torch.float32, device=dev)
     seed, step = int(seed) & (2**64 - 1), int(step) & (2**64 - 1)

@@ -1,4 +1,4 @@
-"""Plain NumPy restatement of the augmentation policy of the staging calls (include/eae.h, "augmentation policy"; csrc/eae_augment.hip),
+"""Plain NumPy restatement of the augmentation policy of the staging calls (include/eae.h, "augmentation policy"; csrc/eae_stage.hip),
 on `mlp_ref.philox4x32_10` and `stage_ref`.
 
 Random draws.  (flip, top, left) are `stage_ref.stage_params`, whatever the policy.  With (seed lo, seed hi) and (step lo, step hi)

@@ -1,5 +1,5 @@
-"""Plain NumPy restatement of the staging kernels' random stream and transform (csrc/eae_misc.h: philox4, stage_draw_params,
-stage_draw_noise4; augment_kernel, stage_bands_kernel, scene_stage_windows_kernel).
+"""Plain NumPy restatement of the staging kernel's random stream and transform without a policy (csrc/eae_stage.h: philox4,
+stage_draw_geom, stage_draw_noise4; csrc/eae_stage.hip: stage_kernel over AugSrcHwc, AugSrcBands, AugSrcScene).
 
 The stream is counter-based Philox4x32-10 (`mlp_ref.philox4x32_10`, itself pinned by the Random123 known-answer vectors), keyed by
 (seed, step):
@@ -90,6 +90,27 @@ def stage_transform(imgs, params, div):
     for n in range(b):
         flip, top, left = (int(v) for v in params[n])
         out[n] = _crop(imgs[n], flip, top, left).astype(np.float32) / div[:, None, None]
+    return out
+
+
+def scene_transform(scene, origins, p, params, div, crop):
+    """fp32 [B,C,P,P] of the P x P windows of a planar scene [C,H,W] at `origins` [B] = (oy, ox) (stage_scene_windows).
+    crop="window": `stage_transform` of the windows; crop="scene": the same flip and crop of the window's neighbourhood in the
+    zero-padded scene, so the crop reads the real pixels around the window."""
+    if isinstance(params, tuple):
+        params = np.stack(params, 1)
+    if crop == "window":
+        return stage_transform(np.stack([scene[:, oy:oy + p, ox:ox + p] for oy, ox in origins]), params, div)
+    assert crop == "scene"
+    div = np.broadcast_to(np.asarray(div, np.float32).reshape(-1), (scene.shape[0],))
+    padded = np.pad(scene, ((0, 0), (4, 4), (4, 4)))
+    out = np.empty((len(origins), scene.shape[0], p, p), np.float32)
+    for b, (oy, ox) in enumerate(origins):
+        flip, top, left = (int(v) for v in params[b])
+        ext = padded[:, oy:oy + p + 8, ox:ox + p + 8]
+        if flip:
+            ext = ext[..., ::-1]
+        out[b] = ext[:, top:top + p, left:left + p].astype(np.float32) / div[:, None, None]
     return out
 
 

@@ -386,21 +386,31 @@ def test_images_do_not_depend_on_the_window_origin():
 
 # ---------------------------------------------------------------------------------------------------- g. off means off
 def test_no_policy_is_the_plain_call():
+    """Plain and no-policy calls run the same kernel (but for the scene), so the plain result is also anchored: to the NumPy restatement (stage_ref.py)
+    with the draws of `stage_params`, and train=False to the division alone."""
     import eae_amd
     rng = np.random.default_rng(47)
     full = eae_amd.Augment(**FULL)
-    data = _dev_uint(rng.integers(0, 10001, (6, 5, HW, HW)).astype(np.uint16))
-    u8 = torch.from_numpy(rng.integers(0, 256, (6, HW, HW, 3)).astype(np.uint8)).cuda()
+    data_np = rng.integers(0, 10001, (6, 5, HW, HW)).astype(np.uint16)
+    u8_np = rng.integers(0, 256, (6, HW, HW, 3)).astype(np.uint8)
+    data, u8 = _dev_uint(data_np), torch.from_numpy(u8_np).cuda()
     scene, arr, div, p, s, (n_h, n_w), ids = _scene_case("uint16")
-    calls = [lambda **kw: eae_amd.stage_bands(data, 10000.0, **kw), lambda **kw: eae_amd.augment_batch(u8, **kw),
-             lambda **kw: eae_amd.stage_scene_windows(scene, div, p, s, _ids_dev(ids), crop="scene", **kw),
-             lambda **kw: eae_amd.stage_scene_windows(scene, div, p, s, _ids_dev(ids), **kw)]
-    for call in calls:
+    origins = [((n // n_w) * s, (n % n_w) * s) for n in ids]
+    calls = [(lambda **kw: eae_amd.stage_bands(data, 10000.0, **kw), lambda g: S.stage_transform(data_np, g, 10000.0)),
+             (lambda **kw: eae_amd.augment_batch(u8, **kw), lambda g: S.stage_transform_hwc(u8_np, g)),
+             (lambda **kw: eae_amd.stage_scene_windows(scene, div, p, s, _ids_dev(ids), crop="scene", **kw),
+              lambda g: S.scene_transform(arr, origins, p, g, div, "scene")),
+             (lambda **kw: eae_amd.stage_scene_windows(scene, div, p, s, _ids_dev(ids), **kw),
+              lambda g: S.scene_transform(arr, origins, p, g, div, "window"))]
+    for call, ref in calls:
         plain = call(seed=9, step=4)
         assert torch.equal(call(seed=9, step=4, augment=None), plain)
         assert torch.equal(call(seed=9, step=4, augment=eae_amd.Augment()), plain)
         assert not torch.equal(call(seed=9, step=4, augment=full), plain)
         assert torch.equal(call(seed=9, step=4, train=False, augment=full), call(train=False))
+        b = len(plain)
+        assert np.array_equal(_np(call(seed=9, step=4, noise_std=0.0)), ref(S.stage_params(9, 4, b)))
+        assert np.array_equal(_np(call(seed=9, step=4, train=False, augment=full)), ref(np.array([(0, 4, 4)] * b)))
 
 
 @pytest.mark.parametrize("crop", ["window", "scene"])

@@ -115,6 +115,33 @@ def test_stage_transform_layout():
     assert np.array_equal(S.stage_transform(img, S.stage_params(3, 5, 1), div), S.stage_transform(img, S.params_array(3, 5, 1), div))
 
 
+@pytest.mark.parametrize("crop", ["window", "scene"])
+def test_scene_transform_is_the_per_pixel_statement(crop):
+    """`scene_transform` against the transform written out pixel by pixel (include/eae.h, eae_scene_stage_windows): output (y, x)
+    reads window-local (sy, sx) = (y + top - 4, x + left - 4), mirrored to P - 1 - sx when flipped; crop="window" reads 0 when the
+    unflipped position leaves the window, crop="scene" when the scene pixel leaves the scene."""
+    c, hs, ws, p = 2, 21, 26, 8
+    scene = np.arange(1, 1 + c * hs * ws).reshape(c, hs, ws).astype(np.uint16)
+    div = np.array([1.0, 3.0], np.float32)
+    origins = [(0, 0), (hs - p, ws - p), (0, ws - p), (hs - p, 0), (5, 7), (6, 9)]
+    params = [(0, 0, 0), (1, 8, 8), (1, 0, 8), (0, 8, 0), (1, 4, 2), (0, 2, 5)]
+    ref = np.zeros((len(origins), c, p, p), np.float32)
+    for b, ((oy, ox), (flip, top, left)) in enumerate(zip(origins, params)):
+        for y in range(p):
+            for x in range(p):
+                sy, sx = y + top - 4, x + left - 4
+                in_window = 0 <= sy < p and 0 <= sx < p
+                if flip:
+                    sx = p - 1 - sx
+                gy, gx = oy + sy, ox + sx
+                if in_window if crop == "window" else (0 <= gy < hs and 0 <= gx < ws):
+                    ref[b, :, y, x] = scene[:, gy, gx].astype(np.float32) / div
+    got = S.scene_transform(scene, origins, p, params, div, crop)
+    assert got.dtype == np.float32 and np.array_equal(got, ref)
+    other = S.scene_transform(scene, origins, p, params, div, "scene" if crop == "window" else "window")
+    assert not np.array_equal(got, other)                          # the corner windows tell the two crops apart
+
+
 # ---------------------------------------------------------------------------------------------------- geometric draws
 @pytest.mark.parametrize("seed,step", SEED_STEPS)
 def test_geometric_draws_are_uniform(seed, step):

@@ -11,7 +11,7 @@ offset: the integer path) and `aug_full_*` (those plus a rotation of up to 15 de
 Every arm walks the same number of batches of the same sizes; the arms alternate inside one process, after a warm-up, and a repetition
 times whole epochs (--min-windows per repetition at least) between device events, ending in a synchronise.  Median, min and max of
 --reps.  The epoch time includes the host side of every batch (argument checks, the C call); the kernels alone come from a separate
-`rocprofv3 --kernel-trace --stats -- python tools/scene_stage_bench.py` run (scene_stage_windows_kernel, stage_bands_kernel).
+`rocprofv3 --kernel-trace --stats -- python tools/scene_stage_bench.py` run (the stage_kernel instantiations of csrc/eae_stage.hip).
 
     python tools/scene_stage_bench.py [--reps 7] [--warmup 2] [--strides 16 64] [--augment]   ->  JSON lines
 """
