@@ -153,7 +153,7 @@ struct eae_ctx {
   double* clip_part = nullptr;     // workspace: EAE_CLIP_MAX_PARTS fp64 partials
   long long psize[T_COUNT];        // elements of the 38 tensors without the layout's rounding
   bool clip_on() const { return clip_max != 0.f; }
-  float* dyn = nullptr;            // device: lr/bc1, sqrt(bc2), weight decay of the current Adam step
+  float* dyn = nullptr;            // device: lr/bc1, sqrt(bc2) of the current Adam step (graph path)
   // optional in-situ timing of ONE launch site (eae_profile_enable(ctx, site); sites: include/eae.h) with HIP events on the
   // stream that launch goes to
   static constexpr int PROF_RING = 64;
@@ -222,11 +222,10 @@ int check_io(eae_ctx* c, const eae_step_io* io, bool need_grad);
 int forward_impl(eae_ctx* c, hipStream_t st, const eae_step_io* io, bool want_grad);
 int backward_impl(eae_ctx* c, hipStream_t st, const eae_step_io* io, const float* dz_ext = nullptr, int part = 0);
 int train_step_eager(eae_ctx* c, hipStream_t st, const eae_step_io* io, float lr);
-// the engine's Adam over the first n arena elements; bad / bad2 = the words that make it refuse the update (default: the context's own)
+// the engine's Adam over the first n arena elements, behind the sum-of-squares launch when eae_set_grad_clip is on; bad / bad2 = the
+// words that make it refuse the update (default: the context's own); dyn = the graph path's form (scalars from c->dyn)
 int launch_adam(eae_ctx* c, hipStream_t st, long long n, float lr, float wd, float grad_scale, const unsigned* bad = nullptr,
-                const unsigned* bad2 = nullptr);
-// with eae_set_grad_clip on: the sum-of-squares launch that goes in front of an optimizer launch, and that launch's clip block
-int clip_prepare(eae_ctx* c, hipStream_t st, EaeClip* clip);
+                const unsigned* bad2 = nullptr, bool dyn = false);
 // optimizer.step(): launch_adam over the whole arena and the host-side state behind it
 int optimizer_step(eae_ctx* c, hipStream_t st, float lr, float wd, float grad_scale, const unsigned* bad = nullptr, const unsigned* bad2 = nullptr);
 // dL/d(pre-sigmoid) from (x_hat, dx_hat) into g (bf16 NHWC-CP), then deconv4's bias gradient db from the per-block partials in `part`

@@ -31,6 +31,7 @@ inline hipError_t eae_smem_attr(const void* func, size_t bytes) {
 
 #include "eae_group.h"
 #include "eae_misc.h"
+#include "eae_optim.h"
 #include "eae_head.h"
 // optional bracket around the MAIN kernel of a launcher that enqueues more than one (weight gradient + slice reduction)
 struct EaeProfHook { void (*begin)(void* user, hipStream_t st); void (*end)(void* user, hipStream_t st); void* user; };

@@ -72,20 +72,3 @@ int eae_launch_pack_all(hipStream_t st, const PackDesc* descs_dev, int ndesc, co
 int eae_pack_assign_blocks(PackDesc* descs_host, int ndesc, unsigned short* blkmap_host, int blkmap_cap);      // returns the total, fills blk0 / nblk / the map
 int eae_launch_pack_flat(hipStream_t st, const PackDesc* descs_all, const unsigned short* blkmap, int blk_begin, int blk_count, const float* params,
                          void* pack_base, Fp8State* q = nullptr, unsigned* clear_word = nullptr);
-int eae_launch_adam(hipStream_t st, float* p, const float* g, float* m, float* v, long long n, double lr, double b1, double b2,
-                    double eps, double wd, long long step);
-// global gradient-norm clipping (eae_set_grad_clip): the partials of eae_launch_grad_sumsq and what the optimizer launch behind it
-// does with them; nullptr = the plain optimizer kernels
-constexpr int EAE_CLIP_MAX_PARTS = 512;
-struct EaeClip { const double* part; int nparts; float max_norm; float* norm_out; };
-int eae_grad_sumsq_parts(long long n);
-// sum of squares over the 38 tensors at poff39[s] .. + sizes38[s] of the gradient arena `g` -> eae_grad_sumsq_parts(poff39[38]) partials
-int eae_launch_grad_sumsq(hipStream_t st, const float* g, const long long* poff39, const long long* sizes38, double* part);
-int eae_launch_adam_dyn(hipStream_t st, float* p, const float* g, float* m, float* v, long long n, double b1, double b2, double eps,
-                        const float* dyn, const unsigned* bad = nullptr, const unsigned* bad2 = nullptr, float* nan_out = nullptr,
-                        const EaeClip* clip = nullptr);
-int eae_launch_set_dyn(hipStream_t st, float* dyn, double lr, double b1, double b2, double wd, long long step);
-int eae_launch_adam_scaled(hipStream_t st, float* p, const float* g, float* m, float* v, long long n, double lr, double b1, double b2,
-                           double eps, double wd, long long step, float gscale, void* zero_buf = nullptr, long long zero_bytes = 0,
-                           const unsigned* bad = nullptr, const unsigned* bad2 = nullptr, float* nan_out = nullptr, int nan_fill = 0,
-                           int max_blocks = 0 /* 0: 2048; the grid-stride loop covers the rest */, const EaeClip* clip = nullptr);

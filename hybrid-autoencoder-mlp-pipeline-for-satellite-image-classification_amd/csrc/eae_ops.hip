@@ -211,5 +211,7 @@ extern "C" int eae_augment(void* stream, const void* in_u8, float* out, int B, i
 }
 extern "C" int eae_op_adam(void* stream, float* p, const float* g, float* m, float* v, long long n, double lr, double b1, double b2,
                            double eps, double wd, long long step) {
-  return eae_launch_adam((hipStream_t)stream, p, g, m, v, n, lr, b1, b2, eps, wd, step);
+  AdamLaunch a;
+  a.p = p; a.g = g; a.m = m; a.v = v; a.n = n; a.lr = lr; a.b1 = b1; a.b2 = b2; a.eps = eps; a.wd = wd; a.step = step;
+  return eae_launch_adam((hipStream_t)stream, a);
 }

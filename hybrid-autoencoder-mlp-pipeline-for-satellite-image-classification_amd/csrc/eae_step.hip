@@ -659,18 +659,20 @@ extern "C" int eae_fp8_scales(eae_ctx* c, float* out18) {
   return 0;
 }
 
-// eae_set_grad_clip: the partial sums of g^2 over the 38 tensors, on the stream of the optimizer launch and right in front of it
-int clip_prepare(eae_ctx* c, hipStream_t st, EaeClip* clip) {
-  RC(eae_launch_grad_sumsq(st, c->G, c->poff, c->psize, c->clip_part));
-  clip->part = c->clip_part; clip->nparts = eae_grad_sumsq_parts(c->arena_len()); clip->max_norm = c->clip_max; clip->norm_out = c->clip_out;
-  return 0;
-}
-int launch_adam(eae_ctx* c, hipStream_t st, long long n, float lr, float wd, float grad_scale, const unsigned* bad, const unsigned* bad2) {
-  EaeClip clip;
-  if (c->clip_on()) RC(clip_prepare(c, st, &clip));
-  return eae_launch_adam_scaled(st, c->P, c->G, c->M, c->V, n, lr, 0.9, 0.999, 1e-8, wd, c->adam_step, grad_scale, c->acc_base,
-                                (long long)c->poison_off, bad ? bad : c->sigwords + 8, bad2 ? bad2 : poison_word(c), c->last_loss, c->nan_exact,
-                                0, c->clip_on() ? &clip : nullptr);
+// dyn: the form a captured step replays -- step size and bias correction come from c->dyn (eae_launch_set_dyn ran on this stream), the
+// step's own memset clears the accumulators and nan_exact is not honoured
+int launch_adam(eae_ctx* c, hipStream_t st, long long n, float lr, float wd, float grad_scale, const unsigned* bad, const unsigned* bad2, bool dyn) {
+  AdamLaunch a;
+  a.p = c->P; a.g = c->G; a.m = c->M; a.v = c->V; a.n = n;
+  a.lr = lr; a.wd = wd; a.step = c->adam_step; a.gscale = grad_scale;
+  a.bad = bad ? bad : c->sigwords + 8; a.bad2 = bad2 ? bad2 : poison_word(c); a.nan_out = c->last_loss;
+  if (dyn) a.dyn = c->dyn;
+  else { a.zero_buf = c->acc_base; a.zero_bytes = (long long)c->poison_off; a.nan_fill = c->nan_exact; }
+  if (c->clip_on()) {      // eae_set_grad_clip: the partial sums of g^2 over the 38 tensors, on this stream and right in front of the optimizer
+    RC(eae_launch_grad_sumsq(st, c->G, c->poff, c->psize, c->clip_part));
+    a.clip = {c->clip_part, eae_grad_sumsq_parts(c->arena_len()), c->clip_max, c->clip_out};
+  }
+  return eae_launch_adam(st, a);
 }
 int optimizer_step(eae_ctx* c, hipStream_t st, float lr, float wd, float grad_scale, const unsigned* bad, const unsigned* bad2) {
   if (!c || !c->P || !c->G || !c->M || !c->V) return eae_set_error(EAE_ERR_STATE, "adam: parameter, gradient and moment arenas must be bound");
@@ -742,7 +744,7 @@ extern "C" int eae_ae_train_step(eae_ctx* c, void* stream, const eae_step_io* io
   }
   if (!ent) return train_step_eager(c, st, io, lr);
   c->adam_step += 1;
-  RC(eae_launch_set_dyn(st, c->dyn, lr, 0.9, 0.999, 0.0, c->adam_step));
+  RC(eae_launch_set_dyn(st, c->dyn, lr, 0.9, 0.999, c->adam_step));
   if (ent && ent->exec) {
     EAE_HIP(hipGraphLaunch(ent->exec, st));
     invalidate_forward(c); c->packed = false; c->acc_clean = false;
@@ -753,10 +755,7 @@ extern "C" int eae_ae_train_step(eae_ctx* c, void* stream, const eae_step_io* io
   c->capturing = capture;
   int rc = forward_impl(c, st, io, true);
   if (!rc) rc = backward_impl(c, st, io);
-  EaeClip clip;
-  if (!rc && c->clip_on()) rc = clip_prepare(c, st, &clip);
-  if (!rc) rc = eae_launch_adam_dyn(st, c->P, c->G, c->M, c->V, c->arena_len(), 0.9, 0.999, 1e-8, c->dyn, c->sigwords + 8, poison_word(c), c->last_loss,
-                                    c->clip_on() ? &clip : nullptr);
+  if (!rc) rc = launch_adam(c, st, c->arena_len(), lr, 0.f, 1.0f, nullptr, nullptr, true);
   c->capturing = false;
   c->packed = false;
   if (capture) {
