@@ -104,6 +104,9 @@ _PROTOS = {
     "eae_op_wgrad_s2": (C.c_int, [vp, EaeSrc, EaeSrc, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_longlong, vp]),
     "eae_op_wgrad_s2_fp8": (C.c_int, [vp, EaeSrc, EaeSrc, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_longlong, vp, vp]),
     "eae_op_conv_s2_fp8": (C.c_int, [vp, C.c_int, EaeSrc, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]),
+    "eae_op_conv_s2_fp8_slots": (C.c_int, [vp, C.c_int, EaeSrc, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp,
+                                          C.c_int, C.c_int]),
+    "eae_op_fp8_scales": (C.c_int, [vp, vp, vp, vp, vp, vp]),
     "eae_op_bn_finalize": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_longlong, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp]),
     "eae_op_bn_eval_coef": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, C.c_float, vp]),
     "eae_op_bn_bwd_finalize": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_longlong, vp, vp, vp, vp, vp]),

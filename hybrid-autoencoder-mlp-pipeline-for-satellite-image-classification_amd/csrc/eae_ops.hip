@@ -13,11 +13,12 @@ static unsigned long long* g_dbg = nullptr; static int g_dbg_block = 0;
 extern "C" int eae_debug_set(void* p, int block) { g_dbg = (unsigned long long*)p; g_dbg_block = block; return 0; }
 #endif
 static int op_conv_s2(void* stream, int kind, eae_src src, int cin, int cout, int B, int Hin, int Win, const void* wpack, const float* bias,
-                      void* out, float* stat_part, int epilogue, const void* yprev, const float* prev_coef, const float* qs, unsigned* amax) {
+                      void* out, float* stat_part, int epilogue, const void* yprev, const float* prev_coef, const float* qs, unsigned* amax,
+                      int amax_slots = 1, int amax_stride = 0) {
   ConvArgs a = ConvArgs();
   a.src = to_src(src); a.wpack = (const bf16_t*)wpack; a.bias = bias; a.out = (bf16_t*)out; a.stat_part = stat_part;
   a.yprev = (const bf16_t*)yprev; a.prev_coef = prev_coef; a.B = B; a.Hin = Hin; a.Win = Win;
-  a.qs = qs; a.amax = amax;
+  a.qs = qs; a.amax = amax; a.amax_mask = amax_slots - 1; a.amax_stride = amax_stride;
 #ifdef EAE_STAMPS
   if (!qs) { a.dbg = g_dbg; a.dbg_block = g_dbg_block; }
 #endif
@@ -38,6 +39,62 @@ extern "C" int eae_op_conv_s2_fp8(void* stream, int kind, eae_src src, int cin, 
                                   const float* qs, unsigned* amax) {
   if (!qs) return eae_set_error(EAE_ERR_ARG, "conv_s2_fp8: qs is NULL");
   return op_conv_s2(stream, kind, src, cin, cout, B, Hin, Win, wpack_e4m3, bias, out, stat_part, epilogue, yprev, prev_coef, qs, amax);
+}
+// the same op reporting into amax_slots words (a power of two) amax_stride words apart, as the engine's launches do: workgroup
+// tile t reports into word (t & (amax_slots - 1)) * amax_stride
+extern "C" int eae_op_conv_s2_fp8_slots(void* stream, int kind, eae_src src, int cin, int cout, int B, int Hin, int Win, const void* wpack_e4m3,
+                                        const float* bias, void* out, float* stat_part, int epilogue, const void* yprev, const float* prev_coef,
+                                        const float* qs, unsigned* amax, int amax_slots, int amax_stride) {
+  if (!qs || !amax) return eae_set_error(EAE_ERR_ARG, "conv_s2_fp8_slots: qs or amax is NULL");
+  if (amax_slots < 1 || (amax_slots & (amax_slots - 1)) || amax_stride < (amax_slots > 1 ? 1 : 0))
+    return eae_set_error(EAE_ERR_ARG, "conv_s2_fp8_slots: amax_slots must be a power of two and amax_stride positive");
+  return op_conv_s2(stream, kind, src, cin, cout, B, Hin, Win, wpack_e4m3, bias, out, stat_part, epilogue, yprev, prev_coef, qs, amax,
+                    amax_slots, amax_stride);
+}
+// fp8_scales_kernel on a state built for the call: amax_bits [3][6][FP8_AMAX_SLOTS] (act, grad, w; slot s of a row sits at word
+// s * FP8_AMAX_STRIDE of the state's row, every other word is 0), scales_in [18] = s_act, s_grad, s_w.  One launch, then the state
+// comes back: scales_out [18], qs_out [6][8] = qs_fwd[2], qs_bwd[2], qs_wg[4] per layer, amax_left = the slot words after the
+// launch.  Every pointer is host memory; synchronises the stream.
+extern "C" int eae_op_fp8_scales(void* stream, const unsigned* amax_bits, const float* scales_in, float* scales_out, float* qs_out,
+                                 unsigned* amax_left) {
+  if (!amax_bits || !scales_in || !scales_out || !qs_out || !amax_left) return eae_set_error(EAE_ERR_ARG, "fp8_scales: NULL argument");
+  hipStream_t st = (hipStream_t)stream;
+  Fp8State* h = new Fp8State;
+  eae_fp8_state_init(h);
+  unsigned (*rows[3])[FP8_AMAX_SLOTS * FP8_AMAX_STRIDE] = {h->amax_act, h->amax_grad, h->amax_w};
+  float* sc[3] = {h->s_act, h->s_grad, h->s_w};
+  for (int k = 0; k < 3; ++k)
+    for (int i = 0; i < 6; ++i) {
+      sc[k][i] = scales_in[k * 6 + i];
+      for (int s = 0; s < FP8_AMAX_SLOTS; ++s) rows[k][i][s * FP8_AMAX_STRIDE] = amax_bits[(k * 6 + i) * FP8_AMAX_SLOTS + s];
+    }
+  Fp8State* dev = nullptr;
+  hipError_t e = hipMalloc(&dev, sizeof(Fp8State));
+  if (e != hipSuccess) { delete h; return eae_set_error(EAE_ERR_HIP, hipGetErrorString(e)); }
+  int rc = 0;
+  e = hipMemcpyAsync(dev, h, sizeof(Fp8State), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);          // (pageable source: the copy must be done before h is written again)
+  if (e == hipSuccess) rc = eae_launch_fp8_scales(st, dev);
+  if (e == hipSuccess && rc == 0) e = hipMemcpyAsync(h, dev, sizeof(Fp8State), hipMemcpyDeviceToHost, st);
+  const hipError_t es = hipStreamSynchronize(st);
+  hipFree(dev);
+  if (e == hipSuccess && rc == 0 && es == hipSuccess) {
+    for (int k = 0; k < 3; ++k)
+      for (int i = 0; i < 6; ++i) {
+        scales_out[k * 6 + i] = sc[k][i];
+        for (int s = 0; s < FP8_AMAX_SLOTS; ++s) amax_left[(k * 6 + i) * FP8_AMAX_SLOTS + s] = rows[k][i][s * FP8_AMAX_STRIDE];
+      }
+    for (int i = 0; i < 6; ++i) {
+      float* q = qs_out + i * 8;
+      q[0] = h->qs_fwd[i][0]; q[1] = h->qs_fwd[i][1]; q[2] = h->qs_bwd[i][0]; q[3] = h->qs_bwd[i][1];
+      for (int j = 0; j < 4; ++j) q[4 + j] = h->qs_wg[i][j];
+    }
+  }
+  delete h;
+  if (e != hipSuccess) return eae_set_error(EAE_ERR_HIP, hipGetErrorString(e));
+  if (rc) return rc;
+  if (es != hipSuccess) return eae_set_error(EAE_ERR_HIP, hipGetErrorString(es));
+  return 0;
 }
 
 // C-band forms of the four edge ops (in_channels 1..16), and the 3-band forms: these at C = 3

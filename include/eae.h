@@ -353,6 +353,18 @@ int eae_op_conv_s2_fp8(void* stream, int kind, eae_src src, int cin, int cout, i
                        const float* qs, unsigned* amax);
 int eae_op_wgrad_s2_fp8(void* stream, eae_src small_src, eae_src big_src, int cs, int cb, int B, int Hs, int Ws, float* scratch,
                         long long scratch_floats, float* dw, const float* qs);
+/* eae_op_conv_s2_fp8 reporting the way the engine's launches do: amax is an array of amax_slots words (a power of two) amax_stride
+ * words apart, and the workgroup of tile t reports into word (t & (amax_slots - 1)) * amax_stride (atomic maximum). */
+int eae_op_conv_s2_fp8_slots(void* stream, int kind, eae_src src, int cin, int cout, int B, int Hin, int Win, const void* wpack_e4m3,
+                             const float* bias, void* out, float* stat_part, int epilogue, const void* yprev, const float* prev_coef,
+                             const float* qs, unsigned* amax, int amax_slots, int amax_stride);
+/* The delayed-scaling kernel of the fp8 variant, run once on a state built for the call (every pointer is HOST memory; synchronises):
+ * amax_bits [3][6][64] = the 64 reporting slots of the activation, gradient and weight maxima of the six 3x3 layers (float bits),
+ * scales_in [18] = s_act[6], s_grad[6], s_w[6] before the launch; scales_out [18] the scales after it, qs_out [6][8] = per layer
+ * {1/s_act, 1/(s_act s_w)}, {1/s_grad, 1/(s_grad s_w)}, {1/s_small, 1/s_big, 1/(s_small s_big), 0} of the weight gradient,
+ * amax_left [3][6][64] = the slots after the launch (cleared). */
+int eae_op_fp8_scales(void* stream, const unsigned* amax_bits, const float* scales_in, float* scales_out, float* qs_out,
+                      unsigned* amax_left);
 /* number of statistics partials per channel (= workgroups) eae_op_conv_s2 writes for this shape */
 int eae_op_conv_s2_ntiles(int kind, int cin, int B, int Hin, int Win);
 /* first / last layer kernels: src3_kind 0 = fp32 NCHW [B,3,H,W], 1 = bf16 NHWC4 [B,H,W,4]; out [B,H/2,W/2,32] */

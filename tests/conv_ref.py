@@ -10,11 +10,18 @@ bf16_round(exact sum + bias) and a weight gradient the exact sum, bit for bit.
 Budget (from the formats, not from the code under test): conv products are multiples of 2^-7 (operand: multiples of 1/8, weight:
 multiples of 1/16), weight-gradient products multiples of 2^-6 (1/8 x 1/8).  With S = sum |a||w| of one output, every partial sum
 is a multiple of 2^-q of magnitude <= S, exact in fp32 as long as S * 2^q < 2^24.
+
+The fp8 twins of the kernels (second half of this file) multiply QUANTISED operands: the same references, grids and budget, with S
+taken from the quantised operands.  Measured on an MI355X (tests/test_gpu_fp8_exact.py): within this budget the four fp8 MFMA forms
+(v_mfma_f32_16x16x32_{fp8,bf8}_{fp8,bf8}) accumulate exactly, as the bf16 form does -- eighths with up to 5 significant bits needed
+no coarsening.
 """
 import itertools
 import os
 
 import numpy as np
+
+from oracle import ae_numpy as _O          # NumPy only: the fp8 conversion (fp8_round, _q8, fp8_bytes_e4m3)
 
 Q_CONV, Q_WGRAD = 7, 6          # products are multiples of 2^-Q
 
@@ -297,3 +304,197 @@ def expected_wgrad_launch(cs, cb, smode, hs, ws, B, scratch_floats):
         slices >>= 1
     per = _cdiv(tiles, slices)
     return geo, tiles, _cdiv(tiles, per), per
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# fp8 twins (igemm8_s2_kernel, wgrad8_s2_kernel): the same references on QUANTISED operands
+#
+# Every scale is a power of two, so scaling and unscaling move no bit: only the fp8 rounding of an operand changes a value, and
+# oracle.ae_numpy.fp8_round / _q8 restate it.  Rounding only coarsens: a multiple of 1/8 with |v| <= 3.5 stays a multiple of 1/8
+# (e4m3 at scales 2^-8 .. 2^8, e5m2 at 2^-16 .. 2^15; `quantised` asserts it for what it returns), the weights k/16 are e4m3 values at
+# s_w = 2^-3 .. 2^8, and the budget above carries over with S taken from the quantised operands (the *_abs twins).
+#
+# The coarse DyadicSrc operands are fp8 values already at scale 1 in modes 0, 1 and 4 (nothing would be rounded): FineSrc stores
+# eighths, so that a share of every operand is changed by the conversion, exact ties among them.
+# ---------------------------------------------------------------------------------------------------------------
+FP8_MAX = {"e4m3": 448.0, "e5m2": 57344.0}
+FINE_VMAX = 3.5
+
+
+def fp8_fmt(mode):
+    """the format a source mode is converted to: the gradient operands (modes 2 and 4: QG / SG / BG of the kernels) go to e5m2"""
+    return "e5m2" if mode in (2, 4) else "e4m3"
+
+
+def _eighths(rng, shape, kmax):
+    return (rng.integers(-kmax, kmax + 1, shape) / 8.0).astype(np.float32)
+
+
+class FineSrc(DyadicSrc):
+    """DyadicSrc on the 1/8 grid: stored tensors and coefficients are bf16- and fp32-exact, the materialised operand is a multiple
+    of 1/8 with |v| <= 3.5 -- and, unlike DyadicSrc's, not an fp8 value throughout."""
+
+    def __init__(self, mode, shape, rng):
+        c = shape[1]
+        bc = lambda v: v[None, :, None, None].astype(np.float64)
+        self.mode, self.coef = mode, None
+        if mode in (0, 4):                                   # as stored: k/8, |k| <= 28
+            y = _eighths(rng, shape, 28)
+            self.tensors, self.value = [y], y.astype(np.float64)
+        elif mode == 1:                                      # max(0, s*y + t): |y| <= 3, s = +-1, |t| <= 1/2
+            y = _eighths(rng, shape, 24)
+            s, t = _pick(rng, (-1.0, 1.0), c), _eighths(rng, c, 4)
+            self.tensors = [y]
+            self.coef = np.stack([s, t, np.zeros(c, np.float32), np.ones(c, np.float32)])
+            self.value = np.maximum(y * bc(s) + bc(t), 0.0)
+        elif mode == 2:                                      # A*g + (B*y + C): |A g| <= 2, |B y| <= 1, |C| <= 1/2
+            g, y = _quarters(rng, shape, 4), _eighths(rng, shape, 8)
+            a_, b_, c_ = _pick(rng, (0.5, 1.0, 2.0), c), _pick(rng, (-1.0, 1.0), c), _quarters(rng, c, 2)
+            self.tensors = [g, y]
+            self.coef = np.stack([a_, b_, c_])
+            self.value = g * bc(a_) + (y * bc(b_) + bc(c_))
+        else:
+            raise ValueError(mode)
+        assert np.abs(self.value).max() <= FINE_VMAX and np.array_equal(self.value * 8, np.round(self.value * 8))
+
+
+def quantised(src, scale, fmt):
+    """_q8 of the bf16 operand (fp64): what the kernel multiplies.  Still on the 1/8 grid."""
+    v32 = src.value.astype(np.float32)
+    assert np.array_equal(v32.astype(np.float64), src.value) and np.array_equal(bf16_round(v32), v32)
+    q = _O._q8(v32, scale, fmt).astype(np.float64)
+    assert np.array_equal(q * 8, np.round(q * 8)) and np.abs(q).max() <= 4.0
+    return q
+
+
+def rounding_shares(value, scale, fmt):
+    """What the conversion at `scale` does to an operand, from the oracle alone: shares of elements it changes, of exact ties (the
+    two fp32 neighbours of the scaled value round to different fp8 values), of saturated and of flushed-to-zero elements."""
+    x = (value * scale).astype(np.float32)
+    assert np.array_equal(x.astype(np.float64), value * scale)
+    r = _O.fp8_round(x, fmt)
+    lo, hi = _O.fp8_round(np.nextafter(x, np.float32(-np.inf)), fmt), _O.fp8_round(np.nextafter(x, np.float32(np.inf)), fmt)
+    return {"changed": float((r != x).mean()), "ties": float(((lo != hi) & (r != x)).mean()),
+            "saturated": float((np.abs(x) > FP8_MAX[fmt]).mean()), "flushed": float(((r == 0) & (x != 0)).mean())}
+
+
+def fp8_round_variant(a, fmt, ties="even", saturate=True):
+    """fp8 rounding with a switch for the tie rule and for the clamp: (even, True) is oracle.fp8_round; the others are the WRONG
+    conversions the power checks of test_conv_reference.py hold the expected bits against."""
+    mant, emin, maxv = (3, -6, 448.0) if fmt == "e4m3" else (2, -14, 57344.0)
+    a = np.asarray(a, np.float64)
+    m = np.abs(a)
+    if saturate:
+        m = np.minimum(m, maxv)
+    q = np.exp2(np.maximum(np.floor(np.log2(np.maximum(m, 1e-300))), emin) - mant)
+    r = (np.round(m / q) if ties == "even" else np.floor(m / q + 0.5)) * q
+    if saturate:
+        r = np.minimum(r, maxv)
+    return np.sign(a) * r
+
+
+# case tables: every instantiation on the four wide grids (the fp8 plan has the 16 x 8 x 1 geometry only, eae_s2_plan)
+IGEMM8_EXACT_CASES = [inst + grid for inst, grid in itertools.product(IGEMM_INSTANCES, GRIDS[2:])]
+WGRAD8_MULTI_TILE = {                                    # case: (tiles, slices, tiles per workgroup) under 64 workgroups
+    (256, 128, 2, 1, 16, 32, 3): (12, 4, 3),
+    (128, 64, 1, 2, 16, 32, 5): (20, 10, 2),
+    (256, 128, 4, 1, 16, 32, 3): (12, 4, 3),             # SRC_RAWG: the form the train step launches
+}
+WGRAD8_EXACT_CASES = [inst + grid for inst, grid in itertools.product(WGRAD_INSTANCES, WGRAD_GRIDS[2:])] + [
+    (256, 128, 2, 1, 16, 32, 3), (128, 64, 1, 2, 16, 32, 5), (64, 32, 1, 2, 16, 32, 3), (256, 128, 4, 1, 16, 32, 3)]
+FP8_SETTINGS = ("regular", "edge")
+REGULAR_SCALE = {"e4m3": 2.0 ** 4, "e5m2": 2.0 ** 12}
+SATURATING_SCALE = {"e4m3": 2.0 ** 8, "e5m2": 2.0 ** 15}       # MAX / s = 1.75: about half of an operand clamps
+FLUSHING_SCALE = {"e4m3": 2.0 ** -7, "e5m2": 2.0 ** -15}       # 1/8 is half of the smallest subnormal / a quarter of it
+WEIGHT_SCALES = (2.0 ** -2, 2.0 ** 0, 2.0 ** 4, 2.0 ** 8)       # k/16 is an e4m3 value at every one of them
+
+
+def edge_kind(idx):
+    """the edge setting of case number idx: even rows saturate, odd rows reach the subnormals and flush.  The tables are instance-major
+    with four grids each, so every instantiation (and with it every format, and both kinds of kernel) gets both."""
+    return "saturating" if idx % 2 == 0 else "flushing"
+
+
+def igemm8_scales(idx, setting, fmt):
+    """(pixel scale, weight scale) of case number idx under a setting"""
+    if setting == "regular":
+        return REGULAR_SCALE[fmt], 2.0 ** 4
+    return (SATURATING_SCALE if edge_kind(idx) == "saturating" else FLUSHING_SCALE)[fmt], WEIGHT_SCALES[(idx // 2) % 4]
+
+
+def wgrad8_scales(idx, setting, fmt_s, fmt_b):
+    """(small scale, big scale, the operand that has the edge scale or None): rows 4i, 4i+1 put it on the small operand, 4i+2, 4i+3
+    on the big one"""
+    s_s, s_b = REGULAR_SCALE[fmt_s], REGULAR_SCALE[fmt_b]
+    if setting == "regular":
+        return s_s, s_b, None
+    table = SATURATING_SCALE if edge_kind(idx) == "saturating" else FLUSHING_SCALE
+    if (idx // 2) % 2 == 0:
+        return table[fmt_s], s_b, "small"
+    return s_s, table[fmt_b], "big"
+
+
+class Igemm8Case:
+    """Row idx of IGEMM8_EXACT_CASES under a setting: operands, scales, the e4m3 weight bytes in the kernel's layout, the exact sum
+    of the quantised operands (+ bias) with its S, and the expected stored output.  `quant` replaces the operand's conversion and
+    `weights` / `operand` the exact sum's inputs: the power checks build wrong references with them."""
+
+    def __init__(self, idx, setting):
+        self.idx, self.setting = idx, setting
+        self.case = kind, cin, cout, smode, epi, hp, wp, B = IGEMM8_EXACT_CASES[idx]
+        rng = np.random.default_rng(41000 + idx)
+        self.hin, self.win = (2 * hp, 2 * wp) if kind == 0 else (hp, wp)
+        self.hout, self.wout = (hp, wp) if kind == 0 else (2 * hp, 2 * wp)
+        self.fmt = fp8_fmt(smode)
+        self.s_pix, self.s_w = igemm8_scales(idx, setting, self.fmt)
+        self.src = FineSrc(smode, (B, cin, self.hin, self.win), rng)
+        self.w = dyadic_weights((cout, cin, 3, 3) if kind == 0 else (cin, cout, 3, 3), rng)
+        w8 = self.w * np.float32(self.s_w)
+        assert np.array_equal(_O.fp8_round(w8, "e4m3"), w8)                      # the pack holds the weights themselves
+        # kernel layout [cout][9][cin]: conv weight [cout][cin][3][3]; transposed-conv weight [cin][cout][3][3]
+        wk = w8.transpose(0, 2, 3, 1) if kind == 0 else w8.transpose(1, 2, 3, 0)
+        self.w_bytes = _O.fp8_bytes_e4m3(np.ascontiguousarray(wk.reshape(cout, 9, cin)))
+        self.bias = dyadic_bias(cout, rng) if epi == 0 else None
+        self.prev = DyadicPrev((B, cout, self.hout, self.wout), rng) if epi == 1 else None
+        self.qa = quantised(self.src, self.s_pix, self.fmt)
+        self.amax = float(np.abs(self.src.value).max())                          # of the bf16 operand, before the conversion
+        self.shares = rounding_shares(self.src.value, self.s_pix, self.fmt)
+        self.exact = self.sum_of(self.qa, self.w)
+        self.S = (conv_s2_abs if kind == 0 else deconv_s2_abs)(self.qa, self.w) + (0.0 if self.bias is None else
+                                                                                   np.abs(self.bias)[None, :, None, None])
+
+    def sum_of(self, operand, weights):
+        kind = self.case[0]
+        y = conv_s2(operand, weights) if kind == 0 else deconv_s2(operand, weights)
+        return y if self.bias is None else y + self.bias[None, :, None, None].astype(np.float64)
+
+    def stored(self, exact):
+        """the bf16 tensor the kernel must store for an exact sum"""
+        ref = bf16_round(exact_f32(exact))
+        return ref if self.prev is None else ref * self.prev.mask               # a decision that lands on 0 gives 0
+
+    def quant_variant(self, ties, saturate):
+        sc = np.float64(self.s_pix)
+        return fp8_round_variant(self.src.value * sc, self.fmt, ties, saturate) / sc
+
+
+class Wgrad8Case:
+    """Row idx of WGRAD8_EXACT_CASES under a setting"""
+
+    def __init__(self, idx, setting):
+        self.idx, self.setting = idx, setting
+        self.case = cs, cb, smode, bmode, hs, ws, B = WGRAD8_EXACT_CASES[idx]
+        rng = np.random.default_rng(42000 + idx)
+        self.fmt_s, self.fmt_b = fp8_fmt(smode), fp8_fmt(bmode)
+        self.s_s, self.s_b, self.edge_on = wgrad8_scales(idx, setting, self.fmt_s, self.fmt_b)
+        self.small = FineSrc(smode, (B, cs, hs, ws), rng)
+        self.big = FineSrc(bmode, (B, cb, 2 * hs, 2 * ws), rng)
+        self.qs, self.qb = quantised(self.small, self.s_s, self.fmt_s), quantised(self.big, self.s_b, self.fmt_b)
+        self.shares_s = rounding_shares(self.small.value, self.s_s, self.fmt_s)
+        self.shares_b = rounding_shares(self.big.value, self.s_b, self.fmt_b)
+        self.exact = wgrad_s2(self.qs, self.qb)
+        self.S = wgrad_s2_abs(self.qs, self.qb)
+
+    def quant_variant(self, which, ties, saturate):
+        src, sc, fmt = (self.small, self.s_s, self.fmt_s) if which == "small" else (self.big, self.s_b, self.fmt_b)
+        return fp8_round_variant(src.value * np.float64(sc), fmt, ties, saturate) / np.float64(sc)

@@ -330,3 +330,220 @@ def test_structured_errors_change_the_expected_bits():
     halves = np.concatenate([R.conv_s2(src.value[..., :32], w), R.conv_s2(src.value[..., 32:], w)], axis=3)
     diff = R.bf16_round(R.exact_f32(halves)) != ref
     assert not diff[..., :16].any() and not diff[..., 17:].any() and diff[..., 16].mean() > 0.5
+
+
+# ---------------------------------------------------------------------------------------------------- the fp8 twins (conv_ref.py)
+def test_fp8_tables_cover_every_instantiation_setting_and_the_multi_tile_loop(monkeypatch):
+    wide = [(8, 16), (16, 32), (8, 32), (24, 16)]
+    assert len(R.IGEMM8_EXACT_CASES) == 14 * 4 and len(set(R.IGEMM8_EXACT_CASES)) == 56
+    assert {c[:5] for c in R.IGEMM8_EXACT_CASES} == set(R.IGEMM_INSTANCES)
+    assert all([c[5:7] for c in R.IGEMM8_EXACT_CASES if c[:5] == inst] == wide for inst in R.IGEMM_INSTANCES)
+    assert [g[:2] for g in R.GRIDS[2:]] == wide and [g[:2] for g in R.WGRAD_GRIDS[2:]] == wide
+    assert all(R.expected_geo(*c[:3], c[5], c[6], c[7]) == R.WIDE for c in R.IGEMM8_EXACT_CASES)
+    assert len(R.WGRAD8_EXACT_CASES) == 13 * 4 + 4 and len(set(R.WGRAD8_EXACT_CASES)) == 56
+    assert {c[:4] for c in R.WGRAD8_EXACT_CASES} == set(R.WGRAD_INSTANCES)
+    assert all([c[4:6] for c in R.WGRAD8_EXACT_CASES[:52] if c[:4] == inst] == wide for inst in R.WGRAD_INSTANCES)
+    assert set(R.WGRAD8_EXACT_CASES[52:]) < set(R.WGRAD_EXACT_CASES) | {(256, 128, 4, 1, 16, 32, 3)}
+    # several tiles per workgroup, one row of them with SRC_RAWG (the form the train step launches)
+    monkeypatch.delenv("EAE_WGRAD_WGS", raising=False)
+    for case, (tiles, slices, per) in R.WGRAD8_MULTI_TILE.items():
+        assert case in R.WGRAD8_EXACT_CASES
+        assert R.expected_wgrad_launch(case[0], case[1], case[2], case[4], case[5], case[6], 6 << 20) == (R.WIDE, tiles, slices, per)
+        assert per > 1 and slices > 1
+    assert any(c[2] == 4 or c[3] == 4 for c in R.WGRAD8_MULTI_TILE)
+    # both edge kinds for every instantiation (so for every format, and for both kernels); the weight scales rotate
+    for i, c in enumerate(R.IGEMM8_EXACT_CASES):
+        assert R.igemm8_scales(i, "regular", R.fp8_fmt(c[3])) == ({"e4m3": 16.0, "e5m2": 4096.0}[R.fp8_fmt(c[3])], 16.0)
+    got = {(c[:5], R.edge_kind(i)) for i, c in enumerate(R.IGEMM8_EXACT_CASES)}
+    assert got == {(inst, k) for inst in R.IGEMM_INSTANCES for k in ("saturating", "flushing")}
+    assert {(R.fp8_fmt(c[3]), R.igemm8_scales(i, "edge", R.fp8_fmt(c[3]))[0]) for i, c in enumerate(R.IGEMM8_EXACT_CASES)} == {
+        ("e4m3", 2.0 ** 8), ("e4m3", 2.0 ** -7), ("e5m2", 2.0 ** 15), ("e5m2", 2.0 ** -15)}
+    assert {R.igemm8_scales(i, "edge", "e4m3")[1] for i in range(56)} == {0.25, 1.0, 16.0, 256.0}
+    # the weight gradient: per instantiation the edge scale once on each operand, saturating and flushing
+    got = set()
+    for i, c in enumerate(R.WGRAD8_EXACT_CASES[:52]):
+        fs, fb = R.fp8_fmt(c[2]), R.fp8_fmt(c[3])
+        s_s, s_b, on = R.wgrad8_scales(i, "edge", fs, fb)
+        assert R.wgrad8_scales(i, "regular", fs, fb) == (R.REGULAR_SCALE[fs], R.REGULAR_SCALE[fb], None)
+        table = R.SATURATING_SCALE if R.edge_kind(i) == "saturating" else R.FLUSHING_SCALE
+        assert (s_s, s_b) == ((table[fs], R.REGULAR_SCALE[fb]) if on == "small" else (R.REGULAR_SCALE[fs], table[fb]))
+        got.add((c[:4], on, R.edge_kind(i)))
+    assert got == {(inst, on, k) for inst in R.WGRAD_INSTANCES for on in ("small", "big") for k in ("saturating", "flushing")}
+
+
+def _fp8_operand_scales():
+    """every (mode, format, scale) the two tables use"""
+    out = set()
+    for setting in R.FP8_SETTINGS:
+        for i, c in enumerate(R.IGEMM8_EXACT_CASES):
+            out.add((c[3], R.fp8_fmt(c[3]), R.igemm8_scales(i, setting, R.fp8_fmt(c[3]))[0]))
+        for i, c in enumerate(R.WGRAD8_EXACT_CASES):
+            s_s, s_b, _ = R.wgrad8_scales(i, setting, R.fp8_fmt(c[2]), R.fp8_fmt(c[3]))
+            out |= {(c[2], R.fp8_fmt(c[2]), s_s), (c[3], R.fp8_fmt(c[3]), s_b)}
+    return sorted(out)
+
+
+def test_fine_sources_stay_on_the_grid_and_are_really_rounded():
+    """The conditions on the INPUTS, from the oracle alone: stored tensors bf16-exact, the operand a multiple of 1/8 within 3.5
+    before and after the conversion at every scale the tables use; at scale 1 and at the regular scales at least 5 % of an operand
+    is changed by the conversion, exact ties among them; the saturating scales clamp and the flushing scales flush a real share."""
+    from oracle import ae_numpy as O
+    used = _fp8_operand_scales()
+    assert {(m, f) for m, f, _ in used} == {(0, "e4m3"), (1, "e4m3"), (2, "e5m2"), (4, "e5m2")}
+    assert len(used) == 12                                                  # regular, saturating, flushing for each
+    for mode, fmt in sorted({(m, f) for m, f, _ in used}):
+        s = R.FineSrc(mode, (2, 64, 16, 32), np.random.default_rng(50 + mode))
+        v32 = s.value.astype(np.float32)
+        assert np.array_equal(R.bf16_round(v32), v32) and np.array_equal(v32.astype(np.float64), s.value)
+        assert np.array_equal(s.value * 8, np.round(s.value * 8)) and np.abs(s.value).max() == 3.5
+        for t in s.tensors:
+            assert np.array_equal(R.bf16_round(t), t)
+        if s.coef is not None:
+            assert all(len(np.unique(row)) > 1 for row in s.coef[:2])
+        if mode == 1:      # the fp32 arithmetic of the load without contraction gives the same value
+            y, (sc, t) = s.tensors[0], (s.coef[0][None, :, None, None], s.coef[1][None, :, None, None])
+            assert np.array_equal(np.maximum((y * sc).astype(np.float32) + t, np.float32(0)).astype(np.float64), s.value)
+        for scale in [1.0] + [sc for m, f, sc in used if (m, f) == (mode, fmt)]:
+            q = R.quantised(s, scale, fmt)                                  # asserts the grid
+            assert np.array_equal(R.fp8_round_variant(s.value * scale, fmt) / scale, q)         # the variant's true setting IS the oracle
+            sh = R.rounding_shares(s.value, scale, fmt)
+            assert sh["changed"] == float((q != s.value).mean())
+            if scale in (1.0, R.REGULAR_SCALE[fmt]):
+                assert sh["changed"] >= 0.05 and sh["ties"] > 0 and sh["saturated"] == 0 and sh["flushed"] == 0, (mode, scale, sh)
+            elif scale == R.SATURATING_SCALE[fmt]:
+                assert sh["saturated"] >= 0.05 and np.abs(q).max() == 1.75 == R.FP8_MAX[fmt] / scale, (mode, scale, sh)
+            else:
+                assert scale == R.FLUSHING_SCALE[fmt] and sh["flushed"] >= 0.01 and sh["ties"] > 0, (mode, scale, sh)
+                # subnormal results are in the operand: nonzero values below the smallest normal number
+                assert ((q != 0) & (np.abs(q) * scale < (2.0 ** -6 if fmt == "e4m3" else 2.0 ** -14))).any()
+    # the documented exception: e5m2 at 2^-16 rounds 3.5 UP to 4 (why S comes from the quantised operand, not from 3.5)
+    assert O._q8(np.float32(3.5), 2.0 ** -16, "e5m2") == 4.0
+    # the weights are e4m3 values at 2^-3 .. 2^8 and not at 2^9
+    w = R.dyadic_weights((64, 32, 3, 3), np.random.default_rng(5))
+    for e in range(-3, 9):
+        assert np.array_equal(O.fp8_round(w * np.float32(2.0 ** e), "e4m3"), w * np.float32(2.0 ** e))
+    assert not np.array_equal(O.fp8_round(w * np.float32(512), "e4m3"), w * np.float32(512))
+
+
+def _edge_presence(value, q, scale, fmt, kind):
+    """the quantised operand of an edge case really holds clamped values, or flushed ones"""
+    lim = R.FP8_MAX[fmt] / scale
+    if kind == "saturating":
+        return bool(((np.abs(value) > lim) & (np.abs(q) == lim)).any())
+    return bool(((value != 0) & (q == 0)).any())
+
+
+@pytest.mark.parametrize("setting", R.FP8_SETTINGS)
+def test_every_igemm8_case_is_exact_in_fp32_and_its_edge_is_reached(setting):
+    for idx in range(len(R.IGEMM8_EXACT_CASES)):
+        k = R.Igemm8Case(idx, setting)
+        R.assert_budget(k.S, R.Q_CONV)
+        assert np.all(np.abs(k.exact) <= k.S)
+        y = R.exact_f32(k.exact)
+        assert np.array_equal(y * 128, np.round(y * 128))
+        assert k.w_bytes.shape == (k.case[2], 9, k.case[1]) and k.w_bytes.dtype == np.uint8
+        if setting == "regular":
+            assert k.shares["changed"] >= 0.05 and k.shares["ties"] > 0, (k.case, k.shares)
+        else:
+            assert _edge_presence(k.src.value, k.qa, k.s_pix, k.fmt, R.edge_kind(idx)), (k.case, k.shares)
+            if R.edge_kind(idx) == "saturating":
+                assert k.amax > R.FP8_MAX[k.fmt] / k.s_pix and k.shares["saturated"] > 0.05      # the reported maximum is the unclamped one
+            else:
+                assert k.shares["flushed"] > 0.01
+
+
+@pytest.mark.parametrize("setting", R.FP8_SETTINGS)
+def test_every_wgrad8_case_is_exact_in_fp32_and_its_edge_is_reached(setting):
+    for idx in range(len(R.WGRAD8_EXACT_CASES)):
+        k = R.Wgrad8Case(idx, setting)
+        R.assert_budget(k.S, R.Q_WGRAD)
+        assert np.all(np.abs(k.exact) <= k.S)
+        dw = R.exact_f32(k.exact)
+        assert dw.shape == k.case[:2] + (3, 3) and np.array_equal(dw * 64, np.round(dw * 64))
+        for sh in (k.shares_s, k.shares_b):
+            if setting == "regular":
+                assert sh["changed"] >= 0.05 and sh["ties"] > 0, (k.case, sh)
+        if setting == "edge":
+            src, q, sc, fmt = (k.small, k.qs, k.s_s, k.fmt_s) if k.edge_on == "small" else (k.big, k.qb, k.s_b, k.fmt_b)
+            assert _edge_presence(src.value, q, sc, fmt, R.edge_kind(idx)), (k.case, k.edge_on)
+
+
+def _halo_swapped(x, kind):
+    """the operand as a kernel would see it that takes the halo column between the first two tiles across from the wrong side of the
+    seam: the conv kind's second tile reads input column 31 (its left halo), here a copy of column 30; the transposed kind's first
+    tile reads input column 16 (its right halo), here a copy of its own last column 15"""
+    x = x.copy()
+    if kind == 0:
+        x[..., 31] = x[..., 30]
+    else:
+        x[..., 16] = x[..., 15]
+    return x
+
+
+IGEMM8_POWER_SAMPLE = [i for i, c in enumerate(R.IGEMM8_EXACT_CASES) if c[6] == 32 and c[1] <= 128]      # two tiles across
+
+
+@pytest.mark.parametrize("idx", IGEMM8_POWER_SAMPLE)
+def test_wrong_conv_kernels_would_change_the_expected_bits(idx):
+    """The power of test_igemm8_exact, shown on its references (never by breaking a kernel): each of four wrong kernels gives a
+    stored output that differs from the expected one in at least one element.  Ties exist at the regular and the flushing scales (at
+    a saturating scale the unclamped range has none on the 1/8 grid: MAX / s = 1.75 and below it the fp8 step is <= 1/8), clamped
+    values at the saturating ones; a dropped tap and a wrong halo column show under every setting."""
+    hit = set()
+    for setting in R.FP8_SETTINGS:
+        k = R.Igemm8Case(idx, setting)
+        kind, cin, cout = k.case[:3]
+        ref = k.stored(k.exact)
+        differs = lambda operand, w: bool((k.stored(k.sum_of(operand, w)) != ref).any())
+        assert not differs(k.quant_variant("even", True), k.w)
+        if setting == "regular" or R.edge_kind(idx) == "flushing":
+            assert differs(k.quant_variant("away", True), k.w)
+            hit.add("away")
+        if setting == "edge" and R.edge_kind(idx) == "saturating":
+            assert differs(k.quant_variant("even", False), k.w)
+            hit.add("unclamped")
+        w = k.w.copy()                                       # one tap of one input channel out of 9 * cin
+        if kind == 0:
+            w[:, cin // 2, 2, 0] = 0
+        else:
+            w[cin // 2, :, 2, 0] = 0
+        assert differs(k.qa, w)
+        # the seam between the first two tiles across: only the outputs of the tile that reads the column as its halo change
+        bad = k.stored(k.sum_of(_halo_swapped(k.qa, kind), k.w))
+        seam = slice(16, None) if kind == 0 else slice(None, 32)
+        mixed = ref.copy()
+        mixed[..., seam] = bad[..., seam]
+        d = mixed != ref
+        col = 16 if kind == 0 else 31
+        assert d[..., col].any() and not np.delete(d, col, axis=3).any()
+    assert {"away"} <= hit
+
+
+WGRAD8_POWER_SAMPLE = [i for i, c in enumerate(R.WGRAD8_EXACT_CASES[:52]) if c[5] == 32 and c[0] <= 128]
+
+
+@pytest.mark.parametrize("idx", WGRAD8_POWER_SAMPLE)
+def test_wrong_wgrad_kernels_would_change_the_expected_bits(idx):
+    for setting in R.FP8_SETTINGS:
+        k = R.Wgrad8Case(idx, setting)
+        ref = R.exact_f32(k.exact)
+        differs = lambda s, b: bool((R.wgrad_s2(s, b) != ref).any())
+        assert not differs(k.quant_variant("small", "even", True), k.quant_variant("big", "even", True))
+        flushing_on = k.edge_on if setting == "edge" and R.edge_kind(idx) == "flushing" else None
+        for which in ("small", "big"):
+            wrong = k.quant_variant(which, "away", True)
+            if setting == "regular" or flushing_on == which or k.edge_on != which:      # (an operand at a saturating scale has no ties)
+                assert differs(wrong, k.qb) if which == "small" else differs(k.qs, wrong)
+        if setting == "edge" and R.edge_kind(idx) == "saturating":
+            wrong = k.quant_variant(k.edge_on, "even", False)
+            assert differs(wrong, k.qb) if k.edge_on == "small" else differs(k.qs, wrong)
+        s = k.qs.copy()                                      # one position of one image dropped from the sum
+        s[0, :, 3, 17] = 0
+        assert differs(s, k.qb)
+        # the second tile across reads big column 31 as its left halo: taken from column 30, only the kx = 0 taps change
+        left, right = k.qs.copy(), k.qs.copy()
+        left[..., 16:] = 0
+        right[..., :16] = 0
+        bad = R.wgrad_s2(left, k.qb) + R.wgrad_s2(right, _halo_swapped(k.qb, 0))
+        d = bad != ref
+        assert d[..., 0].any() and not d[..., 1:].any()
