@@ -3,6 +3,7 @@
 #include "eae_internal.h"
 #include "eae_args.h"
 #include "eae_layers.h"
+#include "eae_wgrad_plan.h"
 #include <atomic>
 #include <functional>
 #include <vector>
@@ -67,7 +68,8 @@ struct eae_ctx {
   hipStream_t sidex[MAXX] = {};
   hipEvent_t ev_joinx[MAXX] = {}, ev_sx[MAXX] = {};
   float* wscratchx[MAXX] = {};
-  float* wscratch_main = nullptr;
+  float* wscratch_main = nullptr;      // conv1's weight gradient: EAE_EDGE_WGRAD_SCRATCH_SLICES partials (eae_wgrad_plan.h)
+  long long wscratch_main_floats = 0;
   // data-parallel hand-off streams: after a gradient step #0 is ordered after gradient tensors 18..37 (classifier, decoder,
   // dec.fc) and #1 after tensors 8..17 (enc.fc, conv4, conv3); tensors 0..7 are complete when the step's join is reached
   hipStream_t dp_stream[2] = {nullptr, nullptr};

@@ -98,7 +98,8 @@ extern "C" int eae_create(const eae_config* cfg, eae_ctx** out) {
     c->nx = ns < 1 ? 0 : (ns - 1 > eae_ctx::MAXX ? eae_ctx::MAXX : ns - 1);
   }
   for (int i = 0; i < c->nx; ++i) o_wscrx[i] = carve(c->wscratch_floats * 4);
-  size_t o_wscrm = carve((size_t)2048 * 288 * c->Cin * 4);
+  c->wscratch_main_floats = EAE_EDGE_WGRAD_SCRATCH_SLICES * eae_edge_wgrad_slice_floats(c->Cin);
+  size_t o_wscrm = carve((size_t)c->wscratch_main_floats * 4);
   size_t o_acc[7], acc_total = 0;
   {
     const int Bi = (int)Bm;
@@ -115,7 +116,7 @@ extern "C" int eae_create(const eae_config* cfg, eae_ctx** out) {
     }
   }
   size_t o_accb = carve(2 * acc_total + 32);  // forward accumulators, then the backward ones (cleared together)   // conv1 weight gradient (last kernel of the backward, runs on the main stream)
-  const int ksplit = (int)(c->K / 128);
+  const int ksplit = (int)(c->K / EAE_FC_KLEN_MIN);      // the most slices eae_fc_klen can ask for
   size_t o_fcp = carve((size_t)ksplit * Bm * c->Lp * 4);
   size_t o_mse = carve(std::max((size_t)eae_edge_tiles((int)Bm, c->H, c->W), (size_t)((Bm * c->H * c->W + 255) / 256)) * edge_lp_stride(c->Cin) * 4);
   const long long hb = eae_head_blocks((int)Bm, 256);     // (the narrow-row variant of wide latents has the most blocks)

@@ -4,6 +4,9 @@
 #include <cstdlib>
 #include "eae_edge.hip.h"
 #include "eae_wgrad.hip.h"
+#include "eae_wgrad_plan.h"
+
+static_assert(EDGE_TILE_ROWS == 2 * E_TH && EDGE_TILE_COLS == 2 * E_TW, "the plan's tiles are the edge kernels'");
 
 static int check_edge_shape(int B, int H, int W) {
   if (B <= 0 || H % 8 || W % 64) return eae_set_error(-2, "edge layer: image height must be a multiple of 8 and width of 64");
@@ -66,27 +69,22 @@ int eae_launch_edge_wgrad(hipStream_t st, int src3_kind, const void* src3, int B
                           unsigned* sig, unsigned sig_val, int (*mid)(void*, GateArgs*), void* mid_user, int C) {
   if (int rc = check_edge_shape(B, H, W)) return rc;
   if (int rc = check_bands(C)) return rc;
-  const int cp = edge_cp(C), slice = 32 * 9 * C;
+  const int cp = edge_cp(C), slice = (int)eae_edge_wgrad_slice_floats(C);
   // the kernel addresses both operands through buffer descriptors with 32-bit byte offsets below OOB_OFF
   if ((long long)B * H * W * 16 >= 0x7fffff00LL) return eae_set_error(-2, "edge_wgrad: batch too large for one launch (2 GB per operand)");
   EdgeWgradArgs a;
   a.bfold = bfold ? *bfold : BnBwdFold();
   a.sig = sig; a.sig_val = sig_val;
   a.src3 = src3; a.B = B; a.H = H; a.W = W; a.side = side; a.part = scratch; a.C = C;
-  a.ntiles = eae_edge_tiles(B, H, W);
-  // Workgroups: each writes a partial, so their number also sets the reduction behind the kernel.  Round 4 re-sweep at B=512 (ms per
-  // step, main / side cap): 1024 / 1024 0.4875-0.4891, 512 / 1024 0.4832, 512 / 512 0.4821, 512 / 256 0.4794-0.4795, 768 / 256 0.4788,
-  // 512 / 128 0.4836, 640 / 192 0.4887, 256 main 0.4930.
+  // the plan (eae_wgrad_plan.h) under this process's caps
   static const int cap = getenv("EAE_EDGE_WGRAD_BLOCKS") ? atoi(getenv("EAE_EDGE_WGRAD_BLOCKS")) : 512;
-  // a launch beside the backward-data chain (deconv4's weight gradient, side stream) takes fewer CUs from it with fewer blocks
   static const int cap_side = getenv("EAE_EDGE_WGRAD_SIDE_BLOCKS") ? atoi(getenv("EAE_EDGE_WGRAD_SIDE_BLOCKS")) : 256;
-  int lim = (src3_kind == SRC3_NHWCP_BF16) ? cap_side : cap;
-  if (eae_geo_mult > 1) lim = lim / eae_geo_mult > 32 ? lim / eae_geo_mult : 32;      // member of a grouped step: the caps are per launch
-  int nblocks = a.ntiles < lim ? a.ntiles : lim;
-  while ((long long)nblocks * slice > scratch_floats && nblocks > 1) nblocks /= 2;
-  a.tiles_per_block = (a.ntiles + nblocks - 1) / nblocks;
-  nblocks = (a.ntiles + a.tiles_per_block - 1) / a.tiles_per_block;
-  if ((long long)nblocks * slice > scratch_floats) return eae_set_error(-2, "edge_wgrad: scratch too small");
+  EdgeWgPlan p;
+  if (!eae_edge_wgrad_plan(p, src3_kind == SRC3_NHWCP_BF16, C, B, H, W, scratch_floats, cap, cap_side, eae_geo_mult))
+    return eae_set_error(-2, "edge_wgrad: scratch too small");
+  a.ntiles = p.ntiles;
+  a.tiles_per_block = p.tiles_per_block;
+  const int nblocks = p.blocks;
 #define CASE1(S, M, P) if (src3_kind == S && smode == M && cp == P) { if (hook) hook->begin(hook->user, st); eae_launch(edge_wgrad_kernel<S, M, P>, edge_wgrad_kernel_g<S, M, P>, dim3(nblocks), dim3(256), 0, st, a); if (hook) hook->end(hook->user, st); EAE_LAUNCH_CHECK(); goto reduce; }
 #define CASE(S, M) CASE1(S, M, 4) CASE1(S, M, 8) CASE1(S, M, 16)
   CASE(SRC3_NCHW_F32, SRC_BNBWD)

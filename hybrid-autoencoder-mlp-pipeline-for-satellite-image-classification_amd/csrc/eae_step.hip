@@ -32,14 +32,10 @@ struct ProfBracket {
   ~ProfBracket() { if (on) prof_hook_end(c, st); }
 };
 
-// split-K of the latent projections: K-range per slice.  128 (32 slices) at the reference's 64x64 inputs; wider inputs keep the number
-// of slices at EAE_FC_SLICES (default 64): K / 128 = 512 slices at 256x256 wrote and re-read 67 MB of partials per projection (ms per
-// config-5 step with 512 / 128 / 64 / 32 / 16 slices: 2.066 / 2.050 / 2.040 / 2.058 / 2.107, with the prefetching K loop of fc_nt_kernel)
+// split-K of the latent projections: K range per slice (eae_wgrad_plan.h) under this process's EAE_FC_SLICES
 int fc_klen(const eae_ctx* c) {
   static const int slices = getenv("EAE_FC_SLICES") ? atoi(getenv("EAE_FC_SLICES")) : 64;
-  long long klen = 128;
-  while (c->K / klen > slices && c->K % (klen * 2) == 0) klen *= 2;
-  return (int)klen;
+  return eae_fc_klen(c->K, slices);
 }
 
 // the [C] sticky non-finite flag words of BN layer l sit behind the layer's [acc_copies][2][C] accumulators (forward or backward half)
@@ -570,7 +566,7 @@ int backward_impl(eae_ctx* c, hipStream_t st, const eae_step_io* io, const float
     struct Mid { eae_ctx* c; hipStream_t st; } mid = {c, st};
     auto mid_fn = [](void* u, GateArgs* g) { Mid* m = static_cast<Mid*>(u); return join_side_begin(m->c, m->st, g); };
     RC(eae_launch_edge_wgrad(st, SRC3_NCHW_F32, io->x, B, H, W, src_bnbwd(c->gy[0], c->y[0], c->coef_b[0]), SRC_BNBWD, c->wscratch_main,
-                             2048LL * 288 * c->Cin, c->grad(T_CONV1_W), prof_hook_for(c, EAE_PROF_CONV1_WGRAD), &bf0, sg.sig, sg.sig_val,
+                             c->wscratch_main_floats, c->grad(T_CONV1_W), prof_hook_for(c, EAE_PROF_CONV1_WGRAD), &bf0, sg.sig, sg.sig_val,
                              +mid_fn, &mid, c->Cin));
   }
   RC(join_side(c, st));                                 // (nothing left to wait for when the gate went with the reduction)

@@ -234,8 +234,8 @@ def wgrad_budget_bound(cs, cb, smode, bmode, hs, ws, B):
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# the tile geometry a case is meant to hit: csrc/eae_conv_plan.h and the launcher of csrc/eae_wgrad_launch.hip as literal tables
-# (the only copy in the tests: test_conv_plan.py compares the library's plan with this one)
+# the tile geometry a case is meant to hit: csrc/eae_conv_plan.h and csrc/eae_wgrad_plan.h as literal tables
+# (the only copy in the tests: test_conv_plan.py and test_wgrad_plan.py compare the C plans with this one)
 # ---------------------------------------------------------------------------------------------------------------
 WIDE = (16, 8, 1)                                                 # position grids that are multiples of 8 rows x 16 columns
 NARROW = {(0, 8): ((8, 8, 2), (8, 8, 1)), (0, 4): ((4, 4, 8), (4, 4, 4)),      # (kind, side): (large tiles, small tiles)
@@ -278,30 +278,52 @@ def expected_ntiles(kind, cin, cout, hp, wp, B, ig_small=None):
     return -1 if geo is None else _tiles(geo, B, hp, wp)
 
 
-def wgrad_workgroups_setting(cs, smode):
-    """the launcher's workgroup budget for a (cs, small mode) layer: 64, or what EAE_WGRAD_WGS=<one-block>[,<wide>[,<last>]] says"""
+def wgrad_workgroups_setting(cs, smode, wgs=None):
+    """the launcher's workgroup budget for a (cs, small mode) layer: 64, or what EAE_WGRAD_WGS=<one-block>[,<wide>[,<last>]] says;
+    wgs: the three budgets (one-block, wide, last) given outright instead of read from the environment"""
     one = wide = last = 64
-    v = [int(t) for t in os.environ.get("EAE_WGRAD_WGS", "").split(",") if t.strip().lstrip("-").isdigit()]
-    if v and v[0] > 0:
-        one = v[0]
-        wide = v[1] if len(v) >= 2 and v[1] > 0 else one
-        last = v[2] if len(v) >= 3 and v[2] > 0 else one
+    if wgs is not None:
+        one, wide, last = wgs
+    else:
+        v = [int(t) for t in os.environ.get("EAE_WGRAD_WGS", "").split(",") if t.strip().lstrip("-").isdigit()]
+        if v and v[0] > 0:
+            one = v[0]
+            wide = v[1] if len(v) >= 2 and v[1] > 0 else one
+            last = v[2] if len(v) >= 3 and v[2] > 0 else one
     if cs == 64 and smode in (2, 4):                               # enc.conv2's weight gradient, the last one of the step
         return last
     return one if cs == 64 else wide                               # 64 x 32 is one 64 x 32 block
 
 
-def expected_wgrad_launch(cs, cb, smode, hs, ws, B, scratch_floats):
+# what a weight-gradient launch is refused for (the launcher's three error texts), in the order the launcher checks
+WGRAD_NO_GEOMETRY, WGRAD_SCRATCH, WGRAD_FP8_NARROW = "unsupported spatial size", "scratch too small", "fp8 needs 16-wide tiles"
+
+
+def expected_wgrad_launch(cs, cb, smode, hs, ws, B, scratch_floats, mult=1, wgs=None, fp8=False):
     """((TW, TH, NI), tiles, slices, tiles per workgroup) of a weight-gradient launch: 16x8x1 tiles on wide small maps, 8x8x2 and
     4x4x8 on the narrow ones; the workgroup budget divided by the (cs/64)(cb/32) blocks gives the position slices, at most one per
-    tile and no more than the scratch holds; a workgroup takes ceil(tiles / slices) consecutive tiles."""
-    geo = WIDE if hs % 8 == 0 and ws % 16 == 0 else {8: (8, 8, 2), 4: (4, 4, 8)}[hs]
-    assert geo == WIDE or hs == ws
+    tile and no more than the scratch holds; a workgroup takes ceil(tiles / slices) consecutive tiles.  mult: the members of a
+    grouped step (eae_set_geometry_mult) share the budget, down to 8 workgroups each; wgs: see wgrad_workgroups_setting.  One of the
+    WGRAD_* strings instead when the launcher refuses: a map without geometry, a scratch below one partial, the fp8 variant on
+    narrow tiles.  This is csrc/eae_wgrad_plan.h restated; test_wgrad_plan.py holds the two together without a GPU."""
+    if hs % 8 == 0 and ws % 16 == 0:
+        geo = WIDE
+    elif hs == ws and hs in (8, 4):
+        geo = {8: (8, 8, 2), 4: (4, 4, 8)}[hs]
+    else:
+        return WGRAD_NO_GEOMETRY
     tiles = _tiles(geo, B, hs, ws)
     nblk, sz = (cs // 64) * (cb // 32), cs * cb * 9
-    slices = min(max(wgrad_workgroups_setting(cs, smode) // nblk, 1), tiles)
+    budget = wgrad_workgroups_setting(cs, smode, wgs)
+    if mult > 1:
+        budget = max(budget // mult, 8)
+    slices = min(max(budget // nblk, 1), tiles)
     while slices * sz > scratch_floats and slices > 1:
         slices >>= 1
+    if slices * sz > scratch_floats:
+        return WGRAD_SCRATCH
+    if fp8 and geo != WIDE:
+        return WGRAD_FP8_NARROW
     per = _cdiv(tiles, slices)
     return geo, tiles, _cdiv(tiles, per), per
 

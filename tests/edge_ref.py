@@ -173,7 +173,7 @@ def deconv4_case(smode, c, H, W, B):
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# the launch a weight-gradient case is meant to be: eae_launch_edge_wgrad restated
+# the launch a weight-gradient case is meant to be: the edge plan of csrc/eae_wgrad_plan.h restated (test_wgrad_plan.py compares the two)
 # ---------------------------------------------------------------------------------------------------------------
 def edge_wgrad_cap_setting(kind):
     """the launcher's workgroup cap for a source kind (read once per process): 512 on the fp32 image or what EAE_EDGE_WGRAD_BLOCKS
@@ -188,15 +188,22 @@ def edge_wgrad_cap_setting(kind):
         return 0                                                   # atoi of no number
 
 
-def expected_edge_wgrad_launch(kind, C, H, W, B, scratch_floats):
+def expected_edge_wgrad_launch(kind, C, H, W, B, scratch_floats, mult=1, caps=None):
     """(tiles, workgroups, tiles per workgroup): at most `cap` workgroups and one per tile, halved while their 288*C-float partials
     do not fit the scratch; a workgroup takes ceil(tiles / workgroups) consecutive tiles, and the workgroups that remain non-empty
-    are launched"""
+    are launched.  mult: the members of a grouped step (eae_set_geometry_mult) share the cap, down to 32 workgroups each; caps: (fp32
+    image, NHWC-CP source) given outright instead of read from the environment.  None when the launcher refuses: a scratch below
+    one partial.  This is csrc/eae_wgrad_plan.h restated; test_wgrad_plan.py holds the two together without a GPU."""
     tiles, sl = edge_tiles(H, W, B), 32 * 9 * C
-    blocks = min(tiles, edge_wgrad_cap_setting(kind))
+    cap = edge_wgrad_cap_setting(kind) if caps is None else caps[kind]
+    if mult > 1:
+        cap = max(cap // mult, 32)
+    blocks = min(tiles, cap)
     while blocks * sl > scratch_floats and blocks > 1:
         blocks //= 2
     per = _cdiv(tiles, blocks)
+    if _cdiv(tiles, per) * sl > scratch_floats:
+        return None
     return tiles, _cdiv(tiles, per), per
 
 

@@ -107,8 +107,9 @@ def test_igemm_exact(lib, kind, cin, cout, smode, epi, hp, wp, B):
         assert np.all(err <= bound), (col, int(np.argmax(err - bound)), float(err.max()))
 
 
-@pytest.mark.parametrize("cs,cb,smode,bmode,hs,ws,B", R.WGRAD_EXACT_CASES)
-def test_wgrad_exact(lib, cs, cb, smode, bmode, hs, ws, B):
+def _wgrad_exact(lib, cs, cb, smode, bmode, hs, ws, B, mult=1):
+    """one weight-gradient launch (as one of `mult` members of a grouped step) on a NaN-preset scratch: dw bit for bit, and the
+    launch conv_ref.expected_wgrad_launch says it is, which is returned"""
     import gpu_util as G
     from eae_amd._lib import check
     rng = np.random.default_rng(32000 + cs + 100 * smode + 10 * bmode + 3 * hs + ws + B)
@@ -120,19 +121,41 @@ def test_wgrad_exact(lib, cs, cb, smode, bmode, hs, ws, B):
     bs, keep_b = _upload(big)
     scratch = torch.full((6 * 1024 * 1024,), float("nan"), dtype=torch.float32, device=G.dev())
     dw = torch.full((cs, cb, 3, 3), float("nan"), dtype=torch.float32, device=G.dev())
-    check(lib.eae_op_wgrad_s2(G.stream(), ss, bs, cs, cb, B, hs, ws, G.ptr(scratch), scratch.numel(), G.ptr(dw)))
+    check(lib.eae_set_geometry_mult(mult))
+    try:
+        check(lib.eae_op_wgrad_s2(G.stream(), ss, bs, cs, cb, B, hs, ws, G.ptr(scratch), scratch.numel(), G.ptr(dw)))
+    finally:
+        check(lib.eae_set_geometry_mult(1))
     torch.cuda.synchronize()
     got = dw.cpu().numpy()
     assert not np.isnan(got).any(), _where(np.isnan(got))
     assert np.array_equal(got, ref), _where(got != ref)
     # the launch this case is meant to be: several position slices leave one partial each at the head of the scratch (a single slice
     # writes dw itself), so the slice count shows there, and with the tile count of the geometry the tiles per workgroup follow
-    geo, tiles, slices, per = R.expected_wgrad_launch(cs, cb, smode, hs, ws, B, scratch.numel())
+    geo, tiles, slices, per = R.expected_wgrad_launch(cs, cb, smode, hs, ws, B, scratch.numel(), mult)
     used = (slices if slices > 1 else 0) * cs * cb * 9
     assert not torch.isnan(scratch[:used]).any() and torch.isnan(scratch[used:]).all(), (geo, tiles, slices, per)
+    return geo, tiles, slices, per
+
+
+@pytest.mark.parametrize("cs,cb,smode,bmode,hs,ws,B", R.WGRAD_EXACT_CASES)
+def test_wgrad_exact(lib, cs, cb, smode, bmode, hs, ws, B):
+    geo, tiles, slices, per = _wgrad_exact(lib, cs, cb, smode, bmode, hs, ws, B)
     hit = R.WGRAD_MULTI_TILE.get(geo)
     if hit is not None and hit[0] == (cs, cb, smode, bmode, hs, ws, B) and "EAE_WGRAD_WGS" not in os.environ:
         assert (tiles, slices, per) == hit[1:] and per > 1
+
+
+@pytest.mark.parametrize("mult,want", [(2, (12, 2, 6)), (8, (12, 1, 12))])
+def test_wgrad_exact_as_a_member_of_a_grouped_step(lib, mult, want):
+    """The members of a grouped step share the workgroup budget (eae_set_geometry_mult): the 16x8x1 multi-tile row, 4 slices of 3
+    tiles alone, runs on 64 / 2 / 16 = 2 slices of 6, and with 8 members on the floor of 8 workgroups -- fewer than its 16 output
+    blocks: one slice, which writes dw itself and leaves the whole scratch untouched.  The result stays the exact sum."""
+    case = (256, 128, 2, 1, 16, 32, 3)
+    assert R.WGRAD_MULTI_TILE[R.WIDE][0] == case
+    geo, tiles, slices, per = _wgrad_exact(lib, *case, mult=mult)
+    if "EAE_WGRAD_WGS" not in os.environ:
+        assert geo == R.WIDE and (tiles, slices, per) == want
 
 
 def test_exact_conv_cases_on_the_large_tiles_and_the_wave_specialised_kernel():

@@ -122,8 +122,9 @@ def test_edge_conv_exact(lib, kind, epi, c, H, W, B):
         assert np.all(err <= bound), (col, int(np.argmax(err - bound)), float(err.max()))
 
 
-@pytest.mark.parametrize("kind,smode,c,H,W,B,slices", E.EDGE_WGRAD_CASES)
-def test_edge_wgrad_exact(lib, kind, smode, c, H, W, B, slices):
+def _edge_wgrad_exact(lib, kind, smode, c, H, W, B, slices, mult=1):
+    """one weight-gradient launch (as one of `mult` members of a grouped step) on a NaN-preset scratch: dw bit for bit, and the
+    launch edge_ref.expected_edge_wgrad_launch says it is, which is returned"""
     import gpu_util as G
     from eae_amd._lib import check
     case = (kind, smode, c, H, W, B, slices)
@@ -135,21 +136,45 @@ def test_edge_wgrad_exact(lib, kind, smode, c, H, W, B, slices):
     nsc = E.edge_wgrad_scratch_floats(case)
     scratch, scratch_guard = _nan(nsc, torch.float32)
     dw, dw_guard = _nan(32 * c * 9, torch.float32)
-    check(lib.eae_op_edge_wgrad_c(G.stream(), kind, G.ptr(xd), c, B, H, W, sd, G.ptr(scratch), nsc, G.ptr(dw)))
+    check(lib.eae_set_geometry_mult(mult))
+    try:
+        check(lib.eae_op_edge_wgrad_c(G.stream(), kind, G.ptr(xd), c, B, H, W, sd, G.ptr(scratch), nsc, G.ptr(dw)))
+    finally:
+        check(lib.eae_set_geometry_mult(1))
     torch.cuda.synchronize()
     got = dw.cpu().numpy().reshape(32, c, 3, 3)
     assert not np.isnan(got).any(), _where(np.isnan(got))
     assert np.array_equal(got, ref), _where(got != ref)
     assert torch.isnan(dw_guard).all() and torch.isnan(scratch_guard).all()
     # the launch this row is meant to be: every workgroup leaves one partial of 288*C floats at the head of the scratch
-    tiles, blocks, per = E.expected_edge_wgrad_launch(kind, c, H, W, B, nsc)
+    tiles, blocks, per = E.expected_edge_wgrad_launch(kind, c, H, W, B, nsc, mult)
     used = blocks * 288 * c
     assert used <= nsc
     written = ~torch.isnan(scratch)
     assert written[:used].all() and not written[used:].any(), (tiles, blocks, per, int(written.sum()), used)
-    unset = "EAE_EDGE_WGRAD_BLOCKS" not in os.environ and "EAE_EDGE_WGRAD_SIDE_BLOCKS" not in os.environ
-    if case in E.EDGE_WGRAD_MULTI_TILE and unset:
+    return tiles, blocks, per
+
+
+def _caps_unset():
+    return "EAE_EDGE_WGRAD_BLOCKS" not in os.environ and "EAE_EDGE_WGRAD_SIDE_BLOCKS" not in os.environ
+
+
+@pytest.mark.parametrize("kind,smode,c,H,W,B,slices", E.EDGE_WGRAD_CASES)
+def test_edge_wgrad_exact(lib, kind, smode, c, H, W, B, slices):
+    case = (kind, smode, c, H, W, B, slices)
+    tiles, blocks, per = _edge_wgrad_exact(lib, *case)
+    if case in E.EDGE_WGRAD_MULTI_TILE and _caps_unset():
         assert (tiles, blocks, per) == E.EDGE_WGRAD_MULTI_TILE[case] and per > 1
+
+
+def test_edge_wgrad_exact_as_a_member_of_a_grouped_step(lib):
+    """The members of a grouped step share the workgroup cap (eae_set_geometry_mult): the row above the main source's cap, 260
+    workgroups of 2 tiles alone, runs with two members under a cap of 512 / 2 = 256 -- 174 workgroups of 3 tiles, the last with one."""
+    case = (0, 2, 3, 8, 64, 520, None)
+    assert E.EDGE_WGRAD_MULTI_TILE[case] == (520, 260, 2)
+    tiles, blocks, per = _edge_wgrad_exact(lib, *case, mult=2)
+    if _caps_unset():
+        assert (tiles, blocks, per) == (520, 174, 3)
 
 
 @pytest.mark.parametrize("smode,c,H,W,B", E.DECONV4_CASES)
