@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "eae_bn_acc.h"    // bn_acc_limit
 
 typedef uint16_t bf16_t;
 
@@ -30,8 +31,12 @@ struct BnAcc {
   unsigned long long* acc;   // [copies][2][C]; zero before the producer runs; nullptr: per-tile partials + finalize kernel
   int copies;                // power of two
   float scale;               // fixed-point scale
-  unsigned long long* flag;  // [C] sticky "a non-finite partial of this channel was seen" words (cleared with the accumulators)
+  unsigned long long* flag;  // [C] sticky "a partial of this channel was not finite or too large" words (cleared with the accumulators)
+  float limit;               // |v * scale| of one contribution stays below this, or it raises the flag (set by the launcher, below)
+  int world;                 // SyncBN replicas whose accumulators are summed before the consumer reads them (0 or 1: none)
 };
+// the launcher's part: it knows how many workgroups contribute to one channel (ConvArgs::ntiles)
+inline void bn_acc_set_limit(BnAcc& b, int contributions) { b.limit = bn_acc_limit(contributions, b.world); }
 struct BnFold {
   const unsigned long long* acc;   // nullptr: the coefficients come from SrcDesc::coef
   int copies;

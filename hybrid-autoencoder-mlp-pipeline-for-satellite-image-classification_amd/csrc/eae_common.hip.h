@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "eae_args.h"      // bf16_t, SRC_* / EPI_*, SrcDesc, BnAcc / BnFold / BnBwdFold
+#include "eae_bn_acc.h"    // the fixed-point arithmetic of the folded BatchNorm finalize
 #include "eae_group.h"
 #include "eae_store_policy.h"
 
@@ -176,8 +177,10 @@ __device__ __forceinline__ void bn_acc_add(const BnAcc& b, int C, int tile_id, i
   // a non-finite partial (diverged run) must poison the statistics like it does in floating point.  It cannot travel inside the
   // wrapping integer sum (round 2 added 2^61 per poisoned partial: eight of them -- every workgroup of a diverged step -- cancel
   // mod 2^64): it sets the channel's sticky flag word instead, and the consumers turn a set flag into NaN coefficients of that channel
+  // The same goes for a finite partial so large that the launch's contributions together could leave the signed 64-bit range
+  // (b.limit = bn_acc_limit(workgroups per channel, SyncBN world), eae_bn_acc.h): the total would wrap without a trace.
   const float sv = v * b.scale;
-  if (fabsf(sv) < 9.0e18f) __hip_atomic_fetch_add(p, (unsigned long long)llrintf(sv), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (bn_acc_fits(sv, b.limit)) __hip_atomic_fetch_add(p, bn_acc_fixed(sv), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   else if (b.flag != nullptr) __hip_atomic_fetch_or(b.flag + ch, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 // Split in two so that the accumulator loads can be ISSUED before the kernel's own first loads (vector-memory results return in
@@ -221,24 +224,15 @@ __device__ __forceinline__ void bn_fold_fwd_finish(const BnFold& f, const BnFold
 #pragma unroll
     for (int g = 1; g < G; ++g) { s1 += red[g * C + ch]; s2 += red[256 + g * C + ch]; }
     const bool poisoned = r.flag != 0ull;
-    const double a = poisoned ? (double)__builtin_nanf("") : (double)s1 * (double)f.inv_scale, b = (double)s2 * (double)f.inv_scale;
-    const double mean = a / f.count;
-    double var = b / f.count - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const float invstd = 1.0f / sqrtf((float)var + f.eps);
-    const float s = f.gamma[ch] * invstd, t = f.beta[ch] - (float)mean * s;
-    table[ch] = s; table[C + ch] = t; table[2 * C + ch] = (float)mean; table[3 * C + ch] = invstd;
+    const BnAccFwd o = bn_acc_fwd_finish(s1, s2, poisoned, f.inv_scale, f.count, f.eps, f.gamma[ch], f.beta[ch]);
+    table[ch] = o.s; table[C + ch] = o.t; table[2 * C + ch] = o.mean; table[3 * C + ch] = o.invstd;
     // The NaN coefficients poison this channel's activations, but not reliably what follows: the packed-bf16 ReLU of the consumers
     // is an integer max, which turns a negative-signed NaN into 0 (measured: a NaN weight of enc.conv2 left every later layer and the
     // loss finite).  The step-wide word makes the step loud whatever the data does: loss_finalize and the optimizer kernel read it.
     if (writer && poisoned && f.poison != nullptr) __hip_atomic_fetch_or(f.poison, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (writer) {
-      f.coef_out[ch] = s; f.coef_out[C + ch] = t; f.coef_out[2 * C + ch] = (float)mean; f.coef_out[3 * C + ch] = invstd;
-      if (f.rm) {
-        const double unb = f.count > 1.f ? var * (double)f.count / ((double)f.count - 1.0) : var;
-        f.rm[ch] = (1.f - f.momentum) * f.rm[ch] + f.momentum * (float)mean;
-        f.rv[ch] = (1.f - f.momentum) * f.rv[ch] + f.momentum * (float)unb;
-      }
+      f.coef_out[ch] = o.s; f.coef_out[C + ch] = o.t; f.coef_out[2 * C + ch] = o.mean; f.coef_out[3 * C + ch] = o.invstd;
+      if (f.rm) bn_acc_running(o, f.count, f.momentum, f.rm[ch], f.rv[ch]);
       if (f.nbt && ch == 0) *f.nbt += 1;
     }
   }
@@ -258,7 +252,7 @@ __device__ __forceinline__ void bn_fold_fwd(const BnFold& f, float* table, long 
 // on the main stream, weight-gradient kernel on a side stream) sums the copies in its prologue, behind its own first loads, and
 // builds the table [3][C] = A, B, Cc of bn_bwd_finalize_kernel in LDS.  Workgroup 0 of the main-stream consumer also stores
 // dgamma / dbeta (and the table, for the per-op entry points and the diagnostics).  Integer sums: independent of the arrival
-// order, so bitwise reproducible.  2^42 fixed point: workgroup sums from 2.3e-13 to 2e6 in magnitude (beyond: NaN).
+// order, so bitwise reproducible.  2^42 fixed point: a quantum of 2.3e-13, workgroup sums below 2^20 / (workgroups per channel) in magnitude (beyond: NaN; eae_bn_acc.h).
 // (A "last workgroup of the producer finalizes" variant was measured first: waiting for the atomics' return values and drawing a
 // ticket cost every producer workgroup two device-scope round trips at its end: 0.558 vs 0.5225 ms per step.)
 // ---------------------------------------------------------------------------------------------------------------
@@ -281,12 +275,8 @@ __device__ __forceinline__ void bn_fold_bwd_finish(const BnBwdFold& f, const BnF
 #pragma unroll
     for (int g = 1; g < G; ++g) { s1 += red[g * C + ch]; s2 += red[256 + g * C + ch]; }
     const bool poisoned = r.flag != 0ull;
-    const float db = poisoned ? __builtin_nanf("") : (float)((double)s1 * (double)f.inv_scale);
-    const float dg = (float)((double)s2 * (double)f.inv_scale);
-    const float mean = f.coef_fwd[2 * C + ch], invstd = f.coef_fwd[3 * C + ch];
-    const float A = f.gamma[ch] * invstd;
-    const float Bc = -A * invstd * dg / f.count;
-    const float Cc = -A * db / f.count - Bc * mean;
+    const BnAccBwd o = bn_acc_bwd_finish(s1, s2, poisoned, f.inv_scale, f.count, f.gamma[ch], f.coef_fwd[2 * C + ch], f.coef_fwd[3 * C + ch]);
+    const float A = o.A, Bc = o.Bc, Cc = o.Cc, dg = o.dgamma, db = o.dbeta;
     table[ch] = A; table[C + ch] = Bc; table[2 * C + ch] = Cc;
     if (writer && poisoned && f.poison != nullptr) __hip_atomic_fetch_or(f.poison, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (writer) {

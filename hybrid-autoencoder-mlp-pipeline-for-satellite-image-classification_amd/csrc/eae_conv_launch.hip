@@ -23,6 +23,7 @@ int run(void (*kern)(ConvArgs), void (*kern_g)(GroupPack<ConvArgs>, int), size_t
   EAE_HIP(eae_smem_attr(eae_rec ? (const void*)kern_g : (const void*)kern, smem));
   ConvArgs b = a;
   b.ntiles = p.ntiles;
+  bn_acc_set_limit(b.bacc, p.ntiles);
   eae_launch(kern, kern_g, dim3(p.grid), dim3(p.threads), smem, st, b);
   EAE_LAUNCH_CHECK();
   return 0;

@@ -24,6 +24,7 @@ int eae_launch_edge_conv(hipStream_t st, int src3_kind, int epi, const EdgeArgs&
   const int cp = edge_cp(a.C);
   dim3 grid(a.B * (a.H / 2 / E_TH) * (a.W / 2 / E_TW));
   a.c.ntiles = (int)grid.x;
+  bn_acc_set_limit(a.c.bacc, a.c.ntiles);
 #define CASE1(S, E, P) if (src3_kind == S && epi == E && cp == P) { eae_launch(edge_conv_kernel<S, E, P>, edge_conv_kernel_g<S, E, P>, grid, dim3(256), 0, st, a); EAE_LAUNCH_CHECK(); return 0; }
 #define CASE(S, E) CASE1(S, E, 4) CASE1(S, E, 8) CASE1(S, E, 16)
   CASE(SRC3_NCHW_F32, EPI_FWD)

@@ -40,7 +40,10 @@ int fc_klen(const eae_ctx* c) {
 
 // the [C] sticky non-finite flag words of BN layer l sit behind the layer's [acc_copies][2][C] accumulators (forward or backward half)
 unsigned long long* acc_flag(const eae_ctx* c, unsigned long long* acc, int l) { return acc + (size_t)c->acc_copies[l] * 2 * BN_LAYERS[l].c; }
-constexpr float ACC_SCALE_FWD = 16777216.f;      // 2^24: sums of y and y^2 over <= 2^21 elements of |y| <~ 1e3 stay far below 2^63
+// 2^24: a workgroup's sums of y and y^2 stay below 2^38 / (workgroups per channel x SyncBN world), or the channel is flagged and the
+// step reads NaN (eae_bn_acc.h).  At batch 512 conv1 has 4096 workgroups per channel: sum y^2 < 2^26 over a tile of 128 positions, an
+// rms of y below 2^9.5 = 724; conv4 (64 workgroups of 128) reaches 2^12.5.  Below the limit the sums are exact to 2^-25 each.
+constexpr float ACC_SCALE_FWD = BN_ACC_SCALE_FWD;
 
 // fp8 variant: weight pack, scales and the amax word of 3x3 layer j (W3 order) for a forward / backward-data launch
 void fp8_conv_args(eae_ctx* c, ConvArgs& a, int j, bool forward, bool p1) {
@@ -55,6 +58,7 @@ void fp8_conv_args(eae_ctx* c, ConvArgs& a, int j, bool forward, bool p1) {
 void fold_producer(eae_ctx* c, ConvArgs& a, int l, bool train) {
   if (!train || !c->fold_fwd) return;
   a.bacc.acc = c->accf[l]; a.bacc.copies = c->acc_copies[l]; a.bacc.scale = ACC_SCALE_FWD; a.bacc.flag = acc_flag(c, c->accf[l], l);
+  a.bacc.world = c->sync_world;       // (the launcher turns it into the limit of one contribution: bn_acc_set_limit)
   a.stat_part = nullptr;
 }
 // consumer side: coefficient table of BN layer l from its accumulators
@@ -98,7 +102,7 @@ int bn_fwd_finalize(eae_ctx* c, hipStream_t st, int l, int ntiles, long long cou
   return eae_launch_bn_eval_coef(st, BN_LAYERS[l].c, c->bn_gamma(l), c->bn_beta(l), c->bn_rmean(l), c->bn_rvar(l), BN_EPS, c->coef_f[l]);
 }
 
-constexpr float ACC_SCALE_BWD = 4398046511104.f;   // 2^42 (eae_common.hip.h, BnBwdFold)
+constexpr float ACC_SCALE_BWD = BN_ACC_SCALE_BWD;   // 2^42 (eae_common.hip.h, BnBwdFold; range: eae_bn_acc.h)
 bool bwd_folded(const eae_ctx* c, int l) { (void)l; return c->fold_bwd && c->sync_world <= 1; }
 int bwd_copies(const eae_ctx* c, int l) { return std::min(c->acc_copies[l], BN_FOLD_KB * (256 / BN_LAYERS[l].c)); }
 // producer side of the folded BatchNorm-backward finalize of layer l: call before launching the kernel whose epilogue takes the sums
@@ -106,6 +110,7 @@ void fold_bwd_producer(eae_ctx* c, ConvArgs& a, int l) {
   if (!bwd_folded(c, l)) return;
   a.stat_part = nullptr;
   a.bacc.acc = c->accb[l]; a.bacc.copies = bwd_copies(c, l); a.bacc.scale = ACC_SCALE_BWD; a.bacc.flag = acc_flag(c, c->accb[l], l);
+  a.bacc.world = 1;                   // (folded only without SyncBN: bwd_folded)
 }
 // consumer side: the kernels that read layer l's (g, y) pair with SRC_BNBWD build A, B, Cc from the accumulators; `writer`: the
 // main-stream consumer, whose workgroup 0 also stores dgamma / dbeta and the table

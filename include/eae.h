@@ -263,7 +263,12 @@ int eae_adam_step_dp(eae_ctx* ctx, void* stream, float lr, float weight_decay, f
  * starting at element `elem_offset` of acc_i64) and once per layer in the backward (kind 1: `count` fp64 sums at element
  * `elem_offset` of sums_f64): the hook all-reduces (SUM) that range over the replicas, enqueued on `stream`, and returns 0.
  * acc_i64: caller-owned device buffer of eae_sync_bn_acc_elems() int64 (zero-initialised); sums_f64: 7*2*256 fp64.
- * world <= 1 or fn NULL switches it off (per-replica statistics, the default: DDP semantics). */
+ * world <= 1 or fn NULL switches it off (per-replica statistics, the default: DDP semantics).
+ * Range of the fixed-point accumulators (csrc/eae_bn_acc.h): with N = workgroups per channel of the layer's
+ * launch x world, a workgroup's sums of y and y^2 must stay below 2^38 / N in the forward (quantum 2^-24) and its sums of g and
+ * g * xhat below 2^20 / N in the backward (quantum 2^-42; with world > 1 the backward sums travel as fp64 and have no limit); a larger
+ * or non-finite sum flags the channel: NaN statistics, NaN losses, no update.  The world enters because the replicas' integers are
+ * summed: eight replicas leave each workgroup an eighth of the range. */
 typedef int (*eae_sync_fn)(void* user, int kind, long long elem_offset, long long count, void* stream);
 long long eae_sync_bn_acc_elems(eae_ctx* ctx);
 int eae_set_sync_bn(eae_ctx* ctx, int world, eae_sync_fn fn, void* user, void* acc_i64, void* sums_f64);
