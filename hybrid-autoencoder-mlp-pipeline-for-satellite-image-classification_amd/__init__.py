@@ -5,7 +5,7 @@ Public surface mirrors the notebook: ``Encoder``, ``Decod
 that restate its inline loops.  All arithmetic runs in hand-written gfx950 HIP kernels behind the
 C ABI declared in ``include/eae.h``.
 """
-from .modules import Encoder, Decoder, SupervisedAutoencoder, MLP  # noqa: F401
+from .modules import Encoder, Decoder, SupervisedAutoencoder, MLP, mlp_from_state_dict  # noqa: F401
 from .augment import augment_batch, stage_bands, Augment  # noqa: F401
 from .train import (fit_autoencoder, grid_search_autoencoder, extract_features, fit_mlp, grid_search_mlp,  # noqa: F401
                     evaluate)
@@ -25,7 +25,7 @@ from .neighbors import knn_search, knn_classify, similar_windows, knn_classify_s
 from . import postprocess  # noqa: F401
 from .postprocess import majority_filter, label_regions, region_table, sieve  # noqa: F401
 
-__all__ = ["Encoder", "Decoder", "SupervisedAutoencoder", "MLP", "fit_autoencoder", "grid_search_autoencoder",
+__all__ = ["Encoder", "Decoder", "SupervisedAutoencoder", "MLP", "mlp_from_state_dict", "fit_autoencoder", "grid_search_autoencoder",
            "extract_features", "fit_mlp", "grid_search_mlp", "evaluate", "augment_batch", "stage_bands", "Augment",
            "confusion_matrix", "classification_report", "loss_heatmap", "ce_mse_ratio_probe", "scene_windows", "encode_scene",
            "classify_scene", "window_grid", "window_invalid_counts", "valid_windows", "scene_reconstruction_error",

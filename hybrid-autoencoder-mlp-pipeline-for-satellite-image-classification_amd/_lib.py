@@ -133,6 +133,8 @@ _PROTOS = {
     "eae_op_adam": (C.c_int, [vp, vp, vp, vp, vp, C.c_longlong, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_longlong]),
     "eae_mlp_layout": (C.c_int, [C.c_int, C.c_int, c_ll_p, c_ll_p]),
     "eae_mlp_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
+    "eae_mlp_layout_ex": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), c_ll_p, c_ll_p]),
+    "eae_mlp_create_ex": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_int, C.POINTER(vp)]),
     "eae_mlp_destroy": (C.c_int, [vp]),
     "eae_mlp_bind": (C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
     "eae_mlp_set_adam_step": (C.c_int, [vp, C.c_longlong]),

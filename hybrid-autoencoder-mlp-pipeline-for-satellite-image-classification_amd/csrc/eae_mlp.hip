@@ -5,31 +5,20 @@
 // kernel launch executed by a single 1024-thread workgroup (BatchNorm1d needs whole-batch statistics anyway); weights
 // stay L1/L2-resident, activations live in a small global workspace, arithmetic is fp32 (matches the reference's dtype).
 // Evaluation (running statistics, rows independent) uses one block per 64 rows.
+// This unit holds every eae_mlp_* entry point and the fixed 128 / 64 kernel.  A context made by eae_mlp_create_ex (any architecture,
+// eae_mlp_ctx.h: general = 1) passes the same checks here and is then handed to the layer-table kernel of eae_mlp_arch.hip.
 #include "eae_internal.h"
 #include "eae_common.hip.h"
 #include <cmath>
 
 #include "eae_mlp.hip.h"
+#include "eae_mlp_ctx.h"
 
 namespace {
 #define MLP_WCE 0
 #include "eae_mlp_kernel.hip.h"
 #undef MLP_WCE
 }  // namespace
-
-struct eae_mlp {
-  int IN, C, Bm;
-  long long off[11], bnoff[5];
-  float *P = nullptr, *G = nullptr, *M = nullptr, *V = nullptr, *bnrun = nullptr;
-  long long* nbt = nullptr;
-  long long adam_step = 0;
-  void* ws = nullptr;
-  float *h1, *a1, *h2, *a2, *dlog, *g2, *g1;
-  const float* class_w = nullptr;              // eae_mlp_set_class_weights: caller-owned [C] or nullptr
-  long long ignore_index = EAE_NO_IGNORE;
-  bool wce() const { return class_w != nullptr || ignore_index != EAE_NO_IGNORE; }
-  long long* valid_acc = nullptr;              // eae_mlp_set_valid_counter: += counted rows of every step that accumulates stats
-};
 
 static long long r4(long long n) { return (n + 3) & ~3LL; }
 
@@ -70,6 +59,7 @@ extern "C" int eae_mlp_destroy(eae_mlp* m) {
 extern "C" int eae_mlp_bind(eae_mlp* m, float* params, float* grads, float* adam_m, float* adam_v, float* bn_running, long long* bn_nbt) {
   if (!m || !params || !bn_running) return eae_set_error(EAE_ERR_ARG, "mlp_bind: ctx, params and bn_running are required");
   m->P = params; m->G = grads; m->M = adam_m; m->V = adam_v; m->bnrun = bn_running; m->nbt = bn_nbt;
+  if (m->general) eae_mlp_arch_bound(m);
   return 0;
 }
 extern "C" int eae_mlp_set_adam_step(eae_mlp* m, long long s) { if (!m) return eae_set_error(EAE_ERR_ARG, "mlp is NULL"); m->adam_step = s; return 0; }
@@ -100,6 +90,10 @@ static int mlp_launch(eae_mlp* m, hipStream_t st, const float* x, const long lon
   a.logits = logits; a.stats = stats; a.dlog_in = dlog_in; a.update_running = dlog_in ? 0 : 1;
   a.ldx = m->IN; a.probs = nullptr; a.plabels = nullptr; a.win0 = 0; a.plane = 0; a.index = nullptr;
   const int grid = train ? 1 : (B + 63) / 64;
+  if (m->general) {
+    const int weighted = m->wce() && labels && !dlog_in;
+    return eae_mlp_arch_launch(m, st, a, weighted, m->class_w, m->ignore_index, stats ? m->valid_acc : nullptr);
+  }
   if (m->wce() && labels && !dlog_in) {
     eae_mlp_launch_wce(st, grid, a, m->class_w, m->ignore_index, stats ? m->valid_acc : nullptr);
   } else {
@@ -169,6 +163,10 @@ int eae_mlp_predict(eae_mlp* m, hipStream_t st, const float* x, int ldx, int B, 
     a.seed = 0; a.step = 0; a.drop_mask = nullptr; a.p_drop = 0.3f;
     a.logits = nullptr; a.stats = nullptr; a.dlog_in = nullptr; a.update_running = 0;
     a.ldx = ldx; a.probs = probs; a.plabels = labels; a.win0 = win0 + b0; a.plane = plane; a.index = index;
+    if (m->general) {
+      if (int rc = eae_mlp_arch_launch(m, st, a, 0, nullptr, EAE_NO_IGNORE, nullptr)) return rc;
+      continue;
+    }
     hipLaunchKernelGGL(mlp_kernel, dim3((nb + 63) / 64), dim3(T), 0, st, a);
     EAE_LAUNCH_CHECK();
   }

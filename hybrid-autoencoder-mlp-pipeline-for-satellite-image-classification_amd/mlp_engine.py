@@ -9,36 +9,59 @@ import torch
 from . import _lib
 from ._lib import check
 from .engine import _ptr, _stream, _require_gpu, class_weight_args
+from .modules import MLP_HIDDEN, MLP_DROPOUT
 
 _ENGINES = weakref.WeakKeyDictionary()
 
 
 class MLPEngine:
-    def __init__(self, mlp, max_batch=256):
+    """general: None takes the fixed 128 / 64 kernel (eae_mlp_create) exactly when the architecture is the default one, hidden (128, 64)
+    with dropout (0.3, 0), and the layer-table kernel (eae_mlp_create_ex) otherwise; True forces the layer-table kernel.
+    drop_mask (forward, train_step): None for the kernel's own Philox masks, or one float32 tensor holding the keep masks [B, w_l] of
+    the layers with a rate above 0, in layer order, back to back ([B, 128] for the default architecture)."""
+
+    def __init__(self, mlp, max_batch=256, general=None):
         self.lib = _lib.load()
         p0 = next(mlp.parameters())
         self.device = p0.device
         _require_gpu(self.device)
         self.input_dim, self.classes, self.max_batch = mlp.input_dim, mlp.num_classes, int(max_batch)
-        poff = (C.c_longlong * 11)()
-        boff = (C.c_longlong * 5)()
-        check(self.lib.eae_mlp_layout(self.input_dim, self.classes, poff, boff))
+        self.hidden, self.dropout = tuple(mlp.hidden), tuple(mlp.dropout)
+        default = (self.hidden, self.dropout) == (MLP_HIDDEN, MLP_DROPOUT)
+        if general is None:
+            general = not default
+        elif not general and not default:
+            raise RuntimeError(f"the fixed kernel serves hidden={MLP_HIDDEN}, dropout={MLP_DROPOUT} only; this MLP has "
+                               f"hidden={self.hidden}, dropout={self.dropout}")
+        self.general = bool(general)
+        nh = len(self.hidden)
+        widths = (C.c_int * nh)(*self.hidden)
+        poff = (C.c_longlong * (4 * nh + 3))()
+        boff = (C.c_longlong * (2 * nh + 1))()
+        check(self.lib.eae_mlp_layout_ex(self.input_dim, self.classes, nh, widths, poff, boff))
         self.poff, self.boff = list(poff), list(boff)
-        n = self.poff[10]
+        n = self.poff[-1]
         dev = self.device
         self.params = torch.zeros(n, dtype=torch.float32, device=dev)
         self.grads = torch.zeros(n, dtype=torch.float32, device=dev)
         self.adam_m = torch.zeros(n, dtype=torch.float32, device=dev)
         self.adam_v = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.bn_running = torch.zeros(self.boff[4], dtype=torch.float32, device=dev)
-        self.bn_nbt = torch.zeros(2, dtype=torch.int64, device=dev)
+        self.bn_running = torch.zeros(self.boff[-1], dtype=torch.float32, device=dev)
+        self.bn_nbt = torch.zeros(nh, dtype=torch.int64, device=dev)
         self.stats = torch.zeros(8, dtype=torch.float32, device=dev)
         self.valid = torch.zeros((), dtype=torch.int64, device=dev)
         self.class_weights, self.ignore_index = None, None
-        net = mlp.net
-        self._slots = [(net[0].weight, 0), (net[0].bias, 1), (net[1].weight, 2), (net[1].bias, 3), (net[4].weight, 4),
-                       (net[4].bias, 5), (net[5].weight, 6), (net[5].bias, 7), (net[7].weight, 8), (net[7].bias, 9)]
-        self._bn = [(net[1], 0), (net[5], 1)]
+        # the Linear / BatchNorm1d modules of mlp.net in order: W, b, gamma, beta per hidden layer, then the last W, b
+        linears = [m for m in mlp.net if isinstance(m, torch.nn.Linear)]
+        bns = [m for m in mlp.net if isinstance(m, torch.nn.BatchNorm1d)]
+        if len(linears) != nh + 1 or len(bns) != nh:
+            raise RuntimeError(f"MLP.net holds {len(linears)} Linear and {len(bns)} BatchNorm1d modules; hidden={self.hidden} needs "
+                               f"{nh + 1} and {nh}")
+        self._slots = []
+        for l, (lin, bn) in enumerate(zip(linears, bns)):
+            self._slots += [(lin.weight, 4 * l), (lin.bias, 4 * l + 1), (bn.weight, 4 * l + 2), (bn.bias, 4 * l + 3)]
+        self._slots += [(linears[-1].weight, 4 * nh), (linears[-1].bias, 4 * nh + 1)]
+        self._bn = [(bn, l) for l, bn in enumerate(bns)]
         with torch.no_grad():
             for p, i in self._slots:
                 v = self.params[self.poff[i]: self.poff[i] + p.numel()].view(p.shape)
@@ -55,7 +78,11 @@ class MLPEngine:
                 bn._buffers["running_mean"], bn._buffers["running_var"] = rm, rv
                 bn._buffers["num_batches_tracked"] = self.bn_nbt[l]
         h = C.c_void_p()
-        check(self.lib.eae_mlp_create(self.input_dim, self.classes, self.max_batch, C.byref(h)))
+        if self.general:
+            rates = (C.c_float * nh)(*self.dropout)
+            check(self.lib.eae_mlp_create_ex(self.input_dim, self.classes, nh, widths, rates, self.max_batch, C.byref(h)))
+        else:
+            check(self.lib.eae_mlp_create(self.input_dim, self.classes, self.max_batch, C.byref(h)))
         self.ctx = h
         check(self.lib.eae_mlp_bind(self.ctx, _ptr(self.params), _ptr(self.grads), _ptr(self.adam_m), _ptr(self.adam_v),
                                     _ptr(self.bn_running), _ptr(self.bn_nbt)))
@@ -140,16 +167,21 @@ def _destroy(lib, ctx):
         pass
 
 
-def mlp_engine_for(mlp, max_batch=None):
+def mlp_engine_for(mlp, max_batch=None, general=None):
+    """The engine attached to `mlp` (built on first use; rebuilt for a bigger max_batch, another device or another kernel choice).
+    general: as for MLPEngine; None keeps whatever kernel an attached engine runs."""
     eng = _ENGINES.get(mlp)
     dev = next(mlp.parameters()).device
     _require_gpu(dev)
     want = max_batch or 256
     old = None
-    if eng is not None and (not eng.attached() or eng.device != dev or eng.max_batch < want):
+    if eng is not None and (not eng.attached() or eng.device != dev or eng.max_batch < want
+                            or (general is not None and bool(general) != eng.general)):
         old, eng = eng, None
     if eng is None:
-        eng = MLPEngine(mlp, max_batch=want)
+        if general is None and old is not None:
+            general = old.general                   # a rebuild for a bigger workspace or another device keeps the kernel choice
+        eng = MLPEngine(mlp, max_batch=want, general=general)
         if old is not None and old.device == dev and (old.class_weights is not None or old.ignore_index is not None):
             eng.set_class_weights(old.class_weights, old.ignore_index)      # the criterion's setting survives a bigger workspace
         _ENGINES[mlp] = eng

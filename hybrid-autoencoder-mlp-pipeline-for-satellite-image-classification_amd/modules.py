@@ -139,24 +139,79 @@ class SupervisedAutoencoder(nn.Module):
         return _engine().autoencoder_forward(self, x)
 
 
-class MLP(nn.Module):
-    """R.md:2549-2566. forward(x [B,input_dim]) -> logits [B,num_classes]."""
+MLP_HIDDEN, MLP_DROPOUT = (128, 64), (0.3, 0.0)          # the reference's classifier (R.md:2549-2566)
 
-    def __init__(self, input_dim, num_classes=10):
+
+def _mlp_arch(hidden, dropout):
+    """(hidden, dropout) as tuples: 1..4 widths in 1..512, one rate in [0, 1) per hidden layer (a scalar: that rate everywhere)."""
+    try:
+        hidden = tuple(hidden)
+    except TypeError:
+        raise ValueError(f"hidden must be a sequence of 1..4 widths, got {hidden!r}") from None
+    if not 1 <= len(hidden) <= 4:
+        raise ValueError(f"hidden must hold 1..4 widths, got {len(hidden)}")
+    for w in hidden:
+        if isinstance(w, bool) or int(w) != w or not 1 <= int(w) <= 512:
+            raise ValueError(f"every hidden width must be an integer in 1..512, got {w!r}")
+    hidden = tuple(int(w) for w in hidden)
+    if isinstance(dropout, (int, float)):
+        dropout = (dropout,) * len(hidden)
+    dropout = tuple(float(p) for p in dropout)
+    if len(dropout) != len(hidden):
+        raise ValueError(f"dropout must be a scalar or one rate per hidden layer ({len(hidden)}), got {len(dropout)}")
+    for p in dropout:
+        if not 0.0 <= p < 1.0:
+            raise ValueError(f"every dropout rate must lie in [0, 1), got {p!r}")
+    return hidden, dropout
+
+
+class MLP(nn.Module):
+    """R.md:2549-2566. forward(x [B,input_dim]) -> logits [B,num_classes].
+
+    hidden: 1..4 hidden widths, each in 1..512; dropout: one rate in [0, 1) per hidden layer, or a scalar for all of them.  ``net`` is
+    the Sequential the reference would write for them: Linear, BatchNorm1d, ReLU and -- only where the rate is above 0 -- Dropout per
+    hidden layer, then the last Linear; the defaults are the reference's classifier with its net.0 ... net.7 state dict."""
+
+    def __init__(self, input_dim, num_classes=10, hidden=MLP_HIDDEN, dropout=MLP_DROPOUT):
         super().__init__()
         self.input_dim = int(input_dim)
         self.num_classes = int(num_classes)
-        self.net = nn.Sequential(
-            LinearParams(self.input_dim, 128),
-            BatchNorm1dParams(128),
-            _Marker("ReLU"),
-            _Marker("Dropout(0.3)"),
-            LinearParams(128, 64),
-            BatchNorm1dParams(64),
-            _Marker("ReLU"),
-            LinearParams(64, self.num_classes),
-        )
+        self.hidden, self.dropout = _mlp_arch(hidden, dropout)
+        layers, k = [], self.input_dim
+        for w, p in zip(self.hidden, self.dropout):
+            layers += [LinearParams(k, w), BatchNorm1dParams(w), _Marker("ReLU")]
+            if p > 0:
+                layers.append(_Marker(f"Dropout({p})"))
+            k = w
+        layers.append(LinearParams(k, self.num_classes))
+        self.net = nn.Sequential(*layers)
 
     def forward(self, x):
         from . import mlp_engine
         return mlp_engine.mlp_forward(self, x)
+
+
+def mlp_from_state_dict(sd, dropout=None):
+    """The classifier of a checkpoint (``MLP.state_dict()``, e.g. a saved MLP_GLOBAL_BEST.pt), with the state loaded: input_dim, hidden
+    and num_classes come from the Linear weight shapes, the places of the Dropout markers from the gaps in the ``net.<i>`` indices.  A
+    rate is not part of a checkpoint: 0.3 where a marker is, unless ``dropout`` (a rate per hidden layer) gives them -- it must agree
+    with the checkpoint about where a marker is."""
+    idx = sorted({int(k.split(".")[1]) for k in sd if k.startswith("net.") and k.endswith(".weight") and sd[k].dim() == 2})
+    if not idx or idx[0] != 0:
+        raise ValueError("not an MLP state dict: no net.0.weight of a Linear")
+    hidden = tuple(int(sd[f"net.{i}.weight"].shape[0]) for i in idx[:-1])
+    # a hidden layer takes 3 indices (Linear, BatchNorm1d, ReLU), 4 with a Dropout marker
+    gaps = [b - a for a, b in zip(idx[:-1], idx[1:])]
+    if not hidden or any(g not in (3, 4) for g in gaps):
+        raise ValueError(f"not an MLP state dict: Linear layers at net indices {idx}")
+    marked = [g == 4 for g in gaps]
+    if dropout is None:
+        rates = tuple(0.3 if m else 0.0 for m in marked)
+    else:
+        _, rates = _mlp_arch(hidden, dropout)
+        if [p > 0 for p in rates] != marked:
+            raise ValueError(f"dropout={dropout!r} disagrees with the checkpoint, whose Dropout markers follow hidden layers "
+                             f"{[l for l, m in enumerate(marked) if m]}")
+    clf = MLP(int(sd["net.0.weight"].shape[1]), int(sd[f"net.{idx[-1]}.weight"].shape[0]), hidden=hidden, dropout=rates)
+    clf.load_state_dict(sd)
+    return clf

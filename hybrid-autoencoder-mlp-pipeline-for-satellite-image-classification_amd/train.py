@@ -602,7 +602,8 @@ def extract_features(loader, encoder):
 
 # ------------------------------------------------------------------------------------------------ MLP
 def fit_mlp(train_dl, val_dl, test_dl, lr, input_dim=64, num_classes=10, num_epochs=30, weight_decay=1e-4, device="cuda",
-            clf=None, stepper=None, alias_best=True, verbose=True, log=print, class_weight=None, ignore_index=None, lr_schedule=None):
+            clf=None, stepper=None, alias_best=True, verbose=True, log=print, class_weight=None, ignore_index=None, lr_schedule=None,
+            hidden=None, dropout=None):
     """One learning rate of the reference's MLP loop (R.md:2619-2697): Adam(lr, weight_decay), CE, accuracy tracking,
     best-validation snapshot, test accuracy.
 
@@ -615,9 +616,13 @@ def fit_mlp(train_dl, val_dl, test_dl, lr, input_dim=64, num_classes=10, num_epo
     The accuracies stay correct / all samples; `stepper.eng.read_valid()` gives the labelled count of the last phase.
 
     lr_schedule: None or a factory of a `schedule` object, as for `fit_autoencoder` (observe() sees the validation LOSS).  The MLP's
-    one-kernel step has no gradient clipping; weight decay and dropout stay its regularisers."""
+    one-kernel step has no gradient clipping; weight decay and dropout stay its regularisers.
+
+    hidden / dropout: the architecture of the classifier built here (`MLP(hidden=, dropout=)`; None: the reference's (128, 64) with
+    Dropout(0.3) after the first layer).  A `clf` passed in brings its own."""
     if clf is None and stepper is None:
-        clf = MLP(input_dim=input_dim, num_classes=num_classes).to(device)
+        arch = {k: v for k, v in (("hidden", hidden), ("dropout", dropout)) if v is not None}
+        clf = MLP(input_dim=input_dim, num_classes=num_classes, **arch).to(device)
     if stepper is None:
         stepper = MLPStepper(clf, lr, weight_decay, max_batch=max(256, _first_batch_size(train_dl)),
                              class_weight=resolve_class_weight(class_weight, train_dl, num_classes), ignore_index=ignore_index)
@@ -667,17 +672,19 @@ def fit_mlp(train_dl, val_dl, test_dl, lr, input_dim=64, num_classes=10, num_epo
 
 def grid_search_mlp(train_dl, val_dl, test_dl, lr_values=(1e-6, 5e-6, 1e-5, 5e-5, 1e-4, 5e-4, 1e-3, 5e-3, 1e-2, 5e-2, 1e-1),
                     input_dim=64, num_epochs=30, out_dir="mlp_best", device="cuda", verbose=True, log=print, fit_fn=None,
-                    class_weight=None, ignore_index=None, num_classes=10, lr_schedule=None):
+                    class_weight=None, ignore_index=None, num_classes=10, lr_schedule=None, hidden=None, dropout=None, weight_decay=None):
     """The reference's MLP learning-rate grid (R.md:2611-2732); saves `out_dir/MLP_GLOBAL_BEST.pt`.  class_weight / ignore_index: the
     criterion of every learning rate, as for `fit_mlp` (a custom fit_fn sees them only when set); num_classes: classes of the classifier and
     of the weight vector (passed on when it is not 10).  lr_schedule: a schedule factory as for `fit_mlp`, a fresh instance per
-    learning rate (passed on only when set)."""
+    learning rate (passed on only when set).  hidden / dropout / weight_decay: the classifier's architecture (`MLP`) and Adam's L2
+    coefficient for every learning rate, each passed on only when set; `modules.mlp_from_state_dict` rebuilds the saved classifier."""
     os.makedirs(out_dir, exist_ok=True)
     fit_fn = fit_fn or fit_mlp
     crit = _criterion_kw(resolve_class_weight(class_weight, train_dl, num_classes), ignore_index)
     if int(num_classes) != 10:
         crit["num_classes"] = int(num_classes)          # a custom fit function sees it only when it is not the default
     crit.update(_training_kw(None, lr_schedule))
+    crit.update({k: v for k, v in (("hidden", hidden), ("dropout", dropout), ("weight_decay", weight_decay)) if v is not None})
     best = {"val": 0, "test": 0, "lr": None, "state": None, "curves": None}
     for lr in lr_values:
         if verbose:

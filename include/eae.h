@@ -467,6 +467,19 @@ typedef struct eae_mlp eae_mlp;
 #define EAE_MLP_NPARAMS 10
 int eae_mlp_layout(int input_dim, int num_classes, long long* param_off /*[11]*/, long long* bn_off /*[5]*/);
 int eae_mlp_create(int input_dim, int num_classes, int max_batch, eae_mlp** out);
+/* The classifier with a configurable architecture: n_hidden in 1..4 hidden layers of widths hidden[l] in 1..512, each
+ * Linear -> BatchNorm1d -> ReLU -> Dropout(p_drop[l]) (no Dropout where p_drop[l] == 0; rates in [0, 1)), then Linear(last, C).
+ * eae_mlp_layout_ex: param_off[4 * n_hidden + 3] = the offsets of W, b, gamma, beta of each hidden layer, the last W and b, then the
+ * total (each tensor rounded up to 4 floats); bn_off[2 * n_hidden + 1] = running mean, running variance of each layer, then the total.
+ * hidden = {128, 64} gives eae_mlp_layout's tables.  eae_mlp_create_ex yields the same opaque handle, served by the layer-table
+ * kernel whatever the architecture (eae_mlp_create keeps the fixed 128 / 64 kernel); every eae_mlp_* entry point below and
+ * eae_scene_classify* accept it with these differences: bn_nbt has one word per hidden layer, and drop_mask holds the keep masks
+ * [B][hidden[l]] of the layers with p_drop[l] > 0, in layer order, back to back.  Hidden layer l draws its mask from Philox4x32-10 with
+ * key (seed lo, seed hi) and counter (b * hidden[l] + j, step lo, step hi, 0x9E3779B9 + l).  Arguments out of range: EAE_ERR_ARG,
+ * before anything is allocated. */
+int eae_mlp_layout_ex(int input_dim, int num_classes, int n_hidden, const int* hidden, long long* param_off, long long* bn_off);
+int eae_mlp_create_ex(int input_dim, int num_classes, int n_hidden, const int* hidden, const float* p_drop, int max_batch,
+                      eae_mlp** out);
 int eae_mlp_destroy(eae_mlp* m);
 int eae_mlp_bind(eae_mlp* m, float* params, float* grads, float* adam_m, float* adam_v, float* bn_running,
                  long long* bn_nbt);
