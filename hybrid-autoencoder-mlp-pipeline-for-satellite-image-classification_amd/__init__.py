@@ -22,6 +22,10 @@ from .cluster import kmeans_fit, kmeans_predict, kmeans_init, cluster_scene, KMe
 from .report import cluster_class_table, name_clusters  # noqa: F401
 from . import neighbors  # noqa: F401
 from .neighbors import knn_search, knn_classify, similar_windows, knn_classify_scene, KNNResult  # noqa: F401
+from . import validity  # noqa: F401
+from .validity import class_distance_sums, silhouette_samples, silhouette_score, class_distance_matrix  # noqa: F401
+from .validity import davies_bouldin_score, calinski_harabasz_score, select_k  # noqa: F401
+from .report import separation_table  # noqa: F401
 from . import postprocess  # noqa: F401
 from .postprocess import majority_filter, label_regions, region_table, sieve  # noqa: F401
 
@@ -33,4 +37,6 @@ __all__ = ["Encoder", "Decoder", "SupervisedAutoencoder", "MLP", "mlp_from_state
            "window_schedule", "drawable_windows", "class_weights", "scene_confusion", "evaluate_scene", "block_split", "footprint_mask",
            "confusion_metrics", "classification_report_from_confusion", "kmeans_fit", "kmeans_predict", "kmeans_init", "cluster_scene",
            "KMeansResult", "cluster_class_table", "name_clusters", "knn_search", "knn_classify", "similar_windows", "knn_classify_scene",
-           "KNNResult", "majority_filter", "label_regions", "region_table", "sieve"]
+           "KNNResult", "majority_filter", "label_regions", "region_table", "sieve", "class_distance_sums", "silhouette_samples",
+           "silhouette_score", "class_distance_matrix", "davies_bouldin_score", "calinski_harabasz_score", "select_k",
+           "separation_table"]

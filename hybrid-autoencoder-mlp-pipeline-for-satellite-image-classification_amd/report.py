@@ -151,6 +151,49 @@ def name_clusters(table):
     return torch.where(table.sum(dim=1) > 0, best, -1)
 
 
+def separation_table(matrix, per_class, names=None, digits=4):
+    """Text table of how the classes sit in the latent space, one line per class: its silhouette (`validity.silhouette_score`'s
+    per_class), its mean intra-class distance (the diagonal of `validity.class_distance_matrix`), the nearest other class by mean
+    distance, that distance, and the ratio inter / intra (above 1: the class is closer to itself than to its nearest neighbour).
+    matrix [K, K] and per_class [K] are NumPy arrays or tensors; names: K strings (default: the class ids).  A class whose row is NaN
+    (empty) has '-' in every column, as has a figure that does not exist (a class of one row has no intra-class distance)."""
+    if hasattr(matrix, "detach"):
+        matrix = matrix.detach().cpu().numpy()
+    if hasattr(per_class, "detach"):
+        per_class = per_class.detach().cpu().numpy()
+    matrix = np.asarray(matrix, dtype=np.float64)
+    per_class = np.asarray(per_class, dtype=np.float64).ravel()
+    if matrix.ndim != 2 or matrix.shape[0] != matrix.shape[1] or matrix.shape[0] < 1:
+        raise ValueError("matrix must be a square [K, K] matrix")
+    k = matrix.shape[0]
+    if per_class.shape[0] != k:
+        raise ValueError(f"per_class must have {k} entries, got {per_class.shape[0]}")
+    names = [str(c) for c in range(k)] if names is None else [str(n) for n in names]
+    if len(names) != k:
+        raise ValueError(f"names must have {k} entries, got {len(names)}")
+    width = max(max(len(n) for n in names), len("class"))
+
+    def num(v):
+        return "{:>10}".format("-") if not np.isfinite(v) else "{:>10.{d}f}".format(v, d=digits)
+
+    head = "{:>{w}s} ".format("class", w=width) + " {:>10} {:>10} {:>{w}s} {:>10} {:>10}".format("silhouette", "intra", "nearest", "inter", "ratio",
+                                                                                              w=width)
+    lines = [head, ""]
+    for a in range(k):
+        inter = matrix[a].copy()
+        inter[a] = np.nan
+        if np.isfinite(inter).any():
+            b = int(np.nanargmin(inter))                       # the first minimum: the lowest class id on a tie
+            near, dist = names[b], inter[b]
+        else:
+            near, dist = "-", np.nan
+        intra = matrix[a, a]
+        ratio = dist / intra if np.isfinite(dist) and np.isfinite(intra) and intra > 0 else np.nan
+        lines.append("{:>{w}s} ".format(names[a], w=width) + " " + num(per_class[a]) + " " + num(intra) + " {:>{w}s}".format(near, w=width)
+                     + " " + num(dist) + " " + num(ratio))
+    return "\n".join(lines) + "\n"
+
+
 def classification_report_from_confusion(cm, digits=4, num_classes=None):
     """`classification_report`'s table from a confusion matrix (`confusion_metrics`: the same matrix forms)."""
     return _report_text(confusion_metrics(cm, num_classes), digits)

@@ -779,6 +779,34 @@ int eae_knn_slices(long long Nq, long long M, int L, int k);
 int eae_knn_search(void* stream, const float* q, long long Nq, const float* bank, long long M, int L, int k, long long self_offset,
                    long long* idx, float* dist, void* workspace, long long workspace_bytes);
 
+/* ------------------------------------------------------------------ latent validity ---------------- */
+/* Sums of distances from query rows to the bank rows of every class (no reference counterpart): what the silhouette coefficient and a
+ * table of class separation are made of.  q [Nq][L] and bank [M][L] fp32 row-major; the bank is SORTED BY CLASS: rows seg[c] ..
+ * seg[c+1]-1 belong to class c, seg int64 [K+1] on the device with 0 <= seg[0] <= ... <= seg[K] <= M (values outside [0, M] are
+ * clamped on the device: nothing outside the bank is read).  Rows outside [seg[0], seg[K]) belong to no class and are never read into
+ * a sum, whatever they hold.  1 <= L <= 256, 1 <= K <= 256, 1 <= Nq, M < 2^31, metric 0 (Euclidean) or 1 (squared Euclidean);
+ * anything else, a NULL q, bank, seg or sums, or a workspace that is NULL or too small where a non-zero size is required is
+ * EAE_ERR_ARG, and nothing is launched.  Stateless; nothing synchronises the host.
+ *
+ * sums[n][c] = sum over the rows m of class c, m != self_pos[n], of d(q_n, b_m), fp32 [Nq][K].
+ * d^2 = max(0, fma(-2, q_n . b_m, ||b_m||^2) + ||q_n||^2), eae_knn_search's expression: the dot product on the f32-input MFMA (a
+ * k-ordered fma chain over L), the norms sequential fma chains; d = sqrtf(d^2) under metric 0, d = d^2 under metric 1.  Each lane of
+ * the kernel adds its distances to one fp32 running sum in a fixed order, partial sums are added in one fixed order, and there are
+ * no float atomics: the result is bitwise identical from run to run for the same arguments.  An empty class gives 0.
+ * self_pos (device int64 [Nq], or NULL for none): the bank row, in the sorted order, that is query n itself and is left out of its
+ * sums; -1 for none.
+ * A query row that holds a NaN or an Inf gets a row of NaN.  Bank rows inside a segment must be finite (a precondition, as for
+ * eae_kmeans_update; such a row would turn the sums of its class into NaN or Inf).  UNDEFINED: finite rows whose squared norm
+ * overflows fp32.
+ * Geometry: a function of (Nq, M, L, K) alone -- seg and self_pos are device data.  No Nq x M array is written anywhere.  When the
+ * query tiles alone cannot fill the device a class's segment is walked by S > 1 workgroups, whose partial sums go to `workspace`
+ * (eae_class_dist_workspace_bytes(...) bytes of device memory, contents irrelevant on entry) and are added by a second kernel in
+ * ascending slice order; otherwise eae_class_dist_workspace_bytes is 0 and workspace may be NULL.
+ * eae_class_dist_workspace_bytes is host only and returns < 0 on bad arguments. */
+long long eae_class_dist_workspace_bytes(long long Nq, long long M, int L, int K);
+int eae_class_dist_sums(void* stream, const float* q, long long Nq, const float* bank, long long M, int L, const long long* seg, int K,
+                        const long long* self_pos, int metric, float* sums, void* workspace, long long workspace_bytes);
+
 /* ------------------------------------------------------------------ map post-processing ------------ */
 /* Cleaning a class map on the device (no reference counterpart): majority filter, connected regions, their table, and a sieve.  A map
  * is a contiguous int64 [H][W] device array as eae_scene_classify / eae_scene_blend write it: a value in [0, K) is a class, K in 1..64,
