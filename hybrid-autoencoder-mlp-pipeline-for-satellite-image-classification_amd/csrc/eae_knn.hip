@@ -1,9 +1,9 @@
 // Latent neighbours (include/eae.h, "latent neighbours"): the k nearest bank rows of every query row, both fp32,
 // scored in exact fp32 on the f32-input MFMA (v_mfma_f32_32x32x2_f32: a k-ordered fma chain) as eae_kmeans_assign scores centroids:
 //   score(n, m) = fma(-2, q_n . b_m, ||b_m||^2), the norm a sequential fma chain -- a function of the two rows alone.
-//   search: D[m][n] = b_m . q_n with the BANK rows as the A operand, so that a lane owns one query (its column of D).  The bank streams
-//           through LDS in 64-row tiles; every query keeps a list of its k best (score, row) pairs, sorted by that pair, in LDS, and a
-//           lane touches it only for a score that beats the list's last entry.  No Nq x M array is written.
+//   search: the bank streams through eae_latent_tile.hip.h's tile body in 64-row tiles (a lane owns one query); every query keeps a
+//           list of its k best (score, row) pairs, sorted by that pair, in LDS, and a lane touches it only for a score that beats the
+//           list's last entry.  No Nq x M array is written.
 //   merge:  with few queries the bank is cut into S slices, one workgroup per (query tile, slice) writes its list to the caller's
 //           workspace, and a second kernel merges the S sorted lists of a query by the same order.  The order is total (a bank row
 //           appears once), so the result is bitwise the same for every S.
@@ -11,15 +11,10 @@
 // showed write-through to gain).  No float atomics.
 #include "eae_internal.h"
 #include "eae_common.hip.h"
-#include "eae_latent.hip.h"
+#include "eae_latent_tile.hip.h"
 
 namespace {
 
-constexpr int KN_NT = 256;          // threads per workgroup: 4 waves
-constexpr int KN_QT = 128;          // queries per workgroup tile, 32 per wave
-constexpr int KN_BT = 64;           // bank rows per LDS tile: two 32-row MFMA tiles
-constexpr int KN_LC = 64;           // columns staged per pass
-constexpr int KN_LDS = KN_LC + 4;   // LDS row stride in floats (see lds_col)
 constexpr int KN_MAXK = 32;
 constexpr int KN_MAXS = 512;        // most bank slices
 constexpr int KN_EMPTY = 0x7fffffff;    // row of an empty list slot: (+Inf, KN_EMPTY) is the greatest pair
@@ -27,190 +22,57 @@ constexpr int KN_EMPTY = 0x7fffffff;    // row of an empty list slot: (+Inf, KN_
 // (s, m) < (ps, pm), lexicographic; false when s is a NaN.  Without short-circuit branches: it sits in unrolled code.
 __device__ __forceinline__ bool pair_less(float s, int m, float ps, int pm) { return (s < ps) | ((s == ps) & (m < pm)); }
 
-// __syncthreads() out of builtins: the header's function is not inlined into a kernel that carries a target attribute (EAE_NO_PK), and
-// a call inside the tile loop costs the kernel its register allocation
-__device__ __forceinline__ void kn_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-// `row_sq_chain`, NaN unless finite (a row with a NaN or an Inf, or whose squared norm overflows)
-__device__ __forceinline__ float row_norm2(const float* p, int L) {
-  const float s = row_sq_chain(p, L);
-  return s - s == 0.f ? s : __builtin_nanf("");
-}
-
 struct SearchArgs {
-  const float* q; const float* bank; long long Nq, M; int L, k; long long self_offset;
+  TileSrc src; long long M; int k; long long self_offset;
   long long* idx; float* dist;      // S == 1: the outputs
   int2* part;                       // S > 1: [S][Nq][k] (score bits, row)
-  long long rows_per_slice;         // a multiple of KN_BT
-  int qvec, bvec;                   // 16-byte loads of q / bank: L % 4 == 0 and an aligned base
+  long long rows_per_slice;         // a multiple of LT_BT
 };
-
-// A staged row holds 64 columns de-interleaved: the 32 even columns, then the 32 odd ones (then 4 floats of padding).  Lane (r, h) of
-// an MFMA step takes column 2 j + h, so a lane's operands of four consecutive steps are one 16-byte LDS read; at a row stride of 68
-// floats the 16 lanes a ds_read_b128 serves together (16 different rows) cover the 64 banks once.
-__device__ __forceinline__ int lds_col(int col) { return (col & 1) * 32 + (col >> 1); }
-
-// rows [row0, row0 + 16 N) x columns [l0, l0 + 64) of src [nrows][L] into registers with 16-byte loads (L % 4 == 0 and an aligned
-// base), zero beyond nrows and beyond L
-template <int N>
-__device__ __forceinline__ void load_rows(float4 (&v)[N], const float* src, long long row0, long long nrows, int L, int l0, int lw, int tid) {
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    const int e = tid + KN_NT * i, row = e >> 4, col = (e & 15) * 4;
-    v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (row0 + row < nrows && col < lw) v[i] = *reinterpret_cast<const float4*>(src + (size_t)(row0 + row) * L + l0 + col);
-  }
-}
-
-// ... and from the registers into dst [16 N][68]
-template <int N>
-__device__ __forceinline__ void store_rows(float* dst, const float4 (&v)[N], int tid) {
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    const int e = tid + KN_NT * i, row = e >> 4, col = (e & 15) * 4;
-    float* d = dst + row * KN_LDS + (col >> 1);
-    *reinterpret_cast<float2*>(d) = make_float2(v[i].x, v[i].z);
-    *reinterpret_cast<float2*>(d + 32) = make_float2(v[i].y, v[i].w);
-  }
-}
-
-// the same rows straight into dst, float by float: any L, any alignment
-template <int ROWS>
-__device__ __forceinline__ void stage_scalar(float* dst, const float* src, long long row0, long long nrows, int L, int l0, int lw, int tid) {
-#pragma unroll 4
-  for (int i = 0; i < ROWS * KN_LC / KN_NT; ++i) {
-    const int e = tid + KN_NT * i, row = e >> 6, col = e & 63;
-    float v = 0.f;
-    if (row0 + row < nrows && col < lw) v = src[(size_t)(row0 + row) * L + l0 + col];
-    dst[row * KN_LDS + lds_col(col)] = v;
-  }
-}
-
-// s continued over the 64 staged columns of a row in ascending column order (the zeros beyond L change nothing: fma(0, 0, s) = s)
-__device__ __forceinline__ float chain64(const float* row, float s) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float4 e = *reinterpret_cast<const float4*>(row + 4 * j), o = *reinterpret_cast<const float4*>(row + 32 + 4 * j);
-    s = __builtin_fmaf(e.x, e.x, s); s = __builtin_fmaf(o.x, o.x, s);
-    s = __builtin_fmaf(e.y, e.y, s); s = __builtin_fmaf(o.y, o.y, s);
-    s = __builtin_fmaf(e.z, e.z, s); s = __builtin_fmaf(o.z, o.z, s);
-    s = __builtin_fmaf(e.w, e.w, s); s = __builtin_fmaf(o.w, o.w, s);
-  }
-  return s;
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // search.  Workgroup (tile, slice): queries 128 tile .. + 127 (wave w owns 32 w .. 32 w + 31 of them) against the bank rows of the
-// slice, in 64-row tiles.  Per bank tile the columns are walked in passes of 64: the bank tile's columns are staged in LDS (and the
-// queries' too -- once per workgroup when L <= 64); the next pass's bank columns are loaded into registers before this pass's MFMAs
-// and written to LDS after them.  Wave 0 continues ||b||^2 of the tile's rows from the staged columns (thread = row, ascending l: the
-// chain does not depend on the pass width), waves 0 and 1 do the same for ||q||^2 during the first bank tile, and every wave that has
-// a query runs one MFMA per 32-row half and pair of columns.  After the last pass a lane holds 32 scores of its query; the two lanes
-// of a query take turns (h = 0, then h = 1) at the query's list.  A bank row that is not finite, lies beyond the slice or is the
-// query's excluded row scores NaN and never enters a list.
+// slice, in 64-row tiles (pair_tile).  After a tile a lane holds 32 dot products, then scores, of its query; the two lanes of a query
+// take turns (h = 0, then h = 1) at the query's list.  A bank row that is not finite, lies beyond the slice or is the query's
+// excluded row scores NaN and never enters a list.
 // ---------------------------------------------------------------------------------------------------------------
-__global__ EAE_NO_PK __launch_bounds__(KN_NT, 2) void knn_search_kernel(SearchArgs a) {
+__global__ EAE_NO_PK __launch_bounds__(LT_NT, 2) void knn_search_kernel(SearchArgs a) {
   extern __shared__ __attribute__((aligned(16))) float kn_lds[];
-  float* qs = kn_lds;                                  // [128][68]
-  float* bs = qs + KN_QT * KN_LDS;                     // [64][68]
-  float* bn = bs + KN_BT * KN_LDS;                     // [64]   ||b||^2 of the tile's rows, NaN for a row that cannot be returned
-  float* qn = bn + KN_BT;                              // [128]  ||q||^2, NaN for a query that is not finite
-  float* ls = qn + KN_QT;                              // [128][k] list scores, ascending
-  int* li = reinterpret_cast<int*>(ls + KN_QT * a.k);  // [128][k] list rows
+  const TileLds lds(kn_lds);                           // bn: NaN for a row that cannot be returned (pair_tile<true>)
+  float* qn = lds.qn;
+  const float* bn = lds.bn;
+  float* ls = kn_lds + LT_FLOATS;                      // [128][k] list scores, ascending
+  int* li = reinterpret_cast<int*>(ls + LT_QT * a.k);  // [128][k] list rows
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
-  const int L = a.L, k = a.k;
-  const long long n0 = (long long)blockIdx.x * KN_QT;
+  const int k = a.k;
+  const long long Nq = a.src.Nq;
+  const long long n0 = (long long)blockIdx.x * LT_QT;
   const long long mb = (long long)blockIdx.y * a.rows_per_slice;
   const long long me = mb + a.rows_per_slice < a.M ? mb + a.rows_per_slice : a.M;
-  const int npass = (L + KN_LC - 1) / KN_LC;
 
-  for (int e = tid; e < KN_QT * k; e += KN_NT) { ls[e] = __builtin_inff(); li[e] = KN_EMPTY; }
-  if (tid < KN_QT) qn[tid] = __builtin_nanf("");
-  kn_barrier();
+  for (int e = tid; e < LT_QT * k; e += LT_NT) { ls[e] = __builtin_inff(); li[e] = KN_EMPTY; }
+  if (tid < LT_QT) qn[tid] = __builtin_nanf("");
+  lt_barrier();
 
   const int qrow = wave * 32 + r;
   const long long n = n0 + qrow;
   const long long excl = a.self_offset >= 0 ? n + a.self_offset : -1;
-  const bool busy = n0 + wave * 32 < a.Nq;                     // the wave has a query
+  const bool busy = n0 + wave * 32 < Nq;                       // the wave has a query
   float* myls = ls + qrow * k;
   int* myli = li + qrow * k;
   float qnrm = 0.f;                                            // waves 0 and 1: thread = query of the tile
+  float4 pre[LT_BT / 16];                                      // the bank columns of the coming pass
+  tile_prefetch(pre, a.src, mb, me, tid);
 
-  float4 pre[KN_BT / 16];                                      // the bank columns of the coming pass (16-byte loads only)
-  if (a.bvec) load_rows(pre, a.bank, mb, me, L, 0, L < KN_LC ? L : KN_LC, tid);
-
-  for (long long m0 = mb; m0 < me; m0 += KN_BT) {
-    f32x16 acc[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
-    float nrm = 0.f;                                           // wave 0: thread = bank row of the tile
-
-    for (int p = 0; p < npass; ++p) {
-      const int l0 = p * KN_LC;
-      const int lw = L - l0 < KN_LC ? L - l0 : KN_LC;          // real columns of this pass
-      kn_barrier();                                         // the previous pass (or tile, or the set-up) is done with the LDS
-      const bool newq = npass > 1 || m0 == mb;
-      if (newq && a.qvec) {
-        float4 qv[KN_QT / 16];
-        load_rows(qv, a.q, n0, a.Nq, L, l0, lw, tid);
-        store_rows(qs, qv, tid);
-      } else if (newq) {
-        stage_scalar<KN_QT>(qs, a.q, n0, a.Nq, L, l0, lw, tid);
-      }
-      if (a.bvec) store_rows(bs, pre, tid);
-      else stage_scalar<KN_BT>(bs, a.bank, m0, me, L, l0, lw, tid);
-      kn_barrier();
-      if (a.bvec) {                                            // the coming pass: the next columns, or the next tile's first
-        const long long m1 = p + 1 < npass ? m0 : m0 + KN_BT;
-        const int l1 = p + 1 < npass ? l0 + KN_LC : 0;
-        if (m1 < me) load_rows(pre, a.bank, m1, me, L, l1, L - l1 < KN_LC ? L - l1 : KN_LC, tid);
-      }
-      if (wave == 0) {
-        nrm = chain64(bs + lane * KN_LDS, nrm);
-        if (p == npass - 1) bn[lane] = (m0 + lane < me && nrm - nrm == 0.f) ? nrm : __builtin_nanf("");
-      }
-      if (m0 == mb && tid < KN_QT) {
-        qnrm = chain64(qs + tid * KN_LDS, qnrm);
-        if (p == npass - 1 && n0 + tid < a.Nq && qnrm - qnrm == 0.f) qn[tid] = qnrm;
-      }
-      if (busy) {
-        const float* zrow = qs + qrow * KN_LDS + h * 32;
-        const float* crow = bs + r * KN_LDS + h * 32;
-        const int nj = ((lw + 1) / 2 + 3) >> 2;                // groups of four column pairs; the last one may run into the zeros
-        // the next group's operands are read while this group's MFMAs run (the read after the last group stays inside the row)
-        float4 nb = *reinterpret_cast<const float4*>(zrow);
-        float4 na0 = *reinterpret_cast<const float4*>(crow);
-        float4 na1 = *reinterpret_cast<const float4*>(crow + 32 * KN_LDS);
-        for (int j = 0; j < nj; ++j) {
-          const float4 b = nb, a0 = na0, a1 = na1;
-          nb = *reinterpret_cast<const float4*>(zrow + 4 * j + 4);
-          na0 = *reinterpret_cast<const float4*>(crow + 4 * j + 4);
-          na1 = *reinterpret_cast<const float4*>(crow + 32 * KN_LDS + 4 * j + 4);
-          acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, b.x, acc[0], 0, 0, 0);
-          acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.x, b.x, acc[1], 0, 0, 0);
-          acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, b.y, acc[0], 0, 0, 0);
-          acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.y, b.y, acc[1], 0, 0, 0);
-          acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.z, b.z, acc[0], 0, 0, 0);
-          acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.z, b.z, acc[1], 0, 0, 0);
-          acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.w, b.w, acc[0], 0, 0, 0);
-          acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.w, b.w, acc[1], 0, 0, 0);
-        }
-      }
-    }
-    kn_barrier();                                           // bn is complete
+  for (long long m0 = mb; m0 < me; m0 += LT_BT) {
+    f32x16 acc[2];                                             // the tile's dot products, then its scores
+    pair_tile<true>(acc, pre, qnrm, a.src, lds, n0, m0, me, m0 + LT_BT, m0 == mb, busy, tid);
     if (!busy) continue;
 
     // The lane's 32 scores of this tile.  Bit c = 16 t + i of `cand`: score c beats the last entry of the query's list as it stands
     // before this tile (the entry only falls: a superset of what will enter).  Then the two lanes of a query take turns at the list,
     // h = 0 first (one wave: its LDS accesses stay in order).
     const int mi0 = (int)m0;                                   // m0 + row < M < 2^31 wherever bn[row] is a number
-    const int erow = excl >= m0 && excl < m0 + KN_BT ? (int)(excl - m0) : -1;
+    const int erow = excl >= m0 && excl < m0 + LT_BT ? (int)(excl - m0) : -1;
     unsigned cand = 0;
     {
       const float thr = myls[k - 1];
@@ -258,13 +120,13 @@ __global__ EAE_NO_PK __launch_bounds__(KN_NT, 2) void knn_search_kernel(SearchAr
   for (int e = lane; e < 32 * k; e += 64) {
     const int qq = e / k, j = e - qq * k, lrow = wave * 32 + qq;
     const long long nn = n0 + lrow;
-    if (nn >= a.Nq) continue;
+    if (nn >= Nq) continue;
     const float s = ls[lrow * k + j];
     const int m = li[lrow * k + j];
     if (a.part) {
       int2 e;
       e.x = __builtin_bit_cast(int, s); e.y = m;
-      a.part[((size_t)blockIdx.y * a.Nq + nn) * k + j] = e;
+      a.part[((size_t)blockIdx.y * Nq + nn) * k + j] = e;
     } else {
       const float nq = qn[lrow];
       const bool none = m == KN_EMPTY || !(nq == nq);
@@ -285,7 +147,7 @@ __global__ EAE_NO_PK __launch_bounds__(64) void knn_merge_kernel(MergeArgs a) {
   const long long n = blockIdx.x;
   for (int s = lane; s < S; s += 64) head[s] = 0;
   if (lane == 0) qnorm = row_norm2(a.q + (size_t)n * a.L, a.L);
-  kn_barrier();
+  lt_barrier();
   const float nq = qnorm;
   const bool bad = !(nq == nq);
   for (int j = 0; j < k; ++j) {
@@ -311,7 +173,7 @@ __global__ EAE_NO_PK __launch_bounds__(64) void knn_merge_kernel(MergeArgs a) {
       a.idx[(size_t)n * k + j] = none ? -1 : (long long)bm;
       if (a.dist) a.dist[(size_t)n * k + j] = none ? __builtin_nanf("") : fmaxf(bsc + nq, 0.f);
     }
-    kn_barrier();
+    lt_barrier();
   }
 }
 
@@ -325,8 +187,8 @@ int knn_dims_ok(long long Nq, long long M, int L, int k) {
 struct KnnPlan { long long tiles, rows_per_slice; int S; };
 KnnPlan knn_plan(long long Nq, long long M) {
   KnnPlan p;
-  p.tiles = (Nq + KN_QT - 1) / KN_QT;
-  const long long nb = (M + KN_BT - 1) / KN_BT;
+  p.tiles = (Nq + LT_QT - 1) / LT_QT;
+  const long long nb = (M + LT_BT - 1) / LT_BT;
   long long want = p.tiles >= 256 ? 1 : 512 / p.tiles;
   const long long most = (nb + 3) / 4;
   if (want > most) want = most;
@@ -334,7 +196,7 @@ KnnPlan knn_plan(long long Nq, long long M) {
   if (want < 1) want = 1;
   const long long tps = (nb + want - 1) / want;                // bank tiles per slice
   p.S = (int)((nb + tps - 1) / tps);                           // no slice is empty
-  p.rows_per_slice = tps * KN_BT;
+  p.rows_per_slice = tps * LT_BT;
   return p;
 }
 
@@ -363,11 +225,10 @@ extern "C" int eae_knn_search(void* stream, const float* q, long long Nq, const 
     return eae_set_error(EAE_ERR_ARG, "knn_search: the workspace is NULL or smaller than eae_knn_workspace_bytes");
   EAE_NO_GROUP("knn_search_kernel");
   const hipStream_t st = (hipStream_t)stream;
-  const SearchArgs a = {q, bank, Nq, M, L, k, self_offset, idx, dist, p.S > 1 ? (int2*)workspace : nullptr, p.rows_per_slice,
-                        (L & 3) == 0 && ((uintptr_t)q & 15) == 0, (L & 3) == 0 && ((uintptr_t)bank & 15) == 0};
-  const size_t lds = ((size_t)(KN_QT + KN_BT) * KN_LDS + KN_BT + KN_QT + (size_t)KN_QT * k * 2) * sizeof(float);
-  EAE_HIP(eae_smem_attr((const void*)knn_search_kernel, (size_t)((KN_QT + KN_BT) * KN_LDS + KN_BT + KN_QT + KN_QT * KN_MAXK * 2) * sizeof(float)));
-  hipLaunchKernelGGL(knn_search_kernel, dim3((unsigned)p.tiles, (unsigned)p.S), dim3(KN_NT), lds, st, a);
+  const SearchArgs a = {tile_src(q, Nq, bank, L), M, k, self_offset, idx, dist, p.S > 1 ? (int2*)workspace : nullptr, p.rows_per_slice};
+  const size_t lds = ((size_t)LT_FLOATS + (size_t)LT_QT * k * 2) * sizeof(float);
+  EAE_HIP(eae_smem_attr((const void*)knn_search_kernel, (size_t)(LT_FLOATS + LT_QT * KN_MAXK * 2) * sizeof(float)));
+  hipLaunchKernelGGL(knn_search_kernel, dim3((unsigned)p.tiles, (unsigned)p.S), dim3(LT_NT), lds, st, a);
   EAE_LAUNCH_CHECK();
   if (p.S > 1) {
     const MergeArgs g = {q, Nq, L, k, p.S, (const int2*)workspace, idx, dist};

@@ -11,7 +11,7 @@ SHAPES = [(1, 1, 1, 1), (129, 33, 3, 32),
           (300, 1031, 256, 7), (257, 300, 128, 32), (1000, 4096, 64, 10),
           (33, 70001, 64, 10),           # long bank, few queries: the bank is cut into slices
           (1, 5000, 64, 10)]
-QUERY_TILE = 128                         # queries per workgroup of knn_search_kernel (KN_QT)
+QUERY_TILE = 128                         # queries per workgroup of knn_search_kernel (LT_QT)
 BOUNDARY_SHAPES = [(QUERY_TILE - 1, 200, 20, 5), (QUERY_TILE, 200, 20, 5), (QUERY_TILE + 1, 200, 20, 5),
                    (516 * QUERY_TILE - 48, 40, 8, 3)]      # 516 query tiles: more than 512 workgroups, more than one round of the device
 

@@ -27,14 +27,24 @@ def _data(nq, m, width, seed):
     return rng.standard_normal((nq, width)).astype(np.float32), rng.standard_normal((m, width)).astype(np.float32)
 
 
-def _c_search(q, bank, k, self_offset=-1, want_dist=True, ws_bytes=None, ws_null=False):
+def _dev(a, offset=False):
+    """a on the device: a fresh allocation (16-byte aligned), or the same rows as a view that starts 4 bytes into one"""
+    if not offset:
+        return torch.from_numpy(a).cuda()
+    t = torch.empty(a.size + 1, dtype=torch.float32, device="cuda")[1:].view(a.shape)
+    t.copy_(torch.from_numpy(a))
+    assert t.data_ptr() % 16 == 4 and t.is_contiguous()
+    return t
+
+
+def _c_search(q, bank, k, self_offset=-1, want_dist=True, ws_bytes=None, ws_null=False, q_offset=False, bank_offset=False):
     """One search call on poisoned outputs and a workspace of NaN bit patterns: (rc, idx, dist) as NumPy."""
     nq, width = q.shape
     m = bank.shape[0]
     lib = _lib.load()
     need = lib.eae_knn_workspace_bytes(nq, m, width, k)
     assert need >= 0
-    qt, bt = torch.from_numpy(q).cuda(), torch.from_numpy(bank).cuda()
+    qt, bt = _dev(q, q_offset), _dev(bank, bank_offset)
     idx = torch.full((nq, k), POISON, dtype=torch.int64, device="cuda")
     dist = torch.full((nq, k), float(POISON), dtype=torch.float32, device="cuda") if want_dist else None
     nb = need if ws_bytes is None else ws_bytes
@@ -75,6 +85,21 @@ def test_the_shapes_cover_both_plans():
     lib = _lib.load()
     s = [lib.eae_knn_slices(*shape) for shape in SHAPES]
     assert min(s) == 1 and max(s) > 1 and lib.eae_knn_slices(33, 70001, 64, 10) > 1
+
+
+@pytest.mark.parametrize("nq,m,width,k,slices", [(130, 600, 68, 5, 3), (40, 200, 8, 3, 1)])
+def test_the_result_does_not_depend_on_the_alignment_of_the_rows(nq, m, width, k, slices):
+    """Rows of a width that is a multiple of 4 are staged with 16-byte loads from a 16-byte aligned base and float by float from any
+    other, queries and bank each for itself: the four combinations give the same bits (staging changes no arithmetic).  The first
+    shape has two query tiles (the second of 2 rows), ten bank tiles (the last of 24 rows) in three slices and two column passes
+    (the second 4 wide); the second one pass, one slice and queries that are staged once."""
+    lib = _lib.load()
+    assert lib.eae_knn_slices(nq, m, width, k) == slices and (lib.eae_knn_workspace_bytes(nq, m, width, k) > 0) == (slices > 1)
+    q, bank = _data(nq, m, width, seed=nq + m + width + k)
+    aligned = _search(q, bank, k)
+    accept(q, bank, k, *aligned)
+    for q_offset, bank_offset in ((False, True), (True, False), (True, True)):
+        assert _same(_search(q, bank, k, q_offset=q_offset, bank_offset=bank_offset), aligned), (q_offset, bank_offset)
 
 
 # ---------------------------------------------------------------------------------------------------- 2. exact order of equal scores

@@ -21,14 +21,24 @@ pytestmark = pytest.mark.gpu
 POISON = -7.0
 
 
-def _c_sums(q, bank, seg, self_pos, metric, ws_bytes=None, ws_null=False):
+def _dev(a, offset=False):
+    """a on the device: a fresh allocation (16-byte aligned), or the same rows as a view that starts 4 bytes into one"""
+    if not offset:
+        return torch.from_numpy(np.array(a)).cuda()
+    t = torch.empty(a.size + 1, dtype=torch.float32, device="cuda")[1:].view(a.shape)
+    t.copy_(torch.from_numpy(np.array(a)))
+    assert t.data_ptr() % 16 == 4 and t.is_contiguous()
+    return t
+
+
+def _c_sums(q, bank, seg, self_pos, metric, ws_bytes=None, ws_null=False, q_offset=False, bank_offset=False):
     """One call on a poisoned output and a workspace of NaN bit patterns: (rc, sums as NumPy)."""
     nq, width = q.shape
     m, k = bank.shape[0], len(seg) - 1
     lib = _lib.load()
     need = lib.eae_class_dist_workspace_bytes(nq, m, width, k)
     assert need >= 0
-    qt, bt = torch.from_numpy(np.array(q)).cuda(), torch.from_numpy(np.array(bank)).cuda()
+    qt, bt = _dev(q, q_offset), _dev(bank, bank_offset)
     st = torch.from_numpy(np.array(seg)).cuda()
     sp = None if self_pos is None else torch.from_numpy(np.array(self_pos)).cuda()
     sums = torch.full((nq, k), POISON, dtype=torch.float32, device="cuda")
@@ -65,6 +75,26 @@ def test_integer_sums_are_exact(shape):
     assert np.array_equal(_bits(got), _bits(_sums(q, bank, seg, self_pos, 1)))                 # two runs, the same bits
     if shape[0] >= 3:
         assert np.isnan(got[1]).all() and not np.isnan(np.delete(got, 1, axis=0)).any()
+
+
+@pytest.mark.parametrize("shape,cut", [((130, 600, 68, 3), True), ((40, 200, 8, 3), False)], ids=str)
+def test_the_sums_do_not_depend_on_the_alignment_of_the_rows(shape, cut):
+    """Rows of a width that is a multiple of 4 are staged with 16-byte loads from a 16-byte aligned base and float by float from any
+    other, queries and bank each for itself: the four combinations give the same bits (staging changes no arithmetic), under both
+    metrics and with a self row for every second query.  The first shape has two query tiles (the second of 2 rows), a class of
+    nine tiles walked in three slices and two column passes (the second 4 wide); the second one pass, one slice and queries that
+    are staged once per workgroup."""
+    assert (_lib.load().eae_class_dist_workspace_bytes(*shape) > 0) == cut
+    q, bank, seg, self_pos = case(shape, "int")
+    ref, _ = case_ref(shape, "int")
+    assert (ref[~np.isnan(ref)] < 2 ** 24).all()
+    for metric in (1, 0):
+        aligned = _sums(q, bank, seg, self_pos, metric)
+        if metric == 1:
+            assert np.array_equal(aligned.astype(np.float64), ref, equal_nan=True)     # exact, as test_integer_sums_are_exact
+        for q_offset, bank_offset in ((False, True), (True, False), (True, True)):
+            got = _sums(q, bank, seg, self_pos, metric, q_offset=q_offset, bank_offset=bank_offset)
+            assert np.array_equal(_bits(got), _bits(aligned)), (metric, q_offset, bank_offset)
 
 
 def test_the_shapes_cover_both_plans():
