@@ -5,6 +5,11 @@ and read back once per epoch phase instead of the reference's per-step ``loss.it
 
 The loops drive a small "stepper" interface so the bookkeeping (weighted epoch means, early stopping, best tracking,
 the reference's aliasing quirks, JSON schema) is testable without a GPU; the default steppers call the HIP engine.
+
+Layout: the steppers; then what the fits share -- `_phase` (one pass of a loader), `_new_autoencoder`, `_cpu_state`, `_only_set`;
+`_fit_epochs`, the one autoencoder epoch loop, written against the group-stepper interface (`fit_autoencoder_group` calls it,
+`fit_autoencoder` through the one-member adapter `_AsGroup`); `run_concurrent`; the grids, whose three drivers share one keyword set
+and one job; the MLP fit and grid.  DESIGN.md section 32.
 """
 from __future__ import annotations
 
@@ -55,30 +60,15 @@ def _group_grad_norms(max_grad_norm, n):
     return vals
 
 
-def _training_kw(max_grad_norm, lr_schedule):
-    """Clipping and schedule as keywords for a fit function, only when set (a custom fit_fn without them keeps working)."""
-    kw = {}
-    if max_grad_norm is not None:
-        kw["max_grad_norm"] = max_grad_norm
-    if lr_schedule is not None:
-        kw["lr_schedule"] = lr_schedule
-    return kw
+def _only_set(**kw):
+    """Optional arguments as keywords for a fit function or a constructor, only when set (a custom fit_fn without them keeps working)."""
+    return {k: v for k, v in kw.items() if v is not None}
 
 
 def _scheduled_lr(stepper, attr):
     if not hasattr(stepper, attr):
         raise RuntimeError(f"lr_schedule needs a stepper with a settable `.{attr}` (the learning rate{'s' if attr == 'lrs' else ''} its "
                            f"train_step uses); {type(stepper).__name__} has none")
-
-
-def _criterion_kw(class_weight, ignore_index):
-    """The two arguments as keywords for a fit function, only when set (a custom fit_fn without them keeps working)."""
-    kw = {}
-    if class_weight is not None:
-        kw["class_weight"] = class_weight
-    if ignore_index is not None:
-        kw["ignore_index"] = ignore_index
-    return kw
 
 
 class AEStepper:
@@ -194,7 +184,110 @@ def _first_batch_size(loader, default=64):
     return int(bs) if bs else default
 
 
+def _phase(stepper, loader, dev, train, *active):
+    """One pass of a loader through a stepper: begin, train_step / eval_step on every batch (moved to the stepper's device if it has
+    one), end -> the stepper's epoch scalars.  A group stepper takes its `active` member list in every call."""
+    stepper.begin(*active)
+    for xb, yb in loader:
+        if dev is not None:
+            xb, yb = _to(xb, dev), _to(yb, dev)
+        (stepper.train_step if train else stepper.eval_step)(xb, yb, *active)
+    return stepper.end(*active)
+
+
+def _new_autoencoder(device, side_streams=None, **kw):
+    model = SupervisedAutoencoder(**kw).to(device)
+    if side_streams is not None:
+        model._eae_side_streams = side_streams      # read when the model's engine is first built (engine.engine_for)
+    return model
+
+
+def _cpu_state(model):
+    """Detached CPU clones of a model's state (or of a state dict): what the grids keep of a configuration and save."""
+    state = model.state_dict() if hasattr(model, "state_dict") else model
+    return {k: v.detach().cpu().clone() for k, v in state.items()}
+
+
 # ------------------------------------------------------------------------------------------------ autoencoder
+def _fit_epochs(train_loader, val_loader, configs, stepper, models, scheds, num_epochs, patience, verbose, emit):
+    """The reference's epoch loop (R.md:656-697) over the (alpha, lr) `configs` of a group stepper (begin / train_step / eval_step / end
+    with the active index list, `lrs`): scheduled learning rates, train phase, validation phase, observe, log line through
+    emit(k, line), strict-< improvement and patience per member; a member that stops early is no longer stepped.  models / scheds: one
+    per configuration, or None.  Returns one result dict per configuration."""
+    n = len(configs)
+    dev = getattr(stepper, "device", None)
+    counter, best = [0] * n, [float("inf")] * n
+    train_curve, val_curve = [[] for _ in range(n)], [[] for _ in range(n)]
+    active = list(range(n))
+    for epoch in range(num_epochs):
+        if not active:
+            break
+        if scheds is not None:
+            for k in active:
+                stepper.lrs[k] = float(scheds[k].lr(epoch, configs[k][1]))
+        if models is not None:
+            for k in active:
+                models[k].train()
+        tr = _phase(stepper, train_loader, dev, True, active)
+        if models is not None:
+            for k in active:
+                models[k].eval()
+        with torch.no_grad():
+            va = _phase(stepper, val_loader, dev, False, active)
+        still = []
+        for j, k in enumerate(active):
+            alpha, lr = configs[k]
+            train_curve[k].append(tr[j][0]); val_curve[k].append(va[j][0])
+            if scheds is not None:
+                scheds[k].observe(va[j][0])
+            if verbose:
+                emit(k, f"[AE α={alpha} LR={lr}] Epoch {epoch + 1} | TrainLoss={tr[j][0]:.4f} | ValLoss={va[j][0]:.4f}"
+                        + (f" | lr={stepper.lrs[k]:.3e}" if scheds is not None else ""))
+            if va[j][0] < best[k]:            # strict improvement, R.md:690
+                best[k] = va[j][0]; counter[k] = 0
+                still.append(k)
+            else:
+                counter[k] += 1
+                if counter[k] >= patience:
+                    if verbose:
+                        emit(k, "Early stopping triggered.")
+                else:
+                    still.append(k)
+        active = still
+    return [{"model": None if models is None else models[k], "train_curve": train_curve[k], "val_curve": val_curve[k],
+             "best_val_loss": best[k], "epochs": len(train_curve[k])} for k in range(n)]
+
+
+class _AsGroup:
+    """A plain stepper (begin() / train_step(x, y) / eval_step(x, y) / end() -> (loss, n), `.lr`) behind the group interface, as
+    member 0.  `lrs[0]` IS the stepper's `.lr`, read and written only when the loop does: without a schedule it is never touched."""
+
+    class _Lr:
+        def __init__(self, stepper):
+            self.stepper = stepper
+
+        def __getitem__(self, k):
+            return self.stepper.lr
+
+        def __setitem__(self, k, lr):
+            self.stepper.lr = lr
+
+    def __init__(self, stepper):
+        self.stepper, self.device, self.lrs = stepper, getattr(stepper, "device", None), self._Lr(stepper)
+
+    def begin(self, active):
+        self.stepper.begin()
+
+    def train_step(self, imgs, labels, active):
+        self.stepper.train_step(imgs, labels)
+
+    def eval_step(self, imgs, labels, active):
+        self.stepper.eval_step(imgs, labels)
+
+    def end(self, active):
+        return [self.stepper.end()]
+
+
 def fit_autoencoder(train_loader, val_loader, alpha, lr, latent_dim=64, num_classes=10, num_epochs=80, patience=15,
                     device="cuda", model=None, stepper=None, head=True, verbose=True, log=print, graph=None, side_streams=None,
                     in_channels=3, class_weight=None, ignore_index=None, max_grad_norm=None, lr_schedule=None):
@@ -216,58 +309,17 @@ def fit_autoencoder(train_loader, val_loader, alpha, lr, latent_dim=64, num_clas
     ``stepper.lr`` before each epoch's train phase, its observe(val_loss) called after each validation phase, and the epoch's log
     line carries the learning rate."""
     if model is None and stepper is None:
-        model = SupervisedAutoencoder(latent_dim=latent_dim, num_classes=num_classes, in_channels=in_channels).to(device)
-        if side_streams is not None:
-            model._eae_side_streams = side_streams      # read when the model's engine is first built (engine.engine_for)
+        model = _new_autoencoder(device, side_streams, latent_dim=latent_dim, num_classes=num_classes, in_channels=in_channels)
     if stepper is None:
         stepper = AEStepper(model, alpha, lr, head=head, graph=graph,
                             max_batch=max(_first_batch_size(train_loader), _first_batch_size(val_loader)),
                             class_weight=resolve_class_weight(class_weight, train_loader, num_classes), ignore_index=ignore_index,
                             max_grad_norm=max_grad_norm)
-    dev = getattr(stepper, "device", None)
-    sched = lr_schedule() if lr_schedule is not None else None
-    if sched is not None:
+    scheds = [lr_schedule()] if lr_schedule is not None else None
+    if scheds is not None:
         _scheduled_lr(stepper, "lr")
-    counter, best_val_loss = 0, float("inf")
-    train_curve, val_curve = [], []
-    for epoch in range(num_epochs):
-        if sched is not None:
-            stepper.lr = float(sched.lr(epoch, lr))
-        if model is not None:
-            model.train()
-        stepper.begin()
-        for imgs, labels in train_loader:
-            if dev is not None:
-                imgs, labels = _to(imgs, dev), _to(labels, dev)
-            stepper.train_step(imgs, labels)
-        train_loss, _ = stepper.end()
-        train_curve.append(train_loss)
-        if model is not None:
-            model.eval()
-        stepper.begin()
-        with torch.no_grad():
-            for imgs, labels in val_loader:
-                if dev is not None:
-                    imgs, labels = _to(imgs, dev), _to(labels, dev)
-                stepper.eval_step(imgs, labels)
-        val_loss, _ = stepper.end()
-        val_curve.append(val_loss)
-        if sched is not None:
-            sched.observe(val_loss)
-        if verbose:
-            log(f"[AE α={alpha} LR={lr}] Epoch {epoch + 1} | TrainLoss={train_loss:.4f} | ValLoss={val_loss:.4f}"
-                + (f" | lr={stepper.lr:.3e}" if sched is not None else ""))
-        if val_loss < best_val_loss:          # strict improvement, R.md:690
-            best_val_loss = val_loss
-            counter = 0
-        else:
-            counter += 1
-            if counter >= patience:
-                if verbose:
-                    log("Early stopping triggered.")
-                break
-    return {"model": model, "train_curve": train_curve, "val_curve": val_curve, "best_val_loss": best_val_loss,
-            "epochs": len(train_curve)}
+    return _fit_epochs(train_loader, val_loader, [(alpha, lr)], _AsGroup(stepper), None if model is None else [model], scheds,
+                       num_epochs, patience, verbose, lambda k, line: log(line))[0]
 
 
 def fit_autoencoder_group(train_loader, val_loader, configs, latent_dim=64, num_classes=10, num_epochs=80, patience=15,
@@ -283,70 +335,19 @@ def fit_autoencoder_group(train_loader, val_loader, configs, latent_dim=64, num_
     configuration gets its own instance (its own plateau state, its own learning rate in ``stepper.lrs[k]``)."""
     n = len(configs)
     if models is None and stepper is None:
-        models = [SupervisedAutoencoder(latent_dim=latent_dim, num_classes=num_classes, in_channels=in_channels).to(device)
-                  for _ in range(n)]
-        for m in models:
-            m._eae_side_streams = 2              # a grouped step is fastest with two side streams (the engine's default is three)
+        # a grouped step is fastest with two side streams (the engine's default is three)
+        models = [_new_autoencoder(device, 2, latent_dim=latent_dim, num_classes=num_classes, in_channels=in_channels) for _ in range(n)]
     if stepper is None:
         stepper = GroupAEStepper(models, [a for a, _ in configs], [l for _, l in configs], head=head,
                                  max_batch=max(_first_batch_size(train_loader), _first_batch_size(val_loader)),
                                  class_weight=resolve_class_weight(class_weight, train_loader, num_classes), ignore_index=ignore_index,
                                  max_grad_norm=max_grad_norm)
-    dev = getattr(stepper, "device", None)
     scheds = [lr_schedule() for _ in range(n)] if lr_schedule is not None else None
     if scheds is not None:
         _scheduled_lr(stepper, "lrs")
     lines = logs if logs is not None else [[] for _ in range(n)]
-    counter, best = [0] * n, [float("inf")] * n
-    train_curve, val_curve = [[] for _ in range(n)], [[] for _ in range(n)]
-    active = list(range(n))
-    for epoch in range(num_epochs):
-        if not active:
-            break
-        if scheds is not None:
-            for k in active:
-                stepper.lrs[k] = float(scheds[k].lr(epoch, configs[k][1]))
-        if models is not None:
-            for k in active:
-                models[k].train()
-        stepper.begin(active)
-        for imgs, labels in train_loader:
-            if dev is not None:
-                imgs, labels = _to(imgs, dev), _to(labels, dev)
-            stepper.train_step(imgs, labels, active)
-        tr = stepper.end(active)
-        if models is not None:
-            for k in active:
-                models[k].eval()
-        stepper.begin(active)
-        with torch.no_grad():
-            for imgs, labels in val_loader:
-                if dev is not None:
-                    imgs, labels = _to(imgs, dev), _to(labels, dev)
-                stepper.eval_step(imgs, labels, active)
-        va = stepper.end(active)
-        still = []
-        for j, k in enumerate(active):
-            alpha, lr = configs[k]
-            train_curve[k].append(tr[j][0]); val_curve[k].append(va[j][0])
-            if scheds is not None:
-                scheds[k].observe(va[j][0])
-            if verbose:
-                lines[k].append(f"[AE α={alpha} LR={lr}] Epoch {epoch + 1} | TrainLoss={tr[j][0]:.4f} | ValLoss={va[j][0]:.4f}"
-                                + (f" | lr={stepper.lrs[k]:.3e}" if scheds is not None else ""))
-            if va[j][0] < best[k]:            # strict improvement, R.md:690
-                best[k] = va[j][0]; counter[k] = 0
-                still.append(k)
-            else:
-                counter[k] += 1
-                if counter[k] >= patience:
-                    if verbose:
-                        lines[k].append("Early stopping triggered.")
-                else:
-                    still.append(k)
-        active = still
-    return [{"model": None if models is None else models[k], "train_curve": train_curve[k], "val_curve": val_curve[k],
-             "best_val_loss": best[k], "epochs": len(train_curve[k])} for k in range(n)]
+    return _fit_epochs(train_loader, val_loader, configs, stepper, models, scheds, num_epochs, patience, verbose,
+                       lambda k, line: lines[k].append(line))
 
 
 _WORKER_STREAMS = {}       # (device, workers) -> the worker streams run_concurrent picked (reused: a context re-checks its side streams per caller's stream)
@@ -486,97 +487,81 @@ def grid_search_autoencoder(train_loader, val_loader, alpha_values=(20, 25, 30, 
     `fit_autoencoder` (lr_schedule is a factory: every configuration gets its own instance); passed on only when set."""
     os.makedirs(out_dir, exist_ok=True)
     fit_fn = fit_fn or fit_autoencoder
-    crit = _criterion_kw(resolve_class_weight(class_weight, train_loader, num_classes), ignore_index)
-    crit.update(_training_kw(max_grad_norm, lr_schedule))
+    # What every fit function is called with.  A custom fit_fn / group_fit_fn sees in_channels (image bands, 1..16) only when it is not 3,
+    # num_classes only when it is not 10, the criterion, the clipping and the schedule only when set.
+    base = dict(latent_dim=latent_dim, num_epochs=num_epochs, patience=patience, device=device, verbose=verbose)
+    opt = {} if int(in_channels) == 3 else {"in_channels": int(in_channels)}
+    opt.update(_only_set(class_weight=resolve_class_weight(class_weight, train_loader, num_classes), ignore_index=ignore_index,
+                         max_grad_norm=max_grad_norm, lr_schedule=lr_schedule))
     if int(num_classes) != 10:
-        crit["num_classes"] = int(num_classes)          # like in_channels: a custom fit function sees it only when it is not the default
+        opt["num_classes"] = int(num_classes)
     results, best = {}, {"loss": float("inf"), "info": None, "state": None, "train": None, "val": None}
     grid = [(alpha, lr) for alpha in alpha_values for lr in lr_values]
-    fitted = None
-    # in_channels (image bands, 1..16) goes to the fit functions; a custom fit_fn / group_fit_fn sees it only when it is not 3
-    bands = {} if int(in_channels) == 3 else {"in_channels": int(in_channels)}
+    # Job index -> the model(s) of that job, for the project's own fit functions only.  Parameter initialisation draws from torch's global
+    # generator: the models are built in grid order, on this thread (K worker threads would draw in timing-dependent order, ADVICE r3).
+    prebuilt = {}
+
+    def build(side_streams):
+        return _new_autoencoder(device, side_streams, latent_dim=latent_dim, num_classes=int(num_classes), in_channels=in_channels)
+
+    def job(i, fit, args, members=0):
+        """Job i of the `concurrent` driver (one configuration: members=0) or of the `grouped` one: run the fit, then keep only a CPU copy
+        of every state -- dropping the model releases the engine (workspace, streams) of a finished configuration.  Returns
+        [(result, lines), ...], one pair per configuration."""
+        def run():
+            lines = [[] for _ in range(members or 1)]
+            how = {"logs": lines} if members else {"log": lines[0].append}
+            own = {("models" if members else "model"): prebuilt.pop(i)} if i in prebuilt else {}
+            rs = fit(train_loader, val_loader, *args, **base, **how, **opt, **own)
+            out = []
+            for r, ln in zip(rs if members else [rs], lines):
+                r = dict(r)
+                r["state"] = None if r.get("model") is None else _cpu_state(r["model"])
+                r["model"] = None
+                out.append((r, ln))
+            return out
+        return run
+
+    done = None
     if grouped and int(grouped) > 1:
         gfit = group_fit_fn or fit_autoencoder_group
         pairs = max(1, int(concurrent_groups or 1))
         chunks = [grid[g0:g0 + int(grouped)] for g0 in range(0, len(grid), int(grouped))]
-        prebuilt = None
         if pairs > 1 and gfit is fit_autoencoder_group:
-            # parameter initialisation draws from torch's global generator: in grid order, on this thread (as for `concurrent`)
-            prebuilt = []
-            for cfgs in chunks:
-                ms = [SupervisedAutoencoder(latent_dim=latent_dim, num_classes=int(num_classes), in_channels=in_channels).to(device) for _ in cfgs]
-                for m in ms:
-                    m._eae_side_streams = 1          # two groups x (caller's stream + one side stream) = the four hardware queues
-                prebuilt.append(ms)
-
-        def group_job(gi):
-            def job():
-                cfgs = chunks[gi]
-                lines = [[] for _ in cfgs]
-                extra = {"models": prebuilt[gi]} if prebuilt is not None else {}
-                rs = gfit(train_loader, val_loader, cfgs, latent_dim=latent_dim, num_epochs=num_epochs, patience=patience, device=device,
-                          verbose=verbose, logs=lines, **bands, **crit, **extra)
-                out = []
-                for r, ln in zip(rs, lines):
-                    r = dict(r)
-                    r["state"] = None if r.get("model") is None else {k: v.detach().cpu().clone() for k, v in r["model"].state_dict().items()}
-                    r["model"] = None           # release the engine (workspace, streams) of a finished configuration
-                    out.append((r, ln))
-                if prebuilt is not None:
-                    prebuilt[gi] = None
-                return out
-            return job
-        done = run_concurrent([group_job(gi) for gi in range(len(chunks))], pairs, device) if pairs > 1 else [group_job(gi)() for gi in range(len(chunks))]
-        fitted = [item for chunk in done for item in chunk]
+            # two groups x (caller's stream + one side stream) = the four hardware queues
+            prebuilt.update((gi, [build(1) for _ in cfgs]) for gi, cfgs in enumerate(chunks))
+        jobs = [job(gi, gfit, (cfgs,), len(cfgs)) for gi, cfgs in enumerate(chunks)]
+        done = run_concurrent(jobs, pairs, device) if pairs > 1 else [run() for run in jobs]
     elif concurrent and int(concurrent) > 1:
-        # parameter initialisation draws from torch's global generator: K worker threads would draw in timing-dependent order (ADVICE r3)
-        prebuilt = {}
         if fit_fn is fit_autoencoder:
-            for (alpha, lr) in grid:
-                m = SupervisedAutoencoder(latent_dim=latent_dim, num_classes=int(num_classes), in_channels=in_channels).to(device)
-                if int(concurrent) >= 3:
-                    m._eae_side_streams = -1
-                prebuilt[(alpha, lr)] = m
-
-        def job_of(alpha, lr):
-            def job():
-                lines = []
-                # Measured on MI355X at B=64 (bench.py `configs.grid_b64`, DESIGN.md section 6): a process reaches the GPU through 4 hardware
-                # queues.  Contexts with the default three streams each share them -- K = 2 / 4 / 8 / 16 reach 1.65x the single-configuration
-                # rate and stay there -- while ONE stream per context lets four configurations run side by side: 487 K vs 352 K images/s
-                # at K = 4.  hipGraph replay of each step is slower than eager (0.7-0.8x), more hardware queues or several processes far slower.
-                extra = {"model": prebuilt.pop((alpha, lr))} if fit_fn is fit_autoencoder else {}
-                r = fit_fn(train_loader, val_loader, alpha, lr, latent_dim=latent_dim, num_epochs=num_epochs, patience=patience,
-                           device=device, verbose=verbose, log=lines.append, **bands, **crit, **extra)
-                r = dict(r)
-                # only the state_dict of a finished configuration is needed below: release its engine (workspace, streams) now
-                r["state"] = None if r.get("model") is None else {k: v.detach().cpu().clone() for k, v in r["model"].state_dict().items()}
-                r["model"] = None
-                return r, lines
-            return job
-        fitted = run_concurrent([job_of(a, l) for a, l in grid], int(concurrent), device)
+            # Measured on MI355X at B=64 (bench.py `configs.grid_b64`, DESIGN.md section 6): a process reaches the GPU through 4 hardware
+            # queues.  Contexts with the default three streams each share them -- K = 2 / 4 / 8 / 16 reach 1.65x the single-configuration
+            # rate and stay there -- while ONE stream per context lets four configurations run side by side: 487 K vs 352 K images/s
+            # at K = 4.  hipGraph replay of each step is slower than eager (0.7-0.8x), more hardware queues or several processes far slower.
+            prebuilt.update((i, build(-1 if int(concurrent) >= 3 else None)) for i in range(len(grid)))
+        done = run_concurrent([job(i, fit_fn, cfg) for i, cfg in enumerate(grid)], int(concurrent), device)
+    fitted = None if done is None else [pair for pairs_of_job in done for pair in pairs_of_job]
     for gi, (alpha, lr) in enumerate(grid):
+        if verbose:
+            log("\n=====================================")
+            log(f"Training AE for α={alpha}, LR={lr}")
+            log("=====================================")
+        if fitted is not None:
+            r, lines = fitted[gi]
             if verbose:
-                log("\n=====================================")
-                log(f"Training AE for α={alpha}, LR={lr}")
-                log("=====================================")
-            if fitted is not None:
-                r, lines = fitted[gi]
-                if verbose:
-                    for ln in lines:
-                        log(ln)
-            else:
-                r = fit_fn(train_loader, val_loader, alpha, lr, latent_dim=latent_dim, num_epochs=num_epochs, patience=patience,
-                           device=device, verbose=verbose, log=log, **bands, **crit)
-            results[(alpha, lr)] = r["best_val_loss"]
-            if r["best_val_loss"] < best["loss"]:
-                state = r.get("state")
-                if state is None and r.get("model") is not None:
-                    state = {k: v.detach().cpu().clone() for k, v in r["model"].state_dict().items()}
-                best.update(loss=r["best_val_loss"], info=(alpha, lr), train=r["train_curve"], val=r["val_curve"], state=state)
-                if verbose:
-                    log("\nNew best AE")
-                    log(f"   α={alpha}, LR={lr}, ValLoss={r['best_val_loss']:.4f}")
+                for ln in lines:
+                    log(ln)
+        else:       # the sequential driver streams: the lines appear while the configuration trains
+            r = fit_fn(train_loader, val_loader, alpha, lr, **base, log=log, **opt)
+        results[(alpha, lr)] = r["best_val_loss"]
+        if r["best_val_loss"] < best["loss"]:
+            state = r.get("state")
+            if state is None and r.get("model") is not None:
+                state = _cpu_state(r["model"])
+            best.update(loss=r["best_val_loss"], info=(alpha, lr), train=r["train_curve"], val=r["val_curve"], state=state)
+            if verbose:
+                log("\nNew best AE")
+                log(f"   α={alpha}, LR={lr}, ValLoss={r['best_val_loss']:.4f}")
     best_path = os.path.join(out_dir, "AE_GLOBAL_BEST.pt")
     if best["state"] is not None:
         torch.save(best["state"], best_path)
@@ -621,8 +606,7 @@ def fit_mlp(train_dl, val_dl, test_dl, lr, input_dim=64, num_classes=10, num_epo
     hidden / dropout: the architecture of the classifier built here (`MLP(hidden=, dropout=)`; None: the reference's (128, 64) with
     Dropout(0.3) after the first layer).  A `clf` passed in brings its own."""
     if clf is None and stepper is None:
-        arch = {k: v for k, v in (("hidden", hidden), ("dropout", dropout)) if v is not None}
-        clf = MLP(input_dim=input_dim, num_classes=num_classes, **arch).to(device)
+        clf = MLP(input_dim=input_dim, num_classes=num_classes, **_only_set(hidden=hidden, dropout=dropout)).to(device)
     if stepper is None:
         stepper = MLPStepper(clf, lr, weight_decay, max_batch=max(256, _first_batch_size(train_dl)),
                              class_weight=resolve_class_weight(class_weight, train_dl, num_classes), ignore_index=ignore_index)
@@ -633,24 +617,16 @@ def fit_mlp(train_dl, val_dl, test_dl, lr, input_dim=64, num_classes=10, num_epo
     curves = {"train_acc": [], "val_acc": [], "train_loss": [], "val_loss": []}
     best_val_acc, best_state = 0, None
 
-    def run(dl, train):
-        stepper.begin()
-        for xb, yb in dl:
-            if dev is not None:
-                xb, yb = _to(xb, dev), _to(yb, dev)
-            (stepper.train_step if train else stepper.eval_step)(xb, yb)
-        return stepper.end()
-
     for e in range(num_epochs):
         if sched is not None:
             stepper.lr = float(sched.lr(e, lr))
         if clf is not None:
             clf.train()
-        tr_loss, tr_acc, _ = run(train_dl, True)
+        tr_loss, tr_acc, _ = _phase(stepper, train_dl, dev, True)
         if clf is not None:
             clf.eval()
         with torch.no_grad():
-            va_loss, va_acc, _ = run(val_dl, False)
+            va_loss, va_acc, _ = _phase(stepper, val_dl, dev, False)
         curves["train_acc"].append(tr_acc); curves["val_acc"].append(va_acc)
         curves["train_loss"].append(tr_loss); curves["val_loss"].append(va_loss)
         if sched is not None:
@@ -666,7 +642,7 @@ def fit_mlp(train_dl, val_dl, test_dl, lr, input_dim=64, num_classes=10, num_epo
         clf.load_state_dict(best_state)
         clf.eval()
     with torch.no_grad():
-        _, test_acc, _ = run(test_dl, False)
+        _, test_acc, _ = _phase(stepper, test_dl, dev, False)
     return {"clf": clf, "best_val_acc": best_val_acc, "test_acc": test_acc, "best_state": best_state, **curves}
 
 
@@ -680,11 +656,10 @@ def grid_search_mlp(train_dl, val_dl, test_dl, lr_values=(1e-6, 5e-6, 1e-5, 5e-5
     coefficient for every learning rate, each passed on only when set; `modules.mlp_from_state_dict` rebuilds the saved classifier."""
     os.makedirs(out_dir, exist_ok=True)
     fit_fn = fit_fn or fit_mlp
-    crit = _criterion_kw(resolve_class_weight(class_weight, train_dl, num_classes), ignore_index)
+    crit = _only_set(class_weight=resolve_class_weight(class_weight, train_dl, num_classes), ignore_index=ignore_index)
     if int(num_classes) != 10:
         crit["num_classes"] = int(num_classes)          # a custom fit function sees it only when it is not the default
-    crit.update(_training_kw(None, lr_schedule))
-    crit.update({k: v for k, v in (("hidden", hidden), ("dropout", dropout), ("weight_decay", weight_decay)) if v is not None})
+    crit.update(_only_set(lr_schedule=lr_schedule, hidden=hidden, dropout=dropout, weight_decay=weight_decay))
     best = {"val": 0, "test": 0, "lr": None, "state": None, "curves": None}
     for lr in lr_values:
         if verbose:
@@ -696,7 +671,7 @@ def grid_search_mlp(train_dl, val_dl, test_dl, lr_values=(1e-6, 5e-6, 1e-5, 5e-5
         if r["best_val_acc"] > best["val"]:
             state = r["best_state"]
             best.update(val=r["best_val_acc"], test=r["test_acc"], lr=lr,
-                        state=None if state is None else {k: v.detach().cpu().clone() for k, v in state.items()},
+                        state=None if state is None else _cpu_state(state),
                         curves={k: r[k] for k in ("train_acc", "val_acc", "train_loss", "val_loss")})
     path = os.path.join(out_dir, "MLP_GLOBAL_BEST.pt")
     if best["state"] is not None:

@@ -182,6 +182,161 @@ def test_grid_search_grouped_same_bookkeeping_and_log_order(tmp_path):
     assert a["results"] == c["results"] and (c["best_alpha"], c["best_lr"]) == (40, 0.1) and par_logs == seq_logs
 
 
+_TABLE = {(20, 0.1): 3.0, (20, 0.2): 2.5, (30, 0.1): 2.5, (30, 0.2): 2.7}
+_DRIVERS = ({}, {"concurrent": 2, "device": "cpu"}, {"grouped": 2})
+
+
+def _fake_fits(seen_kw=None, made=None, say=None):
+    """(fit_fn, group_fit_fn) over _TABLE: each configuration returns a tiny Linear filled with alpha + lr as its "model"; they record
+    the keywords they were called with in `seen_kw`, a weak reference to every model in `made`, and log `say(alpha, lr)`."""
+    import weakref
+
+    def result(alpha, lr):
+        m = torch.nn.Linear(2, 1)
+        with torch.no_grad():
+            m.weight.fill_(alpha + lr); m.bias.fill_(alpha + lr)
+        if made is not None:
+            made.append(weakref.ref(m))
+        return {"model": m, "train_curve": [1.0], "val_curve": [_TABLE[(alpha, lr)]], "best_val_loss": _TABLE[(alpha, lr)], "epochs": 1}
+
+    def fit(tr, va, alpha, lr, log=print, **kw):
+        if seen_kw is not None:
+            seen_kw.append(dict(kw))
+        for ln in (say(alpha, lr) if say else ()):
+            log(ln)
+        return result(alpha, lr)
+
+    def group_fit(tr, va, cfgs, logs=None, **kw):
+        if seen_kw is not None:
+            seen_kw.append(dict(kw))
+        for k, (a, lr) in enumerate(cfgs):
+            logs[k].extend(say(a, lr) if say else ())
+        return [result(a, lr) for a, lr in cfgs]
+    return {"fit_fn": fit, "group_fit_fn": group_fit}
+
+
+def _grid(tmp_path, **kw):
+    return T.grid_search_autoencoder([], [], alpha_values=(20, 30), lr_values=(0.1, 0.2), out_dir=str(tmp_path), **kw)
+
+
+def test_sequential_grid_streams_the_fit_functions_lines(tmp_path):
+    """The sequential driver hands its `log` to the fit function: a configuration's lines appear while it trains, after its header and
+    in front of "New best AE", not when the fit returns."""
+    logs, at = [], []
+
+    def fit(tr, va, alpha, lr, log=print, **kw):
+        for i in (1, 2):
+            at.append(list(logs))            # what the caller has seen when this line is written
+            log(f"line {i} of {alpha} {lr}")
+        return {"model": None, "train_curve": [1.0], "val_curve": [1.0], "best_val_loss": _TABLE[(alpha, lr)], "epochs": 1}
+
+    _grid(tmp_path, fit_fn=fit, log=logs.append)
+    header = ["\n=====================================", "Training AE for α=20, LR=0.1", "====================================="]
+    assert at[0] == header and at[1] == header + ["line 1 of 20 0.1"]
+    assert logs[:7] == header + ["line 1 of 20 0.1", "line 2 of 20 0.1", "\nNew best AE", "   α=20, LR=0.1, ValLoss=3.0000"]
+    second = logs.index("Training AE for α=20, LR=0.2")
+    assert at[2] == logs[:second + 2] and at[3] == logs[:second + 3]
+    assert logs.index("line 2 of 20 0.2") < logs.index("   α=20, LR=0.2, ValLoss=2.5000")
+
+
+def test_what_a_custom_fit_function_sees(tmp_path):
+    """Optional arguments reach a custom fit_fn / group_fit_fn only when set (or not the default), in all three drivers, and the
+    models the grid prebuilds for the project's own fit functions never do."""
+    optional = ("in_channels", "num_classes", "class_weight", "ignore_index", "max_grad_norm", "lr_schedule", "model", "models")
+    w = torch.arange(1.0, 8.0)
+    fac = lambda: None      # noqa: E731
+    given = dict(in_channels=4, num_classes=7, class_weight=w, ignore_index=-1, max_grad_norm=2.0, lr_schedule=fac)
+    for i, driver in enumerate(_DRIVERS):
+        seen = []
+        _grid(tmp_path / f"d{i}", verbose=False, **_fake_fits(seen_kw=seen), **driver)
+        assert len(seen) == (2 if "grouped" in driver else 4)
+        for kw in seen:
+            assert not set(optional) & set(kw), (driver, sorted(kw))
+        seen.clear()
+        _grid(tmp_path / f"s{i}", verbose=False, **_fake_fits(seen_kw=seen), **driver, **given)
+        assert len(seen) == (2 if "grouped" in driver else 4)
+        for kw in seen:
+            assert kw["in_channels"] == 4 and kw["num_classes"] == 7 and kw["class_weight"] is w and kw["ignore_index"] == -1
+            assert kw["max_grad_norm"] == 2.0 and kw["lr_schedule"] is fac
+            assert "model" not in kw and "models" not in kw, (driver, sorted(kw))
+
+
+def test_the_saved_state_is_the_winners(tmp_path):
+    """AE_GLOBAL_BEST.pt holds the state of the first strict minimum in grid order, (20, 0.2), as CPU tensors of its own; the
+    `concurrent` and `grouped` drivers keep only such a copy of every finished configuration and let its model go."""
+    import gc
+    for i, driver in enumerate(_DRIVERS):
+        made, alive = [], []
+
+        def log(line):
+            if line.startswith("Training AE"):          # bookkeeping of one configuration begins
+                if not alive:
+                    gc.collect()
+                alive.append(sum(r() is not None for r in made))
+        out = _grid(tmp_path / f"d{i}", log=log, **_fake_fits(made=made), **driver)
+        assert (out["best_alpha"], out["best_lr"]) == (20, 0.2)
+        state = torch.load(out["best_path"])
+        assert sorted(state) == ["bias", "weight"]
+        assert all(v.device.type == "cpu" and not v.requires_grad for v in state.values())
+        assert torch.equal(state["weight"], torch.full((1, 2), 20.2)) and torch.equal(state["bias"], torch.full((1,), 20.2))
+        assert len(made) == 4
+        if driver:
+            assert alive == [0, 0, 0, 0], (driver, alive)          # every fit has finished, and no result kept its model
+
+
+def test_the_grid_snapshot_does_not_alias_the_model(tmp_path):
+    """The state the grid keeps of a new best is a clone: a fit function that goes on changing the model it returned (the reference
+    returns the LIVE model) does not change what is saved."""
+    for i, driver in enumerate(_DRIVERS):
+        fits = _fake_fits()
+        kept = []
+
+        def keep(fn):
+            def wrapped(*a, **kw):
+                r = fn(*a, **kw)
+                kept.extend(r if isinstance(r, list) else [r])
+                return r
+            return wrapped
+        out = _grid(tmp_path / f"d{i}", verbose=False, fit_fn=keep(fits["fit_fn"]), group_fit_fn=keep(fits["group_fit_fn"]), **driver)
+        saved = torch.load(out["best_path"])
+        for r in kept:
+            for p in r["model"].state_dict().values():
+                assert all(p.data_ptr() != v.data_ptr() for v in saved.values())
+            with torch.no_grad():
+                r["model"].weight.zero_()
+        assert torch.equal(torch.load(out["best_path"])["weight"], torch.full((1, 2), 20.2))
+
+
+class PlainAE:
+    """A plain stepper with nothing but the four calls: no `.lr`, no device."""
+    device = None
+
+    def __init__(self):
+        self.calls = []
+
+    def begin(self):
+        self.calls.append("b")
+
+    def train_step(self, x, y):
+        self.calls.append("t")
+
+    def eval_step(self, x, y):
+        self.calls.append("v")
+
+    def end(self):
+        self.calls.append("e")
+        return 1.0, 8
+
+
+def test_a_plain_stepper_without_lr_runs_unscheduled_and_is_left_alone():
+    st = PlainAE()
+    before = dict(vars(st))
+    r = T.fit_autoencoder(_loader([8, 8]), _loader([8]), alpha=35, lr=1e-3, num_epochs=2, patience=5, stepper=st, model=None, verbose=False)
+    assert r["epochs"] == 2 and r["train_curve"] == [1.0, 1.0] and r["best_val_loss"] == 1.0 and r["model"] is None
+    assert st.calls == ["b", "t", "t", "e", "b", "v", "e"] * 2
+    assert set(vars(st)) == set(before) and not hasattr(st, "lr") and not hasattr(st, "lrs") and st.device is None
+
+
 class ScriptedMLP:
     device = None
 
