@@ -26,6 +26,8 @@ from . import validity  # noqa: F401
 from .validity import class_distance_sums, silhouette_samples, silhouette_score, class_distance_matrix  # noqa: F401
 from .validity import davies_bouldin_score, calinski_harabasz_score, select_k  # noqa: F401
 from .report import separation_table  # noqa: F401
+from . import gaussian  # noqa: F401
+from .gaussian import class_scatter, gaussian_fit, gaussian_predict, gaussian_classify_scene, scatter_axes, GaussianModel  # noqa: F401
 from . import postprocess  # noqa: F401
 from .postprocess import majority_filter, label_regions, region_table, sieve  # noqa: F401
 
@@ -39,4 +41,5 @@ __all__ = ["Encoder", "Decoder", "SupervisedAutoencoder", "MLP", "mlp_from_state
            "KMeansResult", "cluster_class_table", "name_clusters", "knn_search", "knn_classify", "similar_windows", "knn_classify_scene",
            "KNNResult", "majority_filter", "label_regions", "region_table", "sieve", "class_distance_sums", "silhouette_samples",
            "silhouette_score", "class_distance_matrix", "davies_bouldin_score", "calinski_harabasz_score", "select_k",
-           "separation_table"]
+           "separation_table", "class_scatter", "gaussian_fit", "gaussian_predict", "gaussian_classify_scene", "scatter_axes",
+           "GaussianModel"]

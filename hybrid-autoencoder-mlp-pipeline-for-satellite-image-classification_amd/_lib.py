@@ -172,6 +172,9 @@ _PROTOS = {
     "eae_knn_search": (C.c_int, [vp, vp, C.c_longlong, vp, C.c_longlong, C.c_int, C.c_int, C.c_longlong, vp, vp, vp, C.c_longlong]),
     "eae_class_dist_workspace_bytes": (C.c_longlong, [C.c_longlong, C.c_longlong, C.c_int, C.c_int]),
     "eae_class_dist_sums": (C.c_int, [vp, vp, C.c_longlong, vp, C.c_longlong, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, C.c_longlong]),
+    "eae_class_scatter_workspace_bytes": (C.c_longlong, [C.c_longlong, C.c_int, C.c_int]),
+    "eae_class_scatter": (C.c_int, [vp, vp, C.c_longlong, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, C.c_longlong]),
+    "eae_gauss_score": (C.c_int, [vp, vp, C.c_longlong, C.c_int, vp, vp, C.c_longlong, vp, C.c_int, vp, vp, vp, vp]),
     "eae_map_workspace_bytes": (C.c_longlong, [C.c_int, C.c_int]),
     "eae_map_majority": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "eae_map_regions": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_longlong]),

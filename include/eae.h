@@ -807,6 +807,41 @@ long long eae_class_dist_workspace_bytes(long long Nq, long long M, int L, int K
 int eae_class_dist_sums(void* stream, const float* q, long long Nq, const float* bank, long long M, int L, const long long* seg, int K,
                         const long long* self_pos, int metric, float* sums, void* workspace, long long workspace_bytes);
 
+/* ------------------------------------------------------------------ latent Gaussian models --------- */
+/* The two kernels of a Gaussian maximum-likelihood classifier over latents (no reference counterpart): per-class scatter matrices and
+ * per-class quadratic forms.  z [N][L] fp32 row-major; 1 <= L <= 256, 1 <= K <= 256, 1 <= N < 2^31; anything else or a NULL required
+ * pointer is EAE_ERR_ARG and nothing is launched.  Stateless; nothing synchronises the host.
+ *
+ * eae_class_scatter: scatter[k][i][j] = sum over the rows n of class k of (z_n[i] - means[k][i]) (z_n[j] - means[k][j]), fp32
+ * [K][L][L]; means fp32 [K][L] is an input.  The rows come GROUPED BY CLASS: order int64 [N] holds row indices, and positions
+ * seg[k] .. seg[k+1]-1 of it are the rows of class k (seg int64 [K+1] on the device, values clamped into [0, N]).  A row takes part
+ * only if labels[row] == k as well (labels int64 [N]), and an entry of order outside [0, N) is skipped: labels outside [0, K) are
+ * never summed, and nothing outside z is read.  z - m is one fp32 subtraction, the products accumulate on the f32-input MFMA, two rows
+ * an instruction, in the order of `order`.  Only the tiles with i-tile <= j-tile are computed; per-chunk partial tiles go to
+ * `workspace` and a second kernel adds them in ascending chunk order and writes every element and its mirror image from one register:
+ * scatter[k] is bitwise symmetric, every element of the output is written (zeros for a class without rows), there are no float atomics
+ * and the result is bitwise identical from run to run.  The geometry is a function of (N, L, K) alone.  workspace: device memory of at
+ * least eae_class_scatter_workspace_bytes(N, L, K) bytes (host only; < 0 on bad arguments), contents irrelevant on entry; NULL or too
+ * small is EAE_ERR_ARG.  Rows that take part must be finite (a precondition, as for eae_kmeans_update).
+ *
+ * eae_gauss_score: d_k(n) = || W_k^T (z_n - mu_k) ||^2 and score_k(n) = d_k(n) + offset[k] for every row and class.  mu fp32 [K][L],
+ * offset fp32 [K], W fp32: class k's [L][L] matrix starts at element k * w_stride, w_stride = L * L, or 0 for one matrix shared by all
+ * classes (anything else is EAE_ERR_ARG).  z - mu is one fp32 subtraction, u_j = sum_l W[l][j] (z - mu)[l] an l-ordered fma chain on
+ * the f32-input MFMA, d the sum of the squares in one fixed order.  offset[k] == +inf marks class k as absent: its score is +inf and
+ * it is never chosen.
+ *   labels [N] int64: the argmin of the score, the lowest k on a tie (equal classes give equal scores); -1 for a row that holds a NaN
+ *                     or an Inf, or when no class has a score below +inf.
+ *   maha   [N] fp32 or NULL: max(0, d) of the chosen class; NaN for a -1 row.
+ *   best   [N] fp32 or NULL: the chosen score; NaN for a non-finite row, +inf when no class was chosen.
+ *   scores [N][K] fp32 or NULL: every score; a row of NaN for a non-finite row.
+ * No N x K x L array exists anywhere, and a row's outputs depend on its own values and the model alone: not on N, on its position
+ * or on the launch geometry. */
+long long eae_class_scatter_workspace_bytes(long long N, int L, int K);
+int eae_class_scatter(void* stream, const float* z, long long N, int L, const long long* labels, const long long* order,
+                      const long long* seg, int K, const float* means, float* scatter, void* workspace, long long workspace_bytes);
+int eae_gauss_score(void* stream, const float* z, long long N, int L, const float* mu, const float* W, long long w_stride,
+                    const float* offset, int K, long long* labels, float* maha, float* best, float* scores);
+
 /* ------------------------------------------------------------------ map post-processing ------------ */
 /* Cleaning a class map on the device (no reference counterpart): majority filter, connected regions, their table, and a sieve.  A map
  * is a contiguous int64 [H][W] device array as eae_scene_classify / eae_scene_blend write it: a value in [0, K) is a class, K in 1..64,
