@@ -30,6 +30,9 @@ from . import gaussian  # noqa: F401
 from .gaussian import class_scatter, gaussian_fit, gaussian_predict, gaussian_classify_scene, scatter_axes, GaussianModel  # noqa: F401
 from . import postprocess  # noqa: F401
 from .postprocess import majority_filter, label_regions, region_table, sieve  # noqa: F401
+from . import zonal  # noqa: F401
+from .zonal import compact_zones, zonal_stats, zone_labels, paint_zones, classify_zones, zone_confusion, ZonalStats  # noqa: F401
+from .report import zone_table  # noqa: F401
 
 __all__ = ["Encoder", "Decoder", "SupervisedAutoencoder", "MLP", "mlp_from_state_dict", "fit_autoencoder", "grid_search_autoencoder",
            "extract_features", "fit_mlp", "grid_search_mlp", "evaluate", "augment_batch", "stage_bands", "Augment",
@@ -42,4 +45,5 @@ __all__ = ["Encoder", "Decoder", "SupervisedAutoencoder", "MLP", "mlp_from_state
            "KNNResult", "majority_filter", "label_regions", "region_table", "sieve", "class_distance_sums", "silhouette_samples",
            "silhouette_score", "class_distance_matrix", "davies_bouldin_score", "calinski_harabasz_score", "select_k",
            "separation_table", "class_scatter", "gaussian_fit", "gaussian_predict", "gaussian_classify_scene", "scatter_axes",
-           "GaussianModel"]
+           "GaussianModel", "compact_zones", "zonal_stats", "zone_labels", "paint_zones", "classify_zones", "zone_confusion", "ZonalStats",
+           "zone_table"]

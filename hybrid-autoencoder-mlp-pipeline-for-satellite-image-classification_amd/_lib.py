@@ -180,6 +180,9 @@ _PROTOS = {
     "eae_map_regions": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_longlong]),
     "eae_map_region_stats": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp]),
     "eae_map_sieve_pass": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_longlong, vp, vp, vp, C.c_longlong]),
+    "eae_zonal_accumulate": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int,
+                                       C.c_longlong, C.c_int, vp, vp]),
+    "eae_zonal_paint": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_longlong, C.c_longlong, vp]),
 }
 
 EXPORTS = tuple(_PROTOS.keys())

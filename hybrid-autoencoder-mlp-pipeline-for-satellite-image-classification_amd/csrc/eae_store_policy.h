@@ -27,3 +27,9 @@
 #ifndef EAE_WT_OPT
 #define EAE_WT_OPT 0
 #endif
+// ZONAL: zonal_paint (eae_zonal.hip), an output-only pass outside the training step: a wave's two 16-byte stores per lane cover whole
+// 128-byte lines of an int64 raster that nothing in the launch reads back.  Write-through like EPI, the family of the same shape
+// (tools/zonal_bench.py times the pass; -DEAE_WT_ZONAL=0 builds the plain form, which was not measured).
+#ifndef EAE_WT_ZONAL
+#define EAE_WT_ZONAL 16
+#endif

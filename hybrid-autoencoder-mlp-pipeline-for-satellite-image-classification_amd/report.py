@@ -194,6 +194,41 @@ def separation_table(matrix, per_class, names=None, digits=4):
     return "\n".join(lines) + "\n"
 
 
+def zone_table(stats, labels, class_names=None, digits=4):
+    """Text table of an object-based classification, one line per zone: its id, its pixels (votes.sum(1)), the share of them that
+    was classified, its class and the confidence.  stats: `zonal.ZonalStats` (only votes is read); labels: what `zonal.zone_labels`
+    returned, (label, confidence, coverage); class_names: K strings (default: the class ids).  A zone without a label, and a figure
+    that does not exist (NaN), print as '-'."""
+    def host(t):
+        return np.asarray(t.detach().cpu().numpy() if hasattr(t, "detach") else t)
+
+    votes = host(stats.votes)
+    if votes.ndim != 2 or votes.shape[1] < 2:
+        raise ValueError("stats.votes must be a [Z, K+1] table")
+    z, k = votes.shape[0], votes.shape[1] - 1
+    try:
+        label, confidence, coverage = (host(t).ravel() for t in labels)
+    except (TypeError, ValueError):
+        raise ValueError("labels must be the (label, confidence, coverage) triple of zone_labels") from None
+    if not (label.shape[0] == confidence.shape[0] == coverage.shape[0] == z):
+        raise ValueError(f"labels must have {z} entries each, one per zone")
+    names = [str(c) for c in range(k)] if class_names is None else [str(n) for n in class_names]
+    if len(names) != k:
+        raise ValueError(f"class_names must have {k} entries, got {len(names)}")
+    width = max(max(len(n) for n in names), len("class"))
+
+    def num(v):
+        return "{:>10}".format("-") if not np.isfinite(v) else "{:>10.{d}f}".format(v, d=digits)
+
+    lines = ["{:>8} {:>10} {:>10} {:>{w}s} {:>10}".format("zone", "pixels", "coverage", "class", "confidence", w=width), ""]
+    pixels = votes.sum(1)
+    for i in range(z):
+        c = int(label[i])
+        lines.append("{:>8} {:>10} ".format(i, int(pixels[i])) + num(coverage[i]) + " {:>{w}s} ".format(names[c] if 0 <= c < k else "-", w=width)
+                     + num(confidence[i]))
+    return "\n".join(lines) + "\n"
+
+
 def classification_report_from_confusion(cm, digits=4, num_classes=None):
     """`classification_report`'s table from a confusion matrix (`confusion_metrics`: the same matrix forms)."""
     return _report_text(confusion_metrics(cm, num_classes), digits)

@@ -880,6 +880,40 @@ int eae_map_region_stats(void* stream, const long long* regions, int H, int W, i
 int eae_map_sieve_pass(void* stream, const long long* labels, const long long* regions, const int* area, int H, int W,
                        long long min_size, long long* out, long long* changed, void* workspace, long long workspace_bytes);
 
+/* ------------------------------------------------------------------ zonal statistics --------------- */
+/* Object-based classification (no reference counterpart): what a class map says inside every zone of a zone
+ * raster, and a per-zone value painted back at pixel resolution.  zones [H][W] is a device raster of zone ids at the scene's pixel
+ * resolution, int32 (zone_elem_bytes 4) or int64 (8), read natively; an id in [0, Z) is a zone, every other id (negatives: "no
+ * zone") is skipped entirely.  H, W >= 1 and H * W < 2^31.  Stateless; every call goes to `stream` and nothing synchronises the host.
+ *
+ * eae_zonal_accumulate: labels is an int64 [cH][cW] map of cell x cell cells and probs NULL or the float [K][cH][cW] probabilities
+ * of the same cells (eae_scene_classify / eae_scene_blend); mask is NULL or uint8 [H][W]; votes is int64 [Z][K + 1], prob_sums
+ * int64 [Z][K], non-NULL exactly when probs is.  1 <= K <= 64, Z >= 1, Z * (K + 1) <= 2^31 - 1, cell >= 1, oy, ox >= 0.
+ *   For every pixel (y, x) with mask[y][x] == 0 and z = zones[y][x] in [0, Z):
+ *     its cell is ((y + oy) / cell, (x + ox) / cell), as in eae_scene_confusion;
+ *     c = the cell's label when the cell lies inside the map and the label is in [0, K), else K (not classified, not covered, any
+ *         other value);
+ *     votes[z][c] += 1;
+ *     with probs and c < K, for every class j: prob_sums[z][j] += q(probs[j][cell]),
+ *       q(p) = rint(2^32 * min(max(p, 0), 1)) evaluated in double, round-half-even, q(NaN) = 0.
+ *   q <= 2^32 and a zone has fewer than 2^31 pixels: every sum stays below 2^63.  So votes sums to the number of unmasked pixels
+ *   whose id is in range.  accumulate = 0: both tables are cleared first, on the stream; accumulate = 1: the call adds to what they
+ *   hold (several scenes).
+ * Integers only (64-bit integer adds in LDS and in global memory, no float atomics): exact, identical from run to run and independent
+ * of the launch geometry.  The raster and the mask are read once with 16-byte loads; no per-pixel copy of the map or of the ids is made.
+ *
+ * eae_zonal_paint: out[y][x] (int64 [H][W]) = values[zones[y][x]] (values: int64 [Z], Z >= 1) where the id is in [0, Z), else fill.
+ * One pass; no int64 copy of the zone raster.
+ *
+ * Rejected (EAE_ERR_ARG, nothing launched): a NULL zones, labels, votes, values or out; probs without prob_sums or the reverse; a
+ * zone_elem_bytes other than 4 or 8 or a zones pointer that is no multiple of it; K, Z, cell, oy, ox outside the limits above; an
+ * empty raster or map, or H * W >= 2^31; accumulate outside 0..1. */
+int eae_zonal_accumulate(void* stream, const void* zones, int zone_elem_bytes, int H, int W, const long long* labels, const float* probs,
+                         int cH, int cW, int cell, int oy, int ox, const unsigned char* mask, int K, long long Z, int accumulate,
+                         long long* votes, long long* prob_sums);
+int eae_zonal_paint(void* stream, const void* zones, int zone_elem_bytes, int H, int W, const long long* values, long long Z,
+                    long long fill, long long* out);
+
 #ifdef __cplusplus
 }
 #endif
