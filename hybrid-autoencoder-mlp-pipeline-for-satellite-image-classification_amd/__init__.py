@@ -33,6 +33,8 @@ from .postprocess import majority_filter, label_regions, region_table, sieve  # 
 from . import zonal  # noqa: F401
 from .zonal import compact_zones, zonal_stats, zone_labels, paint_zones, classify_zones, zone_confusion, ZonalStats  # noqa: F401
 from .report import zone_table  # noqa: F401
+from . import segment  # noqa: F401
+from .segment import slic_clusters, slic_scene, classify_superpixels, zone_boundaries, Superpixels  # noqa: F401
 
 __all__ = ["Encoder", "Decoder", "SupervisedAutoencoder", "MLP", "mlp_from_state_dict", "fit_autoencoder", "grid_search_autoencoder",
            "extract_features", "fit_mlp", "grid_search_mlp", "evaluate", "augment_batch", "stage_bands", "Augment",
@@ -46,4 +48,4 @@ __all__ = ["Encoder", "Decoder", "SupervisedAutoencoder", "MLP", "mlp_from_state
            "silhouette_score", "class_distance_matrix", "davies_bouldin_score", "calinski_harabasz_score", "select_k",
            "separation_table", "class_scatter", "gaussian_fit", "gaussian_predict", "gaussian_classify_scene", "scatter_axes",
            "GaussianModel", "compact_zones", "zonal_stats", "zone_labels", "paint_zones", "classify_zones", "zone_confusion", "ZonalStats",
-           "zone_table"]
+           "zone_table", "slic_clusters", "slic_scene", "classify_superpixels", "zone_boundaries", "Superpixels"]

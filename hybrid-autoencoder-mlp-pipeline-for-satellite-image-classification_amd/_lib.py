@@ -183,6 +183,9 @@ _PROTOS = {
     "eae_zonal_accumulate": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int,
                                        C.c_longlong, C.c_int, vp, vp]),
     "eae_zonal_paint": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_longlong, C.c_longlong, vp]),
+    "eae_slic_step": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_longlong, vp, vp, vp]),
+    "eae_slic_centres": (C.c_int, [vp, vp, C.c_longlong, C.c_int, vp]),
+    "eae_map_regions_wide": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_longlong]),
 }
 
 EXPORTS = tuple(_PROTOS.keys())

@@ -1,7 +1,9 @@
 // Map post-processing (include/eae.h, "map post-processing"): what cleans a class map on the device.
 //   majority:     mode filter over a clipped (2r+1)^2 window, an int8 tile with its halo in LDS; the classes present in a window are
 //                 gathered into a 64-bit mask and only those are counted, the count in a scalar register per pass.
-//   regions:      connected-component labelling by union-find with union-by-minimum in three launches: every 32 x 32 tile is labelled
+//   regions:      (eae_map_regions for classes in [0, K), eae_map_regions_wide for arbitrary int64 labels: one set of kernels, templated
+//                 on how a cell's label is read and kept)
+//                 connected-component labelling by union-find with union-by-minimum in three launches: every 32 x 32 tile is labelled
 //                 in LDS and its parents written as global linear indices; the tile borders are merged with device-scope atomics on the
 //                 parent array; every cell is flattened to its root.  A root is the smallest linear index of its set, so the result is
 //                 unique: no dependence on the grid, on dispatch order or on the order in which the atomics arrive.
@@ -21,6 +23,19 @@ constexpr int MJ_SIDE = RG_T + 2 * MJ_RMAX;   // 46: tile + halo at the largest 
 constexpr int MJ_LD = 48;             // LDS row stride in bytes
 
 __device__ __forceinline__ int cls_of(long long v, int K) { return v >= 0 && v < (long long)K ? (int)v : -1; }
+
+// How the region kernels read a cell's label and keep it in LDS.  `read` maps the stored value to what two cells are compared by, a
+// negative result being "unclassified".  ClassCell: a class in [0, K), K <= 64, kept as int8 (eae_map_regions).  WideCell: any value
+// >= 0 is a label, kept and compared on all 64 bits (eae_map_regions_wide).
+struct ClassCell {
+  typedef signed char kept_t;
+  int K;
+  __device__ __forceinline__ kept_t read(long long v) const { return (kept_t)cls_of(v, K); }
+};
+struct WideCell {
+  typedef long long kept_t;
+  __device__ __forceinline__ kept_t read(long long v) const { return v >= 0 ? v : -1; }
+};
 
 // ---------------------------------------------------------------------------------------------------------------
 // Union-find with union-by-minimum.  Invariant: p[i] <= i, and a stored value only ever decreases (atomic min).  The root of a set is
@@ -55,25 +70,27 @@ __device__ __forceinline__ void uf_union(int* p, int a, int b) {
 // regions, first kernel: one 32 x 32 tile per workgroup.  Thread (lx, lyb) owns the cells (lx, lyb + 8 i), i < 4.  Cells outside
 // the map and unclassified cells carry class -1 and are never united.  parent[cell] = the global linear index of the cell's root in
 // the tile (the tile's smallest member of the set: row-major order is the same in the tile and in the map), -1 for an unclassified cell.
-__global__ __launch_bounds__(RG_NT) void regions_tile_kernel(const long long* __restrict__ labels, int H, int W, int K, int conn8,
+template <typename Cell>
+__global__ __launch_bounds__(RG_NT) void regions_tile_kernel(const long long* __restrict__ labels, int H, int W, Cell cell, int conn8,
                                                               int tilesX, int* __restrict__ parent) {
+  typedef typename Cell::kept_t kept_t;
   __shared__ int lp[RG_CELLS];
-  __shared__ signed char cl[RG_CELLS];
+  __shared__ kept_t cl[RG_CELLS];
   const int tile = blockIdx.x, ty0 = (tile / tilesX) * RG_T, tx0 = (tile % tilesX) * RG_T;
   const int tid = threadIdx.x, lx = tid & (RG_T - 1), lyb = tid >> 5;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int ly = lyb + 8 * i, li = ly * RG_T + lx, y = ty0 + ly, x = tx0 + lx;
-    int c = -1;
-    if (y < H && x < W) c = cls_of(labels[(size_t)y * W + x], K);
-    cl[li] = (signed char)c;
+    kept_t c = -1;
+    if (y < H && x < W) c = cell.read(labels[(size_t)y * W + x]);
+    cl[li] = c;
     lp[li] = li;
   }
   __syncthreads();
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int ly = lyb + 8 * i, li = ly * RG_T + lx;
-    const int c = cl[li];
+    const kept_t c = cl[li];
     if (c < 0) continue;
     if (lx > 0 && cl[li - 1] == c) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(lp, li, li - 1);
     if (ly > 0) {
@@ -103,7 +120,8 @@ __global__ __launch_bounds__(RG_NT) void regions_tile_kernel(const long long* __
 // their neighbours in the column to the left.  With 8-connectivity the two diagonal neighbours on the far side are taken as well; a
 // pair reached from both kinds of job is united twice, which changes nothing.  Every access to `parent` is a device-scope atomic:
 // workgroups on different XCDs work on the same chains, and a plain load may be served by another XCD's stale L2.
-__global__ __launch_bounds__(RG_NT) void regions_merge_kernel(const long long* __restrict__ labels, int H, int W, int K, int conn8,
+template <typename Cell>
+__global__ __launch_bounds__(RG_NT) void regions_merge_kernel(const long long* __restrict__ labels, int H, int W, Cell cell, int conn8,
                                                                long long nh, long long nv, int* parent) {
   long long j = (long long)blockIdx.x * RG_NT + threadIdx.x;
   long long me, o0, o1 = -1, o2 = -1;                          // the cell and its neighbours across the border; -1: none
@@ -123,11 +141,11 @@ __global__ __launch_bounds__(RG_NT) void regions_merge_kernel(const long long* _
   } else {
     return;
   }
-  const int c = cls_of(labels[me], K);
+  const typename Cell::kept_t c = cell.read(labels[me]);
   if (c < 0) return;
-  if (cls_of(labels[o0], K) == c) uf_union<__HIP_MEMORY_SCOPE_AGENT>(parent, (int)me, (int)o0);
-  if (o1 >= 0 && cls_of(labels[o1], K) == c) uf_union<__HIP_MEMORY_SCOPE_AGENT>(parent, (int)me, (int)o1);
-  if (o2 >= 0 && cls_of(labels[o2], K) == c) uf_union<__HIP_MEMORY_SCOPE_AGENT>(parent, (int)me, (int)o2);
+  if (cell.read(labels[o0]) == c) uf_union<__HIP_MEMORY_SCOPE_AGENT>(parent, (int)me, (int)o0);
+  if (o1 >= 0 && cell.read(labels[o1]) == c) uf_union<__HIP_MEMORY_SCOPE_AGENT>(parent, (int)me, (int)o1);
+  if (o2 >= 0 && cell.read(labels[o2]) == c) uf_union<__HIP_MEMORY_SCOPE_AGENT>(parent, (int)me, (int)o2);
 }
 
 // regions, third kernel: every cell walks to its root.  `parent` is read only here, behind a kernel boundary: plain loads.
@@ -292,31 +310,54 @@ extern "C" int eae_map_majority(void* stream, const long long* in, int H, int W,
   return 0;
 }
 
-extern "C" int eae_map_regions(void* stream, const long long* labels, int H, int W, int K, int connectivity, long long* regions,
-                               void* workspace, long long workspace_bytes) {
-  if (!map_dims_ok(H, W)) return eae_set_error(EAE_ERR_ARG, map_dims_msg);
-  if (!labels || !regions) return eae_set_error(EAE_ERR_ARG, "map_regions: NULL labels or regions");
-  if (K < 1 || K > 64) return eae_set_error(EAE_ERR_ARG, "map_regions: the number of classes must be in 1..64");
-  if (connectivity != 4 && connectivity != 8) return eae_set_error(EAE_ERR_ARG, "map_regions: the connectivity must be 4 or 8");
+namespace {
+
+// the three launches of a region labelling, for either kind of cell; `who` names the call in the messages
+template <typename Cell>
+int map_regions_run(const char* who, void* stream, const long long* labels, int H, int W, Cell cell, int connectivity, long long* regions,
+                    void* workspace, long long workspace_bytes) {
+  static thread_local char msg[160];
+  const char* what = nullptr;
+  if (!labels || !regions) what = "NULL labels or regions";
+  else if (connectivity != 4 && connectivity != 8) what = "the connectivity must be 4 or 8";
+  else if (!workspace || workspace_bytes < (long long)H * W * 8) what = "the workspace is NULL or smaller than eae_map_workspace_bytes";
+  if (what) {
+    snprintf(msg, sizeof msg, "%s: %s", who, what);
+    return eae_set_error(EAE_ERR_ARG, msg);
+  }
   const long long n = (long long)H * W;
-  if (!workspace || workspace_bytes < n * 8)
-    return eae_set_error(EAE_ERR_ARG, "map_regions: the workspace is NULL or smaller than eae_map_workspace_bytes");
   EAE_NO_GROUP("regions_tile_kernel");
   const hipStream_t st = (hipStream_t)stream;
   int* parent = (int*)workspace;
   const int conn8 = connectivity == 8;
   const int tilesX = (W + RG_T - 1) / RG_T, tilesY = (H + RG_T - 1) / RG_T;
-  hipLaunchKernelGGL(regions_tile_kernel, dim3((unsigned)((long long)tilesX * tilesY)), dim3(RG_NT), 0, st, labels, H, W, K, conn8, tilesX,
-                     parent);
+  hipLaunchKernelGGL(regions_tile_kernel<Cell>, dim3((unsigned)((long long)tilesX * tilesY)), dim3(RG_NT), 0, st, labels, H, W, cell, conn8,
+                     tilesX, parent);
   EAE_LAUNCH_CHECK();
   const long long nh = (long long)(tilesY - 1) * W, nv = (long long)(tilesX - 1) * H;
   if (nh + nv > 0) {
-    hipLaunchKernelGGL(regions_merge_kernel, dim3(cell_blocks(nh + nv)), dim3(RG_NT), 0, st, labels, H, W, K, conn8, nh, nv, parent);
+    hipLaunchKernelGGL(regions_merge_kernel<Cell>, dim3(cell_blocks(nh + nv)), dim3(RG_NT), 0, st, labels, H, W, cell, conn8, nh, nv,
+                       parent);
     EAE_LAUNCH_CHECK();
   }
   hipLaunchKernelGGL(regions_flatten_kernel, dim3(cell_blocks(n)), dim3(RG_NT), 0, st, (const int*)parent, n, regions);
   EAE_LAUNCH_CHECK();
   return 0;
+}
+
+}  // namespace
+
+extern "C" int eae_map_regions(void* stream, const long long* labels, int H, int W, int K, int connectivity, long long* regions,
+                               void* workspace, long long workspace_bytes) {
+  if (!map_dims_ok(H, W)) return eae_set_error(EAE_ERR_ARG, map_dims_msg);
+  if (K < 1 || K > 64) return eae_set_error(EAE_ERR_ARG, "map_regions: the number of classes must be in 1..64");
+  return map_regions_run("map_regions", stream, labels, H, W, ClassCell{K}, connectivity, regions, workspace, workspace_bytes);
+}
+
+extern "C" int eae_map_regions_wide(void* stream, const long long* labels, int H, int W, int connectivity, long long* regions,
+                                    void* workspace, long long workspace_bytes) {
+  if (!map_dims_ok(H, W)) return eae_set_error(EAE_ERR_ARG, map_dims_msg);
+  return map_regions_run("map_regions_wide", stream, labels, H, W, WideCell{}, connectivity, regions, workspace, workspace_bytes);
 }
 
 extern "C" int eae_map_region_stats(void* stream, const long long* regions, int H, int W, int* area, int* bbox) {

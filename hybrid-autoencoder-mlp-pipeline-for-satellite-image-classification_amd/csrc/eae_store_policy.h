@@ -33,3 +33,9 @@
 #ifndef EAE_WT_ZONAL
 #define EAE_WT_ZONAL 16
 #endif
+// SLIC: the label store of slic_step (eae_slic.hip), written by the last iteration only: a wave's 64 four-byte stores cover 256
+// consecutive bytes of an int32 raster that nothing in the launch reads back.  Write-through like ZONAL, the family of the same shape
+// (tools/slic_bench.py times the pass; -DEAE_WT_SLIC=0 builds the plain form, which was not measured).
+#ifndef EAE_WT_SLIC
+#define EAE_WT_SLIC 16
+#endif

@@ -7,7 +7,9 @@ functions smooth them before `scene_confusion` scores them, without a trip to th
 A map is an int64 [H, W] tensor on a HIP device, as `classify_scene` returns it: values in [0, num_classes) are classes,
 num_classes in 1..64 (`scene_confusion`'s limit), every other value -- the -1 of a window that was not run included -- is
 "unclassified".  H, W >= 1 and H * W < 2^31.  Every function is stateless, runs on the current stream and reads nothing back unless
-it says so; all results are integers that the semantics define uniquely, so they are identical from run to run.
+it says so; all results are integers that the semantics define uniquely, so they are identical from run to run.  `label_regions`,
+`region_table` and `sieve` also take ``num_classes=None``: the map then holds arbitrary labels (cluster ids, parcel ids), any value
+>= 0 a label compared on all 64 bits, negatives unclassified (`eae_map_regions_wide`; `segment.py` builds its zones this way).
 
 - `majority_filter`: the mode of the classified cells of a clipped (2r+1)^2 window, `passes` times;
 - `label_regions`: connected regions (4- or 8-connectivity), a region's id the smallest linear index y * W + x of its cells;
@@ -42,8 +44,18 @@ def _map_arg(t, what="labels"):
     return h, w
 
 
-def _classes_arg(k):
+def _classes_arg(k, wide=False):
+    """num_classes in 1..64; with ``wide``, None as well: any non-negative value of the map is then a label."""
+    if wide and k is None:
+        return None
     return _int_arg(k, "num_classes", 1, MAX_CLASSES)
+
+
+def _device_arg(device, k):
+    """`_require_gpu`, naming the path the caller asked for when that is the one over arbitrary labels."""
+    if k is None and (device.type != "cuda" or not torch.cuda.is_available()):
+        raise RuntimeError("num_classes=None (arbitrary labels) runs on a HIP device only, like every function here; there is no CPU path")
+    _require_gpu(device)
 
 
 def _connectivity_arg(c):
@@ -61,9 +73,14 @@ def _workspace(h, w, device):
 
 # ---------------------------------------------------------------------------------------------------- the C calls
 def _regions(labels, k, connectivity, ws):
+    """k = None: `eae_map_regions_wide`, every value >= 0 a label."""
     h, w = labels.shape
     regions = torch.empty_like(labels)
-    check(_lib.load().eae_map_regions(_stream(), _ptr(labels), h, w, k, connectivity, _ptr(regions), _ptr(ws), ws.numel()))
+    lib = _lib.load()
+    if k is None:
+        check(lib.eae_map_regions_wide(_stream(), _ptr(labels), h, w, connectivity, _ptr(regions), _ptr(ws), ws.numel()))
+    else:
+        check(lib.eae_map_regions(_stream(), _ptr(labels), h, w, k, connectivity, _ptr(regions), _ptr(ws), ws.numel()))
     return regions
 
 
@@ -102,22 +119,26 @@ def majority_filter(labels, num_classes, radius=1, fill=False, passes=1):
 def label_regions(labels, num_classes, connectivity=4):
     """regions int64 [H, W]: the region of every classified cell, -1 for an unclassified one.  A region is a maximal set of cells that
     share one class and are connected through edges (``connectivity=4``) or edges and corners (8).  A region's id is the smallest
-    linear index y * W + x of its cells: the result is unique, whatever the launch geometry or the order in which tiles are merged."""
+    linear index y * W + x of its cells: the result is unique, whatever the launch geometry or the order in which tiles are merged.
+    ``num_classes=None``: any non-negative value is a label, compared on all 64 bits (cluster ids, parcel ids), negatives are
+    unclassified."""
     h, w = _map_arg(labels)
-    k = _classes_arg(num_classes)
+    k = _classes_arg(num_classes, wide=True)
     connectivity = _connectivity_arg(connectivity)
-    _require_gpu(labels.device)
+    _device_arg(labels.device, k)
     labels = labels.contiguous()
     with torch.cuda.device(labels.device):
         return _regions(labels, k, connectivity, _workspace(h, w, labels.device))
 
 
-def region_table(labels, regions):
+def region_table(labels, regions, num_classes=None):
     """The regions of `label_regions(labels, ...)` as a dict of device tensors, rows by ascending region id: ``id`` int64 [R], ``cls``
     int64 [R] (the class of the region's cells), ``area`` int64 [R] (cells) and ``bbox`` int64 [R, 4] = (y0, x0, y1, x1), inclusive.
     Areas and boxes are integer atomics on the device (exact); compacting them to R rows reads R back, the function's one host
-    read-back."""
+    read-back.  The table is read off ``regions`` alone, so it is the same for class maps and for maps of arbitrary labels;
+    ``num_classes`` (None, or what `label_regions` was given) is checked and otherwise unused."""
     h, w = _map_arg(labels)
+    _classes_arg(num_classes, wide=True)
     if _map_arg(regions, "regions") != (h, w):
         raise RuntimeError(f"regions has shape {list(regions.shape)}, labels {[h, w]}")
     if regions.device != labels.device:
@@ -142,13 +163,14 @@ def sieve(labels, num_classes, min_size, connectivity=4, passes=1, return_change
     6. unclassified cells never change and are never candidates.
 
     Exactly ``passes`` passes run, each on the previous one's output, and nothing is read back.  ``return_changed=True``: returns
-    (map, changed), changed a 0-d int64 device tensor, the number of cells whose class changed in the last pass."""
+    (map, changed), changed a 0-d int64 device tensor, the number of cells whose class changed in the last pass.
+    ``num_classes=None``: any non-negative value is a label (`label_regions`)."""
     h, w = _map_arg(labels)
-    k = _classes_arg(num_classes)
+    k = _classes_arg(num_classes, wide=True)
     min_size = _int_arg(min_size, "min_size", 1, 2 ** 63 - 1)
     connectivity = _connectivity_arg(connectivity)
     passes = _int_arg(passes, "passes", 1, 2 ** 31 - 1)
-    _require_gpu(labels.device)
+    _device_arg(labels.device, k)
     src = labels.contiguous()
     lib = _lib.load()
     changed = torch.empty((), dtype=torch.int64, device=src.device) if return_changed else None

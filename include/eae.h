@@ -914,6 +914,42 @@ int eae_zonal_accumulate(void* stream, const void* zones, int zone_elem_bytes, i
 int eae_zonal_paint(void* stream, const void* zones, int zone_elem_bytes, int H, int W, const long long* values, long long Z,
                     long long fill, long long* out);
 
+/* ------------------------------------------------------------------ superpixels -------------------- */
+/* SLIC superpixels of a scene (no reference counterpart): the segmenter that gives eae_zonal_accumulate a zone
+ * raster.  Integers only, so sums, centres and labels are unique for given inputs, whatever the launch geometry.  data is a device
+ * scene [C][H][W] of dtype EAE_SCENE_U8 / U16 / F32, C in 1..16, H, W >= 1 and H * W < 2^31; divisor a device float [C]; mask NULL or
+ * uint8 [H][W] (non-zero: the pixel takes no part).  The plain arguments are all there is: no window geometry.
+ *   Feature: u_c(y, x) = rint(65535 * min(max(v / d_c, 0), 1)), an integer in 0..65535, evaluated in double from the stored value and
+ *   the float divisor (both converted to double), round-half-even, NaN -> 0 (the comparisons in the order of the zonal q).
+ *   Grid: step S in 2..256, n_h = ceil(H / S), n_w = ceil(W / S); cluster k = i * n_w + j belongs to cell (i, j), the home cell of a
+ *   pixel is (y / S, x / S); n_h * n_w * (C + 3) <= 2^31 - 1.
+ *   Tables: sums int64 [n_h * n_w][C + 3] = (count, sum y, sum x, sum u_0, ..); centres int32 of the same shape = (count, cy, cx,
+ *   mu_0, ..), every mean (2 sum + n) / (2 n) in integers, an empty cluster (n = 0) all zeros.
+ *
+ * eae_slic_step: one iteration.  centres_in == NULL: every unmasked pixel belongs to its home cluster (iteration 0).  Otherwise a
+ * pixel considers the clusters of the cells (i + di, j + dj), di, dj in {-1, 0, 1}, of its home cell (i, j) that lie inside the grid
+ * and have count > 0, and takes the one with the smallest
+ *     D = S^2 * sum_c (u_c - mu_c)^2 + spatial_weight * ((y - cy)^2 + (x - cx)^2)     (64-bit integers; 0 <= spatial_weight <= 2^40)
+ * the lowest cluster id on a tie.  centres_in must come from sums of an earlier step of the same scene (then every pixel has a
+ * candidate, and |y - cy|, |x - cx| < 3 S keep D below 2^63).  sums_out is cleared by the call, on the stream, and receives the sums of
+ * the new assignment; labels_out (int32 [H][W], or NULL: nothing is written, intermediate iterations need no labels) receives the
+ * chosen cluster, -1 for a masked pixel.  A masked pixel contributes nothing.
+ *
+ * eae_slic_centres: centres from sums, one thread per entry; n_clusters >= 1, n_clusters * (C + 3) <= 2^31 - 1.
+ *
+ * eae_map_regions_wide: eae_map_regions for maps whose labels are arbitrary int64 values: any value >= 0 is a label, compared on all
+ * 64 bits, a negative value is unclassified.  The same kernels (templated on how a cell's label is read and kept), the same ids, the
+ * same workspace.
+ *
+ * Rejected (EAE_ERR_ARG, nothing launched, the call's name in eae_last_error()): a NULL data, divisor, sums_out, sums, centres, labels,
+ * regions or workspace; an unknown dtype or a data pointer that is no multiple of the element size; C, H, W, the step, the spatial
+ * weight, the grid or n_clusters outside the limits above; a connectivity other than 4 or 8; a workspace that is too small. */
+int eae_slic_step(void* stream, const void* data, int dtype, int C, int H, int W, const float* divisor, const unsigned char* mask,
+                  int step, long long spatial_weight, const int* centres_in, long long* sums_out, int* labels_out);
+int eae_slic_centres(void* stream, const long long* sums, long long n_clusters, int C, int* centres);
+int eae_map_regions_wide(void* stream, const long long* labels, int H, int W, int connectivity, long long* regions, void* workspace,
+                         long long workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif
