@@ -37,6 +37,10 @@ __global__ EAE_NO_PK __launch_bounds__(256) void scene_windows_kernel(const T* _
 // VALID: over the valid ones of them only (labels >= 0): the same (i, then j) summation order, divided by the float count of valid
 // covering windows; a cell without one gets probabilities 0 and label -1.  (labels is the last argument, read by VALID only: the plain
 // form keeps the argument block it had as a kernel of its own.)
+// Worked: a 2 x 2 grid, k = 2, two classes, probs[0] = {{.5, .25}, {.75, 1}}, probs[1] = 1 - probs[0]; 3 x 3 cells.  Cell (0, 0) has
+// window (0, 0) alone: .5 / .5, a tie, label 0 (the lowest class).  Cell (0, 1): (.5 + .25) / 2 = .375 against .625, label 1.  Cell
+// (1, 1): (.5 + .25 + .75 + 1) / 4 = .625, label 0.  VALID with window (0, 1) invalid: cell (0, 2), covered by that window alone, is
+// 0 / 0 with label -1; cell (0, 1) is window (0, 0)'s .5 / .5, label 0; cell (1, 1) is (.5 + .75 + 1) / 3 = .75 against .25, label 0.
 template <bool VALID>
 __global__ EAE_NO_PK __launch_bounds__(256) void scene_blend_kernel(const float* __restrict__ probs, int K, int nH, int nW, int k,
                                                                 float* __restrict__ cell, long long* __restrict__ cell_labels,

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import eae_amd
+import nodata_ref
 from eae_amd import _lib
 from eae_amd.engine import _stream, _ptr
 from scene_util import _scene, _divisor, _model, _mlp
@@ -152,6 +153,12 @@ def test_partial_batches_and_window_lists(mode):
     assert torch.equal(torch.isnan(rec), torch.isnan(rr)) and torch.equal(torch.nan_to_num(rec, nan=-1.0), torch.nan_to_num(rr, nan=-1.0))
 
 
+def _counts_np(host, mask, pads, mode, fill, nodata, rule):
+    """the border counts by NumPy alone (tests/nodata_ref.py): pad_ref, then the cumulative-sum counts -- no device in the oracle"""
+    ps, pm = nodata_ref.pad_ref(host, mask, pads, mode, fill)
+    return nodata_ref.counts_ref(nodata_ref.rows_ref(nodata_ref.invalid_ref(ps, nodata, rule, pm), P, 32), P, 32)
+
+
 def _invalid_scene():
     """Case A's scene with a block of nodata (0 in every band) near the top-left corner and a mask block near the bottom-right one,
     both within pad distance (14 rows, 5 columns) of the border, so that reflect mirrors them, and both off the outermost row and
@@ -180,9 +187,15 @@ def test_nodata_and_mask_counts_and_classification(mode):
     for rule in ("all", "any"):
         got = eae_amd.window_invalid_counts(scene, P, 32, nodata=0, mask=dmask, rule=rule, **kw)
         assert got.shape == (3, 4) and torch.equal(got, eae_amd.window_invalid_counts(padded, P, 32, nodata=0, mask=pmask, rule=rule))
+        assert np.array_equal(got.cpu().numpy(), _counts_np(host, mask, pads, mode, FILL, 0, rule))
     assert torch.equal(eae_amd.window_invalid_counts(scene, P, 32, nodata=0, mask=dmask, **kw), ref[mode])
     assert torch.equal(eae_amd.window_invalid_counts(scene, P, 32, mask=dmask.bool(), **kw),
                        eae_amd.window_invalid_counts(padded, P, 32, mask=pmask))
+    assert np.array_equal(eae_amd.window_invalid_counts(scene, P, 32, mask=dmask.bool(), **kw).cpu().numpy(),
+                          _counts_np(host, mask, pads, mode, FILL, None, "all"))
+    np_ref = {m: _counts_np(host, mask, pads, m, FILL, 0, "all") for m in MODES}
+    assert all(np.array_equal(ref[m].cpu().numpy(), np_ref[m]) for m in MODES)
+    assert not np.array_equal(np_ref["constant"], np_ref["edge"]) and not np.array_equal(np_ref["edge"], np_ref["reflect"])
     ids = eae_amd.valid_windows(scene, P, 32, nodata=0, mask=dmask, max_invalid=0.1, **kw)
     assert torch.equal(ids, eae_amd.valid_windows(padded, P, 32, nodata=0, mask=pmask, max_invalid=0.1))
     for blend in (False, True):
@@ -200,14 +213,19 @@ def test_constant_fill_matching_nodata_is_invalid():
     got = eae_amd.window_invalid_counts(scene, P, 32, nodata=0, border="constant", fill=0)
     ref = eae_amd.window_invalid_counts(torch.from_numpy(_np_pad(host, pads, "constant", 0)).cuda(), P, 32, nodata=0)
     assert torch.equal(got, ref)
+    assert np.array_equal(got.cpu().numpy(), _counts_np(host, None, pads, "constant", 0, 0, "all"))
     # window (0, 0) holds 50 x 59 real pixels: every other pixel of it is padding, and invalid
     assert int(got[0, 0]) >= P * P - 50 * 59
     other = eae_amd.window_invalid_counts(scene, P, 32, nodata=0, border="constant", fill=FILL)
     assert int(other[0, 0]) == int(got[0, 0]) - (P * P - 50 * 59)
+    assert np.array_equal(other.cpu().numpy(), _counts_np(host, None, pads, "constant", FILL, 0, "all"))
     # fp32: NaN fill against a NaN nodata
     f = _case("C")[0]
     cnt = eae_amd.window_invalid_counts(f, P, 48, nodata=float("nan"), border="constant", fill=float("nan"))
     assert cnt.shape == (1, 4) and int(cnt[0, 1]) == P * P - 40 * P
+    nan = float("nan")
+    ps, _ = nodata_ref.pad_ref(f.cpu().numpy(), None, eae_amd.border_grid(40, 200, P, 48)[2], "constant", nan)
+    assert np.array_equal(cnt.cpu().numpy(), nodata_ref.counts_ref(nodata_ref.rows_ref(nodata_ref.invalid_ref(ps, nan, "all", None), P, 48), P, 48))
 
 
 def test_c_level_rejects():
