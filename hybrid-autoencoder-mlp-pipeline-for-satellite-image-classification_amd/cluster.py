@@ -22,10 +22,10 @@ import torch
 
 from . import _lib
 from ._lib import check
+from ._args import MAX_L, _alloc_workspace, _int_arg, _label_counts, _rows_arg          # noqa: F401  (importable from here as before)
 from .engine import _ptr, _stream, _require_gpu
 
 MAX_K = 256
-MAX_L = 256
 
 
 class KMeansResult(NamedTuple):
@@ -41,26 +41,6 @@ class KMeansResult(NamedTuple):
 
 
 # ---------------------------------------------------------------------------------------------------- host-side validation
-def _rows_arg(t, what, shape="[rows, L]", most=2 ** 31 - 1):
-    """(rows, width) of a float32 [rows, L] tensor, 1 <= L <= MAX_L and 1 <= rows <= most: the one check of latents, centroids, queries
-    and banks (neighbors.py shares it)."""
-    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32:
-        raise RuntimeError(f"{what} must be a float32 tensor {shape}")
-    n, width = int(t.shape[0]), int(t.shape[1])
-    if not 1 <= width <= MAX_L:
-        raise RuntimeError(f"the latent width of {what} must be in 1..{MAX_L}, got {width}")
-    if not 1 <= n <= most:
-        raise RuntimeError(f"the number of rows of {what} must be in 1..{'2^31-1' if most == 2 ** 31 - 1 else most}, got {n}")
-    return n, width
-
-
-def _int_arg(v, name, lo, hi):
-    """An integer argument in lo..hi (bool is no integer here)."""
-    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not lo <= int(v) <= hi:
-        raise RuntimeError(f"{name} must be an integer in {lo}..{hi}, got {v!r}")
-    return int(v)
-
-
 def _k_arg(k, n=None):
     k = _int_arg(k, "k", 1, MAX_K)
     if n is not None and k > n:
@@ -76,11 +56,6 @@ def _centroids_arg(centroids, width, device=None):
     if device is not None and centroids.device != device:
         raise RuntimeError(f"centroids are on {centroids.device}, the latents on {device}")
     return k
-
-
-def _label_counts(labels, k):
-    """Rows per label in [0, k), int64 [k] (integer adds: exact; -1 lands in the dropped slot 0)."""
-    return torch.zeros(k + 1, dtype=torch.int64, device=labels.device).scatter_add_(0, labels + 1, torch.ones_like(labels))[1:]
 
 
 def _fit_args(n, width, k, max_iter, tol, init, device=None):
@@ -106,10 +81,7 @@ def _assign(z, centroids, labels, dist, changed=None, have_prev=False):
 
 
 def _workspace(z, k):
-    nbytes = _lib.load().eae_kmeans_workspace_bytes(z.shape[0], z.shape[1], k)
-    if nbytes < 0:
-        check(int(nbytes))
-    return torch.empty(nbytes, dtype=torch.uint8, device=z.device)
+    return _alloc_workspace(_lib.load().eae_kmeans_workspace_bytes(z.shape[0], z.shape[1], k), z.device)
 
 
 def _update(z, labels, centroids, counts, ws):

@@ -15,7 +15,6 @@ constexpr int KM_NT = 256;        // threads per workgroup: 4 waves
 constexpr int KM_ROWS = 128;      // assign: rows of z per workgroup tile, 32 per wave
 constexpr int KM_LC = 64;         // assign: columns of z and c staged per pass
 constexpr int KM_LDS = KM_LC + 2; // LDS row stride in floats: lane (r, h) reads word r * 66 + kk + h -> bank 2r + h + kk, 64 different banks
-constexpr int KM_MAXK = 256;
 
 // ---------------------------------------------------------------------------------------------------------------
 // assign.  Workgroup tile = 128 rows; wave w owns rows 32 w .. 32 w + 31 of it.  The columns are walked in passes of 64: the z tile's
@@ -145,7 +144,7 @@ struct UpdateArgs {
 template <int KT>
 __global__ EAE_NO_PK __launch_bounds__(KM_NT) void kmeans_partial_kernel(UpdateArgs a) {
   __shared__ float red[KT * 16 * 64];
-  __shared__ int hist[KM_MAXK];
+  __shared__ int hist[LATENT_MAXK];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
   const int L = a.L, K = a.K, lt = blockIdx.y;
   const long long g = blockIdx.x, N = a.N;
@@ -196,7 +195,7 @@ __global__ EAE_NO_PK __launch_bounds__(KM_NT) void kmeans_partial_kernel(UpdateA
   }
 
   if (lt == 0) {
-    for (int k = tid; k < KM_MAXK; k += KM_NT) hist[k] = 0;
+    for (int k = tid; k < LATENT_MAXK; k += KM_NT) hist[k] = 0;
     __syncthreads();
     for (long long n = r0 + tid; n < r1; n += KM_NT) {
       const long long lb = a.labels[n];
@@ -233,17 +232,12 @@ __global__ EAE_NO_PK __launch_bounds__(KM_NT) void kmeans_finalize_kernel(FinalA
   }
 }
 
-int kmeans_dims_ok(long long N, int L, int K) {
-  return latent_dims_ok(N, L) && K >= 1 && K <= KM_MAXK;
-}
-int kmeans_kt(int K) { return K <= 32 ? 1 : K <= 64 ? 2 : K <= 128 ? 4 : 8; }
-
 // The update's geometry, a function of (N, L, K) alone: G row chunks of rpc rows (a multiple of 64: whole 16-row groups for 4 waves),
 // as many as keep the partials near 32 MB, between 128 and 2048, and no more than the rows fill.
 struct UpdatePlan { int Kp, Lp; long long rpc, G; };
 UpdatePlan kmeans_update_plan(long long N, int L, int K) {
   UpdatePlan p;
-  p.Kp = kmeans_kt(K) * 32;
+  p.Kp = latent_tiles32(K) * 32;
   p.Lp = (L + 31) & ~31;
   long long gmax = (32LL << 20) / ((long long)p.Kp * p.Lp * 4);
   gmax = gmax < 128 ? 128 : gmax > 2048 ? 2048 : gmax;
@@ -257,9 +251,7 @@ UpdatePlan kmeans_update_plan(long long N, int L, int K) {
 template <int KT> int launch_assign(hipStream_t st, const AssignArgs& a) {
   const size_t lds = ((size_t)(KM_ROWS + KT * 32) * KM_LDS + KT * 32) * sizeof(float);
   EAE_HIP(eae_smem_attr((const void*)kmeans_assign_kernel<KT>, lds));
-  const long long ntiles = (a.N + KM_ROWS - 1) / KM_ROWS;
-  const unsigned grid = (unsigned)(ntiles < 512 ? ntiles : 512);          // two workgroups on each of 256 CUs, striding over the tiles
-  hipLaunchKernelGGL(kmeans_assign_kernel<KT>, dim3(grid), dim3(KM_NT), lds, st, a);
+  hipLaunchKernelGGL(kmeans_assign_kernel<KT>, dim3(latent_row_tile_grid(a.N, KM_ROWS)), dim3(KM_NT), lds, st, a);
   EAE_LAUNCH_CHECK();
   return 0;
 }
@@ -272,50 +264,37 @@ template <int KT> int launch_partial(hipStream_t st, const UpdateArgs& a, const 
 }  // namespace
 
 extern "C" long long eae_kmeans_workspace_bytes(long long N, int L, int K) {
-  if (!kmeans_dims_ok(N, L, K)) return eae_set_error(EAE_ERR_ARG, "kmeans: N must be in 1..2^31-1, L and K in 1..256");
+  if (!latent_dims_ok(N, L, K)) return eae_set_error(EAE_ERR_ARG, "kmeans: N must be in 1..2^31-1, L and K in 1..256");
   const UpdatePlan p = kmeans_update_plan(N, L, K);
   return p.G * p.Kp * p.Lp * (long long)sizeof(float);
 }
 
 extern "C" int eae_kmeans_assign(void* stream, const float* z, long long N, int L, const float* centroids, int K, long long* labels,
                                  int have_prev, float* dist, long long* changed) {
-  if (!kmeans_dims_ok(N, L, K)) return eae_set_error(EAE_ERR_ARG, "kmeans_assign: N must be in 1..2^31-1, L and K in 1..256");
+  if (!latent_dims_ok(N, L, K)) return eae_set_error(EAE_ERR_ARG, "kmeans_assign: N must be in 1..2^31-1, L and K in 1..256");
   if (!z || !centroids || !labels) return eae_set_error(EAE_ERR_ARG, "kmeans_assign: NULL z, centroids or labels");
   EAE_NO_GROUP("kmeans_assign_kernel");
   const hipStream_t st = (hipStream_t)stream;
   const bool count = have_prev != 0 && changed != nullptr;
   if (count && hipMemsetAsync(changed, 0, sizeof(long long), st) != hipSuccess)
     return eae_set_error(EAE_ERR_HIP, "kmeans_assign: clearing the changed counter failed");
-  const AssignArgs a = {z, centroids, N, L, K, labels, have_prev != 0, dist, count ? (unsigned long long*)changed : nullptr,
-                        (L & 3) == 0 && ((uintptr_t)z & 15) == 0};
-  switch (kmeans_kt(K)) {
-    case 1: return launch_assign<1>(st, a);
-    case 2: return launch_assign<2>(st, a);
-    case 4: return launch_assign<4>(st, a);
-    default: return launch_assign<8>(st, a);
-  }
+  const AssignArgs a = {z, centroids, N, L, K, labels, have_prev != 0, dist, count ? (unsigned long long*)changed : nullptr, latent_vec16(z, L)};
+  return latent_for_tiles(latent_tiles32(K), [&](auto kt) { return launch_assign<kt.value>(st, a); });
 }
 
 extern "C" int eae_kmeans_update(void* stream, const float* z, long long N, int L, const long long* labels, int K, float* centroids,
                                  long long* counts, void* workspace, long long workspace_bytes) {
-  if (!kmeans_dims_ok(N, L, K)) return eae_set_error(EAE_ERR_ARG, "kmeans_update: N must be in 1..2^31-1, L and K in 1..256");
+  if (!latent_dims_ok(N, L, K)) return eae_set_error(EAE_ERR_ARG, "kmeans_update: N must be in 1..2^31-1, L and K in 1..256");
   if (!z || !labels || !centroids || !counts) return eae_set_error(EAE_ERR_ARG, "kmeans_update: NULL z, labels, centroids or counts");
   const UpdatePlan p = kmeans_update_plan(N, L, K);
-  if (!workspace || workspace_bytes < p.G * p.Kp * p.Lp * (long long)sizeof(float))
-    return eae_set_error(EAE_ERR_ARG, "kmeans_update: the workspace is NULL or smaller than eae_kmeans_workspace_bytes");
+  if (const int rc = latent_workspace_check(workspace, workspace_bytes, p.G * p.Kp * p.Lp * (long long)sizeof(float),
+                                            "kmeans_update: the workspace is NULL or smaller than eae_kmeans_workspace_bytes")) return rc;
   EAE_NO_GROUP("kmeans_partial_kernel");
   const hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(counts, 0, (size_t)K * sizeof(long long), st) != hipSuccess)
     return eae_set_error(EAE_ERR_HIP, "kmeans_update: clearing counts failed");
   const UpdateArgs a = {z, labels, N, L, K, p.rpc, (float*)workspace, p.Kp, p.Lp, (unsigned long long*)counts};
-  int rc;
-  switch (kmeans_kt(K)) {
-    case 1: rc = launch_partial<1>(st, a, p); break;
-    case 2: rc = launch_partial<2>(st, a, p); break;
-    case 4: rc = launch_partial<4>(st, a, p); break;
-    default: rc = launch_partial<8>(st, a, p); break;
-  }
-  if (rc) return rc;
+  if (const int rc = latent_for_tiles(latent_tiles32(K), [&](auto kt) { return launch_partial<kt.value>(st, a, p); })) return rc;
   const FinalArgs f = {(const float*)workspace, p.G, p.Kp, p.Lp, L, (const unsigned long long*)counts, centroids};
   hipLaunchKernelGGL(kmeans_finalize_kernel, dim3(K), dim3(KM_NT), 0, st, f);
   EAE_LAUNCH_CHECK();

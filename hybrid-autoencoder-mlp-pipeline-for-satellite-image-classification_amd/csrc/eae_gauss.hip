@@ -14,7 +14,6 @@
 
 namespace {
 
-constexpr int GS_MAXK = 256;
 
 // ---------------------------------------------------------------------------------------------------------------
 // scatter, first kernel.  One wave a workgroup, (g, p, k): chunk g of class k's segment of `order`, tile pair p = (ti <= tj).  The segment
@@ -96,8 +95,6 @@ __global__ EAE_NO_PK __launch_bounds__(256) void gauss_scatter_finalize_kernel(S
     }
   }
 }
-
-int gauss_dims_ok(long long N, int L, int K) { return latent_dims_ok(N, L) && K >= 1 && K <= GS_MAXK; }
 
 // The scatter's geometry, a function of (N, L, K) alone: T tile pairs and G chunks a class, one chunk for every 1024 rows of z, at most
 // 256 and no more than keep the partials near 64 MB.
@@ -235,14 +232,10 @@ __global__ EAE_NO_PK __launch_bounds__(GS_NT, 2) void gauss_score_kernel(ScoreAr
   }
 }
 
-int gauss_jt(int L) { return L <= 32 ? 1 : L <= 64 ? 2 : L <= 128 ? 4 : 8; }
-
 template <int JT> int launch_score(hipStream_t st, const ScoreArgs& a) {
   const size_t lds = ((size_t)GS_ROWS * (gs_lc(JT) + 2) + (size_t)gs_lc(JT) * gs_ws(JT) + gs_lc(JT)) * sizeof(float);
   EAE_HIP(eae_smem_attr((const void*)gauss_score_kernel<JT>, lds));
-  const long long ntiles = (a.N + GS_ROWS - 1) / GS_ROWS;
-  const unsigned grid = (unsigned)(ntiles < 512 ? ntiles : 512);          // two workgroups on each of 256 CUs, striding over the tiles
-  hipLaunchKernelGGL(gauss_score_kernel<JT>, dim3(grid), dim3(GS_NT), lds, st, a);
+  hipLaunchKernelGGL(gauss_score_kernel<JT>, dim3(latent_row_tile_grid(a.N, GS_ROWS)), dim3(GS_NT), lds, st, a);
   EAE_LAUNCH_CHECK();
   return 0;
 }
@@ -250,19 +243,19 @@ template <int JT> int launch_score(hipStream_t st, const ScoreArgs& a) {
 }  // namespace
 
 extern "C" long long eae_class_scatter_workspace_bytes(long long N, int L, int K) {
-  if (!gauss_dims_ok(N, L, K)) return eae_set_error(EAE_ERR_ARG, "class_scatter: N must be in 1..2^31-1, L and K in 1..256");
+  if (!latent_dims_ok(N, L, K)) return eae_set_error(EAE_ERR_ARG, "class_scatter: N must be in 1..2^31-1, L and K in 1..256");
   return gauss_scatter_bytes(gauss_scatter_plan(N, L, K), K);
 }
 
 extern "C" int eae_class_scatter(void* stream, const float* z, long long N, int L, const long long* labels, const long long* order,
                                  const long long* seg, int K, const float* means, float* scatter, void* workspace,
                                  long long workspace_bytes) {
-  if (!gauss_dims_ok(N, L, K)) return eae_set_error(EAE_ERR_ARG, "class_scatter: N must be in 1..2^31-1, L and K in 1..256");
+  if (!latent_dims_ok(N, L, K)) return eae_set_error(EAE_ERR_ARG, "class_scatter: N must be in 1..2^31-1, L and K in 1..256");
   if (!z || !labels || !order || !seg || !means || !scatter)
     return eae_set_error(EAE_ERR_ARG, "class_scatter: NULL z, labels, order, seg, means or scatter");
   const ScatterPlan p = gauss_scatter_plan(N, L, K);
-  if (!workspace || workspace_bytes < gauss_scatter_bytes(p, K))
-    return eae_set_error(EAE_ERR_ARG, "class_scatter: the workspace is NULL or smaller than eae_class_scatter_workspace_bytes");
+  if (const int rc = latent_workspace_check(workspace, workspace_bytes, gauss_scatter_bytes(p, K),
+                                            "class_scatter: the workspace is NULL or smaller than eae_class_scatter_workspace_bytes")) return rc;
   EAE_NO_GROUP("gauss_scatter_kernel");
   const hipStream_t st = (hipStream_t)stream;
   const ScatterArgs a = {z, labels, order, seg, means, N, L, K, p.G, p.T, (float*)workspace};
@@ -276,17 +269,12 @@ extern "C" int eae_class_scatter(void* stream, const float* z, long long N, int 
 
 extern "C" int eae_gauss_score(void* stream, const float* z, long long N, int L, const float* mu, const float* W, long long w_stride,
                                const float* offset, int K, long long* labels, float* maha, float* best, float* scores) {
-  if (!gauss_dims_ok(N, L, K)) return eae_set_error(EAE_ERR_ARG, "gauss_score: N must be in 1..2^31-1, L and K in 1..256");
+  if (!latent_dims_ok(N, L, K)) return eae_set_error(EAE_ERR_ARG, "gauss_score: N must be in 1..2^31-1, L and K in 1..256");
   if (!z || !mu || !W || !offset || !labels) return eae_set_error(EAE_ERR_ARG, "gauss_score: NULL z, mu, W, offset or labels");
   if (w_stride != 0 && w_stride != (long long)L * L)
     return eae_set_error(EAE_ERR_ARG, "gauss_score: w_stride must be L * L (a matrix a class) or 0 (one shared matrix)");
   EAE_NO_GROUP("gauss_score_kernel");
   const hipStream_t st = (hipStream_t)stream;
-  const ScoreArgs a = {z, N, L, K, mu, W, w_stride, offset, labels, maha, best, scores, (L & 3) == 0 && ((uintptr_t)z & 15) == 0};
-  switch (gauss_jt(L)) {
-    case 1: return launch_score<1>(st, a);
-    case 2: return launch_score<2>(st, a);
-    case 4: return launch_score<4>(st, a);
-    default: return launch_score<8>(st, a);
-  }
+  const ScoreArgs a = {z, N, L, K, mu, W, w_stride, offset, labels, maha, best, scores, latent_vec16(z, L)};
+  return latent_for_tiles(latent_tiles32(L), [&](auto jt) { return launch_score<jt.value>(st, a); });
 }

@@ -220,9 +220,8 @@ extern "C" int eae_knn_search(void* stream, const float* q, long long Nq, const 
   if (!q || !bank || !idx) return eae_set_error(EAE_ERR_ARG, "knn_search: NULL q, bank or idx");
   if (self_offset < -1) return eae_set_error(EAE_ERR_ARG, "knn_search: self_offset must be -1 (off) or >= 0");
   const KnnPlan p = knn_plan(Nq, M);
-  const long long need = knn_ws_bytes(p, Nq, k);
-  if (need > 0 && (!workspace || workspace_bytes < need))
-    return eae_set_error(EAE_ERR_ARG, "knn_search: the workspace is NULL or smaller than eae_knn_workspace_bytes");
+  if (const int rc = latent_workspace_check(workspace, workspace_bytes, knn_ws_bytes(p, Nq, k),
+                                            "knn_search: the workspace is NULL or smaller than eae_knn_workspace_bytes")) return rc;
   EAE_NO_GROUP("knn_search_kernel");
   const hipStream_t st = (hipStream_t)stream;
   const SearchArgs a = {tile_src(q, Nq, bank, L), M, k, self_offset, idx, dist, p.S > 1 ? (int2*)workspace : nullptr, p.rows_per_slice};

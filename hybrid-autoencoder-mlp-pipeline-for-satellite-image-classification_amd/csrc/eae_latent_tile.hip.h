@@ -1,5 +1,6 @@
-// The distance-tile body of eae_knn.hip's search kernel (eae_validity.hip's class-distance kernel holds a copy
-// of it until its speed on this body is shown equal, section 31): a
+// The distance-tile body of eae_knn.hip's search kernel.  eae_validity.hip's class-distance kernel takes the
+// constants, the barrier and the staging helpers from here (lds_col, store_rows, stage_scalar, chain64) and keeps a tile loop and a
+// row loader of its own until its speed on pair_tile is shown equal (section 31).  A
 // workgroup of 4 waves holds 128 queries (wave w owns 32 w .. 32 w + 31 of them) and takes the dot products of one 64-row bank tile
 // with them on v_mfma_f32_32x32x2_f32, the BANK rows as the A operand: D[m][n] = b_m . q_n, so a lane owns one query (its column of
 // D) and 16 rows of each 32-row half (acc_row).  Both operands pass through LDS, 64 columns a pass; the norms ||b||^2 and ||q||^2 are
@@ -36,7 +37,7 @@ struct TileSrc {
   int qvec, bvec;                   // 16-byte loads of q / bank: L % 4 == 0 and an aligned base
 };
 inline TileSrc tile_src(const float* q, long long Nq, const float* bank, int L) {
-  return {q, bank, Nq, L, (L & 3) == 0 && ((uintptr_t)q & 15) == 0, (L & 3) == 0 && ((uintptr_t)bank & 15) == 0};
+  return {q, bank, Nq, L, latent_vec16(q, L), latent_vec16(bank, L)};
 }
 
 // A staged row holds 64 columns de-interleaved: the 32 even columns, then the 32 odd ones (then 4 floats of padding).  Lane (r, h) of

@@ -1,6 +1,7 @@
 // Latent validity (include/eae.h, "latent validity"): for every query row the sum of its distances to the bank
-// rows of each class, both fp32, the bank sorted by class -- what a silhouette and a class-separation table are made of.  The third
-// kernel of the family of eae_latent.hip.h; its body is eae_knn.hip's search kernel without the selection:
+// rows of each class, both fp32, the bank sorted by class -- what a silhouette and a class-separation table are made of.  One of the
+// four units of eae_latent.hip.h; its body is eae_knn.hip's search kernel without the selection, on eae_latent_tile.hip.h's constants,
+// barrier and staging helpers, with the tile loop and the row loader written out here:
 //   d^2(n, m) = max(0, fma(-2, q_n . b_m, ||b_m||^2) + ||q_n||^2), the dot product on v_mfma_f32_32x32x2_f32 with the BANK rows as
 //   the A operand (a lane owns one query, its column of D, and 16 rows of a 32-row tile), the norms sequential fma chains.
 //   sums: workgroup (query tile, class, slice) walks the 64-row tiles slice, slice + S, ... of its class's segment; a lane adds its
@@ -11,25 +12,11 @@
 // stores (store policy 0 of eae_store_policy.h).  No float atomics.
 #include "eae_internal.h"
 #include "eae_common.hip.h"
-#include "eae_latent.hip.h"
+#include "eae_latent_tile.hip.h"
 
 namespace {
 
-constexpr int CD_NT = 256;          // threads per workgroup: 4 waves
-constexpr int CD_QT = 128;          // queries per workgroup tile, 32 per wave
-constexpr int CD_BT = 64;           // bank rows per LDS tile: two 32-row MFMA tiles
-constexpr int CD_LC = 64;           // columns staged per pass
-constexpr int CD_LDS = CD_LC + 4;   // LDS row stride in floats (see lds_col)
-constexpr int CD_MAXK = 256;
 constexpr int CD_MAXS = 64;         // most slices of a segment
-
-// __syncthreads() out of builtins, as eae_knn.hip's kn_barrier: the header's function is not inlined into a kernel that carries
-// EAE_NO_PK's target attribute, and a call inside the tile loop costs the kernel its register allocation
-__device__ __forceinline__ void cd_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 
 struct SumArgs {
   const float* q; const float* bank; long long Nq, M; int L, K, S, metric;
@@ -38,58 +25,16 @@ struct SumArgs {
   int qvec, bvec;                   // 16-byte loads of q / bank: L % 4 == 0 and an aligned base
 };
 
-// A staged row holds 64 columns de-interleaved: the 32 even columns, then the 32 odd ones (then 4 floats of padding), the search
-// kernel's layout: lane (r, h) of an MFMA step takes column 2 j + h, so a lane's operands of four steps are one 16-byte LDS read.
-__device__ __forceinline__ int lds_col(int col) { return (col & 1) * 32 + (col >> 1); }
-
-// rows [row0, row0 + 16 N) x columns [l0, l0 + 64) of src [..][L] into registers with 16-byte loads, zero from row `nrows` on and
-// beyond L: no row at or past nrows is read
+// The header's load_rows with the address as this kernel has always formed it, (row0 + row) * L in 64 bits for every load: the one
+// part of the tile body whose instructions differ between the two kernels
 template <int N>
-__device__ __forceinline__ void load_rows(float4 (&v)[N], const float* src, long long row0, long long nrows, int L, int l0, int lw, int tid) {
+__device__ __forceinline__ void cd_load_rows(float4 (&v)[N], const float* src, long long row0, long long nrows, int L, int l0, int lw, int tid) {
 #pragma unroll
   for (int i = 0; i < N; ++i) {
-    const int e = tid + CD_NT * i, row = e >> 4, col = (e & 15) * 4;
+    const int e = tid + LT_NT * i, row = e >> 4, col = (e & 15) * 4;
     v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (row0 + row < nrows && col < lw) v[i] = *reinterpret_cast<const float4*>(src + (size_t)(row0 + row) * L + l0 + col);
   }
-}
-
-// ... and from the registers into dst [16 N][68]
-template <int N>
-__device__ __forceinline__ void store_rows(float* dst, const float4 (&v)[N], int tid) {
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    const int e = tid + CD_NT * i, row = e >> 4, col = (e & 15) * 4;
-    float* d = dst + row * CD_LDS + (col >> 1);
-    *reinterpret_cast<float2*>(d) = make_float2(v[i].x, v[i].z);
-    *reinterpret_cast<float2*>(d + 32) = make_float2(v[i].y, v[i].w);
-  }
-}
-
-// the same rows straight into dst, float by float: any L, any alignment
-template <int ROWS>
-__device__ __forceinline__ void stage_scalar(float* dst, const float* src, long long row0, long long nrows, int L, int l0, int lw, int tid) {
-#pragma unroll 4
-  for (int i = 0; i < ROWS * CD_LC / CD_NT; ++i) {
-    const int e = tid + CD_NT * i, row = e >> 6, col = e & 63;
-    float v = 0.f;
-    if (row0 + row < nrows && col < lw) v = src[(size_t)(row0 + row) * L + l0 + col];
-    dst[row * CD_LDS + lds_col(col)] = v;
-  }
-}
-
-// s continued over the 64 staged columns of a row in ascending column order: row_sq_chain's order (the zeros beyond L change
-// nothing: fma(0, 0, s) = s)
-__device__ __forceinline__ float chain64(const float* row, float s) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float4 e = *reinterpret_cast<const float4*>(row + 4 * j), o = *reinterpret_cast<const float4*>(row + 32 + 4 * j);
-    s = __builtin_fmaf(e.x, e.x, s); s = __builtin_fmaf(o.x, o.x, s);
-    s = __builtin_fmaf(e.y, e.y, s); s = __builtin_fmaf(o.y, o.y, s);
-    s = __builtin_fmaf(e.z, e.z, s); s = __builtin_fmaf(o.z, o.z, s);
-    s = __builtin_fmaf(e.w, e.w, s); s = __builtin_fmaf(o.w, o.w, s);
-  }
-  return s;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -101,23 +46,23 @@ __device__ __forceinline__ float chain64(const float* row, float s) {
 // the device array holds, no row outside the bank is read.  A workgroup without a tile (an empty class, a slice beyond a short
 // segment) takes the queries' norms straight from memory -- the same chain -- and writes 0, or NaN for a query that is not finite.
 // ---------------------------------------------------------------------------------------------------------------
-__global__ EAE_NO_PK __launch_bounds__(CD_NT, 2) void class_dist_kernel(SumArgs a) {
-  __shared__ __attribute__((aligned(16))) float cd_lds[(CD_QT + CD_BT) * CD_LDS + CD_BT + CD_QT];
+__global__ EAE_NO_PK __launch_bounds__(LT_NT, 2) void class_dist_kernel(SumArgs a) {
+  __shared__ __attribute__((aligned(16))) float cd_lds[LT_FLOATS];
   float* qs = cd_lds;                                  // [128][68]
-  float* bs = qs + CD_QT * CD_LDS;                     // [64][68]
-  float* bn = bs + CD_BT * CD_LDS;                     // [64]   ||b||^2 of the tile's rows
-  float* qn = bn + CD_BT;                              // [128]  ||q||^2, NaN for a query that is not finite (or beyond Nq)
+  float* bs = qs + LT_QT * LT_LDS;                     // [64][68]
+  float* bn = bs + LT_BT * LT_LDS;                     // [64]   ||b||^2 of the tile's rows
+  float* qn = bn + LT_BT;                              // [128]  ||q||^2, NaN for a query that is not finite (or beyond Nq)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
   const int L = a.L, c = blockIdx.y, S = a.S;
-  const long long n0 = (long long)blockIdx.x * CD_QT;
+  const long long n0 = (long long)blockIdx.x * LT_QT;
   long long sb = a.seg[c], se = a.seg[c + 1];
   sb = sb < 0 ? 0 : sb;
   se = se > a.M ? a.M : se;
-  const long long ntile = se > sb ? (se - sb + CD_BT - 1) / CD_BT : 0;
+  const long long ntile = se > sb ? (se - sb + LT_BT - 1) / LT_BT : 0;
   const long long t0 = blockIdx.z;
-  const int npass = (L + CD_LC - 1) / CD_LC;
+  const int npass = (L + LT_LC - 1) / LT_LC;
 
-  if (tid < CD_QT) qn[tid] = __builtin_nanf("");
+  if (tid < LT_QT) qn[tid] = __builtin_nanf("");
 
   const int qrow = wave * 32 + r;
   const long long n = n0 + qrow;
@@ -126,17 +71,17 @@ __global__ EAE_NO_PK __launch_bounds__(CD_NT, 2) void class_dist_kernel(SumArgs 
   float sum = 0.f;
 
   if (t0 >= ntile) {                                           // nothing to walk (uniform over the workgroup)
-    if (tid < CD_QT && n0 + tid < a.Nq) {
+    if (tid < LT_QT && n0 + tid < a.Nq) {
       const float s = row_sq_chain(a.q + (size_t)(n0 + tid) * L, L);
       if (s - s == 0.f) qn[tid] = s;
     }
   } else {
     float qnrm = 0.f;                                          // waves 0 and 1: thread = query of the tile
-    float4 pre[CD_BT / 16];                                    // the bank columns of the coming pass (16-byte loads only)
-    if (a.bvec) load_rows(pre, a.bank, sb + t0 * CD_BT, se, L, 0, L < CD_LC ? L : CD_LC, tid);
+    float4 pre[LT_BT / 16];                                    // the bank columns of the coming pass (16-byte loads only)
+    if (a.bvec) cd_load_rows(pre, a.bank, sb + t0 * LT_BT, se, L, 0, L < LT_LC ? L : LT_LC, tid);
 
     for (long long t = t0; t < ntile; t += S) {
-      const long long m0 = sb + t * CD_BT;
+      const long long m0 = sb + t * LT_BT;
       f32x16 acc[2];
 #pragma unroll
       for (int u = 0; u < 2; ++u)
@@ -145,46 +90,46 @@ __global__ EAE_NO_PK __launch_bounds__(CD_NT, 2) void class_dist_kernel(SumArgs 
       float nrm = 0.f;                                         // wave 0: thread = bank row of the tile
 
       for (int p = 0; p < npass; ++p) {
-        const int l0 = p * CD_LC;
-        const int lw = L - l0 < CD_LC ? L - l0 : CD_LC;        // real columns of this pass
-        cd_barrier();                                          // the previous pass (or tile, or the set-up) is done with the LDS
+        const int l0 = p * LT_LC;
+        const int lw = L - l0 < LT_LC ? L - l0 : LT_LC;        // real columns of this pass
+        lt_barrier();                                          // the previous pass (or tile, or the set-up) is done with the LDS
         const bool newq = npass > 1 || t == t0;
         if (newq && a.qvec) {
-          float4 qv[CD_QT / 16];
-          load_rows(qv, a.q, n0, a.Nq, L, l0, lw, tid);
+          float4 qv[LT_QT / 16];
+          cd_load_rows(qv, a.q, n0, a.Nq, L, l0, lw, tid);
           store_rows(qs, qv, tid);
         } else if (newq) {
-          stage_scalar<CD_QT>(qs, a.q, n0, a.Nq, L, l0, lw, tid);
+          stage_scalar<LT_QT>(qs, a.q, n0, a.Nq, L, l0, lw, tid);
         }
         if (a.bvec) store_rows(bs, pre, tid);
-        else stage_scalar<CD_BT>(bs, a.bank, m0, se, L, l0, lw, tid);
-        cd_barrier();
+        else stage_scalar<LT_BT>(bs, a.bank, m0, se, L, l0, lw, tid);
+        lt_barrier();
         if (a.bvec) {                                          // the coming pass: the next columns, or the next tile's first
           const long long t1 = p + 1 < npass ? t : t + S;
-          const int l1 = p + 1 < npass ? l0 + CD_LC : 0;
-          if (t1 < ntile) load_rows(pre, a.bank, sb + t1 * CD_BT, se, L, l1, L - l1 < CD_LC ? L - l1 : CD_LC, tid);
+          const int l1 = p + 1 < npass ? l0 + LT_LC : 0;
+          if (t1 < ntile) cd_load_rows(pre, a.bank, sb + t1 * LT_BT, se, L, l1, L - l1 < LT_LC ? L - l1 : LT_LC, tid);
         }
         if (wave == 0) {
-          nrm = chain64(bs + lane * CD_LDS, nrm);
+          nrm = chain64(bs + lane * LT_LDS, nrm);
           if (p == npass - 1) bn[lane] = nrm;
         }
-        if (t == t0 && tid < CD_QT) {
-          qnrm = chain64(qs + tid * CD_LDS, qnrm);
+        if (t == t0 && tid < LT_QT) {
+          qnrm = chain64(qs + tid * LT_LDS, qnrm);
           if (p == npass - 1 && n0 + tid < a.Nq && qnrm - qnrm == 0.f) qn[tid] = qnrm;
         }
         if (busy) {
-          const float* zrow = qs + qrow * CD_LDS + h * 32;
-          const float* crow = bs + r * CD_LDS + h * 32;
+          const float* zrow = qs + qrow * LT_LDS + h * 32;
+          const float* crow = bs + r * LT_LDS + h * 32;
           const int nj = ((lw + 1) / 2 + 3) >> 2;              // groups of four column pairs; the last one may run into the zeros
           // the next group's operands are read while this group's MFMAs run (the read after the last group stays inside the row)
           float4 nb = *reinterpret_cast<const float4*>(zrow);
           float4 na0 = *reinterpret_cast<const float4*>(crow);
-          float4 na1 = *reinterpret_cast<const float4*>(crow + 32 * CD_LDS);
+          float4 na1 = *reinterpret_cast<const float4*>(crow + 32 * LT_LDS);
           for (int j = 0; j < nj; ++j) {
             const float4 b = nb, a0 = na0, a1 = na1;
             nb = *reinterpret_cast<const float4*>(zrow + 4 * j + 4);
             na0 = *reinterpret_cast<const float4*>(crow + 4 * j + 4);
-            na1 = *reinterpret_cast<const float4*>(crow + 32 * CD_LDS + 4 * j + 4);
+            na1 = *reinterpret_cast<const float4*>(crow + 32 * LT_LDS + 4 * j + 4);
             acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, b.x, acc[0], 0, 0, 0);
             acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.x, b.x, acc[1], 0, 0, 0);
             acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, b.y, acc[0], 0, 0, 0);
@@ -196,14 +141,14 @@ __global__ EAE_NO_PK __launch_bounds__(CD_NT, 2) void class_dist_kernel(SumArgs 
           }
         }
       }
-      cd_barrier();                                            // bn (and, in the first tile, qn) is complete
+      lt_barrier();                                            // bn (and, in the first tile, qn) is complete
       if (!busy) continue;
 
       // The lane's 32 distances of this tile, added in register order.  Rows from `lim` on lie beyond the segment (staged as zeros)
       // and row `erow` is the query itself: both add 0, by a select, whatever their distance is.
       const long long left = se - m0;
-      const int lim = left < CD_BT ? (int)left : CD_BT;
-      const int erow = self >= m0 && self < m0 + CD_BT ? (int)(self - m0) : -1;
+      const int lim = left < LT_BT ? (int)left : LT_BT;
+      const int erow = self >= m0 && self < m0 + LT_BT ? (int)(self - m0) : -1;
       const float nq = qn[qrow];
 #pragma unroll
       for (int u = 0; u < 2; ++u)
@@ -216,7 +161,7 @@ __global__ EAE_NO_PK __launch_bounds__(CD_NT, 2) void class_dist_kernel(SumArgs 
         }
     }
   }
-  cd_barrier();                                                // qn is complete on either path
+  lt_barrier();                                                // qn is complete on either path
 
   // lanes r and r + 32 hold the two halves of query 32 wave + r: h = 0 adds them and writes
   const float other = __shfl_xor(sum, 32, 64);
@@ -236,15 +181,15 @@ __global__ EAE_NO_PK __launch_bounds__(256) void class_dist_add_kernel(const flo
 }
 
 int cd_dims_ok(long long Nq, long long M, int L, int K) {
-  return latent_dims_ok(Nq, L) && latent_dims_ok(M, L) && K >= 1 && K <= CD_MAXK;
+  return latent_dims_ok(Nq, L, K) && latent_dims_ok(M, L);
 }
 
 // The number of slices, a function of (Nq, M) alone (seg is device data: the longest segment the plan can count on is the bank).
 // With 256 query tiles or more a segment is not cut.  Below that it is cut into as many slices as bring the grid of ONE class to
 // 512 workgroups, of at least four 64-row tiles each were the class the whole bank, and never more than 64.
 int cd_slices(long long Nq, long long M) {
-  const long long tiles = (Nq + CD_QT - 1) / CD_QT;
-  const long long nb = (M + CD_BT - 1) / CD_BT;
+  const long long tiles = (Nq + LT_QT - 1) / LT_QT;
+  const long long nb = (M + LT_BT - 1) / LT_BT;
   long long want = tiles >= 256 ? 1 : (512 + tiles - 1) / tiles;
   const long long most = (nb + 3) / 4;
   if (want > most) want = most;
@@ -270,15 +215,13 @@ extern "C" int eae_class_dist_sums(void* stream, const float* q, long long Nq, c
   if (!q || !bank || !seg || !sums) return eae_set_error(EAE_ERR_ARG, "class_dist_sums: NULL q, bank, seg or sums");
   if (metric != 0 && metric != 1) return eae_set_error(EAE_ERR_ARG, "class_dist_sums: metric must be 0 (euclidean) or 1 (squared euclidean)");
   const int S = cd_slices(Nq, M);
-  const long long need = cd_ws_bytes(S, Nq, K);
-  if (need > 0 && (!workspace || workspace_bytes < need))
-    return eae_set_error(EAE_ERR_ARG, "class_dist_sums: the workspace is NULL or smaller than eae_class_dist_workspace_bytes");
+  if (const int rc = latent_workspace_check(workspace, workspace_bytes, cd_ws_bytes(S, Nq, K),
+                                            "class_dist_sums: the workspace is NULL or smaller than eae_class_dist_workspace_bytes")) return rc;
   EAE_NO_GROUP("class_dist_kernel");
   const hipStream_t st = (hipStream_t)stream;
-  const SumArgs a = {q, bank, Nq, M, L, K, S, metric, seg, self_pos, S > 1 ? (float*)workspace : sums,
-                     (L & 3) == 0 && ((uintptr_t)q & 15) == 0, (L & 3) == 0 && ((uintptr_t)bank & 15) == 0};
-  const long long tiles = (Nq + CD_QT - 1) / CD_QT;
-  hipLaunchKernelGGL(class_dist_kernel, dim3((unsigned)tiles, (unsigned)K, (unsigned)S), dim3(CD_NT), 0, st, a);
+  const SumArgs a = {q, bank, Nq, M, L, K, S, metric, seg, self_pos, S > 1 ? (float*)workspace : sums, latent_vec16(q, L), latent_vec16(bank, L)};
+  const long long tiles = (Nq + LT_QT - 1) / LT_QT;
+  hipLaunchKernelGGL(class_dist_kernel, dim3((unsigned)tiles, (unsigned)K, (unsigned)S), dim3(LT_NT), 0, st, a);
   EAE_LAUNCH_CHECK();
   if (S > 1) {
     const long long count = Nq * K;

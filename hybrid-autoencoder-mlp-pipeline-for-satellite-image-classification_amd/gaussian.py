@@ -27,8 +27,8 @@ import torch
 
 from . import _lib
 from ._lib import check
-from . import cluster
-from .cluster import MAX_K, _int_arg, _rows_arg
+from ._args import _alloc_workspace, _int_arg, _rows_arg
+from .cluster import MAX_K, _predict, _update, _workspace
 from .engine import _ptr, _stream, _require_gpu
 
 COVARIANCES = ("full", "tied")
@@ -122,21 +122,18 @@ def _moments(z, labels, k):
     dev = z.device
     lab = labels.to(torch.int64)
     # a row with a NaN or an Inf: NaN distance to the origin from `eae_kmeans_assign`, as `kmeans_init` finds them (no N x L temporary)
-    finite = ~torch.isnan(cluster._predict(z, torch.zeros((1, width), dtype=torch.float32, device=dev))[1])
+    finite = ~torch.isnan(_predict(z, torch.zeros((1, width), dtype=torch.float32, device=dev))[1])
     key = torch.where((lab >= 0) & (lab < k) & finite, lab, k)         # what is not summed sorts into a tail no segment covers
     order = torch.sort(key, stable=True)[1]
     means = torch.zeros((k, width), dtype=torch.float32, device=dev)
     counts = torch.empty(k, dtype=torch.int64, device=dev)
     scatter = torch.empty((k, width, width), dtype=torch.float32, device=dev)
-    nbytes = lib.eae_class_scatter_workspace_bytes(n, width, k)
-    if nbytes < 0:
-        check(int(nbytes))
     with torch.cuda.device(dev):
-        cluster._update(z, key, means, counts, cluster._workspace(z, k))
+        _update(z, key, means, counts, _workspace(z, k))
         seg = torch.cat((torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(counts, 0)))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws = _alloc_workspace(lib.eae_class_scatter_workspace_bytes(n, width, k), dev)
         check(lib.eae_class_scatter(_stream(), _ptr(z), n, width, _ptr(key), _ptr(order), _ptr(seg), k, _ptr(means), _ptr(scatter),
-                                    _ptr(ws), nbytes))
+                                    _ptr(ws), ws.numel()))
     return counts, means, scatter
 
 

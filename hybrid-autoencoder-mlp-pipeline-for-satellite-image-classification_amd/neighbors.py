@@ -21,7 +21,7 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .cluster import MAX_L, _int_arg, _rows_arg          # noqa: F401  one width limit, one check of fp32 rows and of k for both modules
+from ._args import MAX_L, _int_arg, _alloc_workspace, _rows_arg       # noqa: F401  one width limit, one check of fp32 rows and of k
 from .engine import _ptr, _stream, _require_gpu
 from .scene import _host_plan, _scene_latents
 
@@ -77,9 +77,7 @@ def _search(queries, bank, k, self_offset=-1):
     idx = torch.empty((nq, k), dtype=torch.int64, device=queries.device)
     dist = torch.empty((nq, k), dtype=torch.float32, device=queries.device)
     nbytes = lib.eae_knn_workspace_bytes(nq, m, width, k)
-    if nbytes < 0:
-        check(int(nbytes))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=queries.device) if nbytes else None
+    ws = _alloc_workspace(nbytes, queries.device, or_none=True)
     with torch.cuda.device(queries.device):
         check(lib.eae_knn_search(_stream(), _ptr(queries), nq, _ptr(bank), m, width, k, int(self_offset), _ptr(idx), _ptr(dist), _ptr(ws),
                                  nbytes))

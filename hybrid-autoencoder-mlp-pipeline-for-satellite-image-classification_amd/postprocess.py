@@ -22,7 +22,7 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .cluster import _int_arg
+from ._args import _alloc_workspace, _int_arg
 from .engine import _ptr, _stream, _require_gpu
 
 MAX_CLASSES = 64
@@ -65,10 +65,7 @@ def _connectivity_arg(c):
 
 
 def _workspace(h, w, device):
-    nbytes = _lib.load().eae_map_workspace_bytes(h, w)
-    if nbytes < 0:
-        check(int(nbytes))
-    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return _alloc_workspace(_lib.load().eae_map_workspace_bytes(h, w), device)
 
 
 # ---------------------------------------------------------------------------------------------------- the C calls

@@ -28,7 +28,7 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .cluster import _int_arg
+from ._args import _int_arg
 from .engine import _ptr, _stream, _require_gpu
 from .postprocess import _connectivity_arg, _regions, _stats, _workspace
 

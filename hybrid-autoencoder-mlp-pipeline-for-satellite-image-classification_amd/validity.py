@@ -19,7 +19,8 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .cluster import MAX_K, _int_arg, _label_counts, _rows_arg, _update, _workspace, kmeans_fit
+from ._args import _alloc_workspace, _int_arg, _label_counts, _rows_arg
+from .cluster import MAX_K, _fit_args, _update, _workspace, kmeans_fit
 from .engine import _ptr, _stream, _require_gpu
 
 METRICS = ("euclidean", "sqeuclidean")
@@ -113,9 +114,7 @@ def _sums(q, bank, lab, k, metric, self_index, center):
         self_pos = torch.where(inside, inv[self_index.clamp(0, m - 1)], -1)
     lib = _lib.load()
     nbytes = lib.eae_class_dist_workspace_bytes(nq, m, width, k)
-    if nbytes < 0:
-        check(int(nbytes))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    ws = _alloc_workspace(nbytes, dev, or_none=True)
     sums = torch.empty((nq, k), dtype=torch.float32, device=dev)
     q = q.contiguous()
     with torch.cuda.device(dev):
@@ -294,7 +293,6 @@ def _calinski_harabasz(z, labels, k):
 
 # ---------------------------------------------------------------------------------------------------- the choice of k
 def _select_args(z, ks, criterion, sample, max_iter, tol):
-    from .cluster import _fit_args
     n, width = _rows_arg(z, "z", "[N, L]")
     if criterion not in CRITERIA:
         raise RuntimeError(f"criterion must be one of {CRITERIA}, got {criterion!r}")

@@ -26,7 +26,7 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .cluster import _int_arg
+from ._args import _int_arg
 from .engine import _ptr, _stream, _require_gpu
 
 MAX_CLASSES = 64
