@@ -35,6 +35,10 @@ from .zonal import compact_zones, zonal_stats, zone_labels, paint_zones, classif
 from .report import zone_table  # noqa: F401
 from . import segment  # noqa: F401
 from .segment import slic_clusters, slic_scene, classify_superpixels, zone_boundaries, Superpixels  # noqa: F401
+from . import change  # noqa: F401
+from .change import joint_moments, mad_from_moments, mad_fit, mad_transform, detect_change, invariant_regression  # noqa: F401
+from .change import class_transitions, JointMoments, MadModel, ChangeResult  # noqa: F401
+from .report import transition_table  # noqa: F401
 
 __all__ = ["Encoder", "Decoder", "SupervisedAutoencoder", "MLP", "mlp_from_state_dict", "fit_autoencoder", "grid_search_autoencoder",
            "extract_features", "fit_mlp", "grid_search_mlp", "evaluate", "augment_batch", "stage_bands", "Augment",
@@ -48,4 +52,6 @@ __all__ = ["Encoder", "Decoder", "SupervisedAutoencoder", "MLP", "mlp_from_state
            "silhouette_score", "class_distance_matrix", "davies_bouldin_score", "calinski_harabasz_score", "select_k",
            "separation_table", "class_scatter", "gaussian_fit", "gaussian_predict", "gaussian_classify_scene", "scatter_axes",
            "GaussianModel", "compact_zones", "zonal_stats", "zone_labels", "paint_zones", "classify_zones", "zone_confusion", "ZonalStats",
-           "zone_table", "slic_clusters", "slic_scene", "classify_superpixels", "zone_boundaries", "Superpixels"]
+           "zone_table", "slic_clusters", "slic_scene", "classify_superpixels", "zone_boundaries", "Superpixels",
+           "joint_moments", "mad_from_moments", "mad_fit", "mad_transform", "detect_change", "invariant_regression", "class_transitions",
+           "JointMoments", "MadModel", "ChangeResult", "transition_table"]

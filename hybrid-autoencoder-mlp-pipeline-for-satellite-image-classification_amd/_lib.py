@@ -186,6 +186,11 @@ _PROTOS = {
     "eae_slic_step": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_longlong, vp, vp, vp]),
     "eae_slic_centres": (C.c_int, [vp, vp, C.c_longlong, C.c_int, vp]),
     "eae_map_regions_wide": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_longlong]),
+    "eae_change_moments_workspace_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
+    "eae_change_moments": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_float, C.c_int,
+                                     C.c_int, C.c_float, C.c_int, vp, vp, vp, vp, vp, vp, C.c_longlong]),
+    "eae_change_variates": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_float, C.c_int,
+                                      C.c_int, C.c_float, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp]),
 }
 
 EXPORTS = tuple(_PROTOS.keys())

@@ -229,6 +229,35 @@ def zone_table(stats, labels, class_names=None, digits=4):
     return "\n".join(lines) + "\n"
 
 
+def transition_table(table, class_names=None):
+    """Text table of a post-classification comparison, one line per class: its pixels at date A and at date B, how many kept the
+    class, and the class that took the most of what it lost and the one that gave the most of what it gained (with the counts).
+    table: `change.class_transitions`' [K+1, K+1] counts, rows = date A, columns = date B, index K = no class ("-" in the table);
+    class_names: K strings (default: the class ids).  A class that lost or gained nothing prints '-'."""
+    t = np.asarray(table.detach().cpu().numpy() if hasattr(table, "detach") else table)
+    if t.ndim != 2 or t.shape[0] != t.shape[1] or t.shape[0] < 2:
+        raise ValueError("table must be a [K+1, K+1] from-to table")
+    k = t.shape[0] - 1
+    names = [str(c) for c in range(k)] if class_names is None else [str(n) for n in class_names]
+    if len(names) != k:
+        raise ValueError(f"class_names must have {k} entries, got {len(names)}")
+    names = names + ["-"]
+    width = max(max(len(n) for n in names), len("class"))
+
+    def top(v, own):
+        v = v.copy()
+        v[own] = 0
+        j = int(v.argmax())                                  # the lowest index on a tie
+        return "{:>{w}s} {:>10}".format(names[j], int(v[j]), w=width) if v[j] > 0 else "{:>{w}s} {:>10}".format("-", "-", w=width)
+
+    lines = ["{:>{w}s} {:>10} {:>10} {:>10} {:>{v}s} {:>{v}s}".format("class", "date A", "date B", "kept", "lost to", "gained from",
+                                                                      w=width, v=width + 11), ""]
+    for c in range(k):
+        lines.append("{:>{w}s} {:>10} {:>10} {:>10} ".format(names[c], int(t[c].sum()), int(t[:, c].sum()), int(t[c, c]), w=width)
+                     + top(t[c], c) + " " + top(t[:, c], c))
+    return "\n".join(lines) + "\n"
+
+
 def classification_report_from_confusion(cm, digits=4, num_classes=None):
     """`classification_report`'s table from a confusion matrix (`confusion_metrics`: the same matrix forms)."""
     return _report_text(confusion_metrics(cm, num_classes), digits)

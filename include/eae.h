@@ -950,6 +950,50 @@ int eae_slic_centres(void* stream, const long long* sums, long long n_clusters, 
 int eae_map_regions_wide(void* stream, const long long* labels, int H, int W, int connectivity, long long* regions, void* workspace,
                          long long workspace_bytes);
 
+/* ------------------------------------------------------------------ change detection --------------- */
+/* The two passes of an IR-MAD iteration (iteratively reweighted multivariate alteration detection, Nielsen 2007) over two scenes of
+ * one place (no reference counterpart).  a and b are device scenes [C][H][W], contiguous, each of dtype
+ * EAE_SCENE_U8 / U16 / F32 (the two may differ), C in 1..16, H, W >= 1, H * W < 2^31; div_a, div_b device floats [C].  The pixel
+ * vector is v = [x_0 .. x_{C-1}, y_0 .. y_{C-1}], x_c = a_c / div_a[c], y_c = b_c / div_b[c], each one fp32 division.  A pixel is
+ * invalid when mask[y * W + x] != 0 (mask: uint8 [H][W] or NULL), when either scene's nodata test fires (nodata_mode_*, nodata_*,
+ * rule_*: EAE_NODATA_* and EAE_INVALID_* exactly as eae_scene_invalid_counts defines them, per scene), or when a float32 band holds a
+ * NaN or an Inf.  Stateless; every call goes to `stream` and nothing synchronises the host.
+ *
+ * eae_change_moments: out_moments (device double [1 + 2C + (2C)^2]) = N = sum w, then s = sum w (v - p), then S = sum w (v - p)
+ * (v - p)^T row-major, over the valid pixels; out_count (device int64) = the number of valid pixels.  weights: device float [H][W] or
+ * NULL for 1; a weight that is NaN, negative or infinite makes its pixel invalid, a weight of 0 leaves it valid.  pivot: device
+ * float [2C]; v - p is one fp32 subtraction.  The raster is cut into chunks of a fixed number of pixels (a multiple of 256; at most
+ * 4096 chunks), a function of (C, H, W) alone.  A chunk's products w (v - p)_i * (v - p)_j accumulate in fp32 in a fixed order on the
+ * f32-input MFMA (v_mfma_f32_32x32x2_f32; 2C is padded to a power of two D and the 32 x 32 tile carries 32 / D pixel streams on its
+ * diagonal blocks), s and N beside it in the lane; every chunk stores its whole partial to `workspace`, and a second kernel adds the
+ * partials in float64 in ascending chunk order (256 runs of consecutive chunks, then the runs) and writes S[i][j] and S[j][i] from one
+ * register.  No float atomics: S is bitwise symmetric, every output word is written (zeros and a count of 0 when no pixel is valid),
+ * and the result is bitwise identical from run to run.  workspace: device memory of at least
+ * eae_change_moments_workspace_bytes(C, H, W) bytes (host only; < 0 on bad arguments), contents irrelevant on entry.
+ *
+ * eae_change_variates: per valid pixel M_i = sum_j T[j][i] (v_j - mean[j]), i < C: one fp32 fma chain in ascending j (mean: device
+ * float [2C], T: device float [2C][C]); Z = sum_i M_i^2, one fma chain in ascending i; prob = Q(dof / 2, Z / 2), the chi-square
+ * survival function, dof in 1..16, in closed form:
+ *   dof = 2 m:     e^-h sum_{j < m} h^j / j!,                                          h = Z / 2
+ *   dof = 2 m + 1: erfc(sqrt h) + e^-h sum_{j = 1..m} h^(j - 1/2) / Gamma(j + 1/2)
+ * (0 above Z = 256, where every Q is below 2^-126).  out_chi2, out_prob: float [H][W]; out_variates: float [C][H][W]; each may be
+ * NULL.  An invalid pixel gets chi2 = NaN, prob = 0, variates = NaN.  A pixel's results depend on its own values and the model alone:
+ * not on the launch geometry, nor on which outputs are requested.
+ *
+ * Rejected (EAE_ERR_ARG, nothing launched, the call's name in eae_last_error()): a NULL scene, divisor, pivot, out_moments,
+ * out_count, mean, T or workspace; an unknown dtype or a scene pointer that is no multiple of its element size; C, H, W or dof
+ * outside the limits above; an unknown nodata mode or rule, a NaN nodata or a value outside the dtype's range for an integer scene;
+ * a workspace that is too small. */
+long long eae_change_moments_workspace_bytes(int C, int H, int W);
+int eae_change_moments(void* stream, const void* a, const void* b, int dtype_a, int dtype_b, int C, int H, int W, const float* div_a,
+                       const float* div_b, int nodata_mode_a, float nodata_a, int rule_a, int nodata_mode_b, float nodata_b,
+                       int rule_b, const unsigned char* mask, const float* weights, const float* pivot, double* out_moments,
+                       long long* out_count, void* workspace, long long workspace_bytes);
+int eae_change_variates(void* stream, const void* a, const void* b, int dtype_a, int dtype_b, int C, int H, int W, const float* div_a,
+                        const float* div_b, int nodata_mode_a, float nodata_a, int rule_a, int nodata_mode_b, float nodata_b,
+                        int rule_b, const unsigned char* mask, const float* mean, const float* T, int dof, float* out_chi2,
+                        float* out_prob, float* out_variates);
+
 #ifdef __cplusplus
 }
 #endif
