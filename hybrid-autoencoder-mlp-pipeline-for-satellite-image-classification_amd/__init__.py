@@ -39,6 +39,9 @@ from . import change  # noqa: F401
 from .change import joint_moments, mad_from_moments, mad_fit, mad_transform, detect_change, invariant_regression  # noqa: F401
 from .change import class_transitions, JointMoments, MadModel, ChangeResult  # noqa: F401
 from .report import transition_table  # noqa: F401
+from . import register  # noqa: F401
+from .register import match_tiles, fit_transform, resample_scene, coregister, TileMatches, TileGeometry, Registration  # noqa: F401
+from .report import registration_table  # noqa: F401
 
 __all__ = ["Encoder", "Decoder", "SupervisedAutoencoder", "MLP", "mlp_from_state_dict", "fit_autoencoder", "grid_search_autoencoder",
            "extract_features", "fit_mlp", "grid_search_mlp", "evaluate", "augment_batch", "stage_bands", "Augment",
@@ -54,4 +57,5 @@ __all__ = ["Encoder", "Decoder", "SupervisedAutoencoder", "MLP", "mlp_from_state
            "GaussianModel", "compact_zones", "zonal_stats", "zone_labels", "paint_zones", "classify_zones", "zone_confusion", "ZonalStats",
            "zone_table", "slic_clusters", "slic_scene", "classify_superpixels", "zone_boundaries", "Superpixels",
            "joint_moments", "mad_from_moments", "mad_fit", "mad_transform", "detect_change", "invariant_regression", "class_transitions",
-           "JointMoments", "MadModel", "ChangeResult", "transition_table"]
+           "JointMoments", "MadModel", "ChangeResult", "transition_table", "match_tiles", "fit_transform", "resample_scene", "coregister",
+           "TileMatches", "TileGeometry", "Registration", "registration_table"]

@@ -191,6 +191,10 @@ _PROTOS = {
                                      C.c_int, C.c_float, C.c_int, vp, vp, vp, vp, vp, vp, C.c_longlong]),
     "eae_change_variates": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_float, C.c_int,
                                       C.c_int, C.c_float, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp]),
+    "eae_match_tiles": (C.c_int, [vp] + 2 * [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_float, C.c_int, vp]
+                        + [C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "eae_scene_resample": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, C.c_int, C.c_double,
+                                     vp, C.c_int, C.c_int, vp]),
 }
 
 EXPORTS = tuple(_PROTOS.keys())

@@ -19,7 +19,7 @@ SOURCES = ["eae_ctx.hip", "eae_streams.hip", "eae_step.hip", "eae_group.hip", "e
            "eae_conv_launch.hip", "eae_edge_launch.hip", "eae_wgrad_launch.hip", "eae_fc_launch.hip",
            "eae_misc.hip", "eae_optim.hip", "eae_head.hip", "eae_mlp.hip", "eae_mlp_wce.hip", "eae_mlp_arch.hip", "eae_scene.hip", "eae_cluster.hip", "eae_knn.hip",
            "eae_validity.hip", "eae_gauss.hip", "eae_regions.hip", "eae_stage.hip", "eae_zonal.hip", "eae_slic.hip",
-           "eae_change.hip"]
+           "eae_change.hip", "eae_register.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-result"] + os.environ.get("EAE_EXTRA_FLAGS", "").split()
 
 

@@ -11,7 +11,8 @@ statistics settle on the pixels that did not change.  The two passes over the sc
 Conventions: x = a / divisor_a and y = b / divisor_b per band; the pairs come in descending order of rho (the first variate is the
 most stable combination, the last carries the most change); the sign of pair i makes the largest-magnitude entry of Sxx a_i positive;
 a_i^T Sxx a_i = b_i^T Syy b_i = 1; sigma_i = sqrt(2 (1 - rho_i)), not below `SIGMA_FLOOR`; variate_i = (a_i^T (x - mean_a) - b_i^T
-(y - mean_b)) / sigma_i.  The scenes must be co-registered and have the same number of bands.
+(y - mean_b)) / sigma_i.  The scenes must be co-registered and have the same number of bands; `register.coregister` brings a scene
+that is not aligned onto the other's grid and returns the validity raster that ``mask=~valid`` takes.
 
 - `joint_moments`: weighted mean and covariance of the stacked pixel vector [x, y], one pass;
 - `mad_from_moments`: the canonical-correlation solve, host only;

@@ -258,6 +258,24 @@ def transition_table(table, class_names=None):
     return "\n".join(lines) + "\n"
 
 
+def registration_table(registration, shape=None):
+    """Text summary of a `register.Registration`: the matrix (a point (x, y) of scene A -> its place in scene B), the shift it gives
+    at the scene centre (shape = (H, W); default: at the origin), the rmse of the inliers and how many tiles they are."""
+    m = np.asarray(registration.matrix, dtype=np.float64)
+    if m.shape != (2, 3):
+        raise ValueError("registration.matrix must be 2 x 3")
+    x, y = (0.0, 0.0) if shape is None else ((shape[1] - 1) / 2.0, (shape[0] - 1) / 2.0)
+    dx, dy = m[0, 0] * x + m[0, 1] * y + m[0, 2] - x, m[1, 0] * x + m[1, 1] * y + m[1, 2] - y
+    lines = ["{:>12s} {:>14s} {:>14s} {:>14s}".format("", "x", "y", "1"), ""]
+    for name, row in zip(("x in B", "y in B"), m):
+        lines.append("{:>12s} {:>14.8f} {:>14.8f} {:>14.5f}".format(name, *row))
+    lines += ["", "{:>12s} {}".format("model", registration.model),
+              "{:>12s} dx {:+.4f}  dy {:+.4f} px at {}".format("shift", dx, dy, "the origin" if shape is None else "the scene centre"),
+              "{:>12s} {:.4f} px".format("rmse", float(registration.rmse)),
+              "{:>12s} {} of {} tiles".format("inliers", int(np.asarray(registration.inliers).sum()), int(registration.n_tiles))]
+    return "\n".join(lines) + "\n"
+
+
 def classification_report_from_confusion(cm, digits=4, num_classes=None):
     """`classification_report`'s table from a confusion matrix (`confusion_metrics`: the same matrix forms)."""
     return _report_text(confusion_metrics(cm, num_classes), digits)

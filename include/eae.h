@@ -994,6 +994,63 @@ int eae_change_variates(void* stream, const void* a, const void* b, int dtype_a,
                         int rule_b, const unsigned char* mask, const float* mean, const float* T, int dof, float* out_chi2,
                         float* out_prob, float* out_variates);
 
+/* ------------------------------------------------------------------ co-registration ---------------- */
+/* Tie points between two scenes of one place and the resampling of a scene through an affine map (no reference counterpart;
+ * DESIGN.md section 37; tests/register_ref.py is the NumPy definition of everything below).  Scenes are device rasters [C][H][W],
+ * contiguous, of dtype EAE_SCENE_U8 / U16 / F32, C in 1..16, H, W >= 1, H * W < 2^31.  Stateless; every call goes to `stream` and
+ * nothing synchronises the host.
+ *   Coordinates: pixel (y, x) has its centre at the integer point (x, y).  A transform is a row-major 2 x 3 double matrix M that maps
+ *   a point of the DESTINATION grid to a point of the SOURCE grid: sx = (M[0] x + M[1] y) + M[2], sy = (M[3] x + M[4] y) + M[5].  For
+ *   co-registration the destination is A's grid and the source is B: M says where in B a pixel of A lies.
+ *   Feature: the feature of the superpixel step above, u = rint(65535 * min(max(v / d, 0), 1)), evaluated in double from the stored value
+ *   and the float divisor, half to even, an integer in 0..65535; one band of each scene is matched (band_a, band_b; div_a, div_b are
+ *   device floats [Ca] and [Cb], of which the matched band's entry is read).
+ *   Validity: exactly as in the change moments above: a pixel is invalid when its mask byte is set (mask: uint8 [H][W] of the
+ *   scene, or NULL), when the scene's nodata test fires (EAE_NODATA_*, EAE_INVALID_*, per scene, over all C bands of that scene), or
+ *   when a float32 band is NaN or Inf.  A position outside the raster is invalid too.
+ *
+ * eae_match_tiles: the sums that define the zero-mean normalised cross-correlation of n_tiles templates of A with B at every integer
+ * offset of a search window.  tile T in 4..64, radius R in 0..16, n_tiles in 1..2^20; the two scenes may differ in shape, dtype and
+ * band count.  origins_a / origins_b: device int32 [n_tiles][2] = (y, x), the top-left pixel of the template in A and of the
+ * zero-offset window in B; any int32, since everything outside a raster is invalid.  For tile t and offset (dy, dx) in [-R, R]^2,
+ * entry o = (dy + R)(2R + 1) + (dx + R), the sums run over (i, j) in [0, T)^2 and take the pairs whose two pixels are both valid,
+ * A at (ay + i, ax + j) and B at (by + dy + i, bx + dx + j):
+ *     sums[t][o] = (n, sum u_a, sum u_b, sum u_a^2, sum u_b^2, sum u_a u_b)        int64 [n_tiles][(2R + 1)^2][6], all below 2^45
+ * Integers only: the table is unique for given inputs, independent of the launch geometry and identical from run to run.  Every
+ * output word is written (zeros where no pair is valid).
+ *
+ * eae_scene_resample: dst[c][y][x] for every pixel of a destination grid [Hd][Wd] (Hd, Wd >= 1, Hd * Wd < 2^31; same dtype and band
+ * count as src) from the source at (sx, sy) = M (x, y).  matrix is a HOST pointer to 6 doubles, read during the call.  All arithmetic
+ * is float64, one correctly rounded operation at a time and never contracted, in exactly this order:
+ *   nearest (EAE_RESAMPLE_NEAREST):   one tap at floor(s + 0.5) per axis, weight 1.
+ *   bilinear (EAE_RESAMPLE_BILINEAR): x0 = floor(sx), t = sx - x0; taps x0, x0 + 1 with weights (1 - t, t); likewise in y.
+ *   cubic (EAE_RESAMPLE_CUBIC):       Catmull-Rom (a = -0.5, GDAL's cubic); taps x0 - 1 .. x0 + 2 with the Horner forms
+ *       w0 = ((-0.5 t + 1) t - 0.5) t     w1 = ((1.5 t - 2.5) t) t + 1     w2 = ((-1.5 t + 2) t + 0.5) t     w3 = ((0.5 t - 0.5) t) t
+ *   A tap (r, c) takes part when both its axis weights wy[r] and wx[c] are not exactly zero.  value = the sum over the participating
+ *   taps, rows ascending and columns ascending inside a row, of (wy[r] * wx[c]) * v; the first term starts the sum (nothing is added
+ *   to a zero).  An integer dtype stores rint (half to even) of the sum clamped to the dtype's range (cubic overshoots); float32
+ *   one conversion from double.
+ *   An output pixel is valid if and only if sx and sy are finite and every participating tap is a valid source pixel; an invalid one
+ *   gets `fill` in every band (rint of it for an integer dtype) and 0 in out_valid (uint8 [Hd][Wd] or NULL), a valid one 1.  So
+ *   the identity reproduces the source bit for bit, and an integer translation is a shifted copy with `fill` in the uncovered strip,
+ *   for all three methods.
+ *
+ * Rejected (EAE_ERR_ARG, nothing launched, the call's name in eae_last_error()): a NULL scene, divisor, origin table, sums, matrix or
+ * dst; an unknown dtype, method, nodata mode or rule; a scene or dst pointer that is no multiple of its element size; a band index
+ * outside its scene; T, R, n_tiles, C or a shape outside the limits; a nodata value that the dtype cannot hold; a matrix entry that is
+ * not finite; a fill outside an integer dtype's range (NaN included; a float32 scene takes any fill). */
+#define EAE_RESAMPLE_NEAREST 0
+#define EAE_RESAMPLE_BILINEAR 1
+#define EAE_RESAMPLE_CUBIC 2
+int eae_match_tiles(void* stream, const void* a, int dtype_a, int Ca, int Ha, int Wa, int band_a, const float* div_a,
+                    int nodata_mode_a, float nodata_a, int rule_a, const unsigned char* mask_a, const void* b, int dtype_b, int Cb,
+                    int Hb, int Wb, int band_b, const float* div_b, int nodata_mode_b, float nodata_b, int rule_b,
+                    const unsigned char* mask_b, int tile, int radius, int n_tiles, const int* origins_a, const int* origins_b,
+                    long long* sums);
+int eae_scene_resample(void* stream, const void* src, int dtype, int C, int Hs, int Ws, int nodata_mode, float nodata, int rule,
+                       const unsigned char* mask_src, const double* matrix, int method, double fill, void* dst, int Hd, int Wd,
+                       unsigned char* out_valid);
+
 #ifdef __cplusplus
 }
 #endif
